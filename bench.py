@@ -1,15 +1,23 @@
 #!/usr/bin/env python
 """bench.py — throughput of the IVOS-W hot path on MI355X (one process per GPU).
 
-    python bench.py --gpus N --steps K --warmup W            (N > 1: launched by torch.distributed.run, or plainly — it then
-                                                              re-executes itself under torch.distributed.run, one rank per GPU)
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+                                                             (N > 1: launched by torch.distributed.run, or plainly — it then
+                                                              starts torch.distributed.run as a child, one rank per GPU)
+
+A plain run measures the headline only: set-up, warm-up, K timed steps, one JSON line with `metric`, `value`, `unit`,
+`higher_is_better`, `dtype` and `ms_per_step` (+ the run's config).  `--full` adds everything else described below (the oracle
+check, roofline, sustained rate, the DQN leg, the fp32 / bf16x3 modes, front end, recommend_frame, J&F, seg epilogue, CPU baselines,
+the data-parallel and P2P legs); those records exist only in a --full line.  `--dump-outputs DIR` writes what the timed path returned in
+its last step as float32 .npy files (`scores` [B, 1] of the assessment; `policy_params` / `target_params` of the DQN workload); the
+inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 
 Default workload = BASELINE.json configs[1]: the assessment CNN (AssessNet.forward) on a batch of 256
 synthetic 480p (frame, mask) pairs per GPU, bf16 operands / fp32 accumulate, inputs resident in HBM when
 the clock starts.  One "step" = one AssessNet.forward over the batch.  `value` = assessed frames/s over all
 ranks (frames are independent: weak scaling, no data-path collective).
 
-The same JSON line also carries, as `dqn`, the second half of BASELINE's metric: Double-DQN agent steps/s
+A --full line also carries, as `dqn`, the second half of BASELINE's metric: Double-DQN agent steps/s
 (configs[2]/[3]: replay 50k transitions, minibatch 128 per GPU, T=25; device-resident replay gather ->
 3 forwards + loss + BPTT -> [RCCL all-reduce of the 724 KB gradient arena when N>1] -> clamp+Adam ->
 target-sync coin flip).  `--workload dqn` makes that the headline `value` instead.
@@ -173,6 +181,13 @@ def timed(fn, steps, warmup, dev, dist, min_warm_s=0.0, before=None, after=None)
     return dt
 
 
+def dump_outputs(path, arrays, rank, world):
+    """--dump-outputs: the arrays the timed path returned in its last step, one float32 .npy per array (per rank when N > 1)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, (name if world == 1 else f"{name}_rank{rank}") + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def build_assess(args, rank, dev):
     from ivos_w_amd.models.assessment import AssessNet
     net = AssessNet(precision=args.precision, chunk=args.chunk)
@@ -215,7 +230,7 @@ def dqn_dp_critical_path(single_us, timeout_s=150):
         return None
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--workload", "dqn", "--steps", "800", "--warmup", "50",
-           "--no-cpu-baseline"]
+           "--no-cpu-baseline", "--full"]
     try:
         r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=timeout_s)
         line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -313,7 +328,7 @@ def dqn_live_traffic(timeout_s=60):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(tmp, counter)
             cmd = [prof, "--pmc", counter, "-d", d, "-o", "c", "--output-format", "csv", "--", sys.executable, os.path.join(ROOT, "bench.py"),
-                   "--workload", "dqn", "--steps", "96", "--warmup", "8", "--min-warm-s", "0", "--dqn-mode", "plain", "--no-cpu-baseline"]
+                   "--workload", "dqn", "--steps", "96", "--warmup", "8", "--min-warm-s", "0", "--dqn-mode", "plain", "--no-cpu-baseline", "--full"]
             child = subprocess.Popen(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, start_new_session=True)
             try:
                 child.communicate(timeout=timeout_s)
@@ -435,27 +450,29 @@ def bench_assess(args, rank, world, dev, dist):
     def step():
         out["s"] = net(tf, tp)
     tot, spans, cnt = ctypes.c_double(0), ctypes.c_int(0), ctypes.c_int(0)
+    # the tower's span timing (roofline) records its event pairs inside the timed region: --full only
     dt = timed(step, args.steps, args.warmup, dev, dist, args.min_warm_s,
-               before=lambda: lib.ivosw_profile_span_start(),
-               after=lambda: lib.ivosw_profile_span_stop(ctypes.byref(tot), ctypes.byref(spans), ctypes.byref(cnt)))
+               before=(lambda: lib.ivosw_profile_span_start()) if args.full else None,
+               after=(lambda: lib.ivosw_profile_span_stop(ctypes.byref(tot), ctypes.byref(spans), ctypes.byref(cnt))) if args.full else None)
     assert torch.isfinite(out["s"]).all()
     scores = out["s"].clone()
     fps = args.total_batch * args.steps / dt
-    split = bool(lib.ivosw_assess_split({"bf16": L.BF16, "fp32": L.F32, "bf16x3": L.F32X3}[args.precision], args.batch, args.chunk or 0))
-    # one span per ROI chunk; with the two-stream split of the batch the two halves' spans form one group per forward pass
-    assert spans.value == (args.steps if split else args.steps * -(-args.batch // net_chunk(args))), (spans.value, args.steps)
-    conv_ms = tot.value / args.steps
-    launches = cnt.value // args.steps
-    # sustained: the same measurement over >= 1 s, whatever K was
-    sus = None
-    if args.min_warm_s <= 0:
-        sus = {"value": None, "note": "skipped (--min-warm-s 0: profiling run)"}
-    elif dt < 1.0:
-        n = int(1.2 / (dt / args.steps)) + 1
-        sdt = timed(step, n, 0, dev, dist)
-        sus = {"value": round(args.total_batch * n / sdt, 1), "steps": n, "seconds": round(sdt, 3)}
-    else:
-        sus = {"value": round(fps, 1), "steps": args.steps, "seconds": round(dt, 3)}
+    if args.full:
+        split = bool(lib.ivosw_assess_split({"bf16": L.BF16, "fp32": L.F32, "bf16x3": L.F32X3}[args.precision], args.batch, args.chunk or 0))
+        # one span per ROI chunk; with the two-stream split of the batch the two halves' spans form one group per forward pass
+        assert spans.value == (args.steps if split else args.steps * -(-args.batch // net_chunk(args))), (spans.value, args.steps)
+        conv_ms = tot.value / args.steps
+        launches = cnt.value // args.steps
+        # sustained: the same measurement over >= 1 s, whatever K was
+        sus = None
+        if args.min_warm_s <= 0:
+            sus = {"value": None, "note": "skipped (--min-warm-s 0: profiling run)"}
+        elif dt < 1.0:
+            n = int(1.2 / (dt / args.steps)) + 1
+            sdt = timed(step, n, 0, dev, dist)
+            sus = {"value": round(args.total_batch * n / sdt, 1), "steps": n, "seconds": round(sdt, 3)}
+        else:
+            sus = {"value": round(fps, 1), "steps": args.steps, "seconds": round(dt, 3)}
     if args.layer_report and rank == 0:
         L.tune_set(b"STREAMS2", 0)                  # per-launch events: one stream, or the halves' kernels time each other
         lib.ivosw_profile_start()
@@ -469,6 +486,9 @@ def bench_assess(args, rank, world, dev, dist):
         with open(args.layer_report, "w") as f:
             f.write(f"# per-layer conv timing (HIP events around every launch, 3 steps, batch {args.batch}, chunk {args.chunk or 'default'}, {args.precision})\n")
             f.write(buf.value.decode())
+    outputs = {"scores": scores.float().cpu().numpy()} if args.dump_outputs else None
+    if not args.full:
+        return fps, dt, None, {}, outputs
     flops_step = GFLOP_PER_FRAME * 1e9 * args.batch
     achieved = flops_step / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
     peak = {"bf16": PEAK_BF16_TFLOPS, "fp32": PEAK_F32_TFLOPS, "bf16x3": PEAK_BF16_TFLOPS / 3.0}[args.precision]
@@ -516,7 +536,7 @@ def bench_assess(args, rank, world, dev, dist):
         if args.precision == "bf16" and not args.no_fp32:
             extra["fp32"] = bench_fp32(args, dev, tf, tp, scores, pick)
             extra["bf16x3"] = bench_fp32(args, dev, tf, tp, scores, pick, precision="bf16x3")
-    return fps, dt, roof, extra
+    return fps, dt, roof, extra, outputs
 
 
 def net_chunk(args):
@@ -596,7 +616,7 @@ def bench_dqn(args, rank, world, dev, dist, steps, warmup):
     # dqn.collectives.p2p.error, and a process that DIES in that leg still leaves the line behind (LineGuard).  IVOSW_BENCH_P2P=0
     # (or IVOSW_P2P=0) skips the leg.
     legs = ["backend"] if (FORCE_DIST[0] or world > 1) else [None]
-    want_p2p = world > 1 and os.environ.get("IVOSW_BENCH_P2P", "1") != "0" and os.environ.get("IVOSW_P2P", "") != "0" and dev.type == "cuda"
+    want_p2p = args.full and world > 1 and os.environ.get("IVOSW_BENCH_P2P", "1") != "0" and os.environ.get("IVOSW_P2P", "") != "0" and dev.type == "cuda"
 
     def select_leg(name):
         if name is None:
@@ -689,12 +709,15 @@ def bench_dqn(args, rank, world, dev, dist, steps, warmup):
                 "vs_backend": round(leg_us["backend"]["us_per_step"] / us, 3),
                 "scaling_vs_1gpu": round(world * n_leg / d / DQN_1GPU_REF["steps_per_sec"], 3)}
     assert torch.isfinite(agent.policy_net.flat).all() and agent.optimizer.state["step"] >= steps + warmup
+    # what the timed steps left behind, before anything below trains the same agent further (--dump-outputs)
+    outputs = ({"policy_params": agent.policy_net.flat.cpu().numpy(), "target_params": agent.target_net.flat.cpu().numpy()}
+               if args.dump_outputs else None)
     sps = world * steps / dt
     per_gpu_tflops = DQN_GFLOP_PER_STEP * 1e9 * (sps / world) / 1e12
     info = {"us_per_step": round(dt / steps * 1e6, 1), "graph": (cap is not None) if launch_mode is None else launch_mode["mode"] == "graph",
             # whole-job DQN steps/s over the committed single-GPU rate (weak scaling: minibatch 128 per GPU); north_star asks >= 6 at N = 8
             "scaling_vs_1gpu": {"value": round(sps / DQN_1GPU_REF["steps_per_sec"], 3), "n_gpus": world, "reference": DQN_1GPU_REF} if world > 1 or FORCE_DIST[0] else None,
-            "launch_mode": launch_mode,
+            "launch_mode": launch_mode, "_outputs": outputs,
             "step_structure": "data-parallel: gradients -> collective -> clamp + Adam" + (" (emulated at N = 1, no collective)" if world == 1 and not FORCE_DIST[0] else " (forced at N = 1: the collective runs over one rank)" if world == 1 else "") if dp else "single GPU: fused step",
             "collective_path": (("RCCL all-reduce" if BACKEND[0] == "nccl" else "gloo all-reduce staged through host memory") if world > 1 or FORCE_DIST[0] else None),
             "collectives": (leg_us if (world > 1 or FORCE_DIST[0]) and launch_mode is None else None),
@@ -711,7 +734,7 @@ def bench_dqn(args, rank, world, dev, dist, steps, warmup):
     # Agent.update_agent(sample) per episode on COLLATED HOST batches of the replay dataset through a shuffling DataLoader
     # (train_agent.py:175-182, utils/utils_agent.py:244-252), the loss returned as a float every step — and the device loop
     # agent_business takes instead when the loader is this build's own dataset (same minibatches, bit-identical results).
-    if rank == 0 and world == 1:
+    if args.full and rank == 0 and world == 1:
         from torch.utils.data import DataLoader
         from ivos_w_amd.datasets.agent_dataset import DAVIS2017AgentTrain
         from ivos_w_amd.utils import utils_agent
@@ -745,7 +768,7 @@ def bench_dqn(args, rank, world, dev, dist, steps, warmup):
                        "loss.item() per step" % (B, len(ds)))
         info["update_agent_api"] = api
     # Agent.action latency at evaluation size (N = 1, T = 104 frames: host state -> greedy index on the host)
-    if rank == 0:
+    if args.full and rank == 0:
         state = synth.brain_inputs(1, 104, 3)[0]
         agent.cfg = AD(agent.cfg, phase="eval")
         for _ in range(5):
@@ -1012,15 +1035,24 @@ def main():
     ap.add_argument("--no-clock-probe", action="store_true", help="skip the 15 extra forward passes that measure roofline.sclk_mhz / power_w (profiling runs count passes)")
     ap.add_argument("--no-live-traffic", action="store_true", help="do not re-run the forward under rocprofv3 --pmc for roofline.traffic (the committed PMC summary is quoted instead)")
     ap.add_argument("--tower-only", action="store_true", help="(internal: the rocprofv3 --pmc sub-runs) build the inputs, run warmup + steps forward passes, print nothing else")
+    ap.add_argument("--full", action="store_true", help="measure and check everything beyond the headline figure: oracle check, roofline (span timing, "
+                    "clock / power probe, PMC traffic), sustained rate, DQN leg, fp32 / bf16x3 modes, front end, recommend_frame, J&F, seg epilogue, "
+                    "CPU baselines, the DQN data-parallel and P2P legs.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the timed path returned in its last step "
+                    "as DIR/<name>.npy (float32): `scores` of the assessment workload, `policy_params` / `target_params` of the DQN workload")
     args = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("bench.py needs an MI355X: there is no CPU fallback for the hot path")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # a plain `python bench.py --gpus N`: become the launcher — one rank per GPU under torch.distributed.run, exactly the
-        # command the driver uses (rendezvous on 127.0.0.1: the container hostname may not resolve); rank 0 prints the line
-        os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-        os.execv(sys.executable, [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
-                                  "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:])
+        # command the driver uses (rendezvous on 127.0.0.1: the container hostname may not resolve); rank 0 prints the line.
+        # The launcher is a child process and this one never touches the GPU
+        import subprocess
+        env = dict(os.environ)
+        env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+        r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
+                            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.abspath(__file__)] + sys.argv[1:], env=env)
+        raise SystemExit(r.returncode)
+    if not torch.cuda.is_available():
+        raise SystemExit("bench.py needs an MI355X: there is no CPU fallback for the hot path")
     BACKEND[0] = args.backend
     if args.force_dist:
         if args.gpus != 1:
@@ -1052,62 +1084,70 @@ def main():
     if FORCE_DIST[0]:
         line["force_dist"] = f"process group of one rank on {BACKEND[0]}: barrier + max over ranks around every timed region, all-reduce in every DQN step"
     if args.workload == "assess":
-        fps, dt, roof, extra = bench_assess(args, rank, world, dev, dist)
-        if rank == 0 and world == 1 and not args.no_live_traffic and args.batch == 256 and args.precision == "bf16" and not args.chunk:
-            live = live_traffic(roof["kernel"], roof["launches_per_step"], roof["kernel_ms_per_step"])
-            if live is not None:
-                roof.update(live)
-        dqn_sps, dqn_dt, dqn_info = bench_dqn(args, rank, world, dev, dist, args.dqn_steps, 20)
+        fps, dt, roof, extra, outputs = bench_assess(args, rank, world, dev, dist)
         line.update({"metric": "assessed_frames_per_sec", "value": round(fps, 1), "unit": "frames/s",
                      "ms_per_step": round(dt / args.steps * 1e3, 3), "dtype": args.precision,
                      "config": {"workload": (f"AssessNet.forward, batch {args.batch} x 480x854 frame+mask per GPU (BASELINE configs[1])" if args.scaling == "weak" or world == 1 else
                                              f"AssessNet.forward, batch {args.total_batch} x 480x854 frame+mask in total, sharded over the ranks (BASELINE configs[1], strong scaling)"),
                                 "batch_per_gpu": args.batch, "total_batch": args.total_batch, "chunk": args.chunk or "default", "parallelism": f"frames sharded x{world}"},
-                     "roofline": roof, "ablation_build": 0,
-                     "dqn": dict({"metric": "dqn_agent_steps_per_sec", "value": round(dqn_sps, 1), "unit": "minibatch-steps/s (all ranks)",
-                                  "transitions_per_sec": round(dqn_sps * args.minibatch, 1), "minibatch_per_gpu": args.minibatch,
-                                  "replay": args.replay, "T": 25, "steps": args.dqn_steps,
-                                  "dtype": "f32", "collective": (dqn_info.get("collective_path") + " (724 KB)") if world > 1 or FORCE_DIST[0] else None}, **dqn_info)})
-        line.update(extra)
+                     "ablation_build": 0})
+        if args.full:
+            if rank == 0 and world == 1 and not args.no_live_traffic and args.batch == 256 and args.precision == "bf16" and not args.chunk:
+                live = live_traffic(roof["kernel"], roof["launches_per_step"], roof["kernel_ms_per_step"])
+                if live is not None:
+                    roof.update(live)
+            dqn_sps, dqn_dt, dqn_info = bench_dqn(args, rank, world, dev, dist, args.dqn_steps, 20)
+            dqn_info.pop("_outputs")
+            late_p2p = dqn_info.pop("_p2p_leg")
+            line.update({"roofline": roof,
+                         "dqn": dict({"metric": "dqn_agent_steps_per_sec", "value": round(dqn_sps, 1), "unit": "minibatch-steps/s (all ranks)",
+                                      "transitions_per_sec": round(dqn_sps * args.minibatch, 1), "minibatch_per_gpu": args.minibatch,
+                                      "replay": args.replay, "T": 25, "steps": args.dqn_steps,
+                                      "dtype": "f32", "collective": (dqn_info.get("collective_path") + " (724 KB)") if world > 1 or FORCE_DIST[0] else None}, **dqn_info)})
+            line.update(extra)
     else:
         sps, dt, info = bench_dqn(args, rank, world, dev, dist, args.steps, args.warmup)
         roof = info.pop("roofline")
+        outputs = info.pop("_outputs")
+        late_p2p = info.pop("_p2p_leg")
         line.update({"metric": "dqn_agent_steps_per_sec", "value": round(sps, 1), "unit": "minibatch-steps/s",
                      "ms_per_step": round(dt / args.steps * 1e3, 4), "dtype": "f32",
                      "config": {"workload": f"Double-DQN update, replay {args.replay}, minibatch {args.minibatch}/GPU, T=25 (BASELINE configs[2]/[3])",
                                 "parallelism": f"dp{world}"},
                      "roofline": roof, "ablation_build": 0}, **info)
-    if args.workload == "assess":
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
-            line["recommend_frame"] = bench_recommend(rank, dev)
-        line["jf"] = bench_jf(rank, world, dev, dist)
-        line["seg_epilogue"] = bench_seg(rank, world, dev, dist)
-        if args.no_cpu_baseline:
-            line["jf"].pop("cpu_baseline", None)
-            line["seg_epilogue"].pop("cpu_baseline", None)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        line["cpu_baseline"] = cpu_baseline_assess() if args.workload == "assess" else cpu_baseline_dqn()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outputs, rank, world)
+    if args.full:
         if args.workload == "assess":
-            line["dqn"]["cpu_baseline"] = cpu_baseline_dqn()
-            if not FORCE_DIST[0] and not args.no_dp_critical_path:
-                line["dqn"]["dp_critical_path"] = dqn_dp_critical_path(line["dqn"]["us_per_step"])
-            if not args.no_live_traffic:
-                dt_live = dqn_live_traffic()
-                if dt_live is not None:
-                    line["dqn"]["roofline"].update(dt_live)
-    late_p2p = (line["dqn"] if args.workload == "assess" else line).pop("_p2p_leg", None)
-    if late_p2p is not None:
-        # every other number of the line exists now.  Rank 0 hands the line to a watchdog child before the leg starts: if this process
-        # dies in it (a GPU fault aborts the process from inside the HIP runtime, where no Python handler runs), the child prints the
-        # line with the failure recorded; otherwise the leg's record goes into the line and this process prints it as usual.
-        rec = (line["dqn"] if args.workload == "assess" else line)["collectives"]
-        try:
-            guard = LineGuard(line, rec) if rank == 0 else None
-        except Exception:                      # no watchdog (fork refused, ...): the leg still runs, the line is printed below as always
-            guard = None
-        rec["p2p"] = late_p2p()
-        if guard is not None:
-            guard.disarm()
+            if rank == 0 and world == 1 and not args.no_cpu_baseline:
+                line["recommend_frame"] = bench_recommend(rank, dev)
+            line["jf"] = bench_jf(rank, world, dev, dist)
+            line["seg_epilogue"] = bench_seg(rank, world, dev, dist)
+            if args.no_cpu_baseline:
+                line["jf"].pop("cpu_baseline", None)
+                line["seg_epilogue"].pop("cpu_baseline", None)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            line["cpu_baseline"] = cpu_baseline_assess() if args.workload == "assess" else cpu_baseline_dqn()
+            if args.workload == "assess":
+                line["dqn"]["cpu_baseline"] = cpu_baseline_dqn()
+                if not FORCE_DIST[0] and not args.no_dp_critical_path:
+                    line["dqn"]["dp_critical_path"] = dqn_dp_critical_path(line["dqn"]["us_per_step"])
+                if not args.no_live_traffic:
+                    dt_live = dqn_live_traffic()
+                    if dt_live is not None:
+                        line["dqn"]["roofline"].update(dt_live)
+        if late_p2p is not None:
+            # every other number of the line exists now.  Rank 0 hands the line to a watchdog child before the leg starts: if this process
+            # dies in it (a GPU fault aborts the process from inside the HIP runtime, where no Python handler runs), the child prints the
+            # line with the failure recorded; otherwise the leg's record goes into the line and this process prints it as usual.
+            rec = (line["dqn"] if args.workload == "assess" else line)["collectives"]
+            try:
+                guard = LineGuard(line, rec) if rank == 0 else None
+            except Exception:                      # no watchdog (fork refused, ...): the leg still runs, the line is printed below as always
+                guard = None
+            rec["p2p"] = late_p2p()
+            if guard is not None:
+                guard.disarm()
     if rank == 0:
         print(json.dumps(line), flush=True)
     if dist is not None:

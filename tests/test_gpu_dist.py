@@ -124,8 +124,8 @@ def test_bench_multi_rank_branch_under_torchrun(tmp_path, variant):
     ranks, rank 0 prints the line) — on this one-GPU box with both ranks on cuda:0 and the gloo rendezvous (two ranks cannot
     share a device under RCCL).  default: plain launches, the backend's all-reduce (dqn.value), then - as the LAST act of bench.py, the line
     complete and held by a watchdog child - the one-shot peer-to-peer all-reduce (IPC-mapped arenas of the two processes); p2p_leg: IVOSW_BENCH_P2P=0 opts out of it; graph_no_p2p: captured gradient graph + the collective of the backend (IVOSW_P2P=0: gloo staged through host memory).  Frames are sharded (weak scaling), the DQN leg all-reduces
-    its gradient arena every step.  plain: `python bench.py --gpus 2 ...` with NO launcher in front — bench.py re-executes itself under
-    torch.distributed.run (the driver's scaling run may be started that way) and still prints exactly one line."""
+    its gradient arena every step.  plain: `python bench.py --gpus 2 ...` with NO launcher in front — bench.py starts itself under
+    torch.distributed.run as a child process (the driver's scaling run may be started that way) and still prints exactly one line."""
     import json
     import subprocess
     import sys
@@ -148,7 +148,7 @@ def test_bench_multi_rank_branch_under_torchrun(tmp_path, variant):
         extra = ["--scaling", "strong"]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--min-warm-s", "0",
-           "--batch", "16", "--dqn-steps", "30", "--backend", "gloo", "--no-fp32"] + extra
+           "--batch", "16", "--dqn-steps", "30", "--backend", "gloo", "--no-fp32", "--full"] + extra
     if variant == "plain":
         cmd = [sys.executable] + cmd[cmd.index(os.path.join(root, "bench.py")):]
         for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
@@ -387,7 +387,7 @@ def test_bench_force_dist_runs_the_multi_rank_branch_on_rccl():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("IVOSW_FORCE_DIST", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "3", "--warmup", "1", "--batch", "32",
-                        "--min-warm-s", "0", "--dqn-steps", "60", "--no-fp32", "--no-cpu-baseline", "--no-clock-probe", "--no-live-traffic"],
+                        "--min-warm-s", "0", "--dqn-steps", "60", "--no-fp32", "--no-cpu-baseline", "--no-clock-probe", "--no-live-traffic", "--full"],
                        cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

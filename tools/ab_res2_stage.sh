@@ -3,7 +3,7 @@
 mkdir -p gpurun_out
 for r in 1 2; do
   for m in 1 0; do
-    IVOSW_TUNE_RES2_STAGE=$m python bench.py --steps 60 --warmup 5 --no-cpu-baseline --no-live-traffic --workload assess \
+    IVOSW_TUNE_RES2_STAGE=$m python bench.py --full --steps 60 --warmup 5 --no-cpu-baseline --no-live-traffic --workload assess \
         --layer-report gpurun_out/layers_stage$m.txt > gpurun_out/ab_stage${m}_r$r.log 2>&1
     python - <<PY
 import json

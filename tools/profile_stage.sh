@@ -6,8 +6,8 @@ out=gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 export IVOSW_TUNE_RES2_STAGE=1
-BENCH="python bench.py --steps 4 --warmup 1 --min-warm-s 0 --no-fp32 --no-cpu-baseline --no-live-traffic --no-clock-probe --dqn-steps 20"
-rocprofv3 --kernel-trace --stats -d $out/trace -o t -- python bench.py --steps 60 --warmup 10 --min-warm-s 1 --no-fp32 --no-cpu-baseline --no-live-traffic --no-clock-probe --dqn-steps 20 > $out/bench_trace.log 2>&1
+BENCH="python bench.py --full --steps 4 --warmup 1 --min-warm-s 0 --no-fp32 --no-cpu-baseline --no-live-traffic --no-clock-probe --dqn-steps 20"
+rocprofv3 --kernel-trace --stats -d $out/trace -o t -- python bench.py --full --steps 60 --warmup 10 --min-warm-s 1 --no-fp32 --no-cpu-baseline --no-live-traffic --no-clock-probe --dqn-steps 20 > $out/bench_trace.log 2>&1
 db=$(ls $out/trace/*.db 2>/dev/null | head -1)
 [ -n "$db" ] && python tools/rocprof_summary.py $db > $out/kernel_trace_summary.txt
 rocprofv3 --pmc FETCH_SIZE -d $out/pmc_fetch -o f --output-format csv -- $BENCH > $out/bench_fetch.log 2>&1
@@ -25,6 +25,6 @@ for r in rows:
 for k, (n, v) in agg.items():
     print(f"{k:60s} launches {n:4d}  TCP_TOTAL_CACHE_ACCESSES per launch {v / n / 1e6:8.1f} M")
 PY
-python bench.py --steps 120 --warmup 10 --no-cpu-baseline --layer-report $out/layers.txt > $out/bench.json.log 2>&1
+python bench.py --full --steps 120 --warmup 10 --no-cpu-baseline --layer-report $out/layers.txt > $out/bench.json.log 2>&1
 tail -c 600 $out/bench.json.log; head -14 $out/kernel_trace_summary.txt; tail -3 $out/pmc_hbm_traffic.txt; cat $out/pmc_tcp_accesses.txt
 rm -rf $out/trace/*.db.tmp $out/trace/*.db
