@@ -74,6 +74,18 @@ int ivosw_dqn_loss_grad(const float* policy, const float* target,
                         const float* reward_step, const float* reward_done,
                         int B, int T, float gamma, float* grads, float* loss,
                         void* ws, size_t ws_bytes, ivosw_stream_t stream);
+/* The loss option of the _ex entries.  IVOSW_DQN_LOSS_MSE is the two-term MSE above (models/agent.py:149-151), bit for bit what
+ * ivosw_dqn_loss_grad computes.  IVOSW_DQN_LOSS_HUBER generalises it term by term with torch.nn.functional.huber_loss(reduction="mean",
+ * delta): e1 = Qsa-y1, e2 = Qsa-y2, h(e) = e^2/2 if |e| < delta else delta*(|e| - delta/2); loss = mean(h(e1)) + mean(h(e2));
+ * dLoss/dQsa = (clamp(e1,-delta,delta) + clamp(e2,-delta,delta)) / B (delta -> inf: half of MSE).  The targets are unchanged.
+ * huber_delta must be finite and > 0 (for either kind); anything else, or an unknown kind, returns IVOSW_ERR_ARG.              */
+#define IVOSW_DQN_LOSS_MSE 0
+#define IVOSW_DQN_LOSS_HUBER 1
+int ivosw_dqn_loss_grad_ex(const float* policy, const float* target,
+                           const float* state, const float* new_state, const int64_t* action,
+                           const float* reward_step, const float* reward_done,
+                           int B, int T, float gamma, int loss_kind, float huber_delta, float* grads, float* loss,
+                           void* ws, size_t ws_bytes, ivosw_stream_t stream);
 /* Replaces grad.clamp_(-1,1) + optim.Adam.step (models/agent.py:157-160, :101): g = clamp(grad*grad_scale);
  * g += wd*p; m,v update; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps).  step = t >= 1.
  * grad_scale = 1/world_size after a sum all-reduce, 1 otherwise.                                 */
@@ -154,6 +166,16 @@ int ivosw_dqn_step_drawn(float* policy, const float* target, const float* old_io
                          int64_t* action_out, float* reward_step_out, float* reward_done_out, float* grads, float* loss, void* ws,
                          size_t ws_bytes, float* exp_avg, float* exp_avg_sq, void* adam_state, float lr, float beta1, float beta2,
                          float eps, float weight_decay, float clamp, float grad_scale, ivosw_stream_t stream);
+/* The same step with the loss option of ivosw_dqn_loss_grad_ex (IVOSW_DQN_LOSS_MSE: the two-term MSE of models/agent.py:149-151;
+ * IVOSW_DQN_LOSS_HUBER: loss = mean(h(e1)) + mean(h(e2)) with torch's huber_loss h and threshold huber_delta, dLoss/dQsa =
+ * (clamp(e1,-delta,delta) + clamp(e2,-delta,delta)) / B).  A bad kind or delta is refused before anything is launched.            */
+int ivosw_dqn_step_drawn_ex(float* policy, const float* target, const float* old_iou, const float* new_iou, const float* annotated,
+                            const float* next_annotated, const int64_t* action, const float* reward_step, const float* reward_done,
+                            void* draw_state, int n, int B, int T, float gamma, int loss_kind, float huber_delta, int64_t* idx_out,
+                            float* state, float* new_state, int64_t* action_out, float* reward_step_out, float* reward_done_out,
+                            float* grads, float* loss, void* ws, size_t ws_bytes, float* exp_avg, float* exp_avg_sq, void* adam_state,
+                            float lr, float beta1, float beta2, float eps, float weight_decay, float clamp, float grad_scale,
+                            ivosw_stream_t stream);
 
 /* ------------------------------------------------------------------ assessment front end ------ */
 /* Replaces (tp>0.5) + AssessNet.all2yxhw(scale=1.5) (models/assessment.py:165-166,110-161) with no D2H:

@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libivosw_hip.so")
 
 F32, BF16, F32X3 = 0, 1, 2
+DQN_LOSS_MSE, DQN_LOSS_HUBER = 0, 1                  # IVOSW_DQN_LOSS_* (include/ivosw.h)
 BRAIN_NPARAMS = 180993
 ASSESS_NTENSORS = 326
 
@@ -25,6 +26,7 @@ SIGNATURES = {
     "ivosw_brain_argmax": (_i, [_p, _i, _i, _p, _p]),
     "ivosw_dqn_ws_bytes": (_sz, [_i, _i]),
     "ivosw_dqn_loss_grad": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _p, _p, _p, _sz, _p]),
+    "ivosw_dqn_loss_grad_ex": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _i, _f, _p, _p, _p, _sz, _p]),
     "ivosw_clamp_adam": (_i, [_p, _p, _p, _p, _i, _i, _f, _f, _f, _f, _f, _f, _f, _p]),
     "ivosw_adam_state_bytes": (_sz, []),
     "ivosw_clamp_adam_dev": (_i, [_p, _p, _p, _p, _i, _p, _f, _f, _f, _f, _f, _f, _f, _p]),
@@ -43,6 +45,7 @@ SIGNATURES = {
     "ivosw_replay_draw_index": (C.c_ulonglong, [C.c_ulonglong, C.c_uint, C.c_uint, _i]),
     "ivosw_replay_draw_gather": (_i, [_p] * 8 + [_i, _i, _i] + [_p] * 6 + [_p]),
     "ivosw_dqn_step_drawn": (_i, [_p] * 10 + [_i, _i, _i, _f] + [_p] * 9 + [_sz] + [_p] * 3 + [_f] * 7 + [_p]),
+    "ivosw_dqn_step_drawn_ex": (_i, [_p] * 10 + [_i, _i, _i, _f, _i, _f] + [_p] * 9 + [_sz] + [_p] * 3 + [_f] * 7 + [_p]),
     "ivosw_mask_bbox": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "ivosw_roi_sample": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "ivosw_assess_packed_bytes": (_sz, [_i]),

@@ -11,6 +11,7 @@
 #ifdef IVOSW_PROBES
 #include "../../include/ivosw_probe.h"
 #endif
+#include <cmath>
 #include <mutex>
 
 #include "gemm_f32.h"
@@ -1118,8 +1119,8 @@ static void brain_forward_internal(const float* prm, const float* x, int N, int 
 __global__ __launch_bounds__(256) void dqn_head_kernel(const float* __restrict__ q_np, const float* __restrict__ q_nt,
                                                        const float* __restrict__ q_s, const int64_t* __restrict__ action,
                                                        const float* __restrict__ r_step, const float* __restrict__ r_done,
-                                                       int B, int T, float gamma, float* __restrict__ dq,
-                                                       float* __restrict__ loss, float* __restrict__ db4) {
+                                                       int B, int T, float gamma, int loss_kind, float delta,
+                                                       float* __restrict__ dq, float* __restrict__ loss, float* __restrict__ db4) {
     __shared__ float red[2][256];
     float l = 0.f, sdq = 0.f;
     for (int b = threadIdx.x; b < B; b += 256) {
@@ -1137,8 +1138,8 @@ __global__ __launch_bounds__(256) void dqn_head_kernel(const float* __restrict__
         a = min(max(a, 0), T - 1);
         const float qsa = q_s[(size_t)b * T + a];
         const float e1 = qsa - y1, e2 = qsa - y2;
-        l += e1 * e1 + e2 * e2;
-        const float d = (2.0f / (float)B) * (e1 + e2);
+        l += dqn_loss_terms(loss_kind, delta, e1, e2);
+        const float d = dqn_dq(loss_kind, delta, B, e1, e2);
         dq[b] = d;
         sdq += d;
     }
@@ -1288,16 +1289,31 @@ extern "C" size_t ivosw_dqn_ws_bytes(int B, int T) {
     return dqn_ws_floats(B, T) * sizeof(float);
 }
 
+// The loss option of the _ex entries: IVOSW_DQN_LOSS_MSE, or IVOSW_DQN_LOSS_HUBER with a finite delta > 0 (checked for either kind).
+static int check_dqn_loss(const char* who, int loss_kind, float delta) {
+    if (loss_kind != IVOSW_DQN_LOSS_MSE && loss_kind != IVOSW_DQN_LOSS_HUBER) {
+        set_error("%s: unknown loss kind %d (IVOSW_DQN_LOSS_MSE = 0, IVOSW_DQN_LOSS_HUBER = 1)", who, loss_kind);
+        return IVOSW_ERR_ARG;
+    }
+    if (!(std::isfinite(delta) && delta > 0.f)) {
+        set_error("%s: huber_delta must be finite and > 0, got %g", who, (double)delta);
+        return IVOSW_ERR_ARG;
+    }
+    return IVOSW_OK;
+}
+
 // draw != nullptr: the minibatch is drawn and gathered by the encoder launch (state / new_state / action / rewards are then OUTPUTS
 // of the step, written before anything reads them).  defer != nullptr: the fixed-order slab reduction is NOT launched; *defer
 // describes it and the caller folds it into clamp + Adam (ivosw_dqn_step_drawn).  Either needs the fused launch chain
 // (DQN_FUSED / DQN_GROUP / DQN_TAIL at their defaults): *folded says whether it was taken.
 static int dqn_loss_grad_impl(const float* policy, const float* target, const float* state, const float* new_state, const int64_t* action,
-                              const float* reward_step, const float* reward_done, int B, int T, float gamma, float* grads, float* loss,
-                              void* ws, size_t ws_bytes, ivosw_stream_t stream, const EncDraw* draw, ReduceGroup* defer, bool* folded) {
+                              const float* reward_step, const float* reward_done, int B, int T, float gamma, int loss_kind, float delta,
+                              float* grads, float* loss, void* ws, size_t ws_bytes, ivosw_stream_t stream, const EncDraw* draw,
+                              ReduceGroup* defer, bool* folded) {
     IVOSW_REQUIRE(policy && target && state && new_state && action && reward_step && reward_done && grads && loss && ws,
                   "null pointer");
     IVOSW_REQUIRE(B > 0 && T > 0, "B and T must be positive");
+    if (const int rc = check_dqn_loss("ivosw_dqn_loss_grad", loss_kind, delta)) return rc;
     if (ws_bytes < ivosw_dqn_ws_bytes(B, T)) {
         set_error("ivosw_dqn_loss_grad: workspace %zu < %zu", ws_bytes, ivosw_dqn_ws_bytes(B, T));
         return IVOSW_ERR_WS;
@@ -1358,7 +1374,7 @@ static int dqn_loss_grad_impl(const float* policy, const float* target, const fl
         // both nets per launch, then head + decoder backward + dL/dh in one: 4 launches, one stream, no events
         brain_forward_fused(passes, 2, T, st, draw);
         hipLaunchKernelGGL(head_fused_kernel, dim3(B), dim3(256), 0, st, policy, O_W3, O_W4, q_np, w.tgt.q, q_s, action, reward_step,
-                           reward_done, B, T, gamma, d1_s, hs_s, w.dq, w.dd1c, w.w4term, w.hcc, w.dhc, loss, grads + O_B4);
+                           reward_done, B, T, gamma, loss_kind, delta, d1_s, hs_s, w.dq, w.dd1c, w.w4term, w.hcc, w.dhc, loss, grads + O_B4);
     } else {
         fork(0);
         brain_forward_internal(policy, new_state, 2 * B, T, w.pol, st, state, B);
@@ -1367,7 +1383,7 @@ static int dqn_loss_grad_impl(const float* policy, const float* target, const fl
 
         // ---- head: Double-DQN targets, loss, dL/dQsa (agent.py:136-151)
         hipLaunchKernelGGL(dqn_head_kernel, dim3(1), dim3(256), 0, st, q_np, w.tgt.q, q_s, action, reward_step, reward_done,
-                           B, T, gamma, w.dq, loss, grads + O_B4);
+                           B, T, gamma, loss_kind, delta, w.dq, loss, grads + O_B4);
 
         // ---- decoder backward on the B rows that carry loss
         hipLaunchKernelGGL(dec_bwd_rows_kernel, dim3(B), dim3(128), 0, st, policy, w.dq, action, d1_s, hs_s, T, w.dd1c,
@@ -1531,14 +1547,22 @@ static int dqn_loss_grad_impl(const float* policy, const float* target, const fl
     return IVOSW_OK;
 }
 
+extern "C" int ivosw_dqn_loss_grad_ex(const float* policy, const float* target, const float* state,
+                                      const float* new_state, const int64_t* action, const float* reward_step,
+                                      const float* reward_done, int B, int T, float gamma, int loss_kind, float huber_delta,
+                                      float* grads, float* loss, void* ws, size_t ws_bytes, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(grads, "null pointer");
+    IVOSW_ON_DEVICE_OF(grads);
+    return dqn_loss_grad_impl(policy, target, state, new_state, action, reward_step, reward_done, B, T, gamma, loss_kind, huber_delta, grads,
+                              loss, ws, ws_bytes, stream, nullptr, nullptr, nullptr);
+}
+
 extern "C" int ivosw_dqn_loss_grad(const float* policy, const float* target, const float* state,
                                    const float* new_state, const int64_t* action, const float* reward_step,
                                    const float* reward_done, int B, int T, float gamma, float* grads, float* loss,
                                    void* ws, size_t ws_bytes, ivosw_stream_t stream) {
-    IVOSW_REQUIRE(grads, "null pointer");
-    IVOSW_ON_DEVICE_OF(grads);
-    return dqn_loss_grad_impl(policy, target, state, new_state, action, reward_step, reward_done, B, T, gamma, grads, loss, ws, ws_bytes,
-                              stream, nullptr, nullptr, nullptr);
+    return ivosw_dqn_loss_grad_ex(policy, target, state, new_state, action, reward_step, reward_done, B, T, gamma, IVOSW_DQN_LOSS_MSE, 1.0f,
+                                  grads, loss, ws, ws_bytes, stream);
 }
 
 // Clamp + Adam (clamp_adam_dev_kernel's expressions: same bits) with the step's split-K slab reduction folded in: an element of
@@ -1602,18 +1626,21 @@ extern "C" int ivosw_clamp_adam_dev(float* params, const float* grads, float* ex
                                     float beta1, float beta2, float eps, float weight_decay, float clamp, float grad_scale,
                                     ivosw_stream_t stream);
 
-extern "C" int ivosw_dqn_step_drawn(float* policy, const float* target, const float* old_iou, const float* new_iou, const float* annotated,
-                                    const float* next_annotated, const int64_t* action, const float* reward_step, const float* reward_done,
-                                    void* draw_state, int n, int B, int T, float gamma, int64_t* idx_out, float* state, float* new_state,
-                                    int64_t* action_out, float* reward_step_out, float* reward_done_out, float* grads, float* loss, void* ws,
-                                    size_t ws_bytes, float* exp_avg, float* exp_avg_sq, void* adam_state, float lr, float beta1, float beta2,
-                                    float eps, float weight_decay, float clamp, float grad_scale, ivosw_stream_t stream) {
+extern "C" int ivosw_dqn_step_drawn_ex(float* policy, const float* target, const float* old_iou, const float* new_iou, const float* annotated,
+                                       const float* next_annotated, const int64_t* action, const float* reward_step, const float* reward_done,
+                                       void* draw_state, int n, int B, int T, float gamma, int loss_kind, float huber_delta, int64_t* idx_out,
+                                       float* state, float* new_state, int64_t* action_out, float* reward_step_out, float* reward_done_out,
+                                       float* grads, float* loss, void* ws, size_t ws_bytes, float* exp_avg, float* exp_avg_sq, void* adam_state,
+                                       float lr, float beta1, float beta2, float eps, float weight_decay, float clamp, float grad_scale,
+                                       ivosw_stream_t stream) {
     IVOSW_REQUIRE(policy && target && old_iou && new_iou && annotated && next_annotated && action && reward_step && reward_done && draw_state &&
                       idx_out && state && new_state && action_out && reward_step_out && reward_done_out && grads && loss && ws && exp_avg &&
                       exp_avg_sq && adam_state,
                   "null pointer");
     IVOSW_ON_DEVICE_OF(grads);
     IVOSW_REQUIRE(n > 0 && B > 0 && T > 0, "n, B and T must be positive");
+    // refused before anything is launched (the un-folded sequence below would otherwise advance the draw counter first)
+    if (const int rc = check_dqn_loss("ivosw_dqn_step_drawn", loss_kind, huber_delta)) return rc;
     const bool aligned = ((reinterpret_cast<uintptr_t>(policy) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(exp_avg) |
                            reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0;
     bool folded = false;
@@ -1621,8 +1648,8 @@ extern "C" int ivosw_dqn_step_drawn(float* policy, const float* target, const fl
         const EncDraw dr{old_iou, new_iou, annotated, next_annotated, action, reward_step, reward_done, static_cast<DrawState*>(draw_state), n, B, T,
                          idx_out, state, new_state, action_out, reward_step_out, reward_done_out};
         ReduceGroup rg{};
-        const int rc = dqn_loss_grad_impl(policy, target, state, new_state, action_out, reward_step_out, reward_done_out, B, T, gamma, grads, loss,
-                                          ws, ws_bytes, stream, &dr, &rg, &folded);
+        const int rc = dqn_loss_grad_impl(policy, target, state, new_state, action_out, reward_step_out, reward_done_out, B, T, gamma, loss_kind,
+                                          huber_delta, grads, loss, ws, ws_bytes, stream, &dr, &rg, &folded);
         if (rc != IVOSW_OK) return rc;
         if (folded) {
             ReduceOffsets ro{};
@@ -1639,12 +1666,24 @@ extern "C" int ivosw_dqn_step_drawn(float* policy, const float* target, const fl
     int rc = ivosw_replay_draw_gather(old_iou, new_iou, annotated, next_annotated, action, reward_step, reward_done, draw_state, n, B, T, idx_out,
                                       state, new_state, action_out, reward_step_out, reward_done_out, stream);
     if (rc == IVOSW_OK)
-        rc = ivosw_dqn_loss_grad(policy, target, state, new_state, action_out, reward_step_out, reward_done_out, B, T, gamma, grads, loss, ws,
-                                 ws_bytes, stream);
+        rc = ivosw_dqn_loss_grad_ex(policy, target, state, new_state, action_out, reward_step_out, reward_done_out, B, T, gamma, loss_kind,
+                                    huber_delta, grads, loss, ws, ws_bytes, stream);
     if (rc == IVOSW_OK)
         rc = ivosw_clamp_adam_dev(policy, grads, exp_avg, exp_avg_sq, IVOSW_BRAIN_NPARAMS, adam_state, lr, beta1, beta2, eps, weight_decay, clamp,
                                   grad_scale, stream);
     return rc;
+}
+
+extern "C" int ivosw_dqn_step_drawn(float* policy, const float* target, const float* old_iou, const float* new_iou, const float* annotated,
+                                    const float* next_annotated, const int64_t* action, const float* reward_step, const float* reward_done,
+                                    void* draw_state, int n, int B, int T, float gamma, int64_t* idx_out, float* state, float* new_state,
+                                    int64_t* action_out, float* reward_step_out, float* reward_done_out, float* grads, float* loss, void* ws,
+                                    size_t ws_bytes, float* exp_avg, float* exp_avg_sq, void* adam_state, float lr, float beta1, float beta2,
+                                    float eps, float weight_decay, float clamp, float grad_scale, ivosw_stream_t stream) {
+    return ivosw_dqn_step_drawn_ex(policy, target, old_iou, new_iou, annotated, next_annotated, action, reward_step, reward_done, draw_state, n, B,
+                                   T, gamma, IVOSW_DQN_LOSS_MSE, 1.0f, idx_out, state, new_state, action_out, reward_step_out, reward_done_out,
+                                   grads, loss, ws, ws_bytes, exp_avg, exp_avg_sq, adam_state, lr, beta1, beta2, eps, weight_decay, clamp,
+                                   grad_scale, stream);
 }
 
 /* Tuning probe: subsequent fused forwards stamp s_memtime at four points of recurrence step T/2 per workgroup into ts

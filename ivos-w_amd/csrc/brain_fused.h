@@ -324,15 +324,32 @@ __global__ __launch_bounds__(256) void dec_fused_kernel(DecGroup grp, int o_w3, 
         jb.q[r0 + tid] = ((q_s[0][tid] + q_s[1][tid]) + (q_s[2][tid] + q_s[3][tid])) + b4v;
 }
 
+// The per-sample loss terms of the DQN head (IVOSW_DQN_LOSS_*, include/ivosw.h).  MSE: e1^2 + e2^2 and dL/dQsa = 2 (e1 + e2) / B, the
+// expressions models/agent.py:149-151 differentiates.  Huber with threshold delta (torch.nn.functional.huber_loss, mean): h(e) = e^2 / 2
+// for |e| < delta, else delta (|e| - delta / 2), and dL/dQsa = (clamp(e1) + clamp(e2)) / B with clamp to [-delta, delta].
+__device__ __forceinline__ float dqn_huber(float e, float delta) {
+    const float a = fabsf(e);
+    return a < delta ? 0.5f * e * e : delta * (a - 0.5f * delta);
+}
+__device__ __forceinline__ float dqn_loss_terms(int kind, float delta, float e1, float e2) {
+    if (kind == IVOSW_DQN_LOSS_HUBER) return dqn_huber(e1, delta) + dqn_huber(e2, delta);
+    return e1 * e1 + e2 * e2;
+}
+__device__ __forceinline__ float dqn_dq(int kind, float delta, int B, float e1, float e2) {
+    if (kind == IVOSW_DQN_LOSS_HUBER) return (1.0f / (float)B) * (fminf(fmaxf(e1, -delta), delta) + fminf(fmaxf(e2, -delta), delta));
+    return (2.0f / (float)B) * (e1 + e2);
+}
+
 // One workgroup per sample b: Double-DQN target (first maximum of the policy's Q over s', the target net's Q there), the two
-// MSE terms' gradient dL/dQ(s, a), then the decoder backward on row (b, a): dd1 = dq w4 . (d1 > 0), the dW4 term dq d1,
+// loss terms' gradient dL/dQ(s, a) (dqn_dq), then the decoder backward on row (b, a): dd1 = dq w4 . (d1 > 0), the dW4 term dq d1,
 // relu(h) for dW3, and dL/dh = (dd1 W3) . (h > 0) as a 128-long dot product per thread.  Block 0 also forms the batch
 // sums (loss, db4) with the reduction tree of dqn_head_kernel.
 __global__ __launch_bounds__(256) void head_fused_kernel(const float* __restrict__ prm, int o_w3, int o_w4,
                                                          const float* __restrict__ q_np, const float* __restrict__ q_nt,
                                                          const float* __restrict__ q_s, const int64_t* __restrict__ action,
                                                          const float* __restrict__ r_step, const float* __restrict__ r_done,
-                                                         int B, int T, float gamma, const float* __restrict__ d1_s,
+                                                         int B, int T, float gamma, int loss_kind, float delta,
+                                                         const float* __restrict__ d1_s,
                                                          const float* __restrict__ hs_s, float* __restrict__ dq,
                                                          float* __restrict__ dd1c, float* __restrict__ w4term,
                                                          float* __restrict__ hcc, float* __restrict__ dhc,
@@ -376,7 +393,7 @@ __global__ __launch_bounds__(256) void head_fused_kernel(const float* __restrict
             const float y1 = qn * gamma + rs * 0.1f;
             const float y2 = rd * 0.1f;
             const float e1 = qsa - y1, e2 = qsa - y2;
-            const float d = (2.0f / (float)B) * (e1 + e2);
+            const float d = dqn_dq(loss_kind, delta, B, e1, e2);
             d_sh = d;
             dq[b] = d;
         }
@@ -421,8 +438,8 @@ __global__ __launch_bounds__(256) void head_fused_kernel(const float* __restrict
         as = min(max(as, 0), T - 1);
         const float qsa = q_s[(size_t)s * T + as];
         const float e1 = qsa - y1, e2 = qsa - y2;
-        l += e1 * e1 + e2 * e2;
-        sdq += (2.0f / (float)B) * (e1 + e2);
+        l += dqn_loss_terms(loss_kind, delta, e1, e2);
+        sdq += dqn_dq(loss_kind, delta, B, e1, e2);
     }
     red[0][tid] = l;
     red[1][tid] = sdq;

@@ -63,7 +63,8 @@ DEFAULTS = dict(
     davis_interactive=dict(metric="J_AND_F", allow_repeat=1, max_nb_interactions=5, max_time_per_interaction=0, combine_th=0.4),
     agent=dict(save_result_dir="train", reward_csv="reward.csv", pretrain_csv="pretrain.csv", sample_th=0.05, optimizer="adam",
                lr=5e-6, lr_pow=0.9, momentum=0.9, weight_decay=5e-4, memory_size=100000, gamma=0.95, eps_start=0.7, eps_end=0.25,
-               eps_k=5, eps_decay=500, update_rate=0.05, train_batch_size=32),
+               eps_k=5, eps_decay=500, update_rate=0.05, train_batch_size=32,
+               loss="mse", huber_delta=1.0),   # DQN objective: the reference's two-term MSE, or "huber" (threshold huber_delta)
     synth=dict(n_sequences=3, n_frames=30, height=120, width=216, max_objects=3, baseline_runs=30),
 )
 

@@ -4,7 +4,8 @@ Same class surface as /root/reference/models/agent.py (``Brain`` :13-64, ``Agent
 arithmetic replaced by libivosw_hip.so:
 
   Brain.forward        -> ivosw_brain_forward   (batched encoder/gate GEMMs + register-resident LSTM recurrence)
-  Agent.update_agent   -> ivosw_dqn_loss_grad   (3 forwards, two-MSE Double-DQN loss, hand-derived BPTT)
+  Agent.update_agent   -> ivosw_dqn_loss_grad_ex (3 forwards, two-term Double-DQN loss: the reference's MSE, or Huber with
+                                                  cfg.agent.loss = "huber" / huber_delta; hand-derived BPTT)
                           [+ RCCL all-reduce of the flat gradient arena when torch.distributed is up]
                           ivosw_clamp_adam       (clamp [-1,1] + coupled-L2 Adam, one fused kernel)
                           ivosw_copy_f32         (hard target sync)
@@ -162,6 +163,7 @@ class Agent(nn.Module):
         a = cfg.agent
         self.memory_size = a.memory_size
         self.GAMMA = a.gamma
+        self.loss_kind, self.huber_delta = self._loss_option(a)
         self.EPS_START, self.EPS_END, self.EPS_DECAY = a.eps_start, a.eps_end, a.eps_decay
         self.steps_done = 0
         self.update_rate = a.update_rate
@@ -181,6 +183,26 @@ class Agent(nn.Module):
         self.optimizer = FusedClampAdam(self.policy_net, lr=a.lr, weight_decay=a.weight_decay)
         self._ws = L.Workspace()
         self._loss_dev = None
+
+    @staticmethod
+    def _loss_option(a):
+        """cfg.agent.loss ("mse", the reference's two-term MSE and the default; or "huber") and cfg.agent.huber_delta (1.0, torch's
+        default): read with .get, so a config without the keys trains with MSE as before; anything else is refused."""
+        kind = a.get("loss", "mse")
+        if kind not in ("mse", "huber"):
+            raise ValueError(f"agent.loss must be 'mse' or 'huber', got {kind!r}")
+        delta = a.get("huber_delta", 1.0)
+        if isinstance(delta, bool) or not isinstance(delta, (int, float)) or not 0 < delta <= float(np.finfo(np.float32).max):
+            raise ValueError(f"agent.huber_delta must be a finite number > 0, got {delta!r}")
+        return kind, float(delta)
+
+    _LOSS_KINDS = {"mse": L.DQN_LOSS_MSE, "huber": L.DQN_LOSS_HUBER}
+
+    def _loss_args(self):
+        """(loss_kind, huber_delta) as the _ex entries take them (IVOSW_DQN_LOSS_*, fp32)."""
+        if self.loss_kind not in self._LOSS_KINDS:
+            raise ValueError(f"agent.loss_kind must be 'mse' or 'huber', got {self.loss_kind!r}")
+        return self._LOSS_KINDS[self.loss_kind], float(np.float32(self.huber_delta))
 
     # ------------------------------------------------------------------ data-parallel hook
     @staticmethod
@@ -216,10 +238,10 @@ class Agent(nn.Module):
         if self._loss_dev is None or self._loss_dev.device != state.device:
             self._loss_dev = torch.zeros(1, dtype=torch.float32, device=state.device)
         pn, tn = self.policy_net, self.target_net
-        L.check(lib.ivosw_dqn_loss_grad(L.dptr(pn.flat), L.dptr(tn.flat), L.dptr(state), L.dptr(new_state),
-                                        L.dptr(action, torch.int64), L.dptr(r_step), L.dptr(r_done), B, T,
-                                        float(np.float32(self.GAMMA)), L.dptr(pn.flat_grad), L.dptr(self._loss_dev),
-                                        L.dptr(ws), nbytes, L.stream_ptr(state.device)), "dqn_loss_grad")
+        L.check(lib.ivosw_dqn_loss_grad_ex(L.dptr(pn.flat), L.dptr(tn.flat), L.dptr(state), L.dptr(new_state),
+                                           L.dptr(action, torch.int64), L.dptr(r_step), L.dptr(r_done), B, T,
+                                           float(np.float32(self.GAMMA)), *self._loss_args(), L.dptr(pn.flat_grad),
+                                           L.dptr(self._loss_dev), L.dptr(ws), nbytes, L.stream_ptr(state.device)), "dqn_loss_grad")
         return self._loss_dev
 
     def update_agent(self, sample):
@@ -353,7 +375,7 @@ class CapturedDqnStep:
         if fused:
             opt.dev_state()
         self._keys = (pn.flat.data_ptr(), tn.flat.data_ptr(), pn.flat_grad.data_ptr())
-        self._hyper = self._hyper_now()          # lr / betas / eps / weight decay / clamp / grad_scale / gamma are baked into the graph
+        self._hyper = self._hyper_now()          # lr / betas / eps / weight decay / clamp / grad_scale / gamma / loss option are baked in
         self._nbytes, self.graph, self.kernel_nodes, self._onecall_args = nbytes, None, None, None
         if not capture:                          # capture=False: the same launches, enqueued plainly by launch() (LeanDqnLoop)
             return
@@ -379,11 +401,12 @@ class CapturedDqnStep:
                     self._onecall_args = (
                         L.dptr(pn.flat), L.dptr(tn.flat), L.dptr(r.old_iou), L.dptr(r.new_iou), L.dptr(r.ann), L.dptr(r.next_ann),
                         L.dptr(r.action), L.dptr(r.reward_step), L.dptr(r.reward_done), L.dptr(self.draw, torch.uint8), r.n, B, T,
-                        float(np.float32(agent.GAMMA)), L.dptr(self.idx), L.dptr(self.state), L.dptr(self.new_state), L.dptr(self.action),
-                        L.dptr(self.r_step), L.dptr(self.r_done), L.dptr(pn.flat_grad), L.dptr(self.loss), L.dptr(self.ws), nbytes,
+                        float(np.float32(agent.GAMMA)), *agent._loss_args(), L.dptr(self.idx), L.dptr(self.state), L.dptr(self.new_state),
+                        L.dptr(self.action), L.dptr(self.r_step), L.dptr(self.r_done), L.dptr(pn.flat_grad), L.dptr(self.loss), L.dptr(self.ws),
+                        nbytes,
                         L.dptr(os_["exp_avg"]), L.dptr(os_["exp_avg_sq"]), L.dptr(os_["dev"]), g_["lr"], g_["betas"][0], g_["betas"][1],
                         g_["eps"], g_["weight_decay"], g_["clamp"], opt.grad_scale)
-                L.check(lib.ivosw_dqn_step_drawn(*self._onecall_args, st), "dqn_step_drawn")
+                L.check(lib.ivosw_dqn_step_drawn_ex(*self._onecall_args, st), "dqn_step_drawn")
                 continue
             if self.draw is not None:
                 r.sample_drawn(B, self.draw, out=dict(idx=self.idx, state=self.state, new_state=self.new_state, action=self.action,
@@ -393,21 +416,22 @@ class CapturedDqnStep:
                                                 L.dptr(r.action), L.dptr(r.reward_step), L.dptr(r.reward_done), L.dptr(self.idx), B, T,
                                                 L.dptr(self.state), L.dptr(self.new_state), L.dptr(self.action), L.dptr(self.r_step),
                                                 L.dptr(self.r_done), st), "replay_gather")
-            L.check(lib.ivosw_dqn_loss_grad(L.dptr(pn.flat), L.dptr(tn.flat), L.dptr(self.state), L.dptr(self.new_state),
-                                            L.dptr(self.action), L.dptr(self.r_step), L.dptr(self.r_done), B, T,
-                                            float(np.float32(agent.GAMMA)), L.dptr(pn.flat_grad), L.dptr(self.loss),
-                                            L.dptr(self.ws), nbytes, st), "dqn_loss_grad")
+            L.check(lib.ivosw_dqn_loss_grad_ex(L.dptr(pn.flat), L.dptr(tn.flat), L.dptr(self.state), L.dptr(self.new_state),
+                                               L.dptr(self.action), L.dptr(self.r_step), L.dptr(self.r_done), B, T,
+                                               float(np.float32(agent.GAMMA)), *agent._loss_args(), L.dptr(pn.flat_grad),
+                                               L.dptr(self.loss), L.dptr(self.ws), nbytes, st), "dqn_loss_grad")
             if fused:
                 opt.enqueue_dev_step()
 
     def _hyper_now(self):
-        """What the captured launches bake in: gamma always (the loss); the optimizer's values only when clamp + Adam are part of
-        the graph (fused) — the gradient-only graph of the data-parallel step leaves them to the eager update."""
+        """What the captured launches bake in: gamma and the loss option always (the loss); the optimizer's values only when clamp + Adam
+        are part of the graph (fused) — the gradient-only graph of the data-parallel step leaves them to the eager update."""
+        a = self.agent
         if not self.fused:
-            return (float(self.agent.GAMMA),)
-        g = self.agent.optimizer.param_groups[0]
+            return (float(a.GAMMA), a.loss_kind, float(a.huber_delta))
+        g = a.optimizer.param_groups[0]
         return (float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]), float(g["clamp"]),
-                float(self.agent.optimizer.grad_scale), float(self.agent.GAMMA))
+                float(a.optimizer.grad_scale), float(a.GAMMA), a.loss_kind, float(a.huber_delta))
 
     def launch(self):
         """Enqueue one step on the current stream; ``self.loss`` holds the device loss afterwards."""
@@ -415,8 +439,8 @@ class CapturedDqnStep:
         if self._keys != (a.policy_net.flat.data_ptr(), a.target_net.flat.data_ptr(), a.policy_net.flat_grad.data_ptr()):
             raise RuntimeError("the parameter arenas moved (.to() / re-pack) after capture: build a new CapturedDqnStep")
         if self._hyper != self._hyper_now():
-            raise RuntimeError("a hyper-parameter (lr / betas / eps / weight_decay / clamp / grad_scale / gamma) changed after capture: "
-                               "the graph replays the captured values - build a new CapturedDqnStep")
+            raise RuntimeError("a hyper-parameter (lr / betas / eps / weight_decay / clamp / grad_scale / gamma / loss kind / huber_delta) "
+                               "changed after capture: the graph replays the captured values - build a new CapturedDqnStep")
         if self.fused:
             a.optimizer.dev_state()              # resync if an eager step ran in between
         if self.graph is not None:
