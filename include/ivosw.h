@@ -99,6 +99,14 @@ size_t ivosw_adam_state_bytes(void);
 int ivosw_clamp_adam_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int n, void* adam_state,
                          float lr, float beta1, float beta2, float eps, float weight_decay, float clamp,
                          float grad_scale, ivosw_stream_t stream);
+/* cfg.agent.optimizer = "sgd": grad.clamp_(-1,1) + torch.optim.SGD(lr, momentum, dampening=0, weight_decay, nesterov).step in one
+ * kernel: g = clamp(grad*grad_scale); d = g + wd*p; buf = buf*momentum + d; d = nesterov ? d + momentum*buf : buf; p -= lr*d.
+ * momentum_buf [n] starts at zero (torch's first step, buf = d, is then the same update) and is the only state carried from one step
+ * to the next: no step counter, so a captured HIP graph replays the call as it stands.  Refused (IVOSW_ERR_ARG) before any launch:
+ * a NULL pointer, n <= 0, a negative or non-finite lr / momentum / weight_decay, nesterov other than 0 / 1, nesterov with
+ * momentum 0.  grad_scale = 1/world_size after a sum all-reduce, 1 otherwise.                                                      */
+int ivosw_clamp_sgd(float* params, const float* grads, float* momentum_buf, int n, float lr, float momentum, float weight_decay,
+                    int nesterov, float clamp, float grad_scale, ivosw_stream_t stream);
 /* Replaces target_net.load_state_dict(policy_net.state_dict()) (models/agent.py:163-165).        */
 int ivosw_copy_f32(float* dst, const float* src, size_t n, ivosw_stream_t stream);
 
@@ -130,6 +138,12 @@ int ivosw_p2p_allreduce_clamp_adam(const float* grads, float* grads_out, int n, 
                                    unsigned epoch, int timeout_ms, float* params, float* exp_avg, float* exp_avg_sq, int step,
                                    float lr, float beta1, float beta2, float eps, float weight_decay, float clamp,
                                    ivosw_stream_t stream);
+/* ivosw_p2p_allreduce followed by ivosw_clamp_sgd(grad_scale = 1/world) as TWO launches: push, then wait + rank-ordered sum + clamp
+ * + SGD.  The arguments, the timeout and the error word are those of ivosw_p2p_allreduce_clamp_adam, with momentum_buf and SGD's
+ * hyper-parameters in place of Adam's state; the hyper-parameters are refused as by ivosw_clamp_sgd, before any launch.            */
+int ivosw_p2p_allreduce_clamp_sgd(const float* grads, float* grads_out, int n, int rank, int world, void* const* arenas,
+                                  unsigned epoch, int timeout_ms, float* params, float* momentum_buf, float lr, float momentum,
+                                  float weight_decay, int nesterov, float clamp, ivosw_stream_t stream);
 
 /* ------------------------------------------------------------------ replay gather (K11) ------- */
 /* Replaces DataLoader shuffle+collate of memory_pool.csv rows (datasets/agent_dataset.py:71-115,
@@ -176,6 +190,17 @@ int ivosw_dqn_step_drawn_ex(float* policy, const float* target, const float* old
                             float* grads, float* loss, void* ws, size_t ws_bytes, float* exp_avg, float* exp_avg_sq, void* adam_state,
                             float lr, float beta1, float beta2, float eps, float weight_decay, float clamp, float grad_scale,
                             ivosw_stream_t stream);
+/* The same step with clamp + SGD (ivosw_clamp_sgd) in place of clamp + Adam: the arguments of ivosw_dqn_step_drawn_ex up to ws_bytes,
+ * then momentum_buf and SGD's hyper-parameters.  Eight launches, the last one clamp + SGD with the slab reduction folded in; parameters,
+ * momentum buffer, gradient arena, loss, the minibatch outputs and the draw counter end up bit-identical to ivosw_replay_draw_gather +
+ * ivosw_dqn_loss_grad_ex + ivosw_clamp_sgd, which the entry runs itself when a tunable takes the step off the fused chain.  A bad loss
+ * option or SGD hyper-parameter is refused before anything is launched (the draw counter does not move).                            */
+int ivosw_dqn_step_drawn_sgd(float* policy, const float* target, const float* old_iou, const float* new_iou, const float* annotated,
+                             const float* next_annotated, const int64_t* action, const float* reward_step, const float* reward_done,
+                             void* draw_state, int n, int B, int T, float gamma, int loss_kind, float huber_delta, int64_t* idx_out,
+                             float* state, float* new_state, int64_t* action_out, float* reward_step_out, float* reward_done_out,
+                             float* grads, float* loss, void* ws, size_t ws_bytes, float* momentum_buf, float lr, float momentum,
+                             float weight_decay, int nesterov, float clamp, float grad_scale, ivosw_stream_t stream);
 
 /* ------------------------------------------------------------------ assessment front end ------ */
 /* Replaces (tp>0.5) + AssessNet.all2yxhw(scale=1.5) (models/assessment.py:165-166,110-161) with no D2H:

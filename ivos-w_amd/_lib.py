@@ -30,6 +30,7 @@ SIGNATURES = {
     "ivosw_clamp_adam": (_i, [_p, _p, _p, _p, _i, _i, _f, _f, _f, _f, _f, _f, _f, _p]),
     "ivosw_adam_state_bytes": (_sz, []),
     "ivosw_clamp_adam_dev": (_i, [_p, _p, _p, _p, _i, _p, _f, _f, _f, _f, _f, _f, _f, _p]),
+    "ivosw_clamp_sgd": (_i, [_p, _p, _p, _i, _f, _f, _f, _i, _f, _f, _p]),
     "ivosw_copy_f32": (_i, [_p, _p, _sz, _p]),
     "ivosw_p2p_arena_bytes": (_sz, [_i, _sz]),
     "ivosw_p2p_handle_bytes": (_sz, []),
@@ -40,12 +41,14 @@ SIGNATURES = {
     "ivosw_p2p_error": (_i, [_p, C.POINTER(_i)]),
     "ivosw_p2p_allreduce": (_i, [_p, _p, _i, _i, _i, C.POINTER(_p), C.c_uint, _i, _p]),
     "ivosw_p2p_allreduce_clamp_adam": (_i, [_p, _p, _i, _i, _i, C.POINTER(_p), C.c_uint, _i, _p, _p, _p, _i] + [_f] * 6 + [_p]),
+    "ivosw_p2p_allreduce_clamp_sgd": (_i, [_p, _p, _i, _i, _i, C.POINTER(_p), C.c_uint, _i, _p, _p, _f, _f, _f, _i, _f, _p]),
     "ivosw_replay_gather": (_i, [_p] * 8 + [_i, _i] + [_p] * 5 + [_p]),
     "ivosw_replay_draw_state_bytes": (_sz, []),
     "ivosw_replay_draw_index": (C.c_ulonglong, [C.c_ulonglong, C.c_uint, C.c_uint, _i]),
     "ivosw_replay_draw_gather": (_i, [_p] * 8 + [_i, _i, _i] + [_p] * 6 + [_p]),
     "ivosw_dqn_step_drawn": (_i, [_p] * 10 + [_i, _i, _i, _f] + [_p] * 9 + [_sz] + [_p] * 3 + [_f] * 7 + [_p]),
     "ivosw_dqn_step_drawn_ex": (_i, [_p] * 10 + [_i, _i, _i, _f, _i, _f] + [_p] * 9 + [_sz] + [_p] * 3 + [_f] * 7 + [_p]),
+    "ivosw_dqn_step_drawn_sgd": (_i, [_p] * 10 + [_i, _i, _i, _f, _i, _f] + [_p] * 9 + [_sz] + [_p, _f, _f, _f, _i, _f, _f] + [_p]),
     "ivosw_mask_bbox": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "ivosw_roi_sample": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "ivosw_assess_packed_bytes": (_sz, [_i]),

@@ -110,7 +110,7 @@ extern "C" int ivosw_tune_set(const char* key, int value) {
 }
 
 extern "C" const char* ivosw_last_error(void) { return ivosw::g_err; }
-extern "C" int ivosw_version(void) { return 101; }
+extern "C" int ivosw_version(void) { return 102; }
 extern "C" int ivosw_ablation_build(void) { return IVOSW_ABLATION; }
 
 

@@ -1,7 +1,8 @@
-// Fused clamp + Adam over the flat parameter arena (K9), hard target sync (K10), replay gather (K11).
+// Fused clamp + Adam over the flat parameter arena (K9; clamp + SGD with momentum beside it), hard target sync (K10), replay gather (K11).
 // Reference: models/agent.py:157-165 (clamp, optim.Adam(lr, weight_decay) step, target sync),
 // datasets/agent_dataset.py:71-115 + train_agent.py:177-182 (minibatch assembly).
 #include "adam.h"
+#include "sgd.h"
 
 namespace ivosw {
 
@@ -150,9 +151,55 @@ __global__ __launch_bounds__(1024) void clamp_adam_dev_kernel(float* __restrict_
     }
 }
 
+// Clamp + SGD (clamp_sgd_elem) over the flat arena.  Nothing but the momentum buffer carries over from one step to the next, so
+// the launch is capture-safe as it stands: no step counter, no ticket.  VEC: 16 bytes per lane and array, the n % 4 tail elements
+// go to the first threads past the vector part (clamp_adam_dev_kernel's layout).
+template <bool VEC>
+__global__ __launch_bounds__(256) void clamp_sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int n,
+                                                        float lr, float mu, float wd, int nesterov, float clampv, float gscale) {
+    auto upd = [&](float gi, float pi, float& bi) { return clamp_sgd_elem(gi, pi, bi, lr, mu, wd, nesterov, clampv, gscale); };
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (VEC) {
+        const int n4 = n >> 2;
+        if (t < n4) {
+            const float4 g4 = reinterpret_cast<const float4*>(g)[t];
+            float4 p4 = reinterpret_cast<float4*>(p)[t], b4 = reinterpret_cast<float4*>(buf)[t];
+            p4.x = upd(g4.x, p4.x, b4.x); p4.y = upd(g4.y, p4.y, b4.y);
+            p4.z = upd(g4.z, p4.z, b4.z); p4.w = upd(g4.w, p4.w, b4.w);
+            reinterpret_cast<float4*>(buf)[t] = b4; reinterpret_cast<float4*>(p)[t] = p4;
+        } else if (t - n4 < (n & 3)) {
+            const int i = 4 * n4 + (t - n4);
+            float bi = buf[i];
+            p[i] = upd(g[i], p[i], bi);
+            buf[i] = bi;
+        }
+    } else if (t < n) {
+        float bi = buf[t];
+        p[t] = upd(g[t], p[t], bi);
+        buf[t] = bi;
+    }
+}
+
 }  // namespace ivosw
 
 using namespace ivosw;
+
+extern "C" int ivosw_clamp_sgd(float* params, const float* grads, float* momentum_buf, int n, float lr, float momentum, float weight_decay,
+                               int nesterov, float clamp, float grad_scale, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(params && grads && momentum_buf, "null pointer");
+    IVOSW_REQUIRE(n > 0, "n must be positive");
+    if (const int rc = check_sgd("ivosw_clamp_sgd", lr, momentum, weight_decay, nesterov)) return rc;
+    IVOSW_ON_DEVICE_OF(params);
+    const bool vec = ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(momentum_buf)) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(clamp_sgd_kernel<true>, dim3((n / 4 + 3 + 255) / 256), dim3(256), 0, as_stream(stream), params, grads, momentum_buf,
+                           n, lr, momentum, weight_decay, nesterov, clamp, grad_scale);
+    else
+        hipLaunchKernelGGL(clamp_sgd_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream), params, grads, momentum_buf, n, lr,
+                           momentum, weight_decay, nesterov, clamp, grad_scale);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
 
 extern "C" size_t ivosw_adam_state_bytes(void) { return sizeof(AdamDevState); }
 

@@ -21,6 +21,7 @@
 #include <algorithm>
 
 #include "adam.h"
+#include "sgd.h"
 
 namespace ivosw {
 
@@ -156,6 +157,35 @@ __global__ __launch_bounds__(1024) void p2p_reduce_clamp_adam_kernel(float* __re
     }
 }
 
+// The same wait + rank-ordered sum with clamp + SGD (clamp_sgd_elem) applied to the sum; the timeout / error-word contract is
+// p2p_reduce_clamp_adam_kernel's: on a TIMEOUT verdict nothing is updated.
+__global__ __launch_bounds__(1024) void p2p_reduce_clamp_sgd_kernel(float* __restrict__ gout, int n, int world, void* arena, unsigned epoch,
+                                                                    unsigned long long timeout_ticks, float* __restrict__ p,
+                                                                    float* __restrict__ buf, float lr, float mu, float wd, int nesterov,
+                                                                    float clampv, float gscale) {
+    P2pHeader* h = static_cast<P2pHeader*>(arena);
+    const int parity = epoch & 1;
+    if (!p2p_wait_all(h, world, parity, epoch, timeout_ticks)) return;
+    const int i4 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i4 >= n) return;
+    float4 s = *reinterpret_cast<const float4*>(p2p_slot(arena, world, n, parity, 0) + i4);
+    for (int r = 1; r < world; ++r) {
+        const float4 q = *reinterpret_cast<const float4*>(p2p_slot(arena, world, n, parity, r) + i4);
+        s.x += q.x; s.y += q.y; s.z += q.z; s.w += q.w;
+    }
+    const float sv[4] = {s.x, s.y, s.z, s.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int i = i4 + j;
+        if (i < n) {
+            float bi = buf[i];
+            p[i] = clamp_sgd_elem(sv[j], p[i], bi, lr, mu, wd, nesterov, clampv, gscale);
+            buf[i] = bi;
+            if (gout) gout[i] = sv[j];
+        }
+    }
+}
+
 }  // namespace ivosw
 
 using namespace ivosw;
@@ -184,6 +214,32 @@ extern "C" int ivosw_p2p_allreduce_clamp_adam(const float* grads, float* grads_o
     hipLaunchKernelGGL(p2p_reduce_clamp_adam_kernel, dim3(nblk), dim3(1024), 0, st, grads_out, n, world, arenas[rank], epoch,
                        (unsigned long long)std::max(1, timeout_ms) * 100000ull, params, exp_avg, exp_avg_sq, step_size, bc2_sqrt, beta1, beta2,
                        eps, weight_decay, clamp, 1.0f / (float)world);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+// ivosw_p2p_allreduce + ivosw_clamp_sgd(..., grad_scale = 1/world) as two launches: push, then wait + sum + clamp + SGD.  grads_out
+// (may be NULL, may alias grads) receives the summed gradient.
+extern "C" int ivosw_p2p_allreduce_clamp_sgd(const float* grads, float* grads_out, int n, int rank, int world, void* const* arenas,
+                                             unsigned epoch, int timeout_ms, float* params, float* momentum_buf, float lr, float momentum,
+                                             float weight_decay, int nesterov, float clamp, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(grads && arenas && params && momentum_buf, "null pointer");
+    IVOSW_REQUIRE(n > 0 && world > 0 && world <= P2P_MAX_WORLD && rank >= 0 && rank < world && epoch > 0, "bad rank / world / epoch");
+    IVOSW_REQUIRE(epoch < (1u << 30), "epoch must stay below 2^30: the verdict word packs (epoch << 2) | decision");
+    if (const int rc = check_sgd("ivosw_p2p_allreduce_clamp_sgd", lr, momentum, weight_decay, nesterov)) return rc;
+    IVOSW_ON_DEVICE_OF(params);
+    IVOSW_REQUIRE((reinterpret_cast<uintptr_t>(grads) & 15) == 0, "the gradient buffer must be 16-byte aligned");
+    P2pPeers peers{};
+    for (int r = 0; r < world; ++r) {
+        IVOSW_REQUIRE(arenas[r], "null arena");
+        peers.arena[r] = arenas[r];
+    }
+    hipStream_t st = as_stream(stream);
+    const int nblk = ((n + 3) / 4 + 1023) / 1024;
+    hipLaunchKernelGGL(p2p_push_kernel, dim3(nblk), dim3(1024), 0, st, grads, n, rank, world, peers, epoch);
+    hipLaunchKernelGGL(p2p_reduce_clamp_sgd_kernel, dim3(nblk), dim3(1024), 0, st, grads_out, n, world, arenas[rank], epoch,
+                       (unsigned long long)std::max(1, timeout_ms) * 100000ull, params, momentum_buf, lr, momentum, weight_decay, nesterov, clamp,
+                       1.0f / (float)world);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }

@@ -64,7 +64,8 @@ DEFAULTS = dict(
     agent=dict(save_result_dir="train", reward_csv="reward.csv", pretrain_csv="pretrain.csv", sample_th=0.05, optimizer="adam",
                lr=5e-6, lr_pow=0.9, momentum=0.9, weight_decay=5e-4, memory_size=100000, gamma=0.95, eps_start=0.7, eps_end=0.25,
                eps_k=5, eps_decay=500, update_rate=0.05, train_batch_size=32,
-               loss="mse", huber_delta=1.0),   # DQN objective: the reference's two-term MSE, or "huber" (threshold huber_delta)
+               loss="mse", huber_delta=1.0,    # DQN objective: the reference's two-term MSE, or "huber" (threshold huber_delta)
+               nesterov=False),   # update: optimizer "adam" (the reference's) or "sgd" (clamp + SGD with momentum, nesterov); lr_pow is unread
     synth=dict(n_sequences=3, n_frames=30, height=120, width=216, max_objects=3, baseline_runs=30),
 )
 

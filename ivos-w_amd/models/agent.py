@@ -7,13 +7,14 @@ arithmetic replaced by libivosw_hip.so:
   Agent.update_agent   -> ivosw_dqn_loss_grad_ex (3 forwards, two-term Double-DQN loss: the reference's MSE, or Huber with
                                                   cfg.agent.loss = "huber" / huber_delta; hand-derived BPTT)
                           [+ RCCL all-reduce of the flat gradient arena when torch.distributed is up]
-                          ivosw_clamp_adam       (clamp [-1,1] + coupled-L2 Adam, one fused kernel)
+                          ivosw_clamp_adam       (clamp [-1,1] + coupled-L2 Adam, one fused kernel; cfg.agent.optimizer = "sgd":
+                          ivosw_clamp_sgd         clamp + SGD with momentum / nesterov, cfg.agent.momentum / nesterov)
                           ivosw_copy_f32         (hard target sync)
   Agent.action         -> ivosw_brain_forward + ivosw_brain_argmax (first max, like numpy)
 
 torch modules (nn.Linear / nn.LSTMCell) are used only as parameter containers so that ``state_dict()`` keys,
 shapes and default initialisation are the reference's; their ``forward`` is never called.  All ten tensors are
-views into one flat fp32 arena (``Brain.flat``), which is what the C ABI, Adam and the all-reduce operate on.
+views into one flat fp32 arena (``Brain.flat``), which is what the C ABI, the optimizer and the all-reduce operate on.
 """
 import math
 import random
@@ -89,7 +90,14 @@ class Brain(nn.Module):
 
 
 class FusedClampAdam:
-    """``optim.Adam(params, lr, weight_decay)`` + the reference's grad clamp, as one kernel over the flat arena."""
+    """``optim.Adam(params, lr, weight_decay)`` + the reference's grad clamp, as one kernel over the flat arena.
+
+    The interface CapturedDqnStep and parallel.py use, shared with FusedClampSGD: ``kind``, ``step``, ``dev_state`` (the device state a
+    captured step needs, created and synchronised), ``enqueue_dev_step`` (the capture-safe update on the current stream), ``note_dev_steps``
+    (the host counter after n such updates), ``hyper`` (what a capture bakes in) and ``onecall_tail`` (the one-call step's entry and the
+    arguments after its ws_bytes)."""
+
+    kind = "adam"
 
     def __init__(self, brain, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8, clamp=1.0):
         self.brain = brain
@@ -143,6 +151,15 @@ class FusedClampAdam:
         self.state["step"] += n
         self.state["dev_step"] = self.state["step"]
 
+    def hyper(self):
+        g = self.param_groups[0]
+        return (self.kind, float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]), float(g["clamp"]))
+
+    def onecall_tail(self):
+        g, s = self.param_groups[0], self.state
+        return "ivosw_dqn_step_drawn_ex", (L.dptr(s["exp_avg"]), L.dptr(s["exp_avg_sq"]), L.dptr(s["dev"]), g["lr"], g["betas"][0],
+                                           g["betas"][1], g["eps"], g["weight_decay"], g["clamp"], self.grad_scale)
+
     def state_dict(self):
         self._ensure()
         return dict(state={k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.state.items() if not k.startswith("dev")},
@@ -153,6 +170,72 @@ class FusedClampAdam:
         self.state["step"] = int(sd["state"]["step"])
         self.state["exp_avg"].copy_(sd["state"]["exp_avg"])
         self.state["exp_avg_sq"].copy_(sd["state"]["exp_avg_sq"])
+
+
+class FusedClampSGD:
+    """``optim.SGD(params, lr, momentum, dampening=0, weight_decay, nesterov)`` + the reference's grad clamp, as one kernel over the flat
+    arena (ivosw_clamp_sgd).  The momentum buffer starts at zero, which makes torch's first step (buffer = d) the ordinary update, so
+    nothing but the buffer carries over between steps: a captured step replays the update as it stands.  ``state["step"]`` only counts
+    the updates on the host.  Same interface as FusedClampAdam."""
+
+    kind = "sgd"
+
+    def __init__(self, brain, lr, weight_decay, momentum=0.0, nesterov=False, clamp=1.0):
+        self.brain = brain
+        self.param_groups = [dict(params=list(brain.parameters()), lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay,
+                                  nesterov=nesterov, clamp=clamp)]
+        self.state = dict(step=0, momentum_buffer=None)
+        self.grad_scale = 1.0
+
+    def _ensure(self):
+        flat = self.brain.flat
+        if self.state["momentum_buffer"] is None or self.state["momentum_buffer"].device != flat.device:
+            self.state["momentum_buffer"] = torch.zeros_like(flat)
+
+    def zero_grad(self, set_to_none=False):
+        self.brain.flat_grad.zero_()
+
+    def step(self):
+        self._ensure()
+        self.state["step"] += 1
+        self.enqueue_dev_step()
+
+    def dev_state(self):
+        """The device state of the update: the momentum buffer (there is no step counter to synchronise)."""
+        self._ensure()
+        return self.state["momentum_buffer"]
+
+    def enqueue_dev_step(self):
+        """ivosw_clamp_sgd on the current stream (inside a capture: recorded as it is)."""
+        g, b = self.param_groups[0], self.brain
+        L.check(L.lib().ivosw_clamp_sgd(L.dptr(b.flat), L.dptr(b.flat_grad), L.dptr(self.state["momentum_buffer"]), L.BRAIN_NPARAMS, g["lr"],
+                                        g["momentum"], g["weight_decay"], int(g["nesterov"]), g["clamp"], self.grad_scale,
+                                        L.stream_ptr(b.flat.device)), "clamp_sgd")
+
+    def note_dev_steps(self, n=1):
+        self.state["step"] += n
+
+    def hyper(self):
+        g = self.param_groups[0]
+        return (self.kind, float(g["lr"]), float(g["momentum"]), bool(g["nesterov"]), float(g["weight_decay"]), float(g["clamp"]))
+
+    def onecall_tail(self):
+        g = self.param_groups[0]
+        return "ivosw_dqn_step_drawn_sgd", (L.dptr(self.state["momentum_buffer"]), g["lr"], g["momentum"], g["weight_decay"],
+                                            int(g["nesterov"]), g["clamp"], self.grad_scale)
+
+    def state_dict(self):
+        self._ensure()
+        return dict(state=dict(step=self.state["step"], momentum_buffer=self.state["momentum_buffer"].clone()),
+                    param_groups=[{k: v for k, v in self.param_groups[0].items() if k != "params"}])
+
+    def load_state_dict(self, sd):
+        st = sd["state"]
+        if "momentum_buffer" not in st or "exp_avg" in st:
+            raise ValueError("FusedClampSGD.load_state_dict: not an SGD state dict (an Adam one has exp_avg / exp_avg_sq)")
+        self._ensure()
+        self.state["step"] = int(st["step"])
+        self.state["momentum_buffer"].copy_(st["momentum_buffer"])
 
 
 class Agent(nn.Module):
@@ -180,7 +263,12 @@ class Agent(nn.Module):
         self.loss_position = 0
         self.loss_capacity = 32
         self.loss_avg = 0
-        self.optimizer = FusedClampAdam(self.policy_net, lr=a.lr, weight_decay=a.weight_decay)
+        self.optimizer_kind, self.momentum, self.nesterov = self._optimizer_option(a)
+        if self.optimizer_kind == "sgd":
+            self.optimizer = FusedClampSGD(self.policy_net, lr=a.lr, weight_decay=a.weight_decay, momentum=self.momentum,
+                                           nesterov=self.nesterov)
+        else:
+            self.optimizer = FusedClampAdam(self.policy_net, lr=a.lr, weight_decay=a.weight_decay)
         self._ws = L.Workspace()
         self._loss_dev = None
 
@@ -197,6 +285,24 @@ class Agent(nn.Module):
         return kind, float(delta)
 
     _LOSS_KINDS = {"mse": L.DQN_LOSS_MSE, "huber": L.DQN_LOSS_HUBER}
+
+    @staticmethod
+    def _optimizer_option(a):
+        """cfg.agent.optimizer ("adam", the reference's and the default; or "sgd"), cfg.agent.momentum (0.0, torch's default; the CLI and
+        YAML defaults give 0.9) and cfg.agent.nesterov (False): read with .get, so a config without the keys trains with Adam as before,
+        which ignores momentum and nesterov; anything else is refused."""
+        kind = a.get("optimizer", "adam")
+        if kind not in ("adam", "sgd"):
+            raise ValueError(f"agent.optimizer must be 'adam' or 'sgd', got {kind!r}")
+        momentum = a.get("momentum", 0.0)
+        if isinstance(momentum, bool) or not isinstance(momentum, (int, float)) or not 0 <= momentum <= float(np.finfo(np.float32).max):
+            raise ValueError(f"agent.momentum must be a finite number >= 0, got {momentum!r}")
+        nesterov = a.get("nesterov", False)
+        if not isinstance(nesterov, bool):
+            raise ValueError(f"agent.nesterov must be true or false, got {nesterov!r}")
+        if kind == "sgd" and nesterov and momentum == 0:
+            raise ValueError("agent.nesterov needs agent.momentum > 0 (as torch.optim.SGD)")
+        return kind, float(momentum), nesterov
 
     def _loss_args(self):
         """(loss_kind, huber_delta) as the _ex entries take them (IVOSW_DQN_LOSS_*, fp32)."""
@@ -258,9 +364,9 @@ class Agent(nn.Module):
         return self.loss[(self.loss_position - 1) % self.loss_capacity]
 
     def apply_gradients(self, check_every=1):
-        """clamp + Adam on policy_net.flat_grad; with torch.distributed initialised: synchronous data parallel — the gradients are
-        summed over the ranks first (RCCL over xGMI, or the opt-in one-shot P2P all-reduce fused with the update) and averaged
-        inside the kernel, so the clamp sees the averaged gradient as a single large batch would."""
+        """clamp + Adam (or clamp + SGD) on policy_net.flat_grad; with torch.distributed initialised: synchronous data parallel — the
+        gradients are summed over the ranks first (RCCL over xGMI, or the opt-in one-shot P2P all-reduce fused with the update) and
+        averaged inside the kernel, so the clamp sees the averaged gradient as a single large batch would."""
         dist, world = self._world()
         if world > 1 or dist is not None:           # an initialised process group of one rank (IVOSW_FORCE_DIST=1) takes the same path
             from .. import parallel
@@ -341,9 +447,9 @@ class CapturedDqnStep:
     """One Double-DQN training step as ONE HIP-graph launch (models/agent.py:128-160 minus the host coin flip):
 
         replay gather (minibatch indices read from ``self.idx`` on the device) -> 3 forwards + loss + BPTT
-        -> [fused=True: clamp + Adam with the step counter on the device]
+        -> [fused=True: the update — clamp + Adam with the step counter on the device, or clamp + SGD]
 
-    With fused=False the graph stops at the gradients, for the data-parallel step (all-reduce, then the eager clamp+Adam).
+    With fused=False the graph stops at the gradients, for the data-parallel step (all-reduce, then the eager update).
     Replaces ~40 host launches (170-250 us of enqueue per step) by one hipGraphLaunch.  The arithmetic is the eager path's:
     the same entry points are recorded, so results are bit-identical to ``Agent.loss_and_grads`` + ``optimizer.step``."""
 
@@ -359,7 +465,7 @@ class CapturedDqnStep:
         self.agent, self.replay, self.B, self.fused, self.steps = agent, replay, B, fused, int(steps)
         self.draw = draw_state if draw_state is not None else (replay.draw_state(draw_seed) if draw_seed is not None else None)
         if self.steps > 1 and (self.draw is None or not fused):
-            raise ValueError("a multi-step graph needs the in-graph minibatch draw and the fused clamp + Adam")
+            raise ValueError("a multi-step graph needs the in-graph minibatch draw and the fused update")
         T = replay.T
         lib = L.lib()
         self.idx = torch.zeros(B, dtype=torch.int64, device=dev)
@@ -375,8 +481,8 @@ class CapturedDqnStep:
         if fused:
             opt.dev_state()
         self._keys = (pn.flat.data_ptr(), tn.flat.data_ptr(), pn.flat_grad.data_ptr())
-        self._hyper = self._hyper_now()          # lr / betas / eps / weight decay / clamp / grad_scale / gamma / loss option are baked in
-        self._nbytes, self.graph, self.kernel_nodes, self._onecall_args = nbytes, None, None, None
+        self._hyper = self._hyper_now()          # the optimizer's kind and values / grad_scale / gamma / loss option are baked in
+        self._nbytes, self.graph, self.kernel_nodes, self._onecall_args, self._onecall_entry = nbytes, None, None, None, None
         if not capture:                          # capture=False: the same launches, enqueued plainly by launch() (LeanDqnLoop)
             return
         torch.cuda.synchronize(dev)
@@ -395,18 +501,16 @@ class CapturedDqnStep:
             st = L.stream_ptr(dev)
             r = replay
             if self.draw is not None and fused:
-                # draw + gather folded into the encoder launch, the slab reduction into clamp + Adam: 8 kernel nodes per step instead of 10
+                # draw + gather folded into the encoder launch, the slab reduction into the update: 8 kernel nodes per step instead of 10
                 if self._onecall_args is None:   # every pointer and scalar is fixed for the life of the object (launch() checks): built once
-                    g_, os_ = opt.param_groups[0], opt.state
+                    self._onecall_entry, tail = opt.onecall_tail()
                     self._onecall_args = (
                         L.dptr(pn.flat), L.dptr(tn.flat), L.dptr(r.old_iou), L.dptr(r.new_iou), L.dptr(r.ann), L.dptr(r.next_ann),
                         L.dptr(r.action), L.dptr(r.reward_step), L.dptr(r.reward_done), L.dptr(self.draw, torch.uint8), r.n, B, T,
                         float(np.float32(agent.GAMMA)), *agent._loss_args(), L.dptr(self.idx), L.dptr(self.state), L.dptr(self.new_state),
                         L.dptr(self.action), L.dptr(self.r_step), L.dptr(self.r_done), L.dptr(pn.flat_grad), L.dptr(self.loss), L.dptr(self.ws),
-                        nbytes,
-                        L.dptr(os_["exp_avg"]), L.dptr(os_["exp_avg_sq"]), L.dptr(os_["dev"]), g_["lr"], g_["betas"][0], g_["betas"][1],
-                        g_["eps"], g_["weight_decay"], g_["clamp"], opt.grad_scale)
-                L.check(lib.ivosw_dqn_step_drawn_ex(*self._onecall_args, st), "dqn_step_drawn")
+                        nbytes) + tail
+                L.check(getattr(lib, self._onecall_entry)(*self._onecall_args, st), "dqn_step_drawn")
                 continue
             if self.draw is not None:
                 r.sample_drawn(B, self.draw, out=dict(idx=self.idx, state=self.state, new_state=self.new_state, action=self.action,
@@ -424,14 +528,12 @@ class CapturedDqnStep:
                 opt.enqueue_dev_step()
 
     def _hyper_now(self):
-        """What the captured launches bake in: gamma and the loss option always (the loss); the optimizer's values only when clamp + Adam
-        are part of the graph (fused) — the gradient-only graph of the data-parallel step leaves them to the eager update."""
+        """What the captured launches bake in: gamma and the loss option always (the loss); the optimizer's kind and values only when the
+        update is part of the graph (fused) — the gradient-only graph of the data-parallel step leaves them to the eager update."""
         a = self.agent
         if not self.fused:
             return (float(a.GAMMA), a.loss_kind, float(a.huber_delta))
-        g = a.optimizer.param_groups[0]
-        return (float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]), float(g["clamp"]),
-                float(a.optimizer.grad_scale), float(a.GAMMA), a.loss_kind, float(a.huber_delta))
+        return a.optimizer.hyper() + (float(a.optimizer.grad_scale), float(a.GAMMA), a.loss_kind, float(a.huber_delta))
 
     def launch(self):
         """Enqueue one step on the current stream; ``self.loss`` holds the device loss afterwards."""
@@ -439,8 +541,9 @@ class CapturedDqnStep:
         if self._keys != (a.policy_net.flat.data_ptr(), a.target_net.flat.data_ptr(), a.policy_net.flat_grad.data_ptr()):
             raise RuntimeError("the parameter arenas moved (.to() / re-pack) after capture: build a new CapturedDqnStep")
         if self._hyper != self._hyper_now():
-            raise RuntimeError("a hyper-parameter (lr / betas / eps / weight_decay / clamp / grad_scale / gamma / loss kind / huber_delta) "
-                               "changed after capture: the graph replays the captured values - build a new CapturedDqnStep")
+            raise RuntimeError("a hyper-parameter (optimizer kind / lr / betas / eps / momentum / nesterov / weight_decay / clamp / grad_scale / "
+                               "gamma / loss kind / huber_delta) changed after capture: the graph replays the captured values - build a new "
+                               "CapturedDqnStep")
         if self.fused:
             a.optimizer.dev_state()              # resync if an eager step ran in between
         if self.graph is not None:

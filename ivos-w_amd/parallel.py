@@ -5,7 +5,7 @@ on CPU for tests).  Two shapes of work:
     per-frame scores (a few hundred floats) are all-gathered at the end.
   * DQN — synchronous data parallel: every rank samples its own minibatch (rank-offset RNG stream), gradients are
     summed with ONE all-reduce of the flat 180 993-float arena (724 KB), scaled by 1/world inside the fused
-    clamp+Adam kernel (so the clamp sees the averaged gradient), and the target-sync coin comes from a
+    clamp + Adam (or clamp + SGD) kernel (so the clamp sees the averaged gradient), and the target-sync coin comes from a
     shared-seed host RNG so replicas stay bit-identical.
 """
 import os
@@ -182,14 +182,23 @@ class P2PAllReduce:
         return flat
 
     def fused_step(self, brain, optimizer):
-        """All-reduce of ``brain.flat_grad`` + clamp + Adam in TWO launches (push; wait + rank-ordered sum + clamp + Adam):
-        ``ivosw_p2p_allreduce_clamp_adam``.  flat_grad is left holding the SUM over ranks; the optimizer's step counter advances."""
+        """All-reduce of ``brain.flat_grad`` + the update in TWO launches (push; wait + rank-ordered sum + clamp + Adam or SGD):
+        ``ivosw_p2p_allreduce_clamp_adam`` / ``ivosw_p2p_allreduce_clamp_sgd`` by ``optimizer.kind``.  flat_grad is left holding the SUM
+        over ranks; the optimizer's step counter advances."""
         from . import _lib as L
+        if optimizer.kind not in ("adam", "sgd"):
+            raise ValueError(f"P2PAllReduce.fused_step: no fused form for optimizer kind {optimizer.kind!r}")
         optimizer._ensure()
         g = optimizer.param_groups[0]
         optimizer.state["step"] += 1
         self.epoch += 1
         flat, grad = brain.flat, brain.flat_grad
+        if optimizer.kind == "sgd":
+            L.check(L.lib().ivosw_p2p_allreduce_clamp_sgd(
+                L.dptr(grad), L.dptr(grad), self.n, self.rank, self.world, self.table, self.epoch, self.timeout_ms, L.dptr(flat),
+                L.dptr(optimizer.state["momentum_buffer"]), g["lr"], g["momentum"], g["weight_decay"], int(g["nesterov"]), g["clamp"],
+                L.stream_ptr(flat.device)), "p2p_allreduce_clamp_sgd")
+            return
         L.check(L.lib().ivosw_p2p_allreduce_clamp_adam(
             L.dptr(grad), L.dptr(grad), self.n, self.rank, self.world, self.table, self.epoch, self.timeout_ms, L.dptr(flat),
             L.dptr(optimizer.state["exp_avg"]), L.dptr(optimizer.state["exp_avg_sq"]), optimizer.state["step"], g["lr"], g["betas"][0],
@@ -296,8 +305,9 @@ def collective_path(flat_grad):
 
 def data_parallel_step(brain, optimizer, check_every=1):
     """The exchange step of synchronous data parallelism + the optimizer step, on every rank: gradients summed over ranks, scaled by
-    1/world INSIDE the clamp + Adam kernel (the clamp of models/agent.py:157-159 sees the averaged gradient, as one large batch
-    would).  P2P path: two launches (push | wait + sum + clamp + Adam); backend path: all-reduce, then the fused clamp + Adam."""
+    1/world INSIDE the clamp + Adam (or clamp + SGD) kernel (the clamp of models/agent.py:157-159 sees the averaged gradient, as one
+    large batch would).  P2P path: two launches (push | wait + sum + clamp + update, by ``optimizer.kind``); backend path: all-reduce,
+    then ``optimizer.step`` with grad_scale = 1/world."""
     w = world()
     if w < 2:
         optimizer.grad_scale = allreduce_grads(brain.flat_grad, check_every) if collective_active() else 1.0
