@@ -107,6 +107,24 @@ int ivosw_clamp_adam_dev(float* params, const float* grads, float* exp_avg, floa
  * momentum 0.  grad_scale = 1/world_size after a sum all-reduce, 1 otherwise.                                                      */
 int ivosw_clamp_sgd(float* params, const float* grads, float* momentum_buf, int n, float lr, float momentum, float weight_decay,
                     int nesterov, float clamp, float grad_scale, ivosw_stream_t stream);
+/* cfg.agent.lr_schedule = "poly": the learning rate of each update comes from a float32 table on the device,
+ *   lr_table[k] = float32(lr * (1 - min(k, N) / N) ** lr_pow),  k = 0 .. N = lr_steps   (torch's PolynomialLR closed form),
+ * computed once by the caller.  The update that follows k earlier ones (the device step counter before it advances) reads
+ * lr_table[min(k, N)]: the float the eager entries (ivosw_clamp_adam, ivosw_clamp_sgd, the P2P forms) get as lr at host step k, so the
+ * paths agree bit for bit.  The _sched entries take (lr_table, lr_steps) in place of lr; each refuses (IVOSW_ERR_ARG, before any launch)
+ * a NULL pointer or table, lr_steps < 1, and the bad hyper-parameters of its constant-lr form.
+ * ivosw_clamp_adam_dev_sched: ivosw_clamp_adam_dev on the schedule (the same AdamDevState and ticket; betas outside [0, 1) and a
+ * negative or non-finite eps / weight_decay are refused).                                                                              */
+int ivosw_clamp_adam_dev_sched(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int n, void* adam_state,
+                               const float* lr_table, int lr_steps, float beta1, float beta2, float eps, float weight_decay, float clamp,
+                               float grad_scale, ivosw_stream_t stream);
+/* ivosw_clamp_sgd on the schedule.  The constant-lr form keeps no step counter; this one keeps it in sgd_state (ivosw_sgd_state_bytes()
+ * bytes, zeroed before the first step; the int32 at byte 0 is the counter, a caller resumes from host step k by writing k there),
+ * advanced by the last workgroup of each launch so that a captured graph replays the schedule.                                        */
+size_t ivosw_sgd_state_bytes(void);
+int ivosw_clamp_sgd_dev_sched(float* params, const float* grads, float* momentum_buf, int n, void* sgd_state, const float* lr_table,
+                              int lr_steps, float momentum, float weight_decay, int nesterov, float clamp, float grad_scale,
+                              ivosw_stream_t stream);
 /* Replaces target_net.load_state_dict(policy_net.state_dict()) (models/agent.py:163-165).        */
 int ivosw_copy_f32(float* dst, const float* src, size_t n, ivosw_stream_t stream);
 
@@ -201,6 +219,24 @@ int ivosw_dqn_step_drawn_sgd(float* policy, const float* target, const float* ol
                              float* state, float* new_state, int64_t* action_out, float* reward_step_out, float* reward_done_out,
                              float* grads, float* loss, void* ws, size_t ws_bytes, float* momentum_buf, float lr, float momentum,
                              float weight_decay, int nesterov, float clamp, float grad_scale, ivosw_stream_t stream);
+/* The one-call steps on the poly schedule (see ivosw_clamp_adam_dev_sched): ivosw_dqn_step_drawn_ex / ivosw_dqn_step_drawn_sgd with
+ * (lr_table, lr_steps) in place of lr (and sgd_state after momentum_buf).  The same eight launches, the last one the scheduled clamp +
+ * Adam / SGD with the slab reduction folded in; bit-identical to ivosw_replay_draw_gather + ivosw_dqn_loss_grad_ex +
+ * ivosw_clamp_{adam,sgd}_dev_sched, which they run themselves off the fused chain.                                                    */
+int ivosw_dqn_step_drawn_sched(float* policy, const float* target, const float* old_iou, const float* new_iou, const float* annotated,
+                               const float* next_annotated, const int64_t* action, const float* reward_step, const float* reward_done,
+                               void* draw_state, int n, int B, int T, float gamma, int loss_kind, float huber_delta, int64_t* idx_out,
+                               float* state, float* new_state, int64_t* action_out, float* reward_step_out, float* reward_done_out,
+                               float* grads, float* loss, void* ws, size_t ws_bytes, float* exp_avg, float* exp_avg_sq, void* adam_state,
+                               const float* lr_table, int lr_steps, float beta1, float beta2, float eps, float weight_decay, float clamp,
+                               float grad_scale, ivosw_stream_t stream);
+int ivosw_dqn_step_drawn_sgd_sched(float* policy, const float* target, const float* old_iou, const float* new_iou, const float* annotated,
+                                   const float* next_annotated, const int64_t* action, const float* reward_step, const float* reward_done,
+                                   void* draw_state, int n, int B, int T, float gamma, int loss_kind, float huber_delta, int64_t* idx_out,
+                                   float* state, float* new_state, int64_t* action_out, float* reward_step_out, float* reward_done_out,
+                                   float* grads, float* loss, void* ws, size_t ws_bytes, float* momentum_buf, void* sgd_state,
+                                   const float* lr_table, int lr_steps, float momentum, float weight_decay, int nesterov, float clamp,
+                                   float grad_scale, ivosw_stream_t stream);
 
 /* ------------------------------------------------------------------ assessment front end ------ */
 /* Replaces (tp>0.5) + AssessNet.all2yxhw(scale=1.5) (models/assessment.py:165-166,110-161) with no D2H:

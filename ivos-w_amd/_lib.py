@@ -31,6 +31,9 @@ SIGNATURES = {
     "ivosw_adam_state_bytes": (_sz, []),
     "ivosw_clamp_adam_dev": (_i, [_p, _p, _p, _p, _i, _p, _f, _f, _f, _f, _f, _f, _f, _p]),
     "ivosw_clamp_sgd": (_i, [_p, _p, _p, _i, _f, _f, _f, _i, _f, _f, _p]),
+    "ivosw_clamp_adam_dev_sched": (_i, [_p, _p, _p, _p, _i, _p, _p, _i, _f, _f, _f, _f, _f, _f, _p]),
+    "ivosw_sgd_state_bytes": (_sz, []),
+    "ivosw_clamp_sgd_dev_sched": (_i, [_p, _p, _p, _i, _p, _p, _i, _f, _f, _i, _f, _f, _p]),
     "ivosw_copy_f32": (_i, [_p, _p, _sz, _p]),
     "ivosw_p2p_arena_bytes": (_sz, [_i, _sz]),
     "ivosw_p2p_handle_bytes": (_sz, []),
@@ -49,6 +52,8 @@ SIGNATURES = {
     "ivosw_dqn_step_drawn": (_i, [_p] * 10 + [_i, _i, _i, _f] + [_p] * 9 + [_sz] + [_p] * 3 + [_f] * 7 + [_p]),
     "ivosw_dqn_step_drawn_ex": (_i, [_p] * 10 + [_i, _i, _i, _f, _i, _f] + [_p] * 9 + [_sz] + [_p] * 3 + [_f] * 7 + [_p]),
     "ivosw_dqn_step_drawn_sgd": (_i, [_p] * 10 + [_i, _i, _i, _f, _i, _f] + [_p] * 9 + [_sz] + [_p, _f, _f, _f, _i, _f, _f] + [_p]),
+    "ivosw_dqn_step_drawn_sched": (_i, [_p] * 10 + [_i, _i, _i, _f, _i, _f] + [_p] * 9 + [_sz] + [_p] * 3 + [_p, _i] + [_f] * 6 + [_p]),
+    "ivosw_dqn_step_drawn_sgd_sched": (_i, [_p] * 10 + [_i, _i, _i, _f, _i, _f] + [_p] * 9 + [_sz] + [_p, _p, _p, _i, _f, _f, _i, _f, _f] + [_p]),
     "ivosw_mask_bbox": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "ivosw_roi_sample": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "ivosw_assess_packed_bytes": (_sz, [_i]),

@@ -4,7 +4,10 @@
 // p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps).  The clamp comes first (reference models/agent.py:157-159);
 // gscale (= 1/world) is applied before the clamp so that the clamp sees the averaged gradient.
 #pragma once
+#include <cmath>
+
 #include "common.h"
+#include "lr_sched.h"
 
 namespace ivosw {
 
@@ -29,6 +32,21 @@ __device__ __forceinline__ float clamp_adam_elem(float g, float pi, float& mi, f
     vi = fmaf(1.0f - beta2, gi * gi, vi * beta2);
     const float denom = sqrtf(vi) / bc2_sqrt + eps;
     return pi - step_size * (mi / denom);
+}
+
+// The hyper-parameters the scheduled Adam entries refuse (IVOSW_ERR_ARG) before they launch anything: torch.optim.Adam's own checks
+// (betas in [0, 1), eps >= 0, weight_decay >= 0), finite values only.
+inline int check_adam(const char* who, float beta1, float beta2, float eps, float weight_decay) {
+    const char* bad = nullptr;
+    if (!(beta1 >= 0.f && beta1 < 1.f)) bad = "beta1 must be in [0, 1)";
+    else if (!(beta2 >= 0.f && beta2 < 1.f)) bad = "beta2 must be in [0, 1)";
+    else if (!(std::isfinite(eps) && eps >= 0.f)) bad = "eps must be finite and >= 0";
+    else if (!(std::isfinite(weight_decay) && weight_decay >= 0.f)) bad = "weight_decay must be finite and >= 0";
+    if (bad) {
+        set_error("%s: %s (betas %g, %g, eps %g, weight_decay %g)", who, bad, (double)beta1, (double)beta2, (double)eps, (double)weight_decay);
+        return IVOSW_ERR_ARG;
+    }
+    return IVOSW_OK;
 }
 
 // ---- device-resident state of the captured DQN step (dqn.hip owns the kernels; brain.hip's one-call step shares the layouts)

@@ -1600,10 +1600,11 @@ __device__ __forceinline__ float reduce_on_load(float* __restrict__ g, const Red
 
 // One element per lane, 177 workgroups: the slabs (13.5 MB at B = 128, T = 25, fresh in L2) are pulled by the whole chip — with the
 // 45 workgroups of the 16-byte form the launch took 11 us, more than the reduction + update launches it replaces (5.3 + 5.1).
-__global__ __launch_bounds__(1024) void clamp_adam_dev_reduce_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                                     float* __restrict__ v, int n, AdamDevState* __restrict__ st, ReduceGroup rg,
-                                                                     ReduceOffsets ro, float lr, float beta1, float beta2, float eps, float wd,
-                                                                     float clampv, float gscale) {
+// The body is shared with clamp_adam_dev_reduce_sched_kernel, which only picks lr differently.
+__device__ __forceinline__ void clamp_adam_dev_reduce_apply(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, int n, AdamDevState* __restrict__ st, const ReduceGroup& rg,
+                                                            const ReduceOffsets& ro, float lr, float beta1, float beta2, float eps, float wd,
+                                                            float clampv, float gscale) {
     const int step = st->step + 1;
     const double b1t = ipow((double)beta1, step), b2t = ipow((double)beta2, step);
     const float step_size = (float)((double)lr / (1.0 - b1t)), bc2_sqrt = (float)sqrt(1.0 - b2t);
@@ -1623,6 +1624,23 @@ __global__ __launch_bounds__(1024) void clamp_adam_dev_reduce_kernel(float* __re
     }
 }
 
+__global__ __launch_bounds__(1024) void clamp_adam_dev_reduce_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                                     float* __restrict__ v, int n, AdamDevState* __restrict__ st, ReduceGroup rg,
+                                                                     ReduceOffsets ro, float lr, float beta1, float beta2, float eps, float wd,
+                                                                     float clampv, float gscale) {
+    clamp_adam_dev_reduce_apply(p, g, m, v, n, st, rg, ro, lr, beta1, beta2, eps, wd, clampv, gscale);
+}
+
+// The scheduled one-call tail (cfg.agent.lr_schedule = "poly"): lr = lr_table[min(k, lr_steps)] with k the counter left by the previous
+// step (clamp_adam_dev_sched_kernel's choice), the rest clamp_adam_dev_reduce_kernel's.
+__global__ __launch_bounds__(1024) void clamp_adam_dev_reduce_sched_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                                           float* __restrict__ v, int n, AdamDevState* __restrict__ st,
+                                                                           ReduceGroup rg, ReduceOffsets ro, const float* __restrict__ lr_table,
+                                                                           int lr_steps, float beta1, float beta2, float eps, float wd,
+                                                                           float clampv, float gscale) {
+    clamp_adam_dev_reduce_apply(p, g, m, v, n, st, rg, ro, sched_lr(lr_table, lr_steps, st->step), beta1, beta2, eps, wd, clampv, gscale);
+}
+
 // Clamp + SGD (clamp_sgd_elem: the expressions of clamp_sgd_kernel) with the same slab reduction folded in on load.  No step counter, so
 // no ticket: the launch simply repeats under a captured graph.
 __global__ __launch_bounds__(1024) void clamp_sgd_reduce_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf, int n,
@@ -1636,6 +1654,30 @@ __global__ __launch_bounds__(1024) void clamp_sgd_reduce_kernel(float* __restric
     buf[i] = bi;
 }
 
+// The scheduled form: lr = lr_table[min(k, lr_steps)] with k = st->step, the update of clamp_sgd_reduce_kernel, and the device step counter
+// advanced by the last workgroup (clamp_sgd_sched_kernel's ticket).
+__global__ __launch_bounds__(1024) void clamp_sgd_reduce_sched_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf,
+                                                                      int n, SgdDevState* __restrict__ st, ReduceGroup rg, ReduceOffsets ro,
+                                                                      const float* __restrict__ lr_table, int lr_steps, float mu, float wd,
+                                                                      int nesterov, float clampv, float gscale) {
+    const int k = st->step;
+    const float lr = sched_lr(lr_table, lr_steps, k);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const float gi = reduce_on_load(g, rg, ro, i);
+        float bi = buf[i];
+        p[i] = clamp_sgd_elem(gi, p[i], bi, lr, mu, wd, nesterov, clampv, gscale);
+        buf[i] = bi;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (atomicAdd(&st->ticket, 1u) == gridDim.x - 1) {
+            st->step = k + 1;
+            atomicExch(&st->ticket, 0u);
+        }
+    }
+}
+
 extern "C" int ivosw_replay_draw_gather(const float* old_iou, const float* new_iou, const float* annotated, const float* next_annotated,
                                         const int64_t* action, const float* reward_step, const float* reward_done, void* draw_state, int n,
                                         int B, int T, int64_t* idx_out, float* state, float* new_state, int64_t* action_out,
@@ -1645,6 +1687,12 @@ extern "C" int ivosw_clamp_adam_dev(float* params, const float* grads, float* ex
                                     ivosw_stream_t stream);
 extern "C" int ivosw_clamp_sgd(float* params, const float* grads, float* momentum_buf, int n, float lr, float momentum, float weight_decay,
                                int nesterov, float clamp, float grad_scale, ivosw_stream_t stream);
+extern "C" int ivosw_clamp_adam_dev_sched(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int n, void* adam_state,
+                                          const float* lr_table, int lr_steps, float beta1, float beta2, float eps, float weight_decay,
+                                          float clamp, float grad_scale, ivosw_stream_t stream);
+extern "C" int ivosw_clamp_sgd_dev_sched(float* params, const float* grads, float* momentum_buf, int n, void* sgd_state, const float* lr_table,
+                                         int lr_steps, float momentum, float weight_decay, int nesterov, float clamp, float grad_scale,
+                                         ivosw_stream_t stream);
 
 extern "C" int ivosw_dqn_step_drawn_ex(float* policy, const float* target, const float* old_iou, const float* new_iou, const float* annotated,
                                        const float* next_annotated, const int64_t* action, const float* reward_step, const float* reward_done,
@@ -1738,6 +1786,116 @@ extern "C" int ivosw_dqn_step_drawn_sgd(float* policy, const float* target, cons
     if (rc == IVOSW_OK)
         rc = ivosw_clamp_sgd(policy, grads, momentum_buf, IVOSW_BRAIN_NPARAMS, lr, momentum, weight_decay, nesterov, clamp, grad_scale, stream);
     return rc;
+}
+
+// The common part of the two scheduled one-call steps (the caller has checked its arguments): the fused chain with the draw + gather in
+// the encoder launch, then fold(rg, ro) launches the update with the slab reduction folded in; or, off the fused chain, the draw + gather
+// and loss + gradient entries followed by unfold(), the update's own entry.
+template <class Fold, class Unfold>
+static int dqn_step_drawn_sched_run(const char* who, bool aligned, float* policy, const float* target, const float* old_iou, const float* new_iou,
+                                    const float* annotated, const float* next_annotated, const int64_t* action, const float* reward_step,
+                                    const float* reward_done, void* draw_state, int n, int B, int T, float gamma, int loss_kind, float huber_delta,
+                                    int64_t* idx_out, float* state, float* new_state, int64_t* action_out, float* reward_step_out,
+                                    float* reward_done_out, float* grads, float* loss, void* ws, size_t ws_bytes, ivosw_stream_t stream, Fold fold,
+                                    Unfold unfold) {
+    bool folded = false;
+    if (aligned && tune_get("DQN_ONECALL", 1)) {
+        const EncDraw dr{old_iou, new_iou, annotated, next_annotated, action, reward_step, reward_done, static_cast<DrawState*>(draw_state), n, B, T,
+                         idx_out, state, new_state, action_out, reward_step_out, reward_done_out};
+        ReduceGroup rg{};
+        const int rc = dqn_loss_grad_impl(policy, target, state, new_state, action_out, reward_step_out, reward_done_out, B, T, gamma, loss_kind,
+                                          huber_delta, grads, loss, ws, ws_bytes, stream, &dr, &rg, &folded);
+        if (rc != IVOSW_OK) return rc;
+        if (folded) {
+            ReduceOffsets ro{};
+            for (int k = 0; k < REDUCE_MAX; ++k) ro.off[k] = rg.out[k] ? (int)(rg.out[k] - grads) : 0;
+            fold(rg, ro);
+            const hipError_t e = hipGetLastError();
+            if (e != hipSuccess) {
+                set_error("%s: HIP error %s", who, hipGetErrorString(e));
+                return IVOSW_ERR_LAUNCH;
+            }
+            return IVOSW_OK;
+        }
+    }
+    int rc = ivosw_replay_draw_gather(old_iou, new_iou, annotated, next_annotated, action, reward_step, reward_done, draw_state, n, B, T, idx_out,
+                                      state, new_state, action_out, reward_step_out, reward_done_out, stream);
+    if (rc == IVOSW_OK)
+        rc = ivosw_dqn_loss_grad_ex(policy, target, state, new_state, action_out, reward_step_out, reward_done_out, B, T, gamma, loss_kind,
+                                    huber_delta, grads, loss, ws, ws_bytes, stream);
+    if (rc == IVOSW_OK) rc = unfold();
+    return rc;
+}
+
+// ivosw_dqn_step_drawn_ex with the poly learning-rate schedule: the same eight launches, the last one clamp_adam_dev_reduce_sched_kernel.
+extern "C" int ivosw_dqn_step_drawn_sched(float* policy, const float* target, const float* old_iou, const float* new_iou, const float* annotated,
+                                          const float* next_annotated, const int64_t* action, const float* reward_step, const float* reward_done,
+                                          void* draw_state, int n, int B, int T, float gamma, int loss_kind, float huber_delta, int64_t* idx_out,
+                                          float* state, float* new_state, int64_t* action_out, float* reward_step_out, float* reward_done_out,
+                                          float* grads, float* loss, void* ws, size_t ws_bytes, float* exp_avg, float* exp_avg_sq, void* adam_state,
+                                          const float* lr_table, int lr_steps, float beta1, float beta2, float eps, float weight_decay, float clamp,
+                                          float grad_scale, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(policy && target && old_iou && new_iou && annotated && next_annotated && action && reward_step && reward_done && draw_state &&
+                      idx_out && state && new_state && action_out && reward_step_out && reward_done_out && grads && loss && ws && exp_avg &&
+                      exp_avg_sq && adam_state,
+                  "null pointer");
+    IVOSW_REQUIRE(n > 0 && B > 0 && T > 0, "n, B and T must be positive");
+    // refused before anything is launched (the un-folded sequence would otherwise advance the draw counter first)
+    static const char* who = "ivosw_dqn_step_drawn_sched";
+    if (const int rc = check_dqn_loss(who, loss_kind, huber_delta)) return rc;
+    if (const int rc = check_lr_table(who, lr_table, lr_steps)) return rc;
+    if (const int rc = check_adam(who, beta1, beta2, eps, weight_decay)) return rc;
+    IVOSW_ON_DEVICE_OF(grads);
+    const bool aligned = ((reinterpret_cast<uintptr_t>(policy) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(exp_avg) |
+                           reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0;
+    AdamDevState* sd = static_cast<AdamDevState*>(adam_state);
+    const int nprm = IVOSW_BRAIN_NPARAMS;
+    return dqn_step_drawn_sched_run(
+        who, aligned, policy, target, old_iou, new_iou, annotated, next_annotated, action, reward_step, reward_done, draw_state, n, B, T, gamma,
+        loss_kind, huber_delta, idx_out, state, new_state, action_out, reward_step_out, reward_done_out, grads, loss, ws, ws_bytes, stream,
+        [&](const ReduceGroup& rg, const ReduceOffsets& ro) {
+            hipLaunchKernelGGL(clamp_adam_dev_reduce_sched_kernel, dim3((nprm + 1023) / 1024), dim3(1024), 0, as_stream(stream), policy, grads,
+                               exp_avg, exp_avg_sq, nprm, sd, rg, ro, lr_table, lr_steps, beta1, beta2, eps, weight_decay, clamp, grad_scale);
+        },
+        [&] {
+            return ivosw_clamp_adam_dev_sched(policy, grads, exp_avg, exp_avg_sq, nprm, adam_state, lr_table, lr_steps, beta1, beta2, eps,
+                                              weight_decay, clamp, grad_scale, stream);
+        });
+}
+
+// ivosw_dqn_step_drawn_sgd with the poly learning-rate schedule: the same eight launches, the last one clamp_sgd_reduce_sched_kernel.
+extern "C" int ivosw_dqn_step_drawn_sgd_sched(float* policy, const float* target, const float* old_iou, const float* new_iou,
+                                              const float* annotated, const float* next_annotated, const int64_t* action, const float* reward_step,
+                                              const float* reward_done, void* draw_state, int n, int B, int T, float gamma, int loss_kind,
+                                              float huber_delta, int64_t* idx_out, float* state, float* new_state, int64_t* action_out,
+                                              float* reward_step_out, float* reward_done_out, float* grads, float* loss, void* ws, size_t ws_bytes,
+                                              float* momentum_buf, void* sgd_state, const float* lr_table, int lr_steps, float momentum,
+                                              float weight_decay, int nesterov, float clamp, float grad_scale, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(policy && target && old_iou && new_iou && annotated && next_annotated && action && reward_step && reward_done && draw_state &&
+                      idx_out && state && new_state && action_out && reward_step_out && reward_done_out && grads && loss && ws && momentum_buf &&
+                      sgd_state,
+                  "null pointer");
+    IVOSW_REQUIRE(n > 0 && B > 0 && T > 0, "n, B and T must be positive");
+    static const char* who = "ivosw_dqn_step_drawn_sgd_sched";
+    if (const int rc = check_dqn_loss(who, loss_kind, huber_delta)) return rc;
+    if (const int rc = check_lr_table(who, lr_table, lr_steps)) return rc;
+    if (const int rc = check_sgd(who, 0.f, momentum, weight_decay, nesterov)) return rc;
+    IVOSW_ON_DEVICE_OF(grads);
+    const bool aligned = ((reinterpret_cast<uintptr_t>(policy) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(momentum_buf)) &
+                          15) == 0;
+    SgdDevState* sd = static_cast<SgdDevState*>(sgd_state);
+    const int nprm = IVOSW_BRAIN_NPARAMS;
+    return dqn_step_drawn_sched_run(
+        who, aligned, policy, target, old_iou, new_iou, annotated, next_annotated, action, reward_step, reward_done, draw_state, n, B, T, gamma,
+        loss_kind, huber_delta, idx_out, state, new_state, action_out, reward_step_out, reward_done_out, grads, loss, ws, ws_bytes, stream,
+        [&](const ReduceGroup& rg, const ReduceOffsets& ro) {
+            hipLaunchKernelGGL(clamp_sgd_reduce_sched_kernel, dim3((nprm + 1023) / 1024), dim3(1024), 0, as_stream(stream), policy, grads,
+                               momentum_buf, nprm, sd, rg, ro, lr_table, lr_steps, momentum, weight_decay, nesterov, clamp, grad_scale);
+        },
+        [&] {
+            return ivosw_clamp_sgd_dev_sched(policy, grads, momentum_buf, nprm, sgd_state, lr_table, lr_steps, momentum, weight_decay, nesterov,
+                                             clamp, grad_scale, stream);
+        });
 }
 
 extern "C" int ivosw_dqn_step_drawn(float* policy, const float* target, const float* old_iou, const float* new_iou, const float* annotated,

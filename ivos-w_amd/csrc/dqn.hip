@@ -112,10 +112,11 @@ __global__ void quality_state_kernel(const float* __restrict__ scores, int n_obj
 // corrections itself (the float64 expressions of ivosw_clamp_adam: identical bits); the LAST workgroup to finish — a
 // device-scope ticket, taken after the workgroup's own reads and writes — publishes k+1.  No other workgroup can still
 // be reading the state at that point, and nothing but the ticket crosses workgroups, so no fence is needed.
+// The body is shared with clamp_adam_dev_sched_kernel, which only picks lr differently.
 template <bool VEC>
-__global__ __launch_bounds__(1024) void clamp_adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                              float* __restrict__ v, int n, AdamDevState* __restrict__ st, float lr, float beta1,
-                                                              float beta2, float eps, float wd, float clampv, float gscale) {
+__device__ __forceinline__ void clamp_adam_dev_apply(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                     float* __restrict__ v, int n, AdamDevState* __restrict__ st, float lr, float beta1,
+                                                     float beta2, float eps, float wd, float clampv, float gscale) {
     const int step = st->step + 1;
     const double b1t = ipow((double)beta1, step), b2t = ipow((double)beta2, step);
     const float step_size = (float)((double)lr / (1.0 - b1t)), bc2_sqrt = (float)sqrt(1.0 - b2t);
@@ -151,12 +152,30 @@ __global__ __launch_bounds__(1024) void clamp_adam_dev_kernel(float* __restrict_
     }
 }
 
+template <bool VEC>
+__global__ __launch_bounds__(1024) void clamp_adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                              float* __restrict__ v, int n, AdamDevState* __restrict__ st, float lr, float beta1,
+                                                              float beta2, float eps, float wd, float clampv, float gscale) {
+    clamp_adam_dev_apply<VEC>(p, g, m, v, n, st, lr, beta1, beta2, eps, wd, clampv, gscale);
+}
+
+// The scheduled form (cfg.agent.lr_schedule = "poly"): lr = lr_table[min(k, lr_steps)] with k the counter left by the previous launch,
+// one scalar load per wave in place of the lr argument; everything else is clamp_adam_dev_kernel's, ticket and publish included.
+template <bool VEC>
+__global__ __launch_bounds__(1024) void clamp_adam_dev_sched_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                    float* __restrict__ v, int n, AdamDevState* __restrict__ st,
+                                                                    const float* __restrict__ lr_table, int lr_steps, float beta1, float beta2,
+                                                                    float eps, float wd, float clampv, float gscale) {
+    clamp_adam_dev_apply<VEC>(p, g, m, v, n, st, sched_lr(lr_table, lr_steps, st->step), beta1, beta2, eps, wd, clampv, gscale);
+}
+
 // Clamp + SGD (clamp_sgd_elem) over the flat arena.  Nothing but the momentum buffer carries over from one step to the next, so
 // the launch is capture-safe as it stands: no step counter, no ticket.  VEC: 16 bytes per lane and array, the n % 4 tail elements
 // go to the first threads past the vector part (clamp_adam_dev_kernel's layout).
+// The body is shared with clamp_sgd_sched_kernel.
 template <bool VEC>
-__global__ __launch_bounds__(256) void clamp_sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int n,
-                                                        float lr, float mu, float wd, int nesterov, float clampv, float gscale) {
+__device__ __forceinline__ void clamp_sgd_apply(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int n, float lr,
+                                                float mu, float wd, int nesterov, float clampv, float gscale) {
     auto upd = [&](float gi, float pi, float& bi) { return clamp_sgd_elem(gi, pi, bi, lr, mu, wd, nesterov, clampv, gscale); };
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (VEC) {
@@ -177,6 +196,30 @@ __global__ __launch_bounds__(256) void clamp_sgd_kernel(float* __restrict__ p, c
         float bi = buf[t];
         p[t] = upd(g[t], p[t], bi);
         buf[t] = bi;
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void clamp_sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int n,
+                                                        float lr, float mu, float wd, int nesterov, float clampv, float gscale) {
+    clamp_sgd_apply<VEC>(p, g, buf, n, lr, mu, wd, nesterov, clampv, gscale);
+}
+
+// The scheduled form: lr = lr_table[min(k, lr_steps)] with k = st->step, then clamp_sgd_kernel's update, then the last workgroup
+// publishes k + 1 (clamp_adam_dev_kernel's ticket).  1024-lane workgroups, as clamp_adam_dev_kernel: the tickets of one launch serialise
+// on one address, so the launch keeps few of them (45 at n = 180 993).
+template <bool VEC>
+__global__ __launch_bounds__(1024) void clamp_sgd_sched_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
+                                                               int n, SgdDevState* __restrict__ st, const float* __restrict__ lr_table,
+                                                               int lr_steps, float mu, float wd, int nesterov, float clampv, float gscale) {
+    const int k = st->step;
+    clamp_sgd_apply<VEC>(p, g, buf, n, sched_lr(lr_table, lr_steps, k), mu, wd, nesterov, clampv, gscale);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (atomicAdd(&st->ticket, 1u) == gridDim.x - 1) {
+            st->step = k + 1;
+            atomicExch(&st->ticket, 0u);
+        }
     }
 }
 
@@ -201,7 +244,50 @@ extern "C" int ivosw_clamp_sgd(float* params, const float* grads, float* momentu
     return IVOSW_OK;
 }
 
+extern "C" size_t ivosw_sgd_state_bytes(void) { return sizeof(SgdDevState); }
+
+extern "C" int ivosw_clamp_sgd_dev_sched(float* params, const float* grads, float* momentum_buf, int n, void* sgd_state, const float* lr_table,
+                                         int lr_steps, float momentum, float weight_decay, int nesterov, float clamp, float grad_scale,
+                                         ivosw_stream_t stream) {
+    IVOSW_REQUIRE(params && grads && momentum_buf && sgd_state, "null pointer");
+    IVOSW_REQUIRE(n > 0, "n must be positive");
+    if (const int rc = check_lr_table("ivosw_clamp_sgd_dev_sched", lr_table, lr_steps)) return rc;
+    if (const int rc = check_sgd("ivosw_clamp_sgd_dev_sched", 0.f, momentum, weight_decay, nesterov)) return rc;
+    IVOSW_ON_DEVICE_OF(params);
+    SgdDevState* sd = static_cast<SgdDevState*>(sgd_state);
+    const bool vec = ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(momentum_buf)) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(clamp_sgd_sched_kernel<true>, dim3((n / 4 + 3 + 1023) / 1024), dim3(1024), 0, as_stream(stream), params, grads,
+                           momentum_buf, n, sd, lr_table, lr_steps, momentum, weight_decay, nesterov, clamp, grad_scale);
+    else
+        hipLaunchKernelGGL(clamp_sgd_sched_kernel<false>, dim3((n + 1023) / 1024), dim3(1024), 0, as_stream(stream), params, grads, momentum_buf,
+                           n, sd, lr_table, lr_steps, momentum, weight_decay, nesterov, clamp, grad_scale);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
 extern "C" size_t ivosw_adam_state_bytes(void) { return sizeof(AdamDevState); }
+
+extern "C" int ivosw_clamp_adam_dev_sched(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int n, void* adam_state,
+                                          const float* lr_table, int lr_steps, float beta1, float beta2, float eps, float weight_decay,
+                                          float clamp, float grad_scale, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(params && grads && exp_avg && exp_avg_sq && adam_state, "null pointer");
+    IVOSW_REQUIRE(n > 0, "n must be positive");
+    if (const int rc = check_lr_table("ivosw_clamp_adam_dev_sched", lr_table, lr_steps)) return rc;
+    if (const int rc = check_adam("ivosw_clamp_adam_dev_sched", beta1, beta2, eps, weight_decay)) return rc;
+    IVOSW_ON_DEVICE_OF(params);
+    AdamDevState* sd = static_cast<AdamDevState*>(adam_state);
+    const bool vec = ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(exp_avg) |
+                       reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(clamp_adam_dev_sched_kernel<true>, dim3((n / 4 + 3 + 1023) / 1024), dim3(1024), 0, as_stream(stream), params, grads,
+                           exp_avg, exp_avg_sq, n, sd, lr_table, lr_steps, beta1, beta2, eps, weight_decay, clamp, grad_scale);
+    else
+        hipLaunchKernelGGL(clamp_adam_dev_sched_kernel<false>, dim3((n + 1023) / 1024), dim3(1024), 0, as_stream(stream), params, grads,
+                           exp_avg, exp_avg_sq, n, sd, lr_table, lr_steps, beta1, beta2, eps, weight_decay, clamp, grad_scale);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
 
 extern "C" int ivosw_clamp_adam_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int n, void* adam_state,
                                     float lr, float beta1, float beta2, float eps, float weight_decay, float clamp,

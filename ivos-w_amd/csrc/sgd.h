@@ -9,6 +9,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "lr_sched.h"
 
 namespace ivosw {
 
@@ -25,6 +26,16 @@ __device__ __forceinline__ float clamp_sgd_elem(float g, float pi, float& bi, fl
     d = nesterov ? fmaf(mu, bi, d) : bi;
     return fmaf(-lr, d, pi);
 }
+
+// The step counter of a scheduled SGD update (cfg.agent.lr_schedule = "poly"), on the device so that a captured graph replays the
+// schedule: the update reads lr_table[min(step, N)], and the last workgroup of the launch (the ticket, as in clamp_adam_dev_kernel)
+// publishes step + 1.  Layout (8 bytes): the counter is the int32 at byte 0; a caller resumes from host step k by writing k there.
+// The constant-lr update keeps no counter.
+struct SgdDevState {
+    int step;
+    unsigned ticket;
+};
+static_assert(sizeof(SgdDevState) == 8, "SgdDevState layout (step at byte 0, ticket at byte 4)");
 
 // The hyper-parameters every SGD entry refuses (IVOSW_ERR_ARG) before it launches anything.
 inline int check_sgd(const char* who, float lr, float momentum, float weight_decay, int nesterov) {

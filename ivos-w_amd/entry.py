@@ -65,7 +65,9 @@ DEFAULTS = dict(
                lr=5e-6, lr_pow=0.9, momentum=0.9, weight_decay=5e-4, memory_size=100000, gamma=0.95, eps_start=0.7, eps_end=0.25,
                eps_k=5, eps_decay=500, update_rate=0.05, train_batch_size=32,
                loss="mse", huber_delta=1.0,    # DQN objective: the reference's two-term MSE, or "huber" (threshold huber_delta)
-               nesterov=False),   # update: optimizer "adam" (the reference's) or "sgd" (clamp + SGD with momentum, nesterov); lr_pow is unread
+               nesterov=False,    # update: optimizer "adam" (the reference's) or "sgd" (clamp + SGD with momentum, nesterov)
+               lr_schedule="constant", lr_total_steps=0),   # lr: constant (the reference's), or "poly": lr * (1 - min(k, N) / N) ** lr_pow
+                                                            # at update k, N = lr_total_steps (required then)
     synth=dict(n_sequences=3, n_frames=30, height=120, width=216, max_objects=3, baseline_runs=30),
 )
 
@@ -636,9 +638,11 @@ def run_train(cfg):
         curve = gs["curve"][cfg.davis_interactive.metric][:-1]
         auc = float(np.trapz(curve) / (len(curve) - 1))
         history.append(dict(epoch=epoch, auc=auc, final=float(np.mean(out["finals"])), agent_loss=float(np.mean(out["losses"])) if out["losses"] else 0.0,
-                            reward_done=float(np.mean(out["rewards_done"])), updates=agent.optimizer.state["step"]))
+                            reward_done=float(np.mean(out["rewards_done"])), updates=agent.optimizer.state["step"],
+                            lr=agent.optimizer.current_lr()))       # the lr of the next update (the schedule's, at `updates`)
         print(f"# epoch {epoch}: auc:{auc:.4f} final {cfg.davis_interactive.metric}: {history[-1]['final'] * 100:.2f} agent loss: "
-              f"{history[-1]['agent_loss']:.4f} reward_done: {history[-1]['reward_done']:.3f} updates: {history[-1]['updates']}")
+              f"{history[-1]['agent_loss']:.4f} reward_done: {history[-1]['reward_done']:.3f} updates: {history[-1]['updates']} "
+              f"lr: {history[-1]['lr']:.6g}")
     if world > 1:
         # replicas must be bit-identical: compare an exact integer checksum of the parameter bits on every rank
         bits = agent.policy_net.flat.detach().view(torch.int32).to(torch.int64)

@@ -8,7 +8,8 @@ arithmetic replaced by libivosw_hip.so:
                                                   cfg.agent.loss = "huber" / huber_delta; hand-derived BPTT)
                           [+ RCCL all-reduce of the flat gradient arena when torch.distributed is up]
                           ivosw_clamp_adam       (clamp [-1,1] + coupled-L2 Adam, one fused kernel; cfg.agent.optimizer = "sgd":
-                          ivosw_clamp_sgd         clamp + SGD with momentum / nesterov, cfg.agent.momentum / nesterov)
+                          ivosw_clamp_sgd         clamp + SGD with momentum / nesterov, cfg.agent.momentum / nesterov;
+                                                  cfg.agent.lr_schedule = "poly": the lr of each update from a table, see poly_lr_table)
                           ivosw_copy_f32         (hard target sync)
   Agent.action         -> ivosw_brain_forward + ivosw_brain_argmax (first max, like numpy)
 
@@ -89,20 +90,111 @@ class Brain(nn.Module):
         return q
 
 
-class FusedClampAdam:
+LR_SCHEDULES = ("constant", "poly")
+LR_TOTAL_STEPS_MAX = 1 << 24          # the poly schedule's table: N + 1 float32 values on the device, 64 MB at the cap
+
+
+def lr_schedule_option(kind, lr_pow, total_steps):
+    """(schedule, lr_pow, N), checked: ("constant", None, None), or ("poly", lr_pow, N) with lr_pow a finite number >= 0 and N an int in
+    [1, LR_TOTAL_STEPS_MAX].  lr_pow and N are only looked at under "poly".  Anything else is a ValueError."""
+    if not isinstance(kind, str) or kind not in LR_SCHEDULES:
+        raise ValueError(f"agent.lr_schedule must be 'constant' or 'poly', got {kind!r}")
+    if kind == "constant":
+        return "constant", None, None
+    if isinstance(total_steps, bool) or not isinstance(total_steps, int) or not 1 <= total_steps <= LR_TOTAL_STEPS_MAX:
+        raise ValueError(f"agent.lr_total_steps must be an int in [1, {LR_TOTAL_STEPS_MAX}] under lr_schedule 'poly', got {total_steps!r}")
+    if isinstance(lr_pow, bool) or not isinstance(lr_pow, (int, float)) or not (math.isfinite(lr_pow) and lr_pow >= 0):
+        raise ValueError(f"agent.lr_pow must be a finite number >= 0, got {lr_pow!r}")
+    return "poly", float(lr_pow), total_steps
+
+
+def poly_lr_table(lr, lr_pow, total_steps):
+    """lr_k = float32(lr * (1 - min(k, N) / N) ** lr_pow) for k = 0 .. N (torch's PolynomialLR closed form at last_epoch = k): float64
+    Python arithmetic (libm pow; not numpy's vectorised power, whose last bit can differ), rounded to float32 once at the end."""
+    lr, n = float(lr), int(total_steps)
+    return np.array([lr * (1.0 - k / n) ** lr_pow for k in range(n + 1)], dtype=np.float64).astype(np.float32)
+
+
+class _LrSchedule:
+    """The learning-rate schedule of FusedClampAdam and FusedClampSGD.  ``param_groups[0]`` carries ``lr_schedule`` ("constant" or
+    "poly"), ``lr_pow`` and ``lr_total_steps`` next to the base ``lr``.  Under "poly" the update after k earlier ones uses
+    ``poly_lr_table(lr, lr_pow, N)[min(k, N)]``: the eager entries get that float as their lr, and the captured and one-call steps read the
+    same table on the device at their device step counter.  Under "constant" every path passes ``lr`` as before."""
+
+    def _init_schedule(self, lr_schedule, lr_pow, lr_total_steps):
+        kind, lr_pow, n = lr_schedule_option(lr_schedule, lr_pow, lr_total_steps)
+        self.param_groups[0].update(lr_schedule=kind, lr_pow=lr_pow, lr_total_steps=n)
+        self._lr_host = None                    # ((lr, lr_pow, N), the host table) of the schedule in use
+        self._lr_dev = {}                       # (lr, lr_pow, N, device) -> device table; kept, so that a captured graph's stays valid
+
+    def schedule(self):
+        """(schedule, base lr, lr_pow, N) as param_groups[0] holds them now (checked)."""
+        g = self.param_groups[0]
+        kind, lr_pow, n = lr_schedule_option(g.get("lr_schedule", "constant"), g.get("lr_pow"), g.get("lr_total_steps"))
+        return kind, float(g["lr"]), lr_pow, n
+
+    @property
+    def scheduled(self):
+        return self.schedule()[0] == "poly"
+
+    def _lr_table_host(self):
+        _, lr, lr_pow, n = self.schedule()
+        if self._lr_host is None or self._lr_host[0] != (lr, lr_pow, n):
+            self._lr_host = ((lr, lr_pow, n), poly_lr_table(lr, lr_pow, n))
+        return self._lr_host[1]
+
+    def lr_table(self):
+        """The poly table on the parameters' device (float32 [N + 1]), built once per (lr, lr_pow, N) and device and kept for the
+        optimizer's life: a captured step records its address."""
+        host = self._lr_table_host()
+        dev = self.brain.flat.device
+        key = self._lr_host[0] + (str(dev),)
+        t = self._lr_dev.get(key)
+        if t is None:
+            t = self._lr_dev[key] = torch.from_numpy(host).to(dev)
+        return t
+
+    def lr_at(self, k):
+        """The lr of the update that follows k earlier ones."""
+        kind, _, _, n = self.schedule()
+        if kind == "constant":
+            return self.param_groups[0]["lr"]
+        return float(self._lr_table_host()[min(int(k), n)])
+
+    def current_lr(self):
+        """The lr the next update will use."""
+        return self.lr_at(self.state["step"])
+
+    def _schedule_hyper(self):
+        """What a captured step bakes in of the schedule: its kind, lr_pow, N and the device table's address (the base lr is in hyper())."""
+        kind, _, lr_pow, n = self.schedule()
+        return (kind, lr_pow, n, self.lr_table().data_ptr() if kind == "poly" else 0)
+
+    def _load_schedule(self, sd):
+        """The schedule of a state dict's param_groups, when it carries one (checked before anything is changed)."""
+        groups = sd.get("param_groups") or [{}]
+        if "lr_schedule" in groups[0]:
+            g = groups[0]
+            kind, lr_pow, n = lr_schedule_option(g["lr_schedule"], g.get("lr_pow"), g.get("lr_total_steps"))
+            self.param_groups[0].update(lr_schedule=kind, lr_pow=lr_pow, lr_total_steps=n)
+
+
+class FusedClampAdam(_LrSchedule):
     """``optim.Adam(params, lr, weight_decay)`` + the reference's grad clamp, as one kernel over the flat arena.
 
     The interface CapturedDqnStep and parallel.py use, shared with FusedClampSGD: ``kind``, ``step``, ``dev_state`` (the device state a
     captured step needs, created and synchronised), ``enqueue_dev_step`` (the capture-safe update on the current stream), ``note_dev_steps``
-    (the host counter after n such updates), ``hyper`` (what a capture bakes in) and ``onecall_tail`` (the one-call step's entry and the
-    arguments after its ws_bytes)."""
+    (the host counter after n such updates), ``hyper`` (what a capture bakes in), ``onecall_tail`` (the one-call step's entry and the
+    arguments after its ws_bytes) and the learning-rate schedule of _LrSchedule."""
 
     kind = "adam"
 
-    def __init__(self, brain, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8, clamp=1.0):
+    def __init__(self, brain, lr, weight_decay, betas=(0.9, 0.999), eps=1e-8, clamp=1.0, lr_schedule="constant", lr_pow=None,
+                 lr_total_steps=None):
         self.brain = brain
         self.param_groups = [dict(params=list(brain.parameters()), lr=lr, betas=betas, eps=eps,
                                   weight_decay=weight_decay, clamp=clamp)]
+        self._init_schedule(lr_schedule, lr_pow, lr_total_steps)
         self.state = dict(step=0, exp_avg=None, exp_avg_sq=None)
         self.grad_scale = 1.0
 
@@ -118,17 +210,20 @@ class FusedClampAdam:
     def step(self):
         self._ensure()
         g = self.param_groups[0]
+        lr = self.current_lr()
         self.state["step"] += 1
         b = self.brain
         L.check(L.lib().ivosw_clamp_adam(L.dptr(b.flat), L.dptr(b.flat_grad), L.dptr(self.state["exp_avg"]),
                                          L.dptr(self.state["exp_avg_sq"]), L.BRAIN_NPARAMS, self.state["step"],
-                                         g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
+                                         lr, g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"],
                                          g["clamp"], self.grad_scale, L.stream_ptr(b.flat.device)), "clamp_adam")
 
     # -- device-side step state (what a captured HIP graph replays; ivosw_clamp_adam_dev) -------------------------------
     def dev_state(self):
-        """The 32-byte Adam step state on the device, (re)synchronised with the host step counter."""
+        """The 32-byte Adam step state on the device, (re)synchronised with the host step counter (and the schedule's table, when on)."""
         self._ensure()
+        if self.scheduled:
+            self.lr_table()
         dev = self.brain.flat.device
         ds = self.state.get("dev")
         if ds is None or ds.device != dev:
@@ -140,8 +235,16 @@ class FusedClampAdam:
         return ds
 
     def enqueue_dev_step(self):
-        """ivosw_clamp_adam_dev on the current stream (inside a capture: recorded); the caller bumps the host counter per replay."""
+        """ivosw_clamp_adam_dev (ivosw_clamp_adam_dev_sched on the poly schedule) on the current stream (inside a capture: recorded); the
+        caller bumps the host counter per replay."""
         g, b = self.param_groups[0], self.brain
+        if self.scheduled:
+            L.check(L.lib().ivosw_clamp_adam_dev_sched(L.dptr(b.flat), L.dptr(b.flat_grad), L.dptr(self.state["exp_avg"]),
+                                                       L.dptr(self.state["exp_avg_sq"]), L.BRAIN_NPARAMS, L.dptr(self.state["dev"]),
+                                                       L.dptr(self.lr_table()), self.schedule()[3], g["betas"][0], g["betas"][1], g["eps"],
+                                                       g["weight_decay"], g["clamp"], self.grad_scale, L.stream_ptr(b.flat.device)),
+                    "clamp_adam_dev_sched")
+            return
         L.check(L.lib().ivosw_clamp_adam_dev(L.dptr(b.flat), L.dptr(b.flat_grad), L.dptr(self.state["exp_avg"]),
                                              L.dptr(self.state["exp_avg_sq"]), L.BRAIN_NPARAMS, L.dptr(self.state["dev"]),
                                              g["lr"], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], g["clamp"],
@@ -153,10 +256,15 @@ class FusedClampAdam:
 
     def hyper(self):
         g = self.param_groups[0]
-        return (self.kind, float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]), float(g["clamp"]))
+        return (self.kind, float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"]), float(g["clamp"])) + \
+            self._schedule_hyper()
 
     def onecall_tail(self):
         g, s = self.param_groups[0], self.state
+        if self.scheduled:
+            return "ivosw_dqn_step_drawn_sched", (L.dptr(s["exp_avg"]), L.dptr(s["exp_avg_sq"]), L.dptr(s["dev"]), L.dptr(self.lr_table()),
+                                                  self.schedule()[3], g["betas"][0], g["betas"][1], g["eps"], g["weight_decay"], g["clamp"],
+                                                  self.grad_scale)
         return "ivosw_dqn_step_drawn_ex", (L.dptr(s["exp_avg"]), L.dptr(s["exp_avg_sq"]), L.dptr(s["dev"]), g["lr"], g["betas"][0],
                                            g["betas"][1], g["eps"], g["weight_decay"], g["clamp"], self.grad_scale)
 
@@ -167,23 +275,27 @@ class FusedClampAdam:
 
     def load_state_dict(self, sd):
         self._ensure()
+        self._load_schedule(sd)
         self.state["step"] = int(sd["state"]["step"])
         self.state["exp_avg"].copy_(sd["state"]["exp_avg"])
         self.state["exp_avg_sq"].copy_(sd["state"]["exp_avg_sq"])
 
 
-class FusedClampSGD:
+class FusedClampSGD(_LrSchedule):
     """``optim.SGD(params, lr, momentum, dampening=0, weight_decay, nesterov)`` + the reference's grad clamp, as one kernel over the flat
     arena (ivosw_clamp_sgd).  The momentum buffer starts at zero, which makes torch's first step (buffer = d) the ordinary update, so
     nothing but the buffer carries over between steps: a captured step replays the update as it stands.  ``state["step"]`` only counts
-    the updates on the host.  Same interface as FusedClampAdam."""
+    the updates on the host — except on the poly schedule, whose captured updates keep a step counter on the device too (``dev_state``;
+    ivosw_clamp_sgd_dev_sched).  Same interface as FusedClampAdam."""
 
     kind = "sgd"
 
-    def __init__(self, brain, lr, weight_decay, momentum=0.0, nesterov=False, clamp=1.0):
+    def __init__(self, brain, lr, weight_decay, momentum=0.0, nesterov=False, clamp=1.0, lr_schedule="constant", lr_pow=None,
+                 lr_total_steps=None):
         self.brain = brain
         self.param_groups = [dict(params=list(brain.parameters()), lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay,
                                   nesterov=nesterov, clamp=clamp)]
+        self._init_schedule(lr_schedule, lr_pow, lr_total_steps)
         self.state = dict(step=0, momentum_buffer=None)
         self.grad_scale = 1.0
 
@@ -197,30 +309,60 @@ class FusedClampSGD:
 
     def step(self):
         self._ensure()
+        lr = self.current_lr()
         self.state["step"] += 1
-        self.enqueue_dev_step()
+        self._clamp_sgd(lr)
 
-    def dev_state(self):
-        """The device state of the update: the momentum buffer (there is no step counter to synchronise)."""
-        self._ensure()
-        return self.state["momentum_buffer"]
-
-    def enqueue_dev_step(self):
-        """ivosw_clamp_sgd on the current stream (inside a capture: recorded as it is)."""
+    def _clamp_sgd(self, lr):
         g, b = self.param_groups[0], self.brain
-        L.check(L.lib().ivosw_clamp_sgd(L.dptr(b.flat), L.dptr(b.flat_grad), L.dptr(self.state["momentum_buffer"]), L.BRAIN_NPARAMS, g["lr"],
+        L.check(L.lib().ivosw_clamp_sgd(L.dptr(b.flat), L.dptr(b.flat_grad), L.dptr(self.state["momentum_buffer"]), L.BRAIN_NPARAMS, lr,
                                         g["momentum"], g["weight_decay"], int(g["nesterov"]), g["clamp"], self.grad_scale,
                                         L.stream_ptr(b.flat.device)), "clamp_sgd")
 
+    def dev_state(self):
+        """The device state of the update: the momentum buffer.  On the poly schedule also the 8-byte step counter on the device
+        (``state["dev"]``), (re)synchronised with the host counter as FusedClampAdam's, and the schedule's table."""
+        self._ensure()
+        if self.scheduled:
+            self.lr_table()
+            dev = self.brain.flat.device
+            ds = self.state.get("dev")
+            if ds is None or ds.device != dev:
+                ds = torch.zeros(L.lib().ivosw_sgd_state_bytes(), dtype=torch.uint8, device=dev)
+                self.state["dev"], self.state["dev_step"] = ds, 0
+            if self.state["dev_step"] != self.state["step"]:
+                ds[0:4].copy_(torch.from_numpy(np.array([self.state["step"]], dtype=np.int32).view(np.uint8)))
+                self.state["dev_step"] = self.state["step"]
+        return self.state["momentum_buffer"]
+
+    def enqueue_dev_step(self):
+        """ivosw_clamp_sgd on the current stream (inside a capture: recorded as it is); on the poly schedule ivosw_clamp_sgd_dev_sched,
+        which advances the device step counter."""
+        if not self.scheduled:
+            self._clamp_sgd(self.param_groups[0]["lr"])
+            return
+        g, b = self.param_groups[0], self.brain
+        L.check(L.lib().ivosw_clamp_sgd_dev_sched(L.dptr(b.flat), L.dptr(b.flat_grad), L.dptr(self.state["momentum_buffer"]), L.BRAIN_NPARAMS,
+                                                  L.dptr(self.state["dev"]), L.dptr(self.lr_table()), self.schedule()[3], g["momentum"],
+                                                  g["weight_decay"], int(g["nesterov"]), g["clamp"], self.grad_scale,
+                                                  L.stream_ptr(b.flat.device)), "clamp_sgd_dev_sched")
+
     def note_dev_steps(self, n=1):
         self.state["step"] += n
+        if "dev" in self.state:
+            self.state["dev_step"] = self.state["step"]
 
     def hyper(self):
         g = self.param_groups[0]
-        return (self.kind, float(g["lr"]), float(g["momentum"]), bool(g["nesterov"]), float(g["weight_decay"]), float(g["clamp"]))
+        return (self.kind, float(g["lr"]), float(g["momentum"]), bool(g["nesterov"]), float(g["weight_decay"]), float(g["clamp"])) + \
+            self._schedule_hyper()
 
     def onecall_tail(self):
         g = self.param_groups[0]
+        if self.scheduled:
+            return "ivosw_dqn_step_drawn_sgd_sched", (L.dptr(self.state["momentum_buffer"]), L.dptr(self.state["dev"]), L.dptr(self.lr_table()),
+                                                      self.schedule()[3], g["momentum"], g["weight_decay"], int(g["nesterov"]), g["clamp"],
+                                                      self.grad_scale)
         return "ivosw_dqn_step_drawn_sgd", (L.dptr(self.state["momentum_buffer"]), g["lr"], g["momentum"], g["weight_decay"],
                                             int(g["nesterov"]), g["clamp"], self.grad_scale)
 
@@ -234,6 +376,7 @@ class FusedClampSGD:
         if "momentum_buffer" not in st or "exp_avg" in st:
             raise ValueError("FusedClampSGD.load_state_dict: not an SGD state dict (an Adam one has exp_avg / exp_avg_sq)")
         self._ensure()
+        self._load_schedule(sd)
         self.state["step"] = int(st["step"])
         self.state["momentum_buffer"].copy_(st["momentum_buffer"])
 
@@ -247,6 +390,7 @@ class Agent(nn.Module):
         self.memory_size = a.memory_size
         self.GAMMA = a.gamma
         self.loss_kind, self.huber_delta = self._loss_option(a)
+        self.lr_schedule, self.lr_pow, self.lr_total_steps = self._lr_schedule_option(a)
         self.EPS_START, self.EPS_END, self.EPS_DECAY = a.eps_start, a.eps_end, a.eps_decay
         self.steps_done = 0
         self.update_rate = a.update_rate
@@ -264,11 +408,12 @@ class Agent(nn.Module):
         self.loss_capacity = 32
         self.loss_avg = 0
         self.optimizer_kind, self.momentum, self.nesterov = self._optimizer_option(a)
+        sched = dict(lr_schedule=self.lr_schedule, lr_pow=self.lr_pow, lr_total_steps=self.lr_total_steps)
         if self.optimizer_kind == "sgd":
             self.optimizer = FusedClampSGD(self.policy_net, lr=a.lr, weight_decay=a.weight_decay, momentum=self.momentum,
-                                           nesterov=self.nesterov)
+                                           nesterov=self.nesterov, **sched)
         else:
-            self.optimizer = FusedClampAdam(self.policy_net, lr=a.lr, weight_decay=a.weight_decay)
+            self.optimizer = FusedClampAdam(self.policy_net, lr=a.lr, weight_decay=a.weight_decay, **sched)
         self._ws = L.Workspace()
         self._loss_dev = None
 
@@ -303,6 +448,14 @@ class Agent(nn.Module):
         if kind == "sgd" and nesterov and momentum == 0:
             raise ValueError("agent.nesterov needs agent.momentum > 0 (as torch.optim.SGD)")
         return kind, float(momentum), nesterov
+
+    @staticmethod
+    def _lr_schedule_option(a):
+        """cfg.agent.lr_schedule ("constant", the reference's fixed lr and the default; or "poly"), cfg.agent.lr_pow (0.9, the reference's
+        config) and cfg.agent.lr_total_steps (N, required by "poly"; 0 = unset): read with .get, so a config without the keys keeps the
+        constant lr; lr_pow and N are only checked under "poly".  Returns (schedule, lr_pow, N), (schedule, None, None) for "constant";
+        anything else is refused (lr_schedule_option), before anything is allocated."""
+        return lr_schedule_option(a.get("lr_schedule", "constant"), a.get("lr_pow", 0.9), a.get("lr_total_steps", 0))
 
     def _loss_args(self):
         """(loss_kind, huber_delta) as the _ex entries take them (IVOSW_DQN_LOSS_*, fp32)."""
@@ -542,8 +695,8 @@ class CapturedDqnStep:
             raise RuntimeError("the parameter arenas moved (.to() / re-pack) after capture: build a new CapturedDqnStep")
         if self._hyper != self._hyper_now():
             raise RuntimeError("a hyper-parameter (optimizer kind / lr / betas / eps / momentum / nesterov / weight_decay / clamp / grad_scale / "
-                               "gamma / loss kind / huber_delta) changed after capture: the graph replays the captured values - build a new "
-                               "CapturedDqnStep")
+                               "gamma / loss kind / huber_delta / lr schedule: lr_schedule, lr_pow, lr_total_steps) changed after capture: the "
+                               "graph replays the captured values - build a new CapturedDqnStep")
         if self.fused:
             a.optimizer.dev_state()              # resync if an eager step ran in between
         if self.graph is not None:

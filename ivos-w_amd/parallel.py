@@ -184,24 +184,26 @@ class P2PAllReduce:
     def fused_step(self, brain, optimizer):
         """All-reduce of ``brain.flat_grad`` + the update in TWO launches (push; wait + rank-ordered sum + clamp + Adam or SGD):
         ``ivosw_p2p_allreduce_clamp_adam`` / ``ivosw_p2p_allreduce_clamp_sgd`` by ``optimizer.kind``.  flat_grad is left holding the SUM
-        over ranks; the optimizer's step counter advances."""
+        over ranks; the optimizer's step counter advances.  The lr is the optimizer's for this step (``current_lr``: the base lr, or the
+        poly schedule's entry at the step counter before it advances)."""
         from . import _lib as L
         if optimizer.kind not in ("adam", "sgd"):
             raise ValueError(f"P2PAllReduce.fused_step: no fused form for optimizer kind {optimizer.kind!r}")
         optimizer._ensure()
         g = optimizer.param_groups[0]
+        lr = optimizer.current_lr()
         optimizer.state["step"] += 1
         self.epoch += 1
         flat, grad = brain.flat, brain.flat_grad
         if optimizer.kind == "sgd":
             L.check(L.lib().ivosw_p2p_allreduce_clamp_sgd(
                 L.dptr(grad), L.dptr(grad), self.n, self.rank, self.world, self.table, self.epoch, self.timeout_ms, L.dptr(flat),
-                L.dptr(optimizer.state["momentum_buffer"]), g["lr"], g["momentum"], g["weight_decay"], int(g["nesterov"]), g["clamp"],
+                L.dptr(optimizer.state["momentum_buffer"]), lr, g["momentum"], g["weight_decay"], int(g["nesterov"]), g["clamp"],
                 L.stream_ptr(flat.device)), "p2p_allreduce_clamp_sgd")
             return
         L.check(L.lib().ivosw_p2p_allreduce_clamp_adam(
             L.dptr(grad), L.dptr(grad), self.n, self.rank, self.world, self.table, self.epoch, self.timeout_ms, L.dptr(flat),
-            L.dptr(optimizer.state["exp_avg"]), L.dptr(optimizer.state["exp_avg_sq"]), optimizer.state["step"], g["lr"], g["betas"][0],
+            L.dptr(optimizer.state["exp_avg"]), L.dptr(optimizer.state["exp_avg_sq"]), optimizer.state["step"], lr, g["betas"][0],
             g["betas"][1], g["eps"], g["weight_decay"], g["clamp"], L.stream_ptr(flat.device)), "p2p_allreduce_clamp_adam")
 
     def error(self):
