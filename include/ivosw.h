@@ -86,6 +86,17 @@ int ivosw_dqn_loss_grad_ex(const float* policy, const float* target,
                            const float* reward_step, const float* reward_done,
                            int B, int T, float gamma, int loss_kind, float huber_delta, float* grads, float* loss,
                            void* ws, size_t ws_bytes, ivosw_stream_t stream);
+/* Prioritized replay (cfg.agent.replay = "prioritized"): ivosw_dqn_loss_grad_ex with the importance-sampling weights of the minibatch,
+ * weights [B] (ivosw_per_draw_gather).  The same launches, with the weighted head: row b's loss terms become w_b * terms(e1, e2) (loss =
+ * their sum / B, in the same order; w_b * terms is one rounded product) and dLoss/dQsa_b = (w_b * c) * s for dq = c * s (c = 2/B for
+ * MSE, 1/B for Huber; s the sum of the two errors or of the two clamped errors); td_out [B] receives
+ * |e1| + |e2|, what ivosw_per_update takes.  With every weight 1 the results equal ivosw_dqn_loss_grad_ex's bit for bit.  weights and
+ * td_out must not be NULL; the other checks are ivosw_dqn_loss_grad_ex's.                                                          */
+int ivosw_dqn_loss_grad_per(const float* policy, const float* target,
+                            const float* state, const float* new_state, const int64_t* action,
+                            const float* reward_step, const float* reward_done,
+                            int B, int T, float gamma, int loss_kind, float huber_delta, const float* weights, float* td_out,
+                            float* grads, float* loss, void* ws, size_t ws_bytes, ivosw_stream_t stream);
 /* Replaces grad.clamp_(-1,1) + optim.Adam.step (models/agent.py:157-160, :101): g = clamp(grad*grad_scale);
  * g += wd*p; m,v update; p -= lr/(1-b1^t) * m / (sqrt(v)/sqrt(1-b2^t) + eps).  step = t >= 1.
  * grad_scale = 1/world_size after a sum all-reduce, 1 otherwise.                                 */
@@ -185,6 +196,35 @@ int ivosw_replay_draw_gather(const float* old_iou, const float* new_iou, const f
                              const float* reward_done, void* draw_state, int n, int B, int T, int64_t* idx_out,
                              float* state, float* new_state, int64_t* action_out, float* reward_step_out,
                              float* reward_done_out, ivosw_stream_t stream);
+
+/* Prioritized experience replay (Schaul et al. 2016; cfg.agent.replay = "prioritized") on a device sum tree.  A replay of n rows
+ * (1 <= n <= 2^24) keeps a float32 tree [ivosw_per_tree_floats(n)] = [2P], P = the next power of two >= max(n, 2): node 1 is the root,
+ * the children of node i are 2i and 2i+1, the leaf of row r is node P + r (0 for r >= n), slot 0 is unused, and every internal node is
+ * float32(left + right), always recomputed from its two children - the tree is a pure function of its leaves.  per_state is
+ * ivosw_per_state_bytes() bytes on the device: {uint64 seed at byte 0, uint32 draw counter at byte 8 (write it to resume), float
+ * max_priority at byte 16 (1.0 on a fresh replay), the rest the library's (zero)}.
+ * ivosw_per_build: leaves [0, n_old) are copied from old_leaves (device, NULL when n_old = 0), leaves [n_old, n) - rows the tree has not
+ *   seen - are max_priority^alpha, then every internal node is built (log2 P + 1 launches: setup and replay reloads, deterministic).
+ * ivosw_per_draw_gather: draw c (the counter before it advances by one; every call or graph replay advances it) fills slot b < B with
+ *   z = the 64-bit mix of ivosw_replay_draw_index(seed, c, b), u = float32(z >> 40) * 2^-24, x = (tree[1] / B) * (b + u) in fp32; from
+ *   node 1 down: l = tree[2 node], x < l ? go left : (x -= l, go right); row = min(leaf - P, n - 1) (stratified sampling, P(row) =
+ *   leaf / total).  beta_c = beta0 + (1 - beta0) * (min(c, N) / N) in fp32 (beta0 when N = beta_steps = 0), w'_b = (leaf_row * n /
+ *   total)^-beta_c, weights_out[b] = w'_b / max w' (<= 1).  idx_out receives the rows, and the gather is ivosw_replay_gather's on them,
+ *   bit for bit.  One workgroup; B <= 1024.
+ * ivosw_per_update: p_b = td[b] + eps; where a row fills several slots the highest slot wins; its leaf becomes p_b^alpha, every
+ *   ancestor of a touched leaf is recomputed from its children (the tree equals a full rebuild from its leaves, bit for bit), and
+ *   max_priority = max(max_priority, max_b p_b).  One workgroup; rows outside [0, n) are skipped.
+ * Refused (IVOSW_ERR_ARG) before any launch: a NULL pointer, n outside [1, 2^24], n_old outside [0, n], B outside [1, 1024], T < 1,
+ * a negative or non-finite alpha, beta0 outside [0, 1], beta_steps < 0, an eps that is not finite and > 0.                           */
+size_t ivosw_per_state_bytes(void);
+size_t ivosw_per_tree_floats(int n);
+int ivosw_per_build(float* tree, int n, const float* old_leaves, int n_old, void* per_state, float alpha, ivosw_stream_t stream);
+int ivosw_per_draw_gather(const float* old_iou, const float* new_iou, const float* annotated, const float* next_annotated,
+                          const int64_t* action, const float* reward_step, const float* reward_done, const float* tree, void* per_state,
+                          int n, int B, int T, float beta0, int beta_steps, int64_t* idx_out, float* weights_out, float* state,
+                          float* new_state, int64_t* action_out, float* reward_step_out, float* reward_done_out, ivosw_stream_t stream);
+int ivosw_per_update(float* tree, int n, void* per_state, const int64_t* idx, const float* td, int B, float alpha, float eps,
+                     ivosw_stream_t stream);
 
 /* One single-GPU training step of Agent.update_agent's loop (models/agent.py:128-160 minus the host coin of the target sync) as ONE
  * call and EIGHT launches: ivosw_replay_draw_gather + ivosw_dqn_loss_grad + ivosw_clamp_adam_dev with the minibatch draw and gather

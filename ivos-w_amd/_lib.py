@@ -49,6 +49,12 @@ SIGNATURES = {
     "ivosw_replay_draw_state_bytes": (_sz, []),
     "ivosw_replay_draw_index": (C.c_ulonglong, [C.c_ulonglong, C.c_uint, C.c_uint, _i]),
     "ivosw_replay_draw_gather": (_i, [_p] * 8 + [_i, _i, _i] + [_p] * 6 + [_p]),
+    "ivosw_dqn_loss_grad_per": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _i, _f, _p, _p, _p, _p, _p, _sz, _p]),
+    "ivosw_per_state_bytes": (_sz, []),
+    "ivosw_per_tree_floats": (_sz, [_i]),
+    "ivosw_per_build": (_i, [_p, _i, _p, _i, _p, _f, _p]),
+    "ivosw_per_draw_gather": (_i, [_p] * 9 + [_i, _i, _i, _f, _i] + [_p] * 7 + [_p]),
+    "ivosw_per_update": (_i, [_p, _i, _p, _p, _p, _i, _f, _f, _p]),
     "ivosw_dqn_step_drawn": (_i, [_p] * 10 + [_i, _i, _i, _f] + [_p] * 9 + [_sz] + [_p] * 3 + [_f] * 7 + [_p]),
     "ivosw_dqn_step_drawn_ex": (_i, [_p] * 10 + [_i, _i, _i, _f, _i, _f] + [_p] * 9 + [_sz] + [_p] * 3 + [_f] * 7 + [_p]),
     "ivosw_dqn_step_drawn_sgd": (_i, [_p] * 10 + [_i, _i, _i, _f, _i, _f] + [_p] * 9 + [_sz] + [_p, _f, _f, _f, _i, _f, _f] + [_p]),

@@ -65,6 +65,20 @@ __host__ __device__ inline unsigned long long draw_mix(unsigned long long seed, 
     return z ^ (z >> 31);
 }
 
+// Prioritized replay (cfg.agent.replay = "prioritized", dqn.hip): the draw state of the sum-tree draw.  Layout (32 bytes): uint64 seed at
+// byte 0, uint32 draw counter at byte 8 (a caller resumes by writing it), float max_priority at byte 16 (1.0 on a fresh replay); the
+// rest is the library's.
+struct PerState {
+    unsigned long long seed;
+    unsigned counter;
+    unsigned reserved0;
+    float max_priority;
+    unsigned reserved1[3];
+};
+static_assert(sizeof(PerState) == 32, "PerState layout (seed at byte 0, counter at byte 8, max_priority at byte 16)");
+constexpr int PER_N_MAX = 1 << 24;       // rows of a prioritized replay
+constexpr int PER_B_MAX = 1024;          // slots of one draw: one workgroup
+
 // Adam's step counter and bias corrections kept ON the device, so that a captured HIP graph of the DQN step replays
 // correctly: tick advances step, evaluates beta1^t / beta2^t in float64 and publishes step_size / sqrt(bc2).
 // Layout (32 bytes): the step counter is the int32 at byte 16; a caller resumes from host step k by writing k there.

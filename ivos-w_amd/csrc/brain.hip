@@ -1116,12 +1116,14 @@ static void brain_forward_internal(const float* prm, const float* x, int N, int 
 }
 
 // ---------------------------------------------------------------- DQN head: targets, loss, dQ
-// one block; q_next_pol/q_next_tgt/q_state are [B,T]
+// one block; q_next_pol/q_next_tgt/q_state are [B,T].  PER: the weighted head of head_fused_kernel<true> (weights [B] in, td [B] out).
+template <bool PER>
 __global__ __launch_bounds__(256) void dqn_head_kernel(const float* __restrict__ q_np, const float* __restrict__ q_nt,
                                                        const float* __restrict__ q_s, const int64_t* __restrict__ action,
                                                        const float* __restrict__ r_step, const float* __restrict__ r_done,
                                                        int B, int T, float gamma, int loss_kind, float delta,
-                                                       float* __restrict__ dq, float* __restrict__ loss, float* __restrict__ db4) {
+                                                       float* __restrict__ dq, float* __restrict__ loss, float* __restrict__ db4,
+                                                       const float* __restrict__ weights, float* __restrict__ td) {
     __shared__ float red[2][256];
     float l = 0.f, sdq = 0.f;
     for (int b = threadIdx.x; b < B; b += 256) {
@@ -1139,6 +1141,15 @@ __global__ __launch_bounds__(256) void dqn_head_kernel(const float* __restrict__
         a = min(max(a, 0), T - 1);
         const float qsa = q_s[(size_t)b * T + a];
         const float e1 = qsa - y1, e2 = qsa - y2;
+        if (PER) {
+            const float w = weights[b];
+            l += per_weighted(w, dqn_loss_terms(loss_kind, delta, e1, e2));
+            const float d = dqn_dq_w(loss_kind, delta, B, e1, e2, w);
+            dq[b] = d;
+            sdq += d;
+            td[b] = per_td(e1, e2);
+            continue;
+        }
         l += dqn_loss_terms(loss_kind, delta, e1, e2);
         const float d = dqn_dq(loss_kind, delta, B, e1, e2);
         dq[b] = d;
@@ -1310,7 +1321,7 @@ static int check_dqn_loss(const char* who, int loss_kind, float delta) {
 static int dqn_loss_grad_impl(const float* policy, const float* target, const float* state, const float* new_state, const int64_t* action,
                               const float* reward_step, const float* reward_done, int B, int T, float gamma, int loss_kind, float delta,
                               float* grads, float* loss, void* ws, size_t ws_bytes, ivosw_stream_t stream, const EncDraw* draw,
-                              ReduceGroup* defer, bool* folded) {
+                              ReduceGroup* defer, bool* folded, const float* per_weights = nullptr, float* per_td = nullptr) {
     IVOSW_REQUIRE(policy && target && state && new_state && action && reward_step && reward_done && grads && loss && ws,
                   "null pointer");
     IVOSW_REQUIRE(B > 0 && T > 0, "B and T must be positive");
@@ -1374,8 +1385,14 @@ static int dqn_loss_grad_impl(const float* policy, const float* target, const fl
     if (fused) {
         // both nets per launch, then head + decoder backward + dL/dh in one: 4 launches, one stream, no events
         brain_forward_fused(passes, 2, T, st, draw);
-        hipLaunchKernelGGL(head_fused_kernel, dim3(B), dim3(256), 0, st, policy, O_W3, O_W4, q_np, w.tgt.q, q_s, action, reward_step,
-                           reward_done, B, T, gamma, loss_kind, delta, d1_s, hs_s, w.dq, w.dd1c, w.w4term, w.hcc, w.dhc, loss, grads + O_B4);
+        if (per_weights)
+            hipLaunchKernelGGL(head_fused_kernel<true>, dim3(B), dim3(256), 0, st, policy, O_W3, O_W4, q_np, w.tgt.q, q_s, action,
+                               reward_step, reward_done, B, T, gamma, loss_kind, delta, d1_s, hs_s, w.dq, w.dd1c, w.w4term, w.hcc, w.dhc, loss,
+                               grads + O_B4, per_weights, per_td);
+        else
+            hipLaunchKernelGGL(head_fused_kernel<false>, dim3(B), dim3(256), 0, st, policy, O_W3, O_W4, q_np, w.tgt.q, q_s, action,
+                               reward_step, reward_done, B, T, gamma, loss_kind, delta, d1_s, hs_s, w.dq, w.dd1c, w.w4term, w.hcc, w.dhc, loss,
+                               grads + O_B4, nullptr, nullptr);
     } else {
         fork(0);
         brain_forward_internal(policy, new_state, 2 * B, T, w.pol, st, state, B);
@@ -1383,8 +1400,12 @@ static int dqn_loss_grad_impl(const float* policy, const float* target, const fl
         join(1);
 
         // ---- head: Double-DQN targets, loss, dL/dQsa (agent.py:136-151)
-        hipLaunchKernelGGL(dqn_head_kernel, dim3(1), dim3(256), 0, st, q_np, w.tgt.q, q_s, action, reward_step, reward_done,
-                           B, T, gamma, loss_kind, delta, w.dq, loss, grads + O_B4);
+        if (per_weights)
+            hipLaunchKernelGGL(dqn_head_kernel<true>, dim3(1), dim3(256), 0, st, q_np, w.tgt.q, q_s, action, reward_step, reward_done,
+                               B, T, gamma, loss_kind, delta, w.dq, loss, grads + O_B4, per_weights, per_td);
+        else
+            hipLaunchKernelGGL(dqn_head_kernel<false>, dim3(1), dim3(256), 0, st, q_np, w.tgt.q, q_s, action, reward_step, reward_done,
+                               B, T, gamma, loss_kind, delta, w.dq, loss, grads + O_B4, nullptr, nullptr);
 
         // ---- decoder backward on the B rows that carry loss
         hipLaunchKernelGGL(dec_bwd_rows_kernel, dim3(B), dim3(128), 0, st, policy, w.dq, action, d1_s, hs_s, T, w.dd1c,
@@ -1556,6 +1577,17 @@ extern "C" int ivosw_dqn_loss_grad_ex(const float* policy, const float* target, 
     IVOSW_ON_DEVICE_OF(grads);
     return dqn_loss_grad_impl(policy, target, state, new_state, action, reward_step, reward_done, B, T, gamma, loss_kind, huber_delta, grads,
                               loss, ws, ws_bytes, stream, nullptr, nullptr, nullptr);
+}
+
+extern "C" int ivosw_dqn_loss_grad_per(const float* policy, const float* target, const float* state,
+                                       const float* new_state, const int64_t* action, const float* reward_step,
+                                       const float* reward_done, int B, int T, float gamma, int loss_kind, float huber_delta,
+                                       const float* weights, float* td_out, float* grads, float* loss, void* ws, size_t ws_bytes,
+                                       ivosw_stream_t stream) {
+    IVOSW_REQUIRE(grads && weights && td_out, "null pointer");
+    IVOSW_ON_DEVICE_OF(grads);
+    return dqn_loss_grad_impl(policy, target, state, new_state, action, reward_step, reward_done, B, T, gamma, loss_kind, huber_delta, grads,
+                              loss, ws, ws_bytes, stream, nullptr, nullptr, nullptr, weights, td_out);
 }
 
 extern "C" int ivosw_dqn_loss_grad(const float* policy, const float* target, const float* state,

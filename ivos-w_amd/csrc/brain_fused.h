@@ -339,11 +339,31 @@ __device__ __forceinline__ float dqn_dq(int kind, float delta, int B, float e1, 
     if (kind == IVOSW_DQN_LOSS_HUBER) return (1.0f / (float)B) * (fminf(fmaxf(e1, -delta), delta) + fminf(fmaxf(e2, -delta), delta));
     return (2.0f / (float)B) * (e1 + e2);
 }
+// Prioritized replay: a row's importance-sampling weight w scales its loss terms as one rounded product (never an fma with the sum it
+// feeds), and its dL/dQsa as dqn_dq with w folded into the constant factor, (w c) s: the expression shape of dqn_dq, so that w = 1 gives
+// dqn_dq's bits wherever the compiler contracts the sum the value feeds (the db4 sums do).
+__device__ __forceinline__ float per_weighted(float w, float x) {
+#pragma clang fp contract(off)
+    return w * x;
+}
+// td = |e1| + |e2| for the priority update.  The errors pass through an empty asm first: without it the two-element sum lets the SLP
+// vectorizer pair the computations of e1 and e2, which drops a contraction the unweighted head has (and moves e2 by an ulp).
+__device__ __forceinline__ float per_td(float e1, float e2) {
+    asm volatile("" : "+v"(e1), "+v"(e2));
+    return fabsf(e1) + fabsf(e2);
+}
+__device__ __forceinline__ float dqn_dq_w(int kind, float delta, int B, float e1, float e2, float w) {
+    if (kind == IVOSW_DQN_LOSS_HUBER) return (w * (1.0f / (float)B)) * (fminf(fmaxf(e1, -delta), delta) + fminf(fmaxf(e2, -delta), delta));
+    return (w * (2.0f / (float)B)) * (e1 + e2);
+}
 
 // One workgroup per sample b: Double-DQN target (first maximum of the policy's Q over s', the target net's Q there), the two
 // loss terms' gradient dL/dQ(s, a) (dqn_dq), then the decoder backward on row (b, a): dd1 = dq w4 . (d1 > 0), the dW4 term dq d1,
 // relu(h) for dW3, and dL/dh = (dd1 W3) . (h > 0) as a 128-long dot product per thread.  Block 0 also forms the batch
 // sums (loss, db4) with the reduction tree of dqn_head_kernel.
+// PER (prioritized replay): row b's loss terms and dL/dQsa are scaled by weights[b], and td[b] = |e1| + |e2|; PER = false is the
+// unweighted kernel, unchanged (weights and td are not read).
+template <bool PER>
 __global__ __launch_bounds__(256) void head_fused_kernel(const float* __restrict__ prm, int o_w3, int o_w4,
                                                          const float* __restrict__ q_np, const float* __restrict__ q_nt,
                                                          const float* __restrict__ q_s, const int64_t* __restrict__ action,
@@ -353,7 +373,8 @@ __global__ __launch_bounds__(256) void head_fused_kernel(const float* __restrict
                                                          const float* __restrict__ hs_s, float* __restrict__ dq,
                                                          float* __restrict__ dd1c, float* __restrict__ w4term,
                                                          float* __restrict__ hcc, float* __restrict__ dhc,
-                                                         float* __restrict__ loss, float* __restrict__ db4) {
+                                                         float* __restrict__ loss, float* __restrict__ db4,
+                                                         const float* __restrict__ weights, float* __restrict__ td) {
     __shared__ float dd_s[128];
     __shared__ float d_sh;
     __shared__ float red[2][256];
@@ -393,7 +414,13 @@ __global__ __launch_bounds__(256) void head_fused_kernel(const float* __restrict
             const float y1 = qn * gamma + rs * 0.1f;
             const float y2 = rd * 0.1f;
             const float e1 = qsa - y1, e2 = qsa - y2;
-            const float d = dqn_dq(loss_kind, delta, B, e1, e2);
+            float d;
+            if (PER) {
+                d = dqn_dq_w(loss_kind, delta, B, e1, e2, weights[b]);
+                td[b] = per_td(e1, e2);
+            } else {
+                d = dqn_dq(loss_kind, delta, B, e1, e2);
+            }
             d_sh = d;
             dq[b] = d;
         }
@@ -438,8 +465,14 @@ __global__ __launch_bounds__(256) void head_fused_kernel(const float* __restrict
         as = min(max(as, 0), T - 1);
         const float qsa = q_s[(size_t)s * T + as];
         const float e1 = qsa - y1, e2 = qsa - y2;
-        l += dqn_loss_terms(loss_kind, delta, e1, e2);
-        sdq += dqn_dq(loss_kind, delta, B, e1, e2);
+        if (PER) {
+            const float w = weights[s];
+            l += per_weighted(w, dqn_loss_terms(loss_kind, delta, e1, e2));
+            sdq += dqn_dq_w(loss_kind, delta, B, e1, e2, w);
+        } else {
+            l += dqn_loss_terms(loss_kind, delta, e1, e2);
+            sdq += dqn_dq(loss_kind, delta, B, e1, e2);
+        }
     }
     red[0][tid] = l;
     red[1][tid] = sdq;

@@ -223,9 +223,316 @@ __global__ __launch_bounds__(1024) void clamp_sgd_sched_kernel(float* __restrict
     }
 }
 
+// ---------------------------------------------------------------- prioritized replay (cfg.agent.replay = "prioritized")
+// The sum tree of a replay of n rows: P = the next power of two >= max(n, 2), a float32 array [2P].  Node 1 is the root, the children
+// of node i are 2i and 2i + 1, the leaf of row r is node P + r (0 for r >= n), slot 0 is unused, and every internal node is
+// float32(left + right), always recomputed from its two children: the tree is a pure function of its leaves.
+inline int per_leaves(int n) {
+    int P = 2;
+    while (P < n) P <<= 1;
+    return P;
+}
+
+__global__ void per_leaves_kernel(float* __restrict__ tree, int P, int n, const float* __restrict__ old_leaves, int n_old,
+                                  const PerState* __restrict__ st, float alpha) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= P) return;
+    float v = 0.f;
+    if (r < n_old) v = old_leaves[r];
+    else if (r < n) v = powf(st->max_priority, alpha);      // a row the tree has not seen
+    tree[P + r] = v;
+    if (r == 0) tree[0] = 0.f;
+}
+
+__global__ void per_level_kernel(float* __restrict__ tree, int lo) {          // nodes [lo, 2 lo) from their children
+    const int i = lo + blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < 2 * lo) tree[i] = tree[2 * i] + tree[2 * i + 1];
+}
+
+// beta of draw c: beta0 + (1 - beta0) * (min(c, N) / N) in fp32, beta0 when N = 0 (momory_pool.per_beta is the host mirror)
+__device__ __forceinline__ float per_beta(float beta0, int beta_steps, unsigned c) {
+#pragma clang fp contract(off)
+    if (beta_steps == 0) return beta0;
+    const unsigned k = min(c, (unsigned)beta_steps);
+    return beta0 + (1.0f - beta0) * ((float)k / (float)beta_steps);
+}
+
+constexpr int PER_LDS_NODES = 2048;     // nodes [0, 2048): the top 11 levels of the tree, staged in LDS by the draw
+
+// One workgroup.  Draw c = the counter before it advances: slot b descends the tree from the root with
+// x = (total / B) * (b + u), u = float32(draw_mix(seed, c, b) >> 40) * 2^-24 (stratified sampling, P(row) = leaf / total); the top
+// levels come from LDS (one coalesced load), only the last ones are dependent global loads.  Weights w'_b = (leaf * n / total)^-beta_c
+// over their maximum.  Then the gather of replay_gather_kernel for the drawn rows (the same copies: the same bits).
+__global__ __launch_bounds__(1024) void per_draw_gather_kernel(const float* __restrict__ old_iou, const float* __restrict__ new_iou,
+                                                               const float* __restrict__ ann, const float* __restrict__ nann,
+                                                               const int64_t* __restrict__ action, const float* __restrict__ rstep,
+                                                               const float* __restrict__ rdone, const float* __restrict__ tree,
+                                                               PerState* __restrict__ st, int n, int P, int B, int T, float beta0,
+                                                               int beta_steps, int64_t* __restrict__ idx_out, float* __restrict__ weights_out,
+                                                               float* __restrict__ state, float* __restrict__ new_state,
+                                                               int64_t* __restrict__ action_out, float* __restrict__ rstep_out,
+                                                               float* __restrict__ rdone_out) {
+#pragma clang fp contract(off)
+    __shared__ float top[PER_LDS_NODES];
+    __shared__ int rows[PER_B_MAX];
+    __shared__ float wmax[PER_B_MAX / 64];
+    const int tid = threadIdx.x;
+    const int ntop = min(PER_LDS_NODES, 2 * P);
+    for (int i = tid; i < ntop; i += blockDim.x) top[i] = tree[i];
+    const unsigned c = st->counter;
+    const unsigned long long seed = st->seed;
+    __syncthreads();
+    float wp = 0.f;
+    if (tid < B) {
+        const float u = (float)(draw_mix(seed, c, (unsigned)tid) >> 40) * 0x1p-24f;
+        const float total = top[1];
+        float x = (total / (float)B) * ((float)tid + u);
+        int node = 1;
+        while (node < P) {
+            const int l_at = 2 * node;
+            const float l = l_at < ntop ? top[l_at] : tree[l_at];
+            if (x < l) {
+                node = l_at;
+            } else {
+                x -= l;
+                node = l_at + 1;
+            }
+        }
+        const int row = min(node - P, n - 1);
+        const float leaf = P + row < ntop ? top[P + row] : tree[P + row];
+        wp = powf(leaf * (float)n / total, -per_beta(beta0, beta_steps, c));
+        rows[tid] = row;
+        idx_out[tid] = row;
+    }
+    float m = wp;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((tid & 63) == 0) wmax[tid >> 6] = m;
+    __syncthreads();
+    if (tid < B) {
+        float mx = wmax[0];
+        for (int w = 1; w < (int)(blockDim.x >> 6); ++w) mx = fmaxf(mx, wmax[w]);
+        weights_out[tid] = wp / mx;
+        const int src = rows[tid];
+        action_out[tid] = action[src];
+        rstep_out[tid] = rstep[src];
+        rdone_out[tid] = rdone[src];
+    }
+    for (int i = tid; i < B * T; i += blockDim.x) {
+        const int b = i / T;
+        const size_t s = (size_t)rows[b] * T + (i - b * T), d = (size_t)i * 2;
+        state[d] = old_iou[s];
+        state[d + 1] = ann[s];
+        new_state[d] = new_iou[s];
+        new_state[d + 1] = nann[s];
+    }
+    if (tid == 0) st->counter = c + 1;      // every thread read c before the barrier above
+}
+
+// One workgroup.  Slot b's priority is p_b = td_b + eps; the highest slot of a row wins, and its leaf becomes p_b^alpha;
+// max_priority = max(max_priority, max_b p_b).  The winners' rows are ranked (sorted), so that at every level the touched nodes form a
+// sorted list in which a touched sibling is the next entry: entry i (thread i) owns its node while it lives, absorbs its right sibling
+// when that is touched too, and takes an untouched sibling from registers - all of those were loaded from the tree up front, before
+// anything was written (a node this launch writes is never read back from memory).  Every touched node, leaves included, is written
+// once at the end, so the tree equals a full rebuild from its leaves bit for bit.  Rows outside [0, n) are skipped.
+__global__ __launch_bounds__(1024) void per_update_kernel(float* __restrict__ tree, PerState* __restrict__ st, int n, int P, int L,
+                                                          const int64_t* __restrict__ idx, const float* __restrict__ td, int B, float alpha,
+                                                          float eps) {
+#pragma clang fp contract(off)
+    constexpr int LMAX = 24;                 // log2 of the largest P (PER_N_MAX rows)
+    __shared__ int slot_row[PER_B_MAX];
+    __shared__ int win_s[PER_B_MAX];
+    __shared__ int node_s[PER_B_MAX];
+    __shared__ float val_s[PER_B_MAX];
+    __shared__ int nxt_s[PER_B_MAX];
+    __shared__ int dead_s[PER_B_MAX];
+    __shared__ float pmax[PER_B_MAX / 64];
+    __shared__ int m_s;
+    const int tid = threadIdx.x;
+    int row = -1;
+    float p = -INFINITY;
+    if (tid < B) {
+        const int64_t r = idx[tid];
+        row = (r >= 0 && r < n) ? (int)r : -1;
+        p = td[tid] + eps;
+        slot_row[tid] = row;
+    }
+    const float old_max = st->max_priority;
+    float m = p;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+    if ((tid & 63) == 0) pmax[tid >> 6] = m;
+    if (tid == 0) m_s = 0;
+    __syncthreads();
+    bool win = row >= 0;
+    for (int b2 = tid + 1; win && b2 < B; ++b2) win = slot_row[b2] != row;
+    if (tid < B) win_s[tid] = win;
+    __syncthreads();
+    if (win) {
+        int rank = 0;
+        for (int b2 = 0; b2 < B; ++b2) rank += (win_s[b2] && slot_row[b2] < row);
+        node_s[rank] = P + row;
+        val_s[rank] = powf(p, alpha);
+        atomicAdd(&m_s, 1);
+    }
+    __syncthreads();
+    const int cnt = m_s;
+    const bool act = tid < cnt;
+    const int leaf = act ? node_s[tid] : 0;
+    float v = act ? val_s[tid] : 0.f;
+    float sib[LMAX];
+#pragma unroll
+    for (int k = 0; k < LMAX; ++k) sib[k] = tree[(leaf >> k) ^ 1];     // unconditional, all in flight at once: always in bounds
+                                                                        // (leaf >> k < 2 past the root, and leaf = 0 off the list)
+    if (act) {
+        nxt_s[tid] = tid + 1 < cnt ? tid + 1 : -1;
+        dead_s[tid] = 0;
+    }
+    float outv[LMAX + 1];
+    outv[0] = v;
+    unsigned live_levels = act ? 1u : 0u;
+    bool alive = act;
+    int nd = leaf;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < LMAX; ++k) {
+        if (k >= L) continue;                // uniform: every thread sees the same L
+        int j = -1, jn = -1;
+        float sv = 0.f;
+        bool absorb = false;
+        if (alive) {
+            j = nxt_s[tid];
+            if (!(nd & 1) && j >= 0 && node_s[j] == nd + 1) {
+                absorb = true;
+                sv = val_s[j];
+                jn = nxt_s[j];
+            }
+        }
+        __syncthreads();
+        if (absorb) {
+            dead_s[j] = 1;
+            nxt_s[tid] = jn;
+        }
+        __syncthreads();
+        if (alive) {
+            if (dead_s[tid]) {
+                alive = false;
+            } else {
+                v = (nd & 1) ? sib[k] + v : v + (absorb ? sv : sib[k]);
+                nd >>= 1;
+                node_s[tid] = nd;
+                val_s[tid] = v;
+                outv[k + 1] = v;
+                live_levels |= 1u << (k + 1);
+            }
+        }
+        __syncthreads();
+    }
+    if (act) {
+#pragma unroll
+        for (int k = 0; k <= LMAX; ++k)
+            if (live_levels & (1u << k)) tree[leaf >> k] = outv[k];
+    }
+    if (tid == 0) {
+        float mx = old_max;
+        for (int w = 0; w < (int)(blockDim.x >> 6); ++w) mx = fmaxf(mx, pmax[w]);
+        st->max_priority = mx;
+    }
+}
+
 }  // namespace ivosw
 
 using namespace ivosw;
+
+// ---------------------------------------------------------------- prioritized replay: entries
+static int check_per_n(const char* who, int n) {
+    if (n < 1 || n > PER_N_MAX) {
+        set_error("%s: n must be in [1, 2^24], got %d", who, n);
+        return IVOSW_ERR_ARG;
+    }
+    return IVOSW_OK;
+}
+
+static int check_per_alpha(const char* who, float alpha) {
+    if (!(std::isfinite(alpha) && alpha >= 0.f)) {
+        set_error("%s: alpha must be finite and >= 0, got %g", who, (double)alpha);
+        return IVOSW_ERR_ARG;
+    }
+    return IVOSW_OK;
+}
+
+static int check_per_batch(const char* who, int B) {
+    if (B < 1 || B > PER_B_MAX) {
+        set_error("%s: B must be in [1, %d], got %d", who, PER_B_MAX, B);
+        return IVOSW_ERR_ARG;
+    }
+    return IVOSW_OK;
+}
+
+static int per_block(int B) { return std::max(256, (B + 63) / 64 * 64); }
+
+static int per_log2(int P) {
+    int L = 0;
+    while ((1 << L) < P) ++L;
+    return L;
+}
+
+extern "C" size_t ivosw_per_state_bytes(void) { return sizeof(PerState); }
+
+extern "C" size_t ivosw_per_tree_floats(int n) { return (n < 1 || n > PER_N_MAX) ? 0 : 2 * (size_t)per_leaves(n); }
+
+extern "C" int ivosw_per_build(float* tree, int n, const float* old_leaves, int n_old, void* per_state, float alpha, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(tree && per_state, "null pointer");
+    if (const int rc = check_per_n("ivosw_per_build", n)) return rc;
+    IVOSW_REQUIRE(n_old >= 0 && n_old <= n, "n_old must be in [0, n]");
+    IVOSW_REQUIRE(n_old == 0 || old_leaves, "null old_leaves with n_old > 0");
+    if (const int rc = check_per_alpha("ivosw_per_build", alpha)) return rc;
+    IVOSW_ON_DEVICE_OF(tree);
+    hipStream_t st = as_stream(stream);
+    const int P = per_leaves(n);
+    hipLaunchKernelGGL(per_leaves_kernel, dim3((P + 255) / 256), dim3(256), 0, st, tree, P, n, old_leaves, n_old,
+                       static_cast<const PerState*>(per_state), alpha);
+    for (int lo = P / 2; lo >= 1; lo >>= 1)
+        hipLaunchKernelGGL(per_level_kernel, dim3((lo + 255) / 256), dim3(256), 0, st, tree, lo);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_per_draw_gather(const float* old_iou, const float* new_iou, const float* annotated, const float* next_annotated,
+                                     const int64_t* action, const float* reward_step, const float* reward_done, const float* tree,
+                                     void* per_state, int n, int B, int T, float beta0, int beta_steps, int64_t* idx_out,
+                                     float* weights_out, float* state, float* new_state, int64_t* action_out, float* reward_step_out,
+                                     float* reward_done_out, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(old_iou && new_iou && annotated && next_annotated && action && reward_step && reward_done && tree && per_state,
+                  "null input pointer");
+    IVOSW_REQUIRE(idx_out && weights_out && state && new_state && action_out && reward_step_out && reward_done_out, "null output pointer");
+    if (const int rc = check_per_n("ivosw_per_draw_gather", n)) return rc;
+    if (const int rc = check_per_batch("ivosw_per_draw_gather", B)) return rc;
+    IVOSW_REQUIRE(T >= 1, "T must be positive");
+    IVOSW_REQUIRE(beta0 >= 0.f && beta0 <= 1.f, "beta0 must be in [0, 1]");
+    IVOSW_REQUIRE(beta_steps >= 0, "beta_steps must be >= 0");
+    IVOSW_ON_DEVICE_OF(state);
+    hipLaunchKernelGGL(per_draw_gather_kernel, dim3(1), dim3(per_block(B)), 0, as_stream(stream), old_iou, new_iou, annotated,
+                       next_annotated, action, reward_step, reward_done, tree, static_cast<PerState*>(per_state), n, per_leaves(n), B, T,
+                       beta0, beta_steps, idx_out, weights_out, state, new_state, action_out, reward_step_out, reward_done_out);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_per_update(float* tree, int n, void* per_state, const int64_t* idx, const float* td, int B, float alpha, float eps,
+                                ivosw_stream_t stream) {
+    IVOSW_REQUIRE(tree && per_state && idx && td, "null pointer");
+    if (const int rc = check_per_n("ivosw_per_update", n)) return rc;
+    if (const int rc = check_per_batch("ivosw_per_update", B)) return rc;
+    if (const int rc = check_per_alpha("ivosw_per_update", alpha)) return rc;
+    IVOSW_REQUIRE(std::isfinite(eps) && eps > 0.f, "eps must be finite and > 0");
+    IVOSW_ON_DEVICE_OF(tree);
+    const int P = per_leaves(n);
+    hipLaunchKernelGGL(per_update_kernel, dim3(1), dim3(per_block(B)), 0, as_stream(stream), tree, static_cast<PerState*>(per_state), n, P,
+                       per_log2(P), idx, td, B, alpha, eps);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
 
 extern "C" int ivosw_clamp_sgd(float* params, const float* grads, float* momentum_buf, int n, float lr, float momentum, float weight_decay,
                                int nesterov, float clamp, float grad_scale, ivosw_stream_t stream) {

@@ -66,8 +66,11 @@ DEFAULTS = dict(
                eps_k=5, eps_decay=500, update_rate=0.05, train_batch_size=32,
                loss="mse", huber_delta=1.0,    # DQN objective: the reference's two-term MSE, or "huber" (threshold huber_delta)
                nesterov=False,    # update: optimizer "adam" (the reference's) or "sgd" (clamp + SGD with momentum, nesterov)
-               lr_schedule="constant", lr_total_steps=0),   # lr: constant (the reference's), or "poly": lr * (1 - min(k, N) / N) ** lr_pow
+               lr_schedule="constant", lr_total_steps=0,    # lr: constant (the reference's), or "poly": lr * (1 - min(k, N) / N) ** lr_pow
                                                             # at update k, N = lr_total_steps (required then)
+               replay="uniform", per_alpha=0.6, per_beta=0.4, per_beta_steps=0, per_eps=1e-6),
+                                   # minibatches: uniform (the reference's shuffle), or "prioritized": PER with priority exponent per_alpha,
+                                   # IS exponent per_beta annealed to 1 over per_beta_steps draws (0: constant), per_eps added to |TD|
     synth=dict(n_sequences=3, n_frames=30, height=120, width=216, max_objects=3, baseline_runs=30),
 )
 
@@ -579,6 +582,10 @@ def run_train(cfg):
     # (Agent.apply_gradients).  Rank 0 alone writes agent.pt / memory_pool.csv / the summaries into the configured directories;
     # the other ranks keep their (identical) working files under <save_result_dir>/rank<r>.
     from . import parallel
+    prioritized = Agent._replay_option(cfg.agent)[0] == "prioritized"         # (a bad PER option is refused here, before anything runs)
+    if prioritized and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or parallel.forced()):
+        raise SystemExit("[ivos-w] agent.replay=prioritized runs on one GPU only: every rank's TD errors would update its own sum tree "
+                         "and the replicas would diverge (data-parallel PER needs an all-gather of the drawn rows and TD errors)")
     rank, world = 0, 1
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         rank, world, device = parallel.init()
@@ -640,9 +647,13 @@ def run_train(cfg):
         history.append(dict(epoch=epoch, auc=auc, final=float(np.mean(out["finals"])), agent_loss=float(np.mean(out["losses"])) if out["losses"] else 0.0,
                             reward_done=float(np.mean(out["rewards_done"])), updates=agent.optimizer.state["step"],
                             lr=agent.optimizer.current_lr()))       # the lr of the next update (the schedule's, at `updates`)
+        per_note = ""
+        if prioritized and agent.per_replay is not None:                # beta of the next draw, and the largest priority seen so far
+            history[-1].update(per_beta=agent.per_replay.beta_next(), per_max_priority=agent.per_replay.max_priority())
+            per_note = f" per_beta: {history[-1]['per_beta']:.6g} per_max_priority: {history[-1]['per_max_priority']:.6g}"
         print(f"# epoch {epoch}: auc:{auc:.4f} final {cfg.davis_interactive.metric}: {history[-1]['final'] * 100:.2f} agent loss: "
               f"{history[-1]['agent_loss']:.4f} reward_done: {history[-1]['reward_done']:.3f} updates: {history[-1]['updates']} "
-              f"lr: {history[-1]['lr']:.6g}")
+              f"lr: {history[-1]['lr']:.6g}{per_note}")
     if world > 1:
         # replicas must be bit-identical: compare an exact integer checksum of the parameter bits on every rank
         bits = agent.policy_net.flat.detach().view(torch.int32).to(torch.int64)

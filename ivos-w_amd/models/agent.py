@@ -25,7 +25,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib as L
-from .momory_pool import ReplayMemory
+from .momory_pool import PrioritizedReplay, ReplayMemory, per_params
 
 _ORDER = ("encoder_fc1.weight", "encoder_fc1.bias", "encoder_fc2.weight", "encoder_fc2.bias",
           "lstm_cell.weight_ih", "lstm_cell.weight_hh", "decoder_fc1.weight", "decoder_fc1.bias",
@@ -106,6 +106,20 @@ def lr_schedule_option(kind, lr_pow, total_steps):
     if isinstance(lr_pow, bool) or not isinstance(lr_pow, (int, float)) or not (math.isfinite(lr_pow) and lr_pow >= 0):
         raise ValueError(f"agent.lr_pow must be a finite number >= 0, got {lr_pow!r}")
     return "poly", float(lr_pow), total_steps
+
+
+REPLAYS = ("uniform", "prioritized")
+
+
+def replay_option(kind, alpha=0.6, beta0=0.4, beta_steps=0, eps=1e-6):
+    """(replay, alpha, beta0, N_beta, eps), checked: ("uniform", None, None, None, None) - today's minibatches, the PER values not looked
+    at - or ("prioritized", alpha, beta0, N_beta, eps) with alpha finite >= 0, beta0 in [0, 1], N_beta an int >= 0 and eps finite > 0
+    (momory_pool.per_params).  Anything else is a ValueError."""
+    if not isinstance(kind, str) or kind not in REPLAYS:
+        raise ValueError(f"agent.replay must be 'uniform' or 'prioritized', got {kind!r}")
+    if kind == "uniform":
+        return "uniform", None, None, None, None
+    return ("prioritized",) + per_params(alpha, beta0, beta_steps, eps)
 
 
 def poly_lr_table(lr, lr_pow, total_steps):
@@ -391,6 +405,8 @@ class Agent(nn.Module):
         self.GAMMA = a.gamma
         self.loss_kind, self.huber_delta = self._loss_option(a)
         self.lr_schedule, self.lr_pow, self.lr_total_steps = self._lr_schedule_option(a)
+        self.replay_kind, self.per_alpha, self.per_beta, self.per_beta_steps, self.per_eps = self._replay_option(a)
+        self.per_replay = None                      # the PrioritizedReplay of the episode loop (utils_agent._device_update_loop)
         self.EPS_START, self.EPS_END, self.EPS_DECAY = a.eps_start, a.eps_end, a.eps_decay
         self.steps_done = 0
         self.update_rate = a.update_rate
@@ -457,6 +473,20 @@ class Agent(nn.Module):
         anything else is refused (lr_schedule_option), before anything is allocated."""
         return lr_schedule_option(a.get("lr_schedule", "constant"), a.get("lr_pow", 0.9), a.get("lr_total_steps", 0))
 
+    @staticmethod
+    def _replay_option(a):
+        """cfg.agent.replay ("uniform", today's minibatches and the default; or "prioritized") and the PER keys per_alpha (0.6), per_beta
+        (beta0, 0.4), per_beta_steps (0: beta stays beta0) and per_eps (1e-6): read with .get, so a config without them trains as before;
+        checked by replay_option, before anything is allocated."""
+        return replay_option(a.get("replay", "uniform"), a.get("per_alpha", 0.6), a.get("per_beta", 0.4), a.get("per_beta_steps", 0),
+                             a.get("per_eps", 1e-6))
+
+    def prioritized_replay(self, soa, device, seed):
+        """A PrioritizedReplay over `soa` with this agent's PER options."""
+        if self.replay_kind != "prioritized":
+            raise ValueError("agent.replay is not 'prioritized'")
+        return PrioritizedReplay(soa, device, self.per_alpha, self.per_beta, self.per_beta_steps, self.per_eps, seed=seed)
+
     def _loss_args(self):
         """(loss_kind, huber_delta) as the _ex entries take them (IVOSW_DQN_LOSS_*, fp32)."""
         if self.loss_kind not in self._LOSS_KINDS:
@@ -488,7 +518,9 @@ class Agent(nn.Module):
         return state, new_state, action, r_step, r_done       # 'done' is loaded but unused upstream (agent.py:114)
 
     def loss_and_grads(self, sample):
-        """Forward x3 + loss + backward into policy_net.flat_grad (unclamped). Returns the device loss scalar."""
+        """Forward x3 + loss + backward into policy_net.flat_grad (unclamped). Returns the device loss scalar.  A sample that carries
+        ``weights`` (PrioritizedReplay.sample_prioritized) takes the importance-weighted loss (ivosw_dqn_loss_grad_per), and the rows' TD
+        errors |e1| + |e2| stay on the device in ``sample["td"]`` (or ``self.last_td``) for update_priorities."""
         state, new_state, action, r_step, r_done = self._device_batch(sample)
         B, T, _ = state.shape
         lib = L.lib()
@@ -497,6 +529,17 @@ class Agent(nn.Module):
         if self._loss_dev is None or self._loss_dev.device != state.device:
             self._loss_dev = torch.zeros(1, dtype=torch.float32, device=state.device)
         pn, tn = self.policy_net, self.target_net
+        if "weights" in sample:
+            td = sample.get("td")
+            if td is None:
+                td = torch.empty(B, dtype=torch.float32, device=state.device)
+            self.last_td = td
+            L.check(lib.ivosw_dqn_loss_grad_per(L.dptr(pn.flat), L.dptr(tn.flat), L.dptr(state), L.dptr(new_state),
+                                                L.dptr(action, torch.int64), L.dptr(r_step), L.dptr(r_done), B, T,
+                                                float(np.float32(self.GAMMA)), *self._loss_args(), L.dptr(sample["weights"]), L.dptr(td),
+                                                L.dptr(pn.flat_grad), L.dptr(self._loss_dev), L.dptr(ws), nbytes, L.stream_ptr(state.device)),
+                    "dqn_loss_grad_per")
+            return self._loss_dev
         L.check(lib.ivosw_dqn_loss_grad_ex(L.dptr(pn.flat), L.dptr(tn.flat), L.dptr(state), L.dptr(new_state),
                                            L.dptr(action, torch.int64), L.dptr(r_step), L.dptr(r_done), B, T,
                                            float(np.float32(self.GAMMA)), *self._loss_args(), L.dptr(pn.flat_grad),
@@ -504,6 +547,8 @@ class Agent(nn.Module):
         return self._loss_dev
 
     def update_agent(self, sample):
+        """The reference's update on one collated batch.  It stays unweighted under agent.replay = "prioritized": an explicit batch has no
+        draw probabilities; the prioritized episode loop is utils_agent._device_update_loop."""
         if sample is None:
             print("no input")
             return
@@ -616,7 +661,21 @@ class CapturedDqnStep:
         target sync, i.e. launches a multi-step graph only over steps whose coins do not fire (``GraphedDqnLoop``)."""
         dev = torch.device(agent.device)
         self.agent, self.replay, self.B, self.fused, self.steps = agent, replay, B, fused, int(steps)
-        self.draw = draw_state if draw_state is not None else (replay.draw_state(draw_seed) if draw_seed is not None else None)
+        # a PrioritizedReplay: the step is the composed chain draw + gather (ivosw_per_draw_gather) -> weighted loss and gradients
+        # (ivosw_dqn_loss_grad_per) -> the optimizer's device update -> priority update (ivosw_per_update); the draw state is the replay's
+        self.per = isinstance(replay, PrioritizedReplay)
+        if self.per:
+            if not fused:
+                raise ValueError("a prioritized step needs the fused update (agent.replay = 'prioritized' has no data-parallel form)")
+            if draw_state is not None and draw_state is not replay.state:
+                raise ValueError("a prioritized step draws with its replay's own state (PrioritizedReplay.state)")
+            if draw_seed is not None and (int(draw_seed) & 0xFFFF_FFFF_FFFF_FFFF) != replay.seed:
+                raise ValueError(f"a prioritized step draws with its replay's seed ({replay.seed}), not {draw_seed}")
+            self.draw = replay.state
+            self.weights = torch.empty(B, dtype=torch.float32, device=dev)
+            self.td = torch.zeros(B, dtype=torch.float32, device=dev)
+        else:
+            self.draw = draw_state if draw_state is not None else (replay.draw_state(draw_seed) if draw_seed is not None else None)
         if self.steps > 1 and (self.draw is None or not fused):
             raise ValueError("a multi-step graph needs the in-graph minibatch draw and the fused update")
         T = replay.T
@@ -653,6 +712,18 @@ class CapturedDqnStep:
         for _ in range(self.steps):
             st = L.stream_ptr(dev)
             r = replay
+            if self.per:
+                batch = r.sample_prioritized(B, out=dict(idx=self.idx, weights=self.weights, td=self.td, state=self.state,
+                                                         new_state=self.new_state, action=self.action, reward_step=self.r_step,
+                                                         reward_done=self.r_done))
+                L.check(lib.ivosw_dqn_loss_grad_per(L.dptr(pn.flat), L.dptr(tn.flat), L.dptr(self.state), L.dptr(self.new_state),
+                                                    L.dptr(self.action), L.dptr(self.r_step), L.dptr(self.r_done), B, T,
+                                                    float(np.float32(agent.GAMMA)), *agent._loss_args(), L.dptr(batch["weights"]),
+                                                    L.dptr(self.td), L.dptr(pn.flat_grad), L.dptr(self.loss), L.dptr(self.ws), nbytes, st),
+                        "dqn_loss_grad_per")
+                opt.enqueue_dev_step()
+                r.update_priorities(self.idx, self.td)
+                continue
             if self.draw is not None and fused:
                 # draw + gather folded into the encoder launch, the slab reduction into the update: 8 kernel nodes per step instead of 10
                 if self._onecall_args is None:   # every pointer and scalar is fixed for the life of the object (launch() checks): built once
@@ -686,7 +757,8 @@ class CapturedDqnStep:
         a = self.agent
         if not self.fused:
             return (float(a.GAMMA), a.loss_kind, float(a.huber_delta))
-        return a.optimizer.hyper() + (float(a.optimizer.grad_scale), float(a.GAMMA), a.loss_kind, float(a.huber_delta))
+        per = self.replay.hyper() if self.per else ()
+        return a.optimizer.hyper() + (float(a.optimizer.grad_scale), float(a.GAMMA), a.loss_kind, float(a.huber_delta)) + per
 
     def launch(self):
         """Enqueue one step on the current stream; ``self.loss`` holds the device loss afterwards."""
@@ -695,7 +767,8 @@ class CapturedDqnStep:
             raise RuntimeError("the parameter arenas moved (.to() / re-pack) after capture: build a new CapturedDqnStep")
         if self._hyper != self._hyper_now():
             raise RuntimeError("a hyper-parameter (optimizer kind / lr / betas / eps / momentum / nesterov / weight_decay / clamp / grad_scale / "
-                               "gamma / loss kind / huber_delta / lr schedule: lr_schedule, lr_pow, lr_total_steps) changed after capture: the "
+                               "gamma / loss kind / huber_delta / lr schedule: lr_schedule, lr_pow, lr_total_steps / prioritized replay: "
+                               "per_alpha, per_beta, per_beta_steps, per_eps) changed after capture: the "
                                "graph replays the captured values - build a new CapturedDqnStep")
         if self.fused:
             a.optimizer.dev_state()              # resync if an eager step ran in between

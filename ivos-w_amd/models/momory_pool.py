@@ -300,6 +300,105 @@ def draw_indices(seed, counter, B, n):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- prioritized replay (host side)
+PER_N_MAX = 1 << 24               # rows of a prioritized replay (the device tree's limit)
+PER_B_MAX = 1024                  # slots of one prioritized draw (one workgroup)
+
+
+def per_params(alpha, beta0, beta_steps, eps):
+    """(alpha, beta0, N_beta, eps), checked: alpha finite >= 0, beta0 in [0, 1], N_beta an int >= 0, eps finite > 0.  Anything else is a
+    ValueError (named after the cfg.agent keys)."""
+    num = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.floating, np.integer))
+    if not (num(alpha) and np.isfinite(alpha) and alpha >= 0):
+        raise ValueError(f"agent.per_alpha must be a finite number >= 0, got {alpha!r}")
+    if not (num(beta0) and 0 <= beta0 <= 1):
+        raise ValueError(f"agent.per_beta must be a number in [0, 1], got {beta0!r}")
+    if isinstance(beta_steps, bool) or not isinstance(beta_steps, (int, np.integer)) or not 0 <= beta_steps < 2 ** 31:
+        raise ValueError(f"agent.per_beta_steps must be an int >= 0, got {beta_steps!r}")
+    if not (num(eps) and np.isfinite(eps) and 0 < eps <= float(np.finfo(np.float32).max) and np.float32(eps) > 0):
+        raise ValueError(f"agent.per_eps must be a finite number > 0, got {eps!r}")
+    return float(alpha), float(beta0), int(beta_steps), float(eps)
+
+
+def per_tree_leaves(n):
+    """P: the next power of two >= max(n, 2); the tree of n rows is float32 [2P] (ivosw_per_tree_floats)."""
+    P = 2
+    while P < n:
+        P <<= 1
+    return P
+
+
+def _draw_mix(seed, counter, b):
+    z = (seed + 0x9E3779B97F4A7C15 * (counter + 1) + 0xD1B54A32D192ED03 * (b + 1)) & _M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & _M64
+    return z ^ (z >> 31)
+
+
+def per_beta(beta0, beta_steps, counter):
+    """beta of draw ``counter``: float32(beta0 + (1 - beta0) * (min(c, N) / N)), beta0 when N = 0 (the device's fp32 expression)."""
+    f = np.float32
+    if beta_steps == 0:
+        return f(beta0)
+    return f(f(beta0) + f(f(1) - f(beta0)) * f(f(min(int(counter), int(beta_steps))) / f(beta_steps)))
+
+
+def per_draw_rows(tree, seed, counter, B, n):
+    """Host mirror of the prioritized draw (``ivosw_per_draw_gather``) on a given tree (float32 [2P]): slot b of draw ``counter`` descends
+    from the root with x = (total / B) * (b + u), u = float32(mix >> 40) * 2^-24, going left when x < the left child and right (x -= left)
+    otherwise; the row is min(leaf - P, n - 1).  fp32 arithmetic throughout, as on the device."""
+    f = np.float32
+    tree = np.asarray(tree, dtype=np.float32)
+    P = tree.shape[0] // 2
+    step = f(tree[1] / f(B))
+    out = np.empty(B, dtype=np.int64)
+    for b in range(B):
+        u = f(f(_draw_mix(seed & _M64, counter & 0xFFFFFFFF, b) >> 40) * f(2.0 ** -24))
+        x = f(step * f(f(b) + u))
+        node = 1
+        while node < P:
+            left = tree[2 * node]
+            if x < left:
+                node = 2 * node
+            else:
+                x = f(x - left)
+                node = 2 * node + 1
+        out[b] = min(node - P, n - 1)
+    return out
+
+
+def per_rebuild(tree):
+    """Every internal node of a float32 tree [2P] recomputed from its leaves, float32(left + right) level by level (ivosw_per_build)."""
+    t = np.array(tree, dtype=np.float32)
+    lo = t.shape[0] // 4
+    while lo >= 1:
+        t[lo:2 * lo] = t[2 * lo:4 * lo:2] + t[2 * lo + 1:4 * lo:2]
+        lo //= 2
+    return t
+
+
+def per_update_host(tree, max_priority, idx, td, alpha, eps, n):
+    """Host mirror of ``ivosw_per_update`` -> (tree, max_priority): p_b = td_b + eps, the highest slot of a repeated row wins and sets
+    its leaf to p_b ** alpha (float32), every ancestor of a touched leaf is recomputed from its children, and max_priority =
+    max(max_priority, max_b p_b).  Rows outside [0, n) are skipped.  (numpy's float32 power stands in for the device's powf.)"""
+    f = np.float32
+    t = np.array(tree, dtype=np.float32)
+    P = t.shape[0] // 2
+    p = np.asarray(td, dtype=np.float32) + f(eps)
+    last = {}
+    for b, r in enumerate(np.asarray(idx, dtype=np.int64).tolist()):
+        if 0 <= r < n:
+            last[r] = b
+    for r, b in last.items():
+        t[P + r] = np.power(p[b], f(alpha), dtype=np.float32)
+    nodes = {(P + r) >> 1 for r in last}
+    while nodes:
+        for i in nodes:
+            t[i] = t[2 * i] + t[2 * i + 1]
+        nodes = {i >> 1 for i in nodes if i > 1}
+    return t, f(max(f(max_priority), p.max() if len(p) else f(max_priority)))
+
+
 class DeviceReplay:
     """Device-resident SoA replay buffer; ``sample(idx)`` gathers a minibatch with ``ivosw_replay_gather``,
     ``sample_drawn`` draws the indices on the device as well (``ivosw_replay_draw_gather``)."""
@@ -364,3 +463,117 @@ class DeviceReplay:
             L.dptr(out["idx"], torch.int64), L.dptr(out["state"]), L.dptr(out["new_state"]), L.dptr(out["action"], torch.int64),
             L.dptr(out["reward_step"]), L.dptr(out["reward_done"]), L.stream_ptr(self.device)), "replay_draw_gather")
         return out
+
+
+class PrioritizedReplay(DeviceReplay):
+    """Prioritized experience replay (Schaul et al. 2016; cfg.agent.replay = "prioritized") over the same device SoA: a float32 sum tree
+    [2P] whose leaf r is row r's priority ** alpha, and a 32-byte device state {uint64 seed, uint32 draw counter, float max_priority}.
+    ``sample_prioritized`` draws a minibatch with P(row) = leaf / total (``ivosw_per_draw_gather``: stratified, on the device, the
+    counter advances per call or graph replay) and returns the rows' importance-sampling weights; ``update_priorities`` sets the drawn
+    rows' leaves from their TD errors (``ivosw_per_update``).  A fresh tree gives every row max_priority ** alpha (1 to begin with)."""
+
+    def __init__(self, soa, device, alpha=0.6, beta0=0.4, beta_steps=0, eps=1e-6, seed=0, _carry=None):
+        import torch
+        super().__init__(soa, device)
+        if not 1 <= self.n <= PER_N_MAX:
+            raise ValueError(f"a prioritized replay holds 1 .. {PER_N_MAX} rows, got {self.n}")
+        self.alpha, self.beta0, self.beta_steps, self.eps = per_params(alpha, beta0, beta_steps, eps)
+        self.soa = soa
+        lib = self._lib.lib()
+        assert lib.ivosw_per_state_bytes() == 32
+        self.P = per_tree_leaves(self.n)
+        self.tree = torch.empty(int(lib.ivosw_per_tree_floats(self.n)), dtype=torch.float32, device=self.device)
+        old, n_old = None, 0
+        if _carry is not None:                    # rebuilt(): the draw state carries over, and the leaves when the rows are a prefix
+            self.seed = _carry.seed
+            self.state = _carry.state.clone()
+            if _carry._is_prefix_of(soa):
+                old, n_old = _carry.tree[_carry.P:_carry.P + _carry.n], _carry.n
+        else:
+            self.seed = int(seed) & _M64
+            raw = np.zeros(4, dtype=np.uint64)
+            raw[0] = np.uint64(self.seed)
+            raw[2] = np.uint64(np.array([1.0], dtype=np.float32).view(np.uint32)[0])     # max_priority = 1.0 at byte 16
+            self.state = torch.from_numpy(raw.view(np.uint8).copy()).to(self.device)
+        L = self._lib
+        L.check(lib.ivosw_per_build(L.dptr(self.tree), self.n, L.dptr(old) if old is not None else None, n_old, L.dptr(self.state),
+                                    self._f32(self.alpha), L.stream_ptr(self.device)), "per_build")
+        self.carried = n_old
+
+    @staticmethod
+    def _f32(v):
+        return float(np.float32(v))
+
+    def _is_prefix_of(self, soa):
+        keys = ("old_state_iou", "new_state_iou", "annotated_frames", "next_annotated_frames", "action", "reward_step", "reward_done")
+        for k in keys:
+            a, b = np.asarray(self.soa[k]), np.asarray(soa[k])
+            if b.shape[0] < a.shape[0] or a.shape[1:] != b.shape[1:] or a.dtype != b.dtype or not np.array_equal(a, b[:a.shape[0]]):
+                return False
+        return True
+
+    def rebuilt(self, new_soa):
+        """The replay over reloaded rows: the same options, seed, draw counter and max_priority; when the old rows are a prefix of the
+        new ones (exact host comparison) their leaves are kept, otherwise every leaf starts again from max_priority ** alpha."""
+        return PrioritizedReplay(new_soa, self.device, self.alpha, self.beta0, self.beta_steps, self.eps, _carry=self)
+
+    def hyper(self):
+        """What a captured step bakes in: (alpha, beta0, N_beta, eps) and the tree's address."""
+        return (self.alpha, self.beta0, self.beta_steps, self.eps, self.tree.data_ptr(), self.state.data_ptr())
+
+    def new_batch(self, B):
+        """Preallocated outputs of ``sample_prioritized``: the minibatch dict plus idx, weights and td (filled by the weighted loss)."""
+        import torch
+        d = self.device
+        return dict(idx=torch.empty(B, dtype=torch.int64, device=d), weights=torch.empty(B, dtype=torch.float32, device=d),
+                    td=torch.zeros(B, dtype=torch.float32, device=d), state=torch.empty(B, self.T, 2, dtype=torch.float32, device=d),
+                    new_state=torch.empty(B, self.T, 2, dtype=torch.float32, device=d), action=torch.empty(B, dtype=torch.int64, device=d),
+                    reward_step=torch.empty(B, dtype=torch.float32, device=d), reward_done=torch.empty(B, dtype=torch.float32, device=d))
+
+    def sample_prioritized(self, B, out=None):
+        """Draw B rows by priority on the device (advancing the draw counter) and gather them; returns the minibatch dict with idx [B]
+        int64, weights [B] fp32 (max 1) and a td [B] buffer; ``out`` = a dict from ``new_batch`` (what a captured graph records)."""
+        import torch
+        L = self._lib
+        if not 1 <= B <= PER_B_MAX:
+            raise ValueError(f"a prioritized draw takes 1 .. {PER_B_MAX} rows, got {B}")
+        out = out if out is not None else self.new_batch(B)
+        L.check(L.lib().ivosw_per_draw_gather(
+            L.dptr(self.old_iou), L.dptr(self.new_iou), L.dptr(self.ann), L.dptr(self.next_ann), L.dptr(self.action),
+            L.dptr(self.reward_step), L.dptr(self.reward_done), L.dptr(self.tree), L.dptr(self.state, torch.uint8), self.n, B, self.T,
+            self._f32(self.beta0), self.beta_steps, L.dptr(out["idx"], torch.int64), L.dptr(out["weights"]), L.dptr(out["state"]),
+            L.dptr(out["new_state"]), L.dptr(out["action"], torch.int64), L.dptr(out["reward_step"]), L.dptr(out["reward_done"]),
+            L.stream_ptr(self.device)), "per_draw_gather")
+        return out
+
+    def update_priorities(self, idx, td):
+        """Leaves of the rows ``idx`` [B] int64 <- (td + eps) ** alpha (the highest slot of a repeated row wins), ancestors rebuilt,
+        max_priority raised; all on the device."""
+        import torch
+        L = self._lib
+        L.check(L.lib().ivosw_per_update(L.dptr(self.tree), self.n, L.dptr(self.state, torch.uint8), L.dptr(idx, torch.int64), L.dptr(td),
+                                         idx.numel(), self._f32(self.alpha), self._f32(self.eps), L.stream_ptr(self.device)), "per_update")
+
+    # ---- host readers (synchronise) ----
+    def tree_host(self):
+        return self.tree.cpu().numpy()
+
+    def leaves(self):
+        return self.tree[self.P:self.P + self.n].cpu().numpy()
+
+    def _state_host(self):
+        return self.state.cpu().numpy()
+
+    def counter(self):
+        return int(self._state_host()[8:12].view(np.uint32)[0])
+
+    def set_counter(self, c):
+        import torch
+        self.state[8:12].copy_(torch.from_numpy(np.array([c], dtype=np.uint32).view(np.uint8)))
+
+    def max_priority(self):
+        return float(self._state_host()[16:20].view(np.float32)[0])
+
+    def beta_next(self):
+        """beta of the next draw."""
+        return float(per_beta(self.beta0, self.beta_steps, self.counter()))

@@ -227,8 +227,11 @@ def _device_update_loop(agent, loader, max_steps):
     minibatch on the device and runs loss + gradients + [all-reduce] + clamp + Adam + the host coin, and the losses come back in ONE
     device-to-host copy at the end.  Same minibatches, same arithmetic, same coin and RNG streams as ``agent.update_agent(sample)``
     per collated batch: losses, parameters and the agent's loss ring are bit-identical (tests/test_gpu_agent.py).
-    Returns the list of losses, or None when the loader is not of that kind (``IVOSW_UPDATE_PATH=host`` forces None)."""
+    Returns the list of losses, or None when the loader is not of that kind (``IVOSW_UPDATE_PATH=host`` forces None).
+    Under agent.replay = "prioritized" the minibatches come from the prioritized draw instead (_prioritized_update_loop)."""
     import os
+    if getattr(agent, "replay_kind", "uniform") == "prioritized":
+        return _prioritized_update_loop(agent, loader, max_steps)
     ds = getattr(loader, "dataset", None)
     bs = getattr(loader, "batch_sampler", None)
     if os.environ.get("IVOSW_UPDATE_PATH", "") == "host" or ds is None or bs is None or not hasattr(ds, "to_device_replay"):
@@ -260,6 +263,62 @@ def _device_update_loop(agent, loader, max_steps):
         off += len(st)
         loss_dev[k:k + 1].copy_(agent.loss_and_grads(batch))
         agent.apply_gradients(check_every=len(steps))
+        if np.random.random() < agent.update_rate:
+            print("target_net updated!")
+            agent.sync_target()
+    losses = [float(v) for v in loss_dev.cpu().numpy()]
+    for v in losses:
+        agent.note_loss(v)
+    return losses
+
+
+def _prioritized_update_loop(agent, loader, max_steps):
+    """The episode's DQN updates under agent.replay = "prioritized": one step per batch the loader would have yielded (at most
+    max_steps), each = prioritized draw + gather of loader.batch_size rows (PrioritizedReplay.sample_prioritized) -> importance-weighted
+    loss and gradients -> clamp + Adam / SGD (apply_gradients) -> priority update from the rows' TD errors -> the target-sync coin of
+    np.random, as in the uniform loop.  The replay is the dataset's own, uploaded once; the first one is seeded from torch's global
+    generator, and a reloaded dataset gets the previous tree rebuilt over its rows (PrioritizedReplay.rebuilt: the leaves carry over when
+    the old rows are a prefix of the new ones).  Losses come back in one device-to-host copy at the end.
+    Refused (ValueError): a loader that is not a plain DataLoader over this build's replay dataset, IVOSW_UPDATE_PATH=host, an initialised
+    process group (rank-local TD errors would make the replicas' trees diverge)."""
+    import os
+    why = None
+    ds = getattr(loader, "dataset", None)
+    if os.environ.get("IVOSW_UPDATE_PATH", "") == "host":
+        why = "IVOSW_UPDATE_PATH=host selects the per-batch host update, which has no prioritized draw"
+    elif agent._world()[0] is not None:
+        why = "torch.distributed is initialised: data-parallel prioritized replay is not supported (the ranks' trees would diverge)"
+    elif ds is None or not hasattr(ds, "to_device_replay") or getattr(loader, "batch_size", None) is None \
+            or getattr(loader, "num_workers", 0) != 0 or getattr(loader, "collate_fn", None) is not torch.utils.data.default_collate \
+            or getattr(ds, "transform", None) is not None:
+        why = "the loader is not a plain DataLoader (batch_size, no workers, no transform) over the agent replay dataset"
+    elif torch.device(agent.device).type != "cuda":
+        why = "the prioritized replay lives on the GPU"
+    if why is not None:
+        raise ValueError(f"agent.replay = 'prioritized': {why}")
+    if len(ds) == 0:
+        return []
+    dev = torch.device(agent.device)
+    per = getattr(ds, "_per_replay", None)
+    if per is None or per.device != dev:
+        prev = agent.per_replay
+        if prev is None:
+            seed = int(torch.empty((), dtype=torch.int64).random_().item())
+            per = agent.prioritized_replay(ds.soa, dev, seed)
+        else:
+            per = prev.rebuilt(ds.soa)
+        ds._per_replay = agent.per_replay = per
+    B = int(loader.batch_size)
+    n_steps = min(len(loader), max_steps)
+    if n_steps <= 0:
+        return []
+    batch = per.new_batch(B)
+    loss_dev = torch.empty(n_steps, dtype=torch.float32, device=dev)
+    for k in range(n_steps):
+        per.sample_prioritized(B, out=batch)
+        loss_dev[k:k + 1].copy_(agent.loss_and_grads(batch))
+        agent.apply_gradients(check_every=n_steps)
+        per.update_priorities(batch["idx"], batch["td"])
         if np.random.random() < agent.update_rate:
             print("target_net updated!")
             agent.sync_target()
