@@ -138,6 +138,20 @@ int ivosw_clamp_sgd_dev_sched(float* params, const float* grads, float* momentum
                               ivosw_stream_t stream);
 /* Replaces target_net.load_state_dict(policy_net.state_dict()) (models/agent.py:163-165).        */
 int ivosw_copy_f32(float* dst, const float* src, size_t n, ivosw_stream_t stream);
+/* The target-network rule on the device (cfg.agent.target_update = "soft" | "periodic"), applied after the policy update of a step:
+ *   IVOSW_TARGET_SOFT      target[i] = fmaf(tau, policy[i] - target[i], target[i]), tau in (0, 0.5): Polyak averaging, the bits of
+ *                          torch.Tensor.lerp_(policy, tau) on the CPU (period is not looked at);
+ *   IVOSW_TARGET_PERIODIC  target[i] = policy[i] when k % period == 0, k = the launches since the counter was last written, this one
+ *                          included; otherwise nothing is touched (tau is not looked at).
+ * target_state: ivosw_target_state_bytes() (16) bytes, zeroed before the first step.  The int32 at byte 0 is the step counter, a caller
+ * resumes from host step k by writing k there; every workgroup reads it and the last one of the launch advances it, so a captured
+ * graph replays the rule.  One launch.  Refused before anything is launched (IVOSW_ERR_ARG): a NULL state, an unknown mode, under soft a
+ * tau outside (0, 0.5) or not finite, under periodic a period < 1, NULL or identical arenas, n < 1.                                   */
+#define IVOSW_TARGET_SOFT 1
+#define IVOSW_TARGET_PERIODIC 2
+size_t ivosw_target_state_bytes(void);
+int ivosw_target_update(float* target, const float* policy, int n, int mode, float tau, int period, void* target_state,
+                        ivosw_stream_t stream);
 
 /* ------------------------------------------------------------------ one-shot P2P all-reduce --- */
 /* The data-parallel DQN step's gradient all-reduce (Agent.update_agent under torch.distributed; the reference is single
@@ -277,6 +291,24 @@ int ivosw_dqn_step_drawn_sgd_sched(float* policy, const float* target, const flo
                                    float* grads, float* loss, void* ws, size_t ws_bytes, float* momentum_buf, void* sgd_state,
                                    const float* lr_table, int lr_steps, float momentum, float weight_decay, int nesterov, float clamp,
                                    float grad_scale, ivosw_stream_t stream);
+/* The one-call step of either optimizer with the target-network rule (ivosw_target_update) fused into its last launch: the same eight
+ * launches as ivosw_dqn_step_drawn_{ex,sgd,sched,sgd_sched}, the thread that produces a new policy element also writes the target
+ * element, so `target` is written here.  optimizer = IVOSW_OPT_ADAM: opt_buf0 / opt_buf1 = exp_avg / exp_avg_sq, opt_state = the Adam
+ * state, beta1 / beta2 / eps are read.  IVOSW_OPT_SGD: opt_buf0 = the momentum buffer (opt_buf1 unused), momentum / nesterov are read,
+ * opt_state = the SGD state on the schedule (unused otherwise).  lr_table NULL: the constant `lr`; otherwise the poly table of
+ * lr_steps + 1 entries (see ivosw_clamp_adam_dev_sched; `lr` unused).  Bit-identical to the corresponding entry above followed by
+ * ivosw_target_update, which is what it runs off the fused chain.  Refuses what those entries and ivosw_target_update refuse, and an
+ * unknown optimizer, before anything is launched.                                                                                     */
+#define IVOSW_OPT_ADAM 0
+#define IVOSW_OPT_SGD 1
+int ivosw_dqn_step_drawn_tgt(float* policy, float* target, const float* old_iou, const float* new_iou, const float* annotated,
+                             const float* next_annotated, const int64_t* action, const float* reward_step, const float* reward_done,
+                             void* draw_state, int n, int B, int T, float gamma, int loss_kind, float huber_delta, int64_t* idx_out,
+                             float* state, float* new_state, int64_t* action_out, float* reward_step_out, float* reward_done_out,
+                             float* grads, float* loss, void* ws, size_t ws_bytes, int optimizer, float* opt_buf0, float* opt_buf1,
+                             void* opt_state, float lr, const float* lr_table, int lr_steps, float beta1, float beta2, float eps,
+                             float momentum, int nesterov, float weight_decay, float clamp, float grad_scale, int target_mode, float tau,
+                             int target_period, void* target_state, ivosw_stream_t stream);
 
 /* ------------------------------------------------------------------ assessment front end ------ */
 /* Replaces (tp>0.5) + AssessNet.all2yxhw(scale=1.5) (models/assessment.py:165-166,110-161) with no D2H:

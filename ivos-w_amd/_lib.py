@@ -13,6 +13,8 @@ LIB_PATH = os.path.join(_HERE, "libivosw_hip.so")
 
 F32, BF16, F32X3 = 0, 1, 2
 DQN_LOSS_MSE, DQN_LOSS_HUBER = 0, 1                  # IVOSW_DQN_LOSS_* (include/ivosw.h)
+TARGET_SOFT, TARGET_PERIODIC = 1, 2                  # IVOSW_TARGET_*
+OPT_ADAM, OPT_SGD = 0, 1                             # IVOSW_OPT_*
 BRAIN_NPARAMS = 180993
 ASSESS_NTENSORS = 326
 
@@ -35,6 +37,8 @@ SIGNATURES = {
     "ivosw_sgd_state_bytes": (_sz, []),
     "ivosw_clamp_sgd_dev_sched": (_i, [_p, _p, _p, _i, _p, _p, _i, _f, _f, _i, _f, _f, _p]),
     "ivosw_copy_f32": (_i, [_p, _p, _sz, _p]),
+    "ivosw_target_state_bytes": (_sz, []),
+    "ivosw_target_update": (_i, [_p, _p, _i, _i, _f, _i, _p, _p]),
     "ivosw_p2p_arena_bytes": (_sz, [_i, _sz]),
     "ivosw_p2p_handle_bytes": (_sz, []),
     "ivosw_p2p_alloc": (_i, [_sz, C.POINTER(_p), _p, _sz]),
@@ -60,6 +64,8 @@ SIGNATURES = {
     "ivosw_dqn_step_drawn_sgd": (_i, [_p] * 10 + [_i, _i, _i, _f, _i, _f] + [_p] * 9 + [_sz] + [_p, _f, _f, _f, _i, _f, _f] + [_p]),
     "ivosw_dqn_step_drawn_sched": (_i, [_p] * 10 + [_i, _i, _i, _f, _i, _f] + [_p] * 9 + [_sz] + [_p] * 3 + [_p, _i] + [_f] * 6 + [_p]),
     "ivosw_dqn_step_drawn_sgd_sched": (_i, [_p] * 10 + [_i, _i, _i, _f, _i, _f] + [_p] * 9 + [_sz] + [_p, _p, _p, _i, _f, _f, _i, _f, _f] + [_p]),
+    "ivosw_dqn_step_drawn_tgt": (_i, [_p] * 10 + [_i, _i, _i, _f, _i, _f] + [_p] * 9 + [_sz] + [_i, _p, _p, _p, _f, _p, _i, _f, _f, _f, _f, _i, _f, _f, _f] +
+                                 [_i, _f, _i, _p] + [_p]),
     "ivosw_mask_bbox": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "ivosw_roi_sample": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "ivosw_assess_packed_bytes": (_sz, [_i]),

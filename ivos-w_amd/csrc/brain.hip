@@ -18,6 +18,7 @@
 #include "brain_fused.h"
 #include "brain_bwd.h"
 #include "sgd.h"
+#include "target.h"
 
 namespace ivosw {
 
@@ -1710,6 +1711,80 @@ __global__ __launch_bounds__(1024) void clamp_sgd_reduce_sched_kernel(float* __r
     }
 }
 
+// The one-call tails with the target-network rule fused in (cfg.agent.target_update = "soft" | "periodic", target.h): the thread that
+// has just produced p_new also writes the target element, so the step keeps its eight launches.  The target arena was last read by the
+// head kernel, earlier in the stream.  The update is clamp_adam_dev_reduce[_sched]_kernel's, expression by expression (same bits); both
+// counters are read by every workgroup before the last one (the Adam state's ticket) advances them.
+struct TargetArgs {
+    float* t;
+    TargetDevState* st;
+    int mode;
+    float tau;
+    int period;
+};
+
+template <bool SCHED>
+__global__ __launch_bounds__(1024) void adam_tail_tgt_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                             float* __restrict__ v, int n, AdamDevState* __restrict__ st, ReduceGroup rg,
+                                                             ReduceOffsets ro, float lr_const, const float* __restrict__ lr_table, int lr_steps,
+                                                             float beta1, float beta2, float eps, float wd, float clampv, float gscale,
+                                                             TargetArgs ta) {
+    const float lr = SCHED ? sched_lr(lr_table, lr_steps, st->step) : lr_const;
+    const int k = ta.st->step;
+    const bool fires = target_fires(k, ta.period);
+    const int step = st->step + 1;
+    const double b1t = ipow((double)beta1, step), b2t = ipow((double)beta2, step);
+    const float step_size = (float)((double)lr / (1.0 - b1t)), bc2_sqrt = (float)sqrt(1.0 - b2t);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const float gi = reduce_on_load(g, rg, ro, i);
+        float mi = m[i], vi = v[i];
+        const float pn = clamp_adam_elem(gi, p[i], mi, vi, step_size, bc2_sqrt, beta1, beta2, eps, wd, clampv, gscale);
+        p[i] = pn;
+        m[i] = mi; v[i] = vi;
+        target_elem(ta.t, i, pn, ta.mode, ta.tau, fires);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (atomicAdd(&st->ticket, 1u) == gridDim.x - 1) {
+            st->b1t = b1t; st->b2t = b2t; st->step = step; st->step_size = step_size; st->bc2_sqrt = bc2_sqrt;
+            ta.st->step = k + 1;
+            atomicExch(&st->ticket, 0u);
+        }
+    }
+}
+
+// The SGD tails (clamp_sgd_reduce[_sched]_kernel's update) with the rule fused in.  The constant-lr update has no counter of its own: the
+// ticket is the target state's; the scheduled one advances both counters under the SGD state's.
+template <bool SCHED>
+__global__ __launch_bounds__(1024) void sgd_tail_tgt_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf, int n,
+                                                            SgdDevState* __restrict__ st, ReduceGroup rg, ReduceOffsets ro, float lr_const,
+                                                            const float* __restrict__ lr_table, int lr_steps, float mu, float wd, int nesterov,
+                                                            float clampv, float gscale, TargetArgs ta) {
+    const int ks = SCHED ? st->step : 0;
+    const float lr = SCHED ? sched_lr(lr_table, lr_steps, ks) : lr_const;
+    const int k = ta.st->step;
+    const bool fires = target_fires(k, ta.period);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const float gi = reduce_on_load(g, rg, ro, i);
+        float bi = buf[i];
+        const float pn = clamp_sgd_elem(gi, p[i], bi, lr, mu, wd, nesterov, clampv, gscale);
+        p[i] = pn;
+        buf[i] = bi;
+        target_elem(ta.t, i, pn, ta.mode, ta.tau, fires);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned* ticket = SCHED ? &st->ticket : &ta.st->ticket;
+        if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
+            if (SCHED) st->step = ks + 1;
+            ta.st->step = k + 1;
+            atomicExch(ticket, 0u);
+        }
+    }
+}
+
 extern "C" int ivosw_replay_draw_gather(const float* old_iou, const float* new_iou, const float* annotated, const float* next_annotated,
                                         const int64_t* action, const float* reward_step, const float* reward_done, void* draw_state, int n,
                                         int B, int T, int64_t* idx_out, float* state, float* new_state, int64_t* action_out,
@@ -1725,6 +1800,8 @@ extern "C" int ivosw_clamp_adam_dev_sched(float* params, const float* grads, flo
 extern "C" int ivosw_clamp_sgd_dev_sched(float* params, const float* grads, float* momentum_buf, int n, void* sgd_state, const float* lr_table,
                                          int lr_steps, float momentum, float weight_decay, int nesterov, float clamp, float grad_scale,
                                          ivosw_stream_t stream);
+extern "C" int ivosw_target_update(float* target, const float* policy, int n, int mode, float tau, int period, void* target_state,
+                                   ivosw_stream_t stream);
 
 extern "C" int ivosw_dqn_step_drawn_ex(float* policy, const float* target, const float* old_iou, const float* new_iou, const float* annotated,
                                        const float* next_annotated, const int64_t* action, const float* reward_step, const float* reward_done,
@@ -1927,6 +2004,88 @@ extern "C" int ivosw_dqn_step_drawn_sgd_sched(float* policy, const float* target
         [&] {
             return ivosw_clamp_sgd_dev_sched(policy, grads, momentum_buf, nprm, sgd_state, lr_table, lr_steps, momentum, weight_decay, nesterov,
                                              clamp, grad_scale, stream);
+        });
+}
+
+// The one-call step of any optimizer with the target-network rule in its last launch (cfg.agent.target_update = "soft" | "periodic"): the
+// eight launches of ivosw_dqn_step_drawn_{ex,sgd,sched,sgd_sched}, the last one adam_tail_tgt_kernel / sgd_tail_tgt_kernel, which also
+// writes `target`.  optimizer: IVOSW_OPT_ADAM (opt_buf0 / opt_buf1 = exp_avg / exp_avg_sq, opt_state = the Adam state; beta1, beta2, eps) or
+// IVOSW_OPT_SGD (opt_buf0 = the momentum buffer, opt_buf1 unused; momentum, nesterov; opt_state = the SGD state, needed on the schedule
+// only).  lr_table NULL: the constant `lr`; else the poly schedule's table of lr_steps + 1 entries (`lr` unused).  Off the fused chain: the
+// draw + gather, loss + gradient and update entries, then ivosw_target_update — the same results.
+extern "C" int ivosw_dqn_step_drawn_tgt(float* policy, float* target, const float* old_iou, const float* new_iou, const float* annotated,
+                                        const float* next_annotated, const int64_t* action, const float* reward_step, const float* reward_done,
+                                        void* draw_state, int n, int B, int T, float gamma, int loss_kind, float huber_delta, int64_t* idx_out,
+                                        float* state, float* new_state, int64_t* action_out, float* reward_step_out, float* reward_done_out,
+                                        float* grads, float* loss, void* ws, size_t ws_bytes, int optimizer, float* opt_buf0, float* opt_buf1,
+                                        void* opt_state, float lr, const float* lr_table, int lr_steps, float beta1, float beta2, float eps,
+                                        float momentum, int nesterov, float weight_decay, float clamp, float grad_scale, int target_mode,
+                                        float tau, int target_period, void* target_state, ivosw_stream_t stream) {
+    static const char* who = "ivosw_dqn_step_drawn_tgt";
+    // everything is refused before anything is launched (the un-folded sequence would otherwise advance the draw counter first)
+    if (const int rc = check_target(who, target_state, target_mode, tau, target_period)) return rc;
+    IVOSW_REQUIRE(optimizer == IVOSW_OPT_ADAM || optimizer == IVOSW_OPT_SGD, "unknown optimizer (IVOSW_OPT_ADAM or IVOSW_OPT_SGD)");
+    const bool adam = optimizer == IVOSW_OPT_ADAM, sched = lr_table != nullptr;
+    IVOSW_REQUIRE(policy && target && old_iou && new_iou && annotated && next_annotated && action && reward_step && reward_done && draw_state &&
+                      idx_out && state && new_state && action_out && reward_step_out && reward_done_out && grads && loss && ws && opt_buf0,
+                  "null pointer");
+    IVOSW_REQUIRE(!adam || (opt_buf1 && opt_state), "null pointer (Adam needs exp_avg_sq and its state)");
+    IVOSW_REQUIRE(adam || !sched || opt_state, "null pointer (scheduled SGD needs its state)");
+    IVOSW_REQUIRE(target != policy, "target and policy must be different arenas");
+    IVOSW_REQUIRE(n > 0 && B > 0 && T > 0, "n, B and T must be positive");
+    if (const int rc = check_dqn_loss(who, loss_kind, huber_delta)) return rc;
+    if (sched)
+        if (const int rc = check_lr_table(who, lr_table, lr_steps)) return rc;
+    if (adam) {
+        if (const int rc = check_adam(who, beta1, beta2, eps, weight_decay)) return rc;
+    } else {
+        if (const int rc = check_sgd(who, sched ? 0.f : lr, momentum, weight_decay, nesterov)) return rc;
+    }
+    IVOSW_ON_DEVICE_OF(grads);
+    const bool aligned = ((reinterpret_cast<uintptr_t>(policy) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(opt_buf0) |
+                           (adam ? reinterpret_cast<uintptr_t>(opt_buf1) : 0)) & 15) == 0;
+    if (target_mode == TARGET_SOFT) target_period = 1;      // not looked at under soft; keeps any value off the kernel's modulo
+    const TargetArgs ta{target, static_cast<TargetDevState*>(target_state), target_mode, tau, target_period};
+    const int nprm = IVOSW_BRAIN_NPARAMS;
+    const dim3 grid((nprm + 1023) / 1024), block(1024);
+    hipStream_t hs = as_stream(stream);
+    return dqn_step_drawn_sched_run(
+        who, aligned, policy, target, old_iou, new_iou, annotated, next_annotated, action, reward_step, reward_done, draw_state, n, B, T, gamma,
+        loss_kind, huber_delta, idx_out, state, new_state, action_out, reward_step_out, reward_done_out, grads, loss, ws, ws_bytes, stream,
+        [&](const ReduceGroup& rg, const ReduceOffsets& ro) {
+            if (adam) {
+                AdamDevState* sd = static_cast<AdamDevState*>(opt_state);
+                if (sched)
+                    hipLaunchKernelGGL(adam_tail_tgt_kernel<true>, grid, block, 0, hs, policy, grads, opt_buf0, opt_buf1, nprm, sd, rg, ro, lr, lr_table,
+                                       lr_steps, beta1, beta2, eps, weight_decay, clamp, grad_scale, ta);
+                else
+                    hipLaunchKernelGGL(adam_tail_tgt_kernel<false>, grid, block, 0, hs, policy, grads, opt_buf0, opt_buf1, nprm, sd, rg, ro, lr, lr_table,
+                                       lr_steps, beta1, beta2, eps, weight_decay, clamp, grad_scale, ta);
+            } else {
+                SgdDevState* sd = static_cast<SgdDevState*>(opt_state);
+                if (sched)
+                    hipLaunchKernelGGL(sgd_tail_tgt_kernel<true>, grid, block, 0, hs, policy, grads, opt_buf0, nprm, sd, rg, ro, lr, lr_table, lr_steps,
+                                       momentum, weight_decay, nesterov, clamp, grad_scale, ta);
+                else
+                    hipLaunchKernelGGL(sgd_tail_tgt_kernel<false>, grid, block, 0, hs, policy, grads, opt_buf0, nprm, sd, rg, ro, lr, lr_table, lr_steps,
+                                       momentum, weight_decay, nesterov, clamp, grad_scale, ta);
+            }
+        },
+        [&] {
+            int rc;
+            if (adam && sched)
+                rc = ivosw_clamp_adam_dev_sched(policy, grads, opt_buf0, opt_buf1, nprm, opt_state, lr_table, lr_steps, beta1, beta2, eps, weight_decay,
+                                                clamp, grad_scale, stream);
+            else if (adam)
+                rc = ivosw_clamp_adam_dev(policy, grads, opt_buf0, opt_buf1, nprm, opt_state, lr, beta1, beta2, eps, weight_decay, clamp, grad_scale,
+                                          stream);
+            else if (sched)
+                rc = ivosw_clamp_sgd_dev_sched(policy, grads, opt_buf0, nprm, opt_state, lr_table, lr_steps, momentum, weight_decay, nesterov, clamp,
+                                               grad_scale, stream);
+            else
+                rc = ivosw_clamp_sgd(policy, grads, opt_buf0, nprm, lr, momentum, weight_decay, nesterov, clamp, grad_scale, stream);
+            if (rc == IVOSW_OK) rc = ivosw_target_update(target, policy, nprm, target_mode, tau, target_period, target_state, stream);
+            return rc;
         });
 }
 

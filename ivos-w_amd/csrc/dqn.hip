@@ -3,6 +3,7 @@
 // datasets/agent_dataset.py:71-115 + train_agent.py:177-182 (minibatch assembly).
 #include "adam.h"
 #include "sgd.h"
+#include "target.h"
 
 namespace ivosw {
 
@@ -214,6 +215,45 @@ __global__ __launch_bounds__(1024) void clamp_sgd_sched_kernel(float* __restrict
                                                                int lr_steps, float mu, float wd, int nesterov, float clampv, float gscale) {
     const int k = st->step;
     clamp_sgd_apply<VEC>(p, g, buf, n, sched_lr(lr_table, lr_steps, k), mu, wd, nesterov, clampv, gscale);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (atomicAdd(&st->ticket, 1u) == gridDim.x - 1) {
+            st->step = k + 1;
+            atomicExch(&st->ticket, 0u);
+        }
+    }
+}
+
+// The target-network rule as a launch of its own (target.h: soft = t += tau * (p - t) in one fma, periodic = copy every period-th step),
+// for every chain that does not end in the one-call step's fused tail.  Every workgroup reads the counter, the last one to finish
+// publishes counter + 1 (clamp_sgd_sched_kernel's ticket; 1024-lane workgroups for the same reason).  VEC: 16 bytes per lane and array,
+// the n % 4 tail elements go to the first threads past the vector part.
+template <bool VEC>
+__global__ __launch_bounds__(1024) void target_update_kernel(float* __restrict__ t, const float* __restrict__ p, int n, int mode, float tau,
+                                                             int period, TargetDevState* __restrict__ st) {
+    const int k = st->step;
+    const bool fires = target_fires(k, period);
+    const int id = blockIdx.x * blockDim.x + threadIdx.x;
+    if (mode == TARGET_SOFT || fires) {
+        if (VEC) {
+            const int n4 = n >> 2;
+            if (id < n4) {
+                const float4 p4 = reinterpret_cast<const float4*>(p)[id];
+                float4 t4 = p4;
+                if (mode == TARGET_SOFT) {
+                    t4 = reinterpret_cast<float4*>(t)[id];
+                    t4.x = fmaf(tau, p4.x - t4.x, t4.x); t4.y = fmaf(tau, p4.y - t4.y, t4.y);
+                    t4.z = fmaf(tau, p4.z - t4.z, t4.z); t4.w = fmaf(tau, p4.w - t4.w, t4.w);
+                }
+                reinterpret_cast<float4*>(t)[id] = t4;
+            } else if (id - n4 < (n & 3)) {
+                const int i = 4 * n4 + (id - n4);
+                target_elem(t, i, p[i], mode, tau, fires);
+            }
+        } else if (id < n) {
+            target_elem(t, id, p[id], mode, tau, fires);
+        }
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
         if (atomicAdd(&st->ticket, 1u) == gridDim.x - 1) {
@@ -652,6 +692,28 @@ extern "C" int ivosw_copy_f32(float* dst, const float* src, size_t n, ivosw_stre
         set_error("ivosw_copy_f32: %s", hipGetErrorString(e));
         return IVOSW_ERR_LAUNCH;
     }
+    return IVOSW_OK;
+}
+
+extern "C" size_t ivosw_target_state_bytes(void) { return sizeof(TargetDevState); }
+
+extern "C" int ivosw_target_update(float* target, const float* policy, int n, int mode, float tau, int period, void* target_state,
+                                   ivosw_stream_t stream) {
+    if (const int rc = check_target("ivosw_target_update", target_state, mode, tau, period)) return rc;
+    IVOSW_REQUIRE(target && policy, "null pointer");
+    IVOSW_REQUIRE(target != policy, "target and policy must be different arenas");
+    IVOSW_REQUIRE(n > 0, "n must be positive");
+    IVOSW_ON_DEVICE_OF(target);
+    if (mode == TARGET_SOFT) period = 1;         // not looked at under soft: any value is accepted, none reaches the kernel's modulo
+    TargetDevState* sd = static_cast<TargetDevState*>(target_state);
+    const bool vec = ((reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(policy)) & 15) == 0;
+    if (vec)
+        hipLaunchKernelGGL(target_update_kernel<true>, dim3((n / 4 + 3 + 1023) / 1024), dim3(1024), 0, as_stream(stream), target, policy, n, mode,
+                           tau, period, sd);
+    else
+        hipLaunchKernelGGL(target_update_kernel<false>, dim3((n + 1023) / 1024), dim3(1024), 0, as_stream(stream), target, policy, n, mode, tau,
+                           period, sd);
+    IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }
 

@@ -68,9 +68,12 @@ DEFAULTS = dict(
                nesterov=False,    # update: optimizer "adam" (the reference's) or "sgd" (clamp + SGD with momentum, nesterov)
                lr_schedule="constant", lr_total_steps=0,    # lr: constant (the reference's), or "poly": lr * (1 - min(k, N) / N) ** lr_pow
                                                             # at update k, N = lr_total_steps (required then)
-               replay="uniform", per_alpha=0.6, per_beta=0.4, per_beta_steps=0, per_eps=1e-6),
+               replay="uniform", per_alpha=0.6, per_beta=0.4, per_beta_steps=0, per_eps=1e-6,
                                    # minibatches: uniform (the reference's shuffle), or "prioritized": PER with priority exponent per_alpha,
                                    # IS exponent per_beta annealed to 1 over per_beta_steps draws (0: constant), per_eps added to |TD|
+               target_update="coin", tau=0.005, target_period=20),
+                                   # target net: "coin" (the reference's hard sync with probability update_rate per step), "soft" (Polyak
+                                   # averaging with tau after every step) or "periodic" (hard sync every target_period-th step), on the device
     synth=dict(n_sequences=3, n_frames=30, height=120, width=216, max_objects=3, baseline_runs=30),
 )
 
@@ -583,6 +586,7 @@ def run_train(cfg):
     # the other ranks keep their (identical) working files under <save_result_dir>/rank<r>.
     from . import parallel
     prioritized = Agent._replay_option(cfg.agent)[0] == "prioritized"         # (a bad PER option is refused here, before anything runs)
+    Agent._target_option(cfg.agent)                                           # (so is a bad target option; every mode runs data-parallel)
     if prioritized and (int(os.environ.get("WORLD_SIZE", "1")) > 1 or parallel.forced()):
         raise SystemExit("[ivos-w] agent.replay=prioritized runs on one GPU only: every rank's TD errors would update its own sum tree "
                          "and the replicas would diverge (data-parallel PER needs an all-gather of the drawn rows and TD errors)")
@@ -651,9 +655,14 @@ def run_train(cfg):
         if prioritized and agent.per_replay is not None:                # beta of the next draw, and the largest priority seen so far
             history[-1].update(per_beta=agent.per_replay.beta_next(), per_max_priority=agent.per_replay.max_priority())
             per_note = f" per_beta: {history[-1]['per_beta']:.6g} per_max_priority: {history[-1]['per_max_priority']:.6g}"
+        history[-1].update(target_update=agent.target_update)
+        tgt_note = f" target: {agent.target_update}"
+        if agent.target_update == "periodic":                           # hard syncs so far: one every target_period-th update
+            history[-1].update(target_syncs=agent.target_steps // agent.target_period)
+            tgt_note += f" syncs: {history[-1]['target_syncs']}"
         print(f"# epoch {epoch}: auc:{auc:.4f} final {cfg.davis_interactive.metric}: {history[-1]['final'] * 100:.2f} agent loss: "
               f"{history[-1]['agent_loss']:.4f} reward_done: {history[-1]['reward_done']:.3f} updates: {history[-1]['updates']} "
-              f"lr: {history[-1]['lr']:.6g}{per_note}")
+              f"lr: {history[-1]['lr']:.6g}{per_note}{tgt_note}")
     if world > 1:
         # replicas must be bit-identical: compare an exact integer checksum of the parameter bits on every rank
         bits = agent.policy_net.flat.detach().view(torch.int32).to(torch.int64)

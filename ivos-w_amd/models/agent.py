@@ -10,7 +10,8 @@ arithmetic replaced by libivosw_hip.so:
                           ivosw_clamp_adam       (clamp [-1,1] + coupled-L2 Adam, one fused kernel; cfg.agent.optimizer = "sgd":
                           ivosw_clamp_sgd         clamp + SGD with momentum / nesterov, cfg.agent.momentum / nesterov;
                                                   cfg.agent.lr_schedule = "poly": the lr of each update from a table, see poly_lr_table)
-                          ivosw_copy_f32         (hard target sync)
+                          ivosw_copy_f32         (hard target sync on the reference's host coin, cfg.agent.target_update = "coin";
+                          ivosw_target_update     "soft" / "periodic": the rule on the device, fused into the one-call step's last launch)
   Agent.action         -> ivosw_brain_forward + ivosw_brain_argmax (first max, like numpy)
 
 torch modules (nn.Linear / nn.LSTMCell) are used only as parameter containers so that ``state_dict()`` keys,
@@ -127,6 +128,50 @@ def poly_lr_table(lr, lr_pow, total_steps):
     Python arithmetic (libm pow; not numpy's vectorised power, whose last bit can differ), rounded to float32 once at the end."""
     lr, n = float(lr), int(total_steps)
     return np.array([lr * (1.0 - k / n) ** lr_pow for k in range(n + 1)], dtype=np.float64).astype(np.float32)
+
+
+TARGET_UPDATES = ("coin", "soft", "periodic")
+_TARGET_MODES = {"soft": L.TARGET_SOFT, "periodic": L.TARGET_PERIODIC}
+
+
+def target_update_option(kind, tau=0.005, period=20):
+    """(target_update, tau, period), checked: ("coin", None, None) - the reference's host coin, tau and period not looked at -, ("soft",
+    tau, None) with tau a number in the open interval (0, 0.5), or ("periodic", None, period) with period an int in [1, 2**31 - 1].
+    Anything else is a ValueError."""
+    if not isinstance(kind, str) or kind not in TARGET_UPDATES:
+        raise ValueError(f"agent.target_update must be 'coin', 'soft' or 'periodic', got {kind!r}")
+    if kind == "coin":
+        return "coin", None, None
+    if kind == "soft":
+        if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not 0 < tau < 0.5 or not 0 < float(np.float32(tau)) < 0.5:
+            raise ValueError(f"agent.tau must be a number in the open interval (0, 0.5), got {tau!r} (torch's lerp changes formula at 0.5; "
+                             "for hard copies use agent.target_update='periodic' with agent.target_period)")
+        return "soft", float(tau), None
+    if isinstance(period, bool) or not isinstance(period, int) or not 1 <= period < 2 ** 31:
+        raise ValueError(f"agent.target_period must be an int in [1, 2**31 - 1], got {period!r}")
+    return "periodic", None, period
+
+
+def target_update_mirror(target, policy, kind, tau=None, period=None, k=1):
+    """Host mirror of ivosw_target_update: the float32 target after step k (counted from 1) given the float32 policy after that step's
+    update.  soft: fmaf(float32(tau), p - t, t) with ONE rounding - the product-sum is formed in float64 rounded to odd (an error-free
+    two-sum decides the sticky bit), which the final rounding to float32 turns into the correctly rounded result.  periodic: a copy of
+    the policy when k % period == 0, the target unchanged otherwise."""
+    t, p = np.asarray(target, dtype=np.float32), np.asarray(policy, dtype=np.float32)
+    if kind == "periodic":
+        return p.copy() if k % period == 0 else t.copy()
+    if kind != "soft":
+        raise ValueError(f"no device rule for target_update {kind!r}")
+    a = np.float64(np.float32(tau)) * (p - t).astype(np.float64)          # exact: 24 x 24 bits
+    b = t.astype(np.float64)
+    s = a + b
+    bb = s - a
+    err = (a - (s - bb)) + (b - bb)                                         # two-sum: a + b == s + err exactly
+    even = (s.view(np.int64) & 1) == 0
+    fix = (err != 0) & even
+    toward = np.where((err > 0), np.inf, -np.inf)
+    s = np.where(fix, np.nextafter(s, toward), s)                           # round to odd
+    return s.astype(np.float32)
 
 
 class _LrSchedule:
@@ -282,6 +327,13 @@ class FusedClampAdam(_LrSchedule):
         return "ivosw_dqn_step_drawn_ex", (L.dptr(s["exp_avg"]), L.dptr(s["exp_avg_sq"]), L.dptr(s["dev"]), g["lr"], g["betas"][0],
                                            g["betas"][1], g["eps"], g["weight_decay"], g["clamp"], self.grad_scale)
 
+    def onecall_tgt_tail(self):
+        """ivosw_dqn_step_drawn_tgt's arguments from `optimizer` to `grad_scale`."""
+        g, s = self.param_groups[0], self.state
+        table, n = (L.dptr(self.lr_table()), self.schedule()[3]) if self.scheduled else (None, 0)
+        return (L.OPT_ADAM, L.dptr(s["exp_avg"]), L.dptr(s["exp_avg_sq"]), L.dptr(s["dev"]), g["lr"], table, n, g["betas"][0], g["betas"][1],
+                g["eps"], 0.0, 0, g["weight_decay"], g["clamp"], self.grad_scale)
+
     def state_dict(self):
         self._ensure()
         return dict(state={k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.state.items() if not k.startswith("dev")},
@@ -380,6 +432,13 @@ class FusedClampSGD(_LrSchedule):
         return "ivosw_dqn_step_drawn_sgd", (L.dptr(self.state["momentum_buffer"]), g["lr"], g["momentum"], g["weight_decay"],
                                             int(g["nesterov"]), g["clamp"], self.grad_scale)
 
+    def onecall_tgt_tail(self):
+        """ivosw_dqn_step_drawn_tgt's arguments from `optimizer` to `grad_scale`."""
+        g, s = self.param_groups[0], self.state
+        table, n, dev = (L.dptr(self.lr_table()), self.schedule()[3], L.dptr(s["dev"])) if self.scheduled else (None, 0, None)
+        return (L.OPT_SGD, L.dptr(s["momentum_buffer"]), None, dev, g["lr"], table, n, 0.0, 0.0, 0.0, g["momentum"], int(g["nesterov"]),
+                g["weight_decay"], g["clamp"], self.grad_scale)
+
     def state_dict(self):
         self._ensure()
         return dict(state=dict(step=self.state["step"], momentum_buffer=self.state["momentum_buffer"].clone()),
@@ -407,6 +466,9 @@ class Agent(nn.Module):
         self.lr_schedule, self.lr_pow, self.lr_total_steps = self._lr_schedule_option(a)
         self.replay_kind, self.per_alpha, self.per_beta, self.per_beta_steps, self.per_eps = self._replay_option(a)
         self.per_replay = None                      # the PrioritizedReplay of the episode loop (utils_agent._device_update_loop)
+        self.target_update, self.tau, self.target_period = self._target_option(a)
+        self.target_steps = 0                       # steps the device rule has seen (soft / periodic); resumed by load_target_state
+        self._target_dev, self._target_dev_step = None, 0
         self.EPS_START, self.EPS_END, self.EPS_DECAY = a.eps_start, a.eps_end, a.eps_decay
         self.steps_done = 0
         self.update_rate = a.update_rate
@@ -480,6 +542,14 @@ class Agent(nn.Module):
         checked by replay_option, before anything is allocated."""
         return replay_option(a.get("replay", "uniform"), a.get("per_alpha", 0.6), a.get("per_beta", 0.4), a.get("per_beta_steps", 0),
                              a.get("per_eps", 1e-6))
+
+    @staticmethod
+    def _target_option(a):
+        """cfg.agent.target_update ("coin", the reference's hard sync with probability update_rate and the default; "soft": Polyak
+        averaging with cfg.agent.tau (0.005) after every step; "periodic": a hard sync every cfg.agent.target_period-th (20) step): read
+        with .get, so a config without the keys keeps the coin; tau and target_period are only checked under their mode
+        (target_update_option), before anything is allocated.  update_rate is only read under "coin"."""
+        return target_update_option(a.get("target_update", "coin"), a.get("tau", 0.005), a.get("target_period", 20))
 
     def prioritized_replay(self, soa, device, seed):
         """A PrioritizedReplay over `soa` with this agent's PER options."""
@@ -555,10 +625,8 @@ class Agent(nn.Module):
         loss = self.loss_and_grads(sample)
         self._update_avg_loss(loss)                 # synchronises (loss.item(), models/agent.py:166): the P2P error word rides with it
         self.apply_gradients()
-        # hard target sync with probability update_rate; np.random is seeded identically on every rank
-        if np.random.random() < self.update_rate:
+        if self.target_step():
             print("target_net updated!")
-            self.sync_target()
         return self.loss[(self.loss_position - 1) % self.loss_capacity]
 
     def apply_gradients(self, check_every=1):
@@ -576,6 +644,70 @@ class Agent(nn.Module):
         pn, tn = self.policy_net, self.target_net
         L.check(L.lib().ivosw_copy_f32(L.dptr(tn.flat), L.dptr(pn.flat), L.BRAIN_NPARAMS,
                                        L.stream_ptr(pn.flat.device)), "copy_f32")
+
+    # ------------------------------------------------------------------ target-network rule
+    def target_step(self):
+        """The target rule after one policy update, where the reference flips its coin.  "coin": one np.random draw, a hard sync
+        (sync_target) with probability update_rate; np.random is seeded identically on every rank.  "soft" / "periodic": no random number
+        is drawn - ivosw_target_update is enqueued, a pure function of device state, the same on every rank.  Returns whether the target
+        was hard-synced."""
+        if self.target_update == "coin":
+            if np.random.random() < self.update_rate:
+                self.sync_target()
+                return True
+            return False
+        self.target_dev_state()
+        self.enqueue_target_update()
+        return self.note_target_steps(1) > 0
+
+    def target_hyper(self):
+        """(target_update, tau, period) as the attributes hold them now (checked): what a captured step bakes in."""
+        return target_update_option(self.target_update, self.tau, self.target_period)
+
+    def target_dev_state(self):
+        """The 16-byte state of the device rule (the step counter at byte 0), created on first use and (re)synchronised with
+        ``target_steps``."""
+        dev = self.policy_net.flat.device
+        ds = self._target_dev
+        if ds is None or ds.device != dev:
+            ds = self._target_dev = torch.zeros(L.lib().ivosw_target_state_bytes(), dtype=torch.uint8, device=dev)
+            self._target_dev_step = 0
+        if self._target_dev_step != self.target_steps:
+            ds[0:4].copy_(torch.from_numpy(np.array([self.target_steps], dtype=np.int32).view(np.uint8)))
+            self._target_dev_step = self.target_steps
+        return ds
+
+    def _target_args(self):
+        """(mode, tau, period) as the C entries take them (IVOSW_TARGET_*, fp32 tau)."""
+        kind, tau, period = self.target_hyper()
+        if kind == "coin":
+            raise ValueError("agent.target_update = 'coin' has no device rule (Agent.target_step flips the coin)")
+        return _TARGET_MODES[kind], float(np.float32(tau)) if tau is not None else 0.0, period if period is not None else 1
+
+    def enqueue_target_update(self):
+        """ivosw_target_update on the current stream (inside a capture: recorded); the caller has called target_dev_state and bumps the
+        host counter per replay (note_target_steps)."""
+        pn, tn = self.policy_net, self.target_net
+        L.check(L.lib().ivosw_target_update(L.dptr(tn.flat), L.dptr(pn.flat), L.BRAIN_NPARAMS, *self._target_args(),
+                                            L.dptr(self._target_dev), L.stream_ptr(pn.flat.device)), "target_update")
+
+    def note_target_steps(self, n=1):
+        """The host counter after n device steps of the rule; returns how many of them hard-synced the target (0 under soft)."""
+        before = self.target_steps
+        self.target_steps += n
+        self._target_dev_step = self.target_steps
+        if self.target_update != "periodic":
+            return 0
+        return self.target_steps // self.target_period - before // self.target_period
+
+    def target_state(self):
+        """What a resume restores of the target rule besides the two networks: the mode and the step counter."""
+        return dict(target_update=self.target_update, target_steps=int(self.target_steps))
+
+    def load_target_state(self, sd):
+        if sd.get("target_update", self.target_update) != self.target_update:
+            raise ValueError(f"the saved target state is for target_update {sd['target_update']!r}, this agent runs {self.target_update!r}")
+        self.target_steps = int(sd["target_steps"])          # the device counter follows at the next step (target_dev_state)
 
     # ------------------------------------------------------------------ acting
     def action(self, state, verbose=True, device_out=None):
@@ -645,9 +777,12 @@ class CapturedDqnStep:
     """One Double-DQN training step as ONE HIP-graph launch (models/agent.py:128-160 minus the host coin flip):
 
         replay gather (minibatch indices read from ``self.idx`` on the device) -> 3 forwards + loss + BPTT
-        -> [fused=True: the update — clamp + Adam with the step counter on the device, or clamp + SGD]
+        -> [fused=True: the update — clamp + Adam with the step counter on the device, or clamp + SGD
+            -> under agent.target_update = "soft" / "periodic" the target rule: in the update's own launch on the one-call chain,
+               ivosw_target_update elsewhere.  Under "coin" the caller flips the coin (Agent.target_step) after the launch.]
 
-    With fused=False the graph stops at the gradients, for the data-parallel step (all-reduce, then the eager update).
+    With fused=False the graph stops at the gradients, for the data-parallel step (all-reduce, then the eager update, then
+    Agent.target_step in every mode).
     Replaces ~40 host launches (170-250 us of enqueue per step) by one hipGraphLaunch.  The arithmetic is the eager path's:
     the same entry points are recorded, so results are bit-identical to ``Agent.loss_and_grads`` + ``optimizer.step``."""
 
@@ -657,8 +792,9 @@ class CapturedDqnStep:
         generator seeded with it), ``self.idx`` then holds the rows of the last launch.  draw_state: share another captured
         step's generator state instead of creating one.  steps > 1 (needs the in-graph draw and fused=True): that many
         consecutive training steps per launch — everything a step changes (parameters, Adam moments and step counter, draw
-        counter) lives on the device, so the recorded sequence simply repeats; the caller owns the host-side coin of the
-        target sync, i.e. launches a multi-step graph only over steps whose coins do not fire (``GraphedDqnLoop``)."""
+        counter, the target rule's counter) lives on the device, so the recorded sequence simply repeats; under
+        agent.target_update = "coin" the caller owns the host-side coin of the target sync, i.e. launches a multi-step graph only over
+        steps whose coins do not fire (``GraphedDqnLoop``)."""
         dev = torch.device(agent.device)
         self.agent, self.replay, self.B, self.fused, self.steps = agent, replay, B, fused, int(steps)
         # a PrioritizedReplay: the step is the composed chain draw + gather (ivosw_per_draw_gather) -> weighted loss and gradients
@@ -690,8 +826,11 @@ class CapturedDqnStep:
         nbytes = lib.ivosw_dqn_ws_bytes(B, T)
         self.ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
         pn, tn, opt = agent.policy_net, agent.target_net, agent.optimizer
+        self.tgt = fused and agent.target_hyper()[0] != "coin"          # the target rule is part of the step
         if fused:
             opt.dev_state()
+        if self.tgt:
+            agent.target_dev_state()
         self._keys = (pn.flat.data_ptr(), tn.flat.data_ptr(), pn.flat_grad.data_ptr())
         self._hyper = self._hyper_now()          # the optimizer's kind and values / grad_scale / gamma / loss option are baked in
         self._nbytes, self.graph, self.kernel_nodes, self._onecall_args, self._onecall_entry = nbytes, None, None, None, None
@@ -723,11 +862,17 @@ class CapturedDqnStep:
                         "dqn_loss_grad_per")
                 opt.enqueue_dev_step()
                 r.update_priorities(self.idx, self.td)
+                if self.tgt:
+                    agent.enqueue_target_update()
                 continue
             if self.draw is not None and fused:
                 # draw + gather folded into the encoder launch, the slab reduction into the update: 8 kernel nodes per step instead of 10
                 if self._onecall_args is None:   # every pointer and scalar is fixed for the life of the object (launch() checks): built once
-                    self._onecall_entry, tail = opt.onecall_tail()
+                    if self.tgt:                 # the rule rides in the update's launch: still 8 kernel nodes
+                        self._onecall_entry = "ivosw_dqn_step_drawn_tgt"
+                        tail = opt.onecall_tgt_tail() + agent._target_args() + (L.dptr(agent._target_dev),)
+                    else:
+                        self._onecall_entry, tail = opt.onecall_tail()
                     self._onecall_args = (
                         L.dptr(pn.flat), L.dptr(tn.flat), L.dptr(r.old_iou), L.dptr(r.new_iou), L.dptr(r.ann), L.dptr(r.next_ann),
                         L.dptr(r.action), L.dptr(r.reward_step), L.dptr(r.reward_done), L.dptr(self.draw, torch.uint8), r.n, B, T,
@@ -750,6 +895,8 @@ class CapturedDqnStep:
                                                L.dptr(self.loss), L.dptr(self.ws), nbytes, st), "dqn_loss_grad")
             if fused:
                 opt.enqueue_dev_step()
+            if self.tgt:
+                agent.enqueue_target_update()
 
     def _hyper_now(self):
         """What the captured launches bake in: gamma and the loss option always (the loss); the optimizer's kind and values only when the
@@ -758,7 +905,7 @@ class CapturedDqnStep:
         if not self.fused:
             return (float(a.GAMMA), a.loss_kind, float(a.huber_delta))
         per = self.replay.hyper() if self.per else ()
-        return a.optimizer.hyper() + (float(a.optimizer.grad_scale), float(a.GAMMA), a.loss_kind, float(a.huber_delta)) + per
+        return a.optimizer.hyper() + (float(a.optimizer.grad_scale), float(a.GAMMA), a.loss_kind, float(a.huber_delta)) + per + a.target_hyper()
 
     def launch(self):
         """Enqueue one step on the current stream; ``self.loss`` holds the device loss afterwards."""
@@ -768,16 +915,19 @@ class CapturedDqnStep:
         if self._hyper != self._hyper_now():
             raise RuntimeError("a hyper-parameter (optimizer kind / lr / betas / eps / momentum / nesterov / weight_decay / clamp / grad_scale / "
                                "gamma / loss kind / huber_delta / lr schedule: lr_schedule, lr_pow, lr_total_steps / prioritized replay: "
-                               "per_alpha, per_beta, per_beta_steps, per_eps) changed after capture: the "
+                               "per_alpha, per_beta, per_beta_steps, per_eps / target rule: target_update, tau, target_period) changed after capture: the "
                                "graph replays the captured values - build a new CapturedDqnStep")
         if self.fused:
             a.optimizer.dev_state()              # resync if an eager step ran in between
+        if self.tgt:
+            a.target_dev_state()
         if self.graph is not None:
             self.graph.launch()
         else:
             self._enqueue()
         if self.fused:
             a.optimizer.note_dev_steps(self.steps)
+        self.target_syncs = a.note_target_steps(self.steps) if self.tgt else 0      # hard syncs inside this launch (periodic)
         return self.loss
 
 
@@ -787,7 +937,9 @@ class GraphedDqnLoop:
     update_rate``, one coin per step, in step order).  Steps are launched ``block`` at a time as ONE hipGraphLaunch whenever
     none of the block's coins fires (an 8.7 us bubble separates consecutive graph launches: per step it is 1/block of that);
     a block with a firing coin runs step by step with the sync where the reference has it.  Same coin stream, same minibatch
-    stream (device counter), same arithmetic: results equal the step-by-step loop's bit for bit."""
+    stream (device counter), same arithmetic: results equal the step-by-step loop's bit for bit.
+    Under agent.target_update = "soft" / "periodic" the rule is part of every captured step and no coin is drawn: EVERY full block is one
+    graph launch, and ``syncs`` counts the hard syncs of the periodic rule (steps // period; 0 under soft)."""
 
     def __init__(self, agent, replay, B, draw_seed, block=8, draw_state=None):
         self.agent, self.block = agent, int(block)
@@ -802,6 +954,13 @@ class GraphedDqnLoop:
         done, loss = 0, None
         while done < n:
             k = min(self.block, n - done)
+            if self.one.tgt:                                       # the rule is inside the graphs: no host coin
+                for st in ((self.many,) if k == self.block and self.many is not None else (self.one,) * k):
+                    loss = st.launch()
+                    self.launches += 1
+                    self.syncs += st.target_syncs
+                done += k
+                continue
             coins = np.random.random(k) < a.update_rate            # the same draws, in the same order, as k scalar calls
             if k == self.block and self.many is not None and not coins.any():
                 loss = self.many.launch()
@@ -833,8 +992,9 @@ class LeanDqnLoop:
         a, loss = self.agent, None
         for _ in range(n):
             loss = self.step.launch()               # ivosw_dqn_step_drawn: eight plain launches, the step counters on the device
-            if np.random.random() < a.update_rate:
-                a.sync_target()
+            if self.step.tgt:                       # soft / periodic: the rule ran in the step's last launch
+                self.syncs += self.step.target_syncs
+            elif a.target_step():
                 self.syncs += 1
         return loss
 

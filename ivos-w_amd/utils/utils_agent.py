@@ -224,7 +224,7 @@ def _device_update_loop(agent, loader, max_steps):
     plain DataLoader over this build's own replay dataset (datasets/agent_dataset.py): the dataset's SoA is uploaded once
     (DeviceReplay), the loader's OWN batch sampler supplies the minibatch indices — the same indices, drawn from torch's global
     generator in the same order as iterating the loader would (its base seed first, then the sampler's) — each step gathers its
-    minibatch on the device and runs loss + gradients + [all-reduce] + clamp + Adam + the host coin, and the losses come back in ONE
+    minibatch on the device and runs loss + gradients + [all-reduce] + clamp + Adam + the target rule (Agent.target_step: the host coin), and the losses come back in ONE
     device-to-host copy at the end.  Same minibatches, same arithmetic, same coin and RNG streams as ``agent.update_agent(sample)``
     per collated batch: losses, parameters and the agent's loss ring are bit-identical (tests/test_gpu_agent.py).
     Returns the list of losses, or None when the loader is not of that kind (``IVOSW_UPDATE_PATH=host`` forces None).
@@ -263,9 +263,8 @@ def _device_update_loop(agent, loader, max_steps):
         off += len(st)
         loss_dev[k:k + 1].copy_(agent.loss_and_grads(batch))
         agent.apply_gradients(check_every=len(steps))
-        if np.random.random() < agent.update_rate:
+        if agent.target_step():                  # the coin of np.random, or the device rule (agent.target_update)
             print("target_net updated!")
-            agent.sync_target()
     losses = [float(v) for v in loss_dev.cpu().numpy()]
     for v in losses:
         agent.note_loss(v)
@@ -275,8 +274,8 @@ def _device_update_loop(agent, loader, max_steps):
 def _prioritized_update_loop(agent, loader, max_steps):
     """The episode's DQN updates under agent.replay = "prioritized": one step per batch the loader would have yielded (at most
     max_steps), each = prioritized draw + gather of loader.batch_size rows (PrioritizedReplay.sample_prioritized) -> importance-weighted
-    loss and gradients -> clamp + Adam / SGD (apply_gradients) -> priority update from the rows' TD errors -> the target-sync coin of
-    np.random, as in the uniform loop.  The replay is the dataset's own, uploaded once; the first one is seeded from torch's global
+    loss and gradients -> clamp + Adam / SGD (apply_gradients) -> priority update from the rows' TD errors -> the target rule
+    (Agent.target_step), as in the uniform loop.  The replay is the dataset's own, uploaded once; the first one is seeded from torch's global
     generator, and a reloaded dataset gets the previous tree rebuilt over its rows (PrioritizedReplay.rebuilt: the leaves carry over when
     the old rows are a prefix of the new ones).  Losses come back in one device-to-host copy at the end.
     Refused (ValueError): a loader that is not a plain DataLoader over this build's replay dataset, IVOSW_UPDATE_PATH=host, an initialised
@@ -319,9 +318,8 @@ def _prioritized_update_loop(agent, loader, max_steps):
         loss_dev[k:k + 1].copy_(agent.loss_and_grads(batch))
         agent.apply_gradients(check_every=n_steps)
         per.update_priorities(batch["idx"], batch["td"])
-        if np.random.random() < agent.update_rate:
+        if agent.target_step():                  # the coin of np.random, or the device rule (agent.target_update)
             print("target_net updated!")
-            agent.sync_target()
     losses = [float(v) for v in loss_dev.cpu().numpy()]
     for v in losses:
         agent.note_loss(v)
