@@ -321,6 +321,23 @@ int ivosw_mask_bbox(const float* tp, int B, int H, int W, float* yxhw, int32_t* 
 int ivosw_roi_sample(const float* tf, const float* tp, const float* yxhw, int B, int H, int W,
                      int dtype, void* roi, ivosw_stream_t stream);
 
+/* 8-bit frames.  RGBX8 is the device format of a decoded video: uint8 [n,H,W,4], bytes 0..2 = R, G, B, byte 3 written as 0 and never
+ * read, base 4-byte aligned.  The colour value of byte v is float32(v) / float32(255), correctly rounded (np.float32(v) / 255., torch's
+ * uint8 -> float() / 255); everything behind that conversion is the fp32 entries' arithmetic in the same order, so each _u8 entry is
+ * bit-identical to its fp32 counterpart run on float32(u8) / 255, in every dtype.  A quarter of the bytes of fp32 frames on the device
+ * and over PCIe, and half the sampler's gathers (one 8-byte load brings both x taps of all three colours).
+ * ivosw_frames_pack_u8: one pass, once per video, from a decoder layout to RGBX8: src = IVOSW_U8_HWC3 [n,H,W,3] (cv2 / PIL after the
+ *   channel flip) or IVOSW_U8_CHW3 [n,3,H,W], device memory; rgbx [n,H,W,4].  16-byte stores when src is 4-byte and rgbx 16-byte
+ *   aligned (and, for CHW, H*W % 4 == 0); any other alignment takes the per-pixel path.  Needs n, H, W >= 1.
+ * ivosw_roi_sample_u8: ivosw_roi_sample with rgbx [B,H,W,4] in place of tf.
+ * Refused (IVOSW_ERR_ARG) before anything is launched: a NULL pointer, an rgbx that is not 4-byte aligned, an unknown layout, and the
+ * size limits of the fp32 entries (H, W > 1 for the sampler).  No device allocation; capture-safe like the fp32 entries.              */
+#define IVOSW_U8_HWC3 0
+#define IVOSW_U8_CHW3 1
+int ivosw_frames_pack_u8(const uint8_t* src, int layout, int n, int H, int W, uint8_t* rgbx, ivosw_stream_t stream);
+int ivosw_roi_sample_u8(const uint8_t* rgbx, const float* tp, const float* yxhw, int B, int H, int W,
+                        int dtype, void* roi, ivosw_stream_t stream);
+
 /* ------------------------------------------------------------------ assessment network -------- */
 /* Packed weights (BN folded in fp32, K-major repack, stem conv1|conv1_p concatenated along Cin).
  * `tensors` is a HOST array of 326 DEVICE pointers, one per entry of AssessNet.state_dict() in
@@ -350,6 +367,15 @@ int ivosw_assess_forward(const void* packed, int dtype, const float* tf, const f
 int ivosw_assess_forward_objects(const void* packed, int dtype, const float* tf, int n_frames, const float* masks,
                                  long mask_stride_frame, long mask_stride_obj, int n_obj, int H, int W, float* scores,
                                  void* ws, size_t ws_bytes, int chunk, ivosw_stream_t stream);
+/* ivosw_assess_forward / ivosw_assess_forward_objects on RGBX8 frames (see ivosw_frames_pack_u8): rgbx [B,H,W,4] / [n_frames,H,W,4] in
+ * place of tf, everything else - chunking, the two-stream split, taps, the workspace of ivosw_assess_ws_bytes, the refusals - unchanged,
+ * plus the refusal of an rgbx that is not 4-byte aligned.  Scores and taps are bit-identical to the fp32 entries on float32(u8) / 255. */
+int ivosw_assess_forward_u8(const void* packed, int dtype, const uint8_t* rgbx, const float* tp,
+                            int B, int H, int W, float* scores, void* ws, size_t ws_bytes, int chunk,
+                            int tap_stage, void* tap_out, ivosw_stream_t stream);
+int ivosw_assess_forward_objects_u8(const void* packed, int dtype, const uint8_t* rgbx, int n_frames, const float* masks,
+                                    long mask_stride_frame, long mask_stride_obj, int n_obj, int H, int W, float* scores,
+                                    void* ws, size_t ws_bytes, int chunk, ivosw_stream_t stream);
 /* Replaces `mask_quality[:] = pred.mean(1); state = np.stack([mask_quality, counts], 1)` (utils/utils_agent.py:120-121) on
  * the device: scores [n_obj][n_frames] fp32 (as ivosw_assess_forward_objects writes them), counts [n_frames] fp32 ->
  * quality [n_frames] float64 (numpy's float64 mean of the float32 predictions, same summation order) and

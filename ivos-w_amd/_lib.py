@@ -15,6 +15,7 @@ F32, BF16, F32X3 = 0, 1, 2
 DQN_LOSS_MSE, DQN_LOSS_HUBER = 0, 1                  # IVOSW_DQN_LOSS_* (include/ivosw.h)
 TARGET_SOFT, TARGET_PERIODIC = 1, 2                  # IVOSW_TARGET_*
 OPT_ADAM, OPT_SGD = 0, 1                             # IVOSW_OPT_*
+U8_HWC3, U8_CHW3 = 0, 1                              # IVOSW_U8_* (source layouts of ivosw_frames_pack_u8)
 BRAIN_NPARAMS = 180993
 ASSESS_NTENSORS = 326
 
@@ -68,12 +69,16 @@ SIGNATURES = {
                                  [_i, _f, _i, _p] + [_p]),
     "ivosw_mask_bbox": (_i, [_p, _i, _i, _i, _p, _p, _p]),
     "ivosw_roi_sample": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
+    "ivosw_frames_pack_u8": (_i, [_p, _i, _i, _i, _i, _p, _p]),
+    "ivosw_roi_sample_u8": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "ivosw_assess_packed_bytes": (_sz, [_i]),
     "ivosw_assess_pack": (_i, [_p, _i, C.POINTER(_p), _i, _p]),
     "ivosw_assess_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "ivosw_assess_split": (_i, [_i, _i, _i]),
     "ivosw_assess_forward": (_i, [_p, _i, _p, _p, _i, _i, _i, _p, _p, _sz, _i, _i, _p, _p]),
     "ivosw_assess_forward_objects": (_i, [_p, _i, _p, _i, _p, C.c_long, C.c_long, _i, _i, _i, _p, _p, _sz, _i, _p]),
+    "ivosw_assess_forward_u8": (_i, [_p, _i, _p, _p, _i, _i, _i, _p, _p, _sz, _i, _i, _p, _p]),
+    "ivosw_assess_forward_objects_u8": (_i, [_p, _i, _p, _i, _p, C.c_long, C.c_long, _i, _i, _i, _p, _p, _sz, _i, _p]),
     "ivosw_quality_state": (_i, [_p, _i, _i, _p, _p, _p, _p]),
     "ivosw_assess_dominant_kernel": (C.c_char_p, [_i]),
     "ivosw_jf_ws_bytes": (_sz, [_i, _i, _i, _i]),

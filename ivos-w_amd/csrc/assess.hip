@@ -323,30 +323,52 @@ extern "C" const char* ivosw_assess_dominant_kernel(int dtype) {
     return dtype == IVOSW_BF16 ? "conv_igemm*|conv1x1_wide*|conv3x3_patch*|bneck*|res2_stage*|res2_chain_kernel*|gemm_8phase*|stage_first*|stem_pool*" : dtype == IVOSW_F32X3 ? "conv_igemm*|stem_pool_x3*" : "conv_igemm*";   // the tower's contraction kernels (one family)
 }
 
-static int assess_forward_impl(const void* packed, int dtype, const float* tf, const float* tp, const SampleMap& sm, int B, int H, int W,
+static int assess_forward_impl(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int B, int H, int W,
                                float* scores, void* ws, size_t ws_bytes, int chunk, int tap_stage, void* tap_out,
                                ivosw_stream_t stream);
 
 extern "C" int ivosw_assess_forward(const void* packed, int dtype, const float* tf, const float* tp, int B, int H, int W,
                                     float* scores, void* ws, size_t ws_bytes, int chunk, int tap_stage, void* tap_out,
                                     ivosw_stream_t stream) {
-    return assess_forward_impl(packed, dtype, tf, tp, SampleMap{B, (long)H * W, 0}, B, H, W, scores, ws, ws_bytes, chunk, tap_stage,
+    return assess_forward_impl(packed, dtype, FrameSrc{tf, 0}, tp, SampleMap{B, (long)H * W, 0}, B, H, W, scores, ws, ws_bytes, chunk, tap_stage,
                                tap_out, stream);
+}
+
+static int assess_forward_objects_impl(const void* packed, int dtype, const FrameSrc& fs, int n_frames, const float* masks,
+                                       long mask_stride_frame, long mask_stride_obj, int n_obj, int H, int W, float* scores, void* ws,
+                                       size_t ws_bytes, int chunk, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(n_frames > 0 && n_obj > 0, "n_frames and n_obj must be positive");
+    IVOSW_REQUIRE((long)n_frames * n_obj < (1L << 30), "too many (frame, object) units for one call");
+    IVOSW_REQUIRE(mask_stride_frame >= (long)H * W || n_frames == 1, "mask planes of consecutive frames overlap");
+    IVOSW_REQUIRE(mask_stride_obj >= 0 && mask_stride_frame >= 0, "negative mask stride");
+    return assess_forward_impl(packed, dtype, fs, masks, SampleMap{n_frames, mask_stride_frame, mask_stride_obj}, n_frames * n_obj, H,
+                               W, scores, ws, ws_bytes, chunk, 0, nullptr, stream);
 }
 
 extern "C" int ivosw_assess_forward_objects(const void* packed, int dtype, const float* tf, int n_frames, const float* masks,
                                             long mask_stride_frame, long mask_stride_obj, int n_obj, int H, int W, float* scores,
                                             void* ws, size_t ws_bytes, int chunk, ivosw_stream_t stream) {
-    IVOSW_REQUIRE(n_frames > 0 && n_obj > 0, "n_frames and n_obj must be positive");
-    IVOSW_REQUIRE((long)n_frames * n_obj < (1L << 30), "too many (frame, object) units for one call");
-    IVOSW_REQUIRE(mask_stride_frame >= (long)H * W || n_frames == 1, "mask planes of consecutive frames overlap");
-    IVOSW_REQUIRE(mask_stride_obj >= 0 && mask_stride_frame >= 0, "negative mask stride");
-    return assess_forward_impl(packed, dtype, tf, masks, SampleMap{n_frames, mask_stride_frame, mask_stride_obj}, n_frames * n_obj, H,
-                               W, scores, ws, ws_bytes, chunk, 0, nullptr, stream);
+    return assess_forward_objects_impl(packed, dtype, FrameSrc{tf, 0}, n_frames, masks, mask_stride_frame, mask_stride_obj, n_obj, H, W,
+                                       scores, ws, ws_bytes, chunk, stream);
+}
+
+// the same two entries on RGBX8 frames (ivosw_frames_pack_u8): only the sampler's colour source differs
+extern "C" int ivosw_assess_forward_u8(const void* packed, int dtype, const uint8_t* rgbx, const float* tp, int B, int H, int W,
+                                       float* scores, void* ws, size_t ws_bytes, int chunk, int tap_stage, void* tap_out,
+                                       ivosw_stream_t stream) {
+    return assess_forward_impl(packed, dtype, FrameSrc{rgbx, 1}, tp, SampleMap{B, (long)H * W, 0}, B, H, W, scores, ws, ws_bytes, chunk,
+                               tap_stage, tap_out, stream);
+}
+
+extern "C" int ivosw_assess_forward_objects_u8(const void* packed, int dtype, const uint8_t* rgbx, int n_frames, const float* masks,
+                                               long mask_stride_frame, long mask_stride_obj, int n_obj, int H, int W, float* scores,
+                                               void* ws, size_t ws_bytes, int chunk, ivosw_stream_t stream) {
+    return assess_forward_objects_impl(packed, dtype, FrameSrc{rgbx, 1}, n_frames, masks, mask_stride_frame, mask_stride_obj, n_obj, H, W,
+                                       scores, ws, ws_bytes, chunk, stream);
 }
 
 // units [u0, u0 + B) of the batch on stream st with their own workspace; `slot` = which of the (up to two) concurrent profiler spans
-static void assess_forward_range(const void* packed, int dtype, const float* tf, const float* tp, const SampleMap& sm, int u0, int B,
+static void assess_forward_range(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int u0, int B,
                                  int H, int W, float* scores, void* ws, int chunk, int tap_stage, void* tap_out, int slot, hipStream_t st);
 
 // One helper stream + two events per device for the two-stream split (created on first use, all-or-nothing; the call holds
@@ -381,10 +403,11 @@ Side2* side2_for_current_device() {
 }
 }  // namespace
 
-static int assess_forward_impl(const void* packed, int dtype, const float* tf, const float* tp, const SampleMap& sm, int B, int H, int W,
+static int assess_forward_impl(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int B, int H, int W,
                                float* scores, void* ws, size_t ws_bytes, int chunk, int tap_stage, void* tap_out,
                                ivosw_stream_t stream) {
-    IVOSW_REQUIRE(packed && tf && tp && scores && ws, "null pointer");
+    IVOSW_REQUIRE(packed && fs.p && tp && scores && ws, "null pointer");
+    IVOSW_REQUIRE(!fs.u8 || (reinterpret_cast<uintptr_t>(fs.p) & 3) == 0, "rgbx must be 4-byte aligned");
     IVOSW_ON_DEVICE_OF(scores);
     IVOSW_REQUIRE(dtype == IVOSW_F32 || dtype == IVOSW_BF16 || dtype == IVOSW_F32X3, "dtype must be IVOSW_F32, IVOSW_BF16 or IVOSW_F32X3");
     IVOSW_REQUIRE(B > 0 && H > 1 && W > 1, "B must be positive and H, W > 1");
@@ -412,8 +435,8 @@ static int assess_forward_impl(const void* packed, int dtype, const float* tf, c
         bool ok = hipEventRecord(sd->ev[0], st) == hipSuccess && hipStreamWaitEvent(sd->stream, sd->ev[0], 0) == hipSuccess;
         if (ok) {
             span_group_begin();
-            assess_forward_range(packed, dtype, tf, tp, sm, 0, B0, H, W, scores, ws, std::min(default_chunk(dtype), B0), 0, nullptr, 0, st);
-            assess_forward_range(packed, dtype, tf, tp, sm, B0, B1, H, W, scores + B0, ws1, std::min(default_chunk(dtype), B1), 0, nullptr, 1, sd->stream);
+            assess_forward_range(packed, dtype, fs, tp, sm, 0, B0, H, W, scores, ws, std::min(default_chunk(dtype), B0), 0, nullptr, 0, st);
+            assess_forward_range(packed, dtype, fs, tp, sm, B0, B1, H, W, scores + B0, ws1, std::min(default_chunk(dtype), B1), 0, nullptr, 1, sd->stream);
             span_group_end();
             ok = hipEventRecord(sd->ev[1], sd->stream) == hipSuccess && hipStreamWaitEvent(st, sd->ev[1], 0) == hipSuccess;
             if (!ok) {
@@ -426,12 +449,12 @@ static int assess_forward_impl(const void* packed, int dtype, const float* tf, c
         }
         (void)hipGetLastError();        // the fork failed before anything was enqueued on the side stream: run on one stream
     }
-    assess_forward_range(packed, dtype, tf, tp, sm, 0, B, H, W, scores, ws, chunk, tap_stage, tap_out, 0, st);
+    assess_forward_range(packed, dtype, fs, tp, sm, 0, B, H, W, scores, ws, chunk, tap_stage, tap_out, 0, st);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }
 
-static void assess_forward_range(const void* packed, int dtype, const float* tf, const float* tp, const SampleMap& sm, int u0, int B,
+static void assess_forward_range(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int u0, int B,
                                  int H, int W, float* scores, void* ws, int chunk, int tap_stage, void* tap_out, int slot, hipStream_t st) {
     const Plan& P = plan_for(dtype);
     const size_t es = (dtype == IVOSW_BF16) ? 2 : 4;
@@ -693,7 +716,7 @@ static void assess_forward_range(const void* packed, int dtype, const float* tf,
                     const int nb = std::min(cs[0], f1 + n1 - f0);
                     // K3: ROI crop-resize + normalise -> NHWC4
                     span_close(st, slot);
-                    launch_roi_sample(tf, tp, bf.yxhw + (size_t)f0 * 4, u0 + f0, nb, H, W, dtype, sm, nrm, bf.roi, st);
+                    launch_roi_sample(fs, tp, bf.yxhw + (size_t)f0 * 4, u0 + f0, nb, H, W, dtype, sm, nrm, bf.roi, st);
                     tap(1, bf.roi, nb * E_ROI * es);
                     // K4: stem 7x7/2 (RGB|P) + BN + ReLU, then 3x3/2 max pool (bf16: one fused kernel unless the stem tap is wanted)
                     span_open(st, slot);

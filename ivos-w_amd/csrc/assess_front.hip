@@ -8,6 +8,8 @@
 // Both kernels are HBM-bound streaming/gather work; no LDS staging is needed (each input byte is read once).
 #include <limits.h>
 
+#include <algorithm>
+
 #include "common.h"
 #include "front.h"
 
@@ -231,14 +233,176 @@ __global__ __launch_bounds__(256) void roi_sample_kernel(const float* __restrict
     }
 }
 
-void launch_roi_sample(const float* tf, const float* tp, const float* yxhw, int b0, int B, int H, int W, int dtype,
+// ---------------------------------------------------------------- 8-bit frames (RGBX8: uint8 [n,H,W,4], bytes R, G, B, 0)
+// byte k of w as float32(v) / float32(255), correctly rounded - what np.float32(v) / 255. and torch's uint8 -> float() / 255 give on the host.
+// Division by the constant as a reciprocal product plus one Newton step on the exact residual (q = v r, e = v - 255 q, q + e r: the
+// tail of the hardware's own fp32 division, 3 VALU instructions instead of ~11 and no denormal-mode switch); that it rounds like the
+// division for every one of the 256 bytes is checked in exact arithmetic by tests/test_frames_u8_option.py and on the device by
+// tests/test_gpu_frames_u8.py.  The byte extraction and the conversion are one instruction (v_cvt_f32_ubyte<k>).
+__device__ __forceinline__ float u8_unit(uint32_t w, int k) {
+    const float v = (float)((w >> (8 * k)) & 0xffu);
+    constexpr float r = 1.0f / 255.0f;
+    const float q = v * r;
+    const float e = __builtin_fmaf(-q, 255.0f, v);
+    return __builtin_fmaf(e, r, q);
+}
+
+// grid ceil(max(groups, tail) / 256), block 256: a byte-shuffling copy from a decoder layout to RGBX8, once per video.  The n frames are
+// one flat run of P = n*H*W pixels.  Fast path (vec: 4-byte aligned source, 16-byte aligned destination, and for CHW planes of a multiple
+// of 4 pixels): thread g turns three dword loads (HWC: 12 consecutive bytes; CHW: 4 bytes of each plane) into ONE 16-byte store of four
+// pixels; the P % 4 pixels behind the last group - or, without vec, every pixel - take the scalar path (3 byte loads, one dword store).
+__global__ __launch_bounds__(256) void frames_pack_u8_kernel(const uint8_t* __restrict__ src, int layout, int vec, size_t P, size_t plane,
+                                                             uint8_t* __restrict__ dst) {
+    const size_t g = (size_t)blockIdx.x * 256 + threadIdx.x;
+    const size_t groups = vec ? P / 4 : 0;
+    if (g < groups) {
+        uint4 o;
+        if (layout == IVOSW_U8_HWC3) {
+            const uint32_t* s = reinterpret_cast<const uint32_t*>(src + g * 12);
+            const uint32_t w0 = s[0], w1 = s[1], w2 = s[2];        // r0 g0 b0 r1 | g1 b1 r2 g2 | b2 r3 g3 b3
+            o.x = w0 & 0xffffffu;
+            o.y = (w0 >> 24) | ((w1 & 0xffffu) << 8);
+            o.z = (w1 >> 16) | ((w2 & 0xffu) << 16);
+            o.w = w2 >> 8;
+        } else {
+            const size_t q = g * 4, f = q / plane, i = q - f * plane;      // plane % 4 == 0: the group lies inside one frame
+            const uint8_t* s = src + f * 3 * plane + i;
+            const uint32_t r = *reinterpret_cast<const uint32_t*>(s), gg = *reinterpret_cast<const uint32_t*>(s + plane),
+                           b = *reinterpret_cast<const uint32_t*>(s + 2 * plane);
+            o.x = (r & 0xffu) | ((gg & 0xffu) << 8) | ((b & 0xffu) << 16);
+            o.y = ((r >> 8) & 0xffu) | (((gg >> 8) & 0xffu) << 8) | (((b >> 8) & 0xffu) << 16);
+            o.z = ((r >> 16) & 0xffu) | (((gg >> 16) & 0xffu) << 8) | (((b >> 16) & 0xffu) << 16);
+            o.w = (r >> 24) | ((gg >> 24) << 8) | ((b >> 24) << 16);
+        }
+        *reinterpret_cast<uint4*>(dst + g * 16) = o;
+    }
+    const size_t q = groups * 4 + g;
+    if (q < P) {
+        uint32_t r, gg, b;
+        if (layout == IVOSW_U8_HWC3) {
+            r = src[q * 3]; gg = src[q * 3 + 1]; b = src[q * 3 + 2];
+        } else {
+            const size_t f = q / plane, i = q - f * plane;
+            const uint8_t* s = src + f * 3 * plane + i;
+            r = s[0]; gg = s[plane]; b = s[2 * plane];
+        }
+        *reinterpret_cast<uint32_t*>(dst + q * 4) = r | (gg << 8) | (b << 16);
+    }
+}
+
+// two neighbouring RGBX8 pixels with one 8-byte load from a 4-byte-aligned address
+struct __attribute__((packed, aligned(4))) PairU32 { uint32_t x, y; };
+__device__ __forceinline__ uint2 ld_pair_u32(const uint8_t* p) {
+    const PairU32 v = *reinterpret_cast<const PairU32*>(p);
+    return make_uint2(v.x, v.y);
+}
+
+// roi_sample_kernel with the colours read from RGBX8 frames: the same geometry (thread = output column, ROI_R rows per workgroup, two
+// rows in flight), theta, taps, weights, zero padding, products, sums and (f - mean) / std, in the same order.  The three colour pair
+// loads of a source row become ONE 8-byte load at 4 * (yc * W + xb) that holds both x taps of all colours (4 pair loads per output
+// pixel with the mask's instead of 8); the edge selection (t0_hi / t1_lo) picks a whole pixel word before its bytes are converted.
+// The mask plane stays fp32 with its own pair load.  Results are bit-identical to roi_sample_kernel on float32(u8) / 255.
+template <typename T>
+__global__ __launch_bounds__(256) void roi_sample_u8_kernel(const uint8_t* __restrict__ rgbx, const float* __restrict__ tp,
+                                                            const float* __restrict__ yxhw, int b0, SampleMap sm, int H, int W, RoiNorm nrm,
+                                                            T* __restrict__ roi) {
+    constexpr int GPS = 256 / ROI_R;
+    const int b = blockIdx.x / GPS, i0 = (blockIdx.x % GPS) * ROI_R, j = threadIdx.x;
+    const int bg = b0 + b, fr = bg % sm.n_frames;
+    const float ry = yxhw[b * 4 + 0], rx = yxhw[b * 4 + 1], rh = yxhw[b * 4 + 2], rw = yxhw[b * 4 + 3];
+    const float ymin = __fsub_rn(ry, rh / 2.0f), ymax = __fadd_rn(ry, rh / 2.0f);
+    const float xmin = __fsub_rn(rx, rw / 2.0f), xmax = __fadd_rn(rx, rw / 2.0f);
+    const float wm = (float)(W - 1), hm = (float)(H - 1);
+    const float t00 = __fsub_rn(xmax, xmin) / wm, t02 = __fsub_rn(__fadd_rn(xmin, xmax), wm) / wm;
+    const float t11 = __fsub_rn(ymax, ymin) / hm, t12 = __fsub_rn(__fadd_rn(ymin, ymax), hm) / hm;
+    const float gx = __fadd_rn(__fmul_rn(lin_m1_1(j, 256), t00), t02);
+    const float sx = __fmul_rn(__fmul_rn(__fadd_rn(gx, 1.0f), 0.5f), wm);
+    const float x0f = floorf(sx);
+    const int x0 = (int)x0f;
+    const float wx1 = __fsub_rn(sx, x0f), wx0 = __fsub_rn(__fadd_rn(x0f, 1.0f), sx);
+    const bool vx0 = x0 >= 0 && x0 < W, vx1 = x0 + 1 >= 0 && x0 + 1 < W;
+    const int xb = min(max(x0, 0), W - 2);
+    const bool t0_hi = x0 >= W - 1, t1_lo = x0 < 0;
+    const uint8_t* srcf = rgbx + (size_t)fr * H * W * 4;
+    const float* srcp = tp + (size_t)(bg / sm.n_frames) * sm.stride_obj + (size_t)fr * sm.stride_frame;
+    float mu[3], sd[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        mu[c] = nrm.dev ? nrm.dev[c] : nrm.mean[c];
+        sd[c] = nrm.dev ? nrm.dev[3 + c] : nrm.std[c];
+    }
+    T* dst = roi + (((size_t)b * 256 + i0) * 256 + j) * 4;
+#pragma unroll 1
+    for (int r0 = 0; r0 < ROI_R; r0 += 2) {
+        uint32_t px[2][4];                                         // the four taps' pixel words: nw, ne, sw, se
+        float m[2][4], k[2][4];
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+            const int i = i0 + r0 + rr;
+            const float gy = __fadd_rn(__fmul_rn(lin_m1_1(i, 256), t11), t12);
+            const float sy = __fmul_rn(__fmul_rn(__fadd_rn(gy, 1.0f), 0.5f), hm);
+            const float y0f = floorf(sy);
+            const int y0 = (int)y0f;
+            const float wy1 = __fsub_rn(sy, y0f), wy0 = __fsub_rn(__fadd_rn(y0f, 1.0f), sy);
+            const bool vy0 = y0 >= 0 && y0 < H, vy1 = y0 + 1 >= 0 && y0 + 1 < H;
+            const int yc0 = min(max(y0, 0), H - 1), yc1 = min(max(y0 + 1, 0), H - 1);
+            const int o0 = yc0 * W + xb, o1 = yc1 * W + xb;        // pixels o0, o0 + 1 < H * W <= INT_MAX (checked by the host)
+            const float w_nw = __fmul_rn(wx0, wy0), w_ne = __fmul_rn(wx1, wy0), w_sw = __fmul_rn(wx0, wy1), w_se = __fmul_rn(wx1, wy1);
+            k[rr][0] = (vy0 && vx0) ? w_nw : 0.f; k[rr][1] = (vy0 && vx1) ? w_ne : 0.f;
+            k[rr][2] = (vy1 && vx0) ? w_sw : 0.f; k[rr][3] = (vy1 && vx1) ? w_se : 0.f;
+            const uint2 c0 = ld_pair_u32(srcf + (size_t)o0 * 4), c1 = ld_pair_u32(srcf + (size_t)o1 * 4);
+            const float2 p0 = ld_pair(srcp + o0), p1 = ld_pair(srcp + o1);
+            px[rr][0] = t0_hi ? c0.y : c0.x; px[rr][1] = t1_lo ? c0.x : c0.y;
+            px[rr][2] = t0_hi ? c1.y : c1.x; px[rr][3] = t1_lo ? c1.x : c1.y;
+            m[rr][0] = t0_hi ? p0.y : p0.x; m[rr][1] = t1_lo ? p0.x : p0.y;
+            m[rr][2] = t0_hi ? p1.y : p1.x; m[rr][3] = t1_lo ? p1.x : p1.y;
+        }
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+            float out[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                float v[4];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) v[t] = c < 3 ? u8_unit(px[rr][t], c) : m[rr][t];
+                // roi_sample_kernel's four product-sums compile to a chain of four FMAs in both instantiations (see the NOTE there:
+                // __fmul_rn / __fadd_rn contract).  Written with the same operators here, hipcc packed the products of two channels
+                // (v_pk_mul_f32) in the bf16 instantiation and added them unfused, one rounding more per tap than the float kernel.
+                // The explicit FMAs pin the float kernel's arithmetic; tests/test_gpu_frames_u8.py holds the two bit-identical.
+                float acc = 0.f;
+                acc = __builtin_fmaf(v[0], k[rr][0], acc);
+                acc = __builtin_fmaf(v[1], k[rr][1], acc);
+                acc = __builtin_fmaf(v[2], k[rr][2], acc);
+                acc = __builtin_fmaf(v[3], k[rr][3], acc);
+                if (c < 3) acc = __fsub_rn(acc, mu[c]) / sd[c];
+                out[c] = acc;
+            }
+            T* d = dst + (size_t)(r0 + rr) * 256 * 4;
+            if constexpr (sizeof(T) == 4) {
+                *reinterpret_cast<float4*>(d) = make_float4(out[0], out[1], out[2], out[3]);
+            } else {
+                *reinterpret_cast<uint2*>(d) = make_uint2(pack2_bf16(out[0], out[1]), pack2_bf16(out[2], out[3]));
+            }
+        }
+    }
+}
+
+void launch_roi_sample(const FrameSrc& fs, const float* tp, const float* yxhw, int b0, int B, int H, int W, int dtype,
                        const SampleMap& sm, const RoiNorm& nrm, void* roi, hipStream_t st) {
+    const dim3 grid(B * (256 / ROI_R)), block(256);
+    if (fs.u8) {
+        const uint8_t* rgbx = static_cast<const uint8_t*>(fs.p);
+        if (dtype != IVOSW_BF16)
+            hipLaunchKernelGGL(roi_sample_u8_kernel<float>, grid, block, 0, st, rgbx, tp, yxhw, b0, sm, H, W, nrm, static_cast<float*>(roi));
+        else
+            hipLaunchKernelGGL(roi_sample_u8_kernel<bf16_t>, grid, block, 0, st, rgbx, tp, yxhw, b0, sm, H, W, nrm, static_cast<bf16_t*>(roi));
+        return;
+    }
+    const float* tf = static_cast<const float*>(fs.p);
     if (dtype != IVOSW_BF16)
-        hipLaunchKernelGGL(roi_sample_kernel<float>, dim3(B * (256 / ROI_R)), dim3(256), 0, st, tf, tp, yxhw, b0, sm, H, W, nrm,
-                           static_cast<float*>(roi));
+        hipLaunchKernelGGL(roi_sample_kernel<float>, grid, block, 0, st, tf, tp, yxhw, b0, sm, H, W, nrm, static_cast<float*>(roi));
     else
-        hipLaunchKernelGGL(roi_sample_kernel<bf16_t>, dim3(B * (256 / ROI_R)), dim3(256), 0, st, tf, tp, yxhw, b0, sm, H, W, nrm,
-                           static_cast<bf16_t*>(roi));
+        hipLaunchKernelGGL(roi_sample_kernel<bf16_t>, grid, block, 0, st, tf, tp, yxhw, b0, sm, H, W, nrm, static_cast<bf16_t*>(roi));
 }
 
 }  // namespace ivosw
@@ -263,7 +427,38 @@ extern "C" int ivosw_roi_sample(const float* tf, const float* tp, const float* y
     IVOSW_REQUIRE((long)H * W <= INT_MAX && B <= (1 << 24), "frame or batch too large (H * W <= INT_MAX, B <= 2^24)");
     IVOSW_REQUIRE(dtype == IVOSW_F32 || dtype == IVOSW_BF16 || dtype == IVOSW_F32X3, "dtype must be IVOSW_F32, IVOSW_BF16 or IVOSW_F32X3");
     RoiNorm nrm{{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}, nullptr};  // Encoder.mean/std (assessment.py:41-44)
-    launch_roi_sample(tf, tp, yxhw, 0, B, H, W, dtype, SampleMap{B, (long)H * W, 0}, nrm, roi, as_stream(stream));
+    launch_roi_sample(FrameSrc{tf, 0}, tp, yxhw, 0, B, H, W, dtype, SampleMap{B, (long)H * W, 0}, nrm, roi, as_stream(stream));
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_frames_pack_u8(const uint8_t* src, int layout, int n, int H, int W, uint8_t* rgbx, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(src && rgbx, "null pointer");
+    IVOSW_REQUIRE(layout == IVOSW_U8_HWC3 || layout == IVOSW_U8_CHW3, "layout must be IVOSW_U8_HWC3 or IVOSW_U8_CHW3");
+    IVOSW_REQUIRE(n > 0 && H > 0 && W > 0, "n, H, W must be positive");
+    IVOSW_REQUIRE((long)H * W <= INT_MAX && n <= (1 << 24), "frame or video too large (H * W <= INT_MAX, n <= 2^24)");
+    IVOSW_REQUIRE((reinterpret_cast<uintptr_t>(rgbx) & 3) == 0, "rgbx must be 4-byte aligned");
+    IVOSW_ON_DEVICE_OF(rgbx);
+    const size_t plane = (size_t)H * W, P = plane * (size_t)n;
+    const int vec = (reinterpret_cast<uintptr_t>(src) & 3) == 0 && (reinterpret_cast<uintptr_t>(rgbx) & 15) == 0 &&
+                    (layout == IVOSW_U8_HWC3 || plane % 4 == 0);
+    const size_t threads = vec ? std::max(P / 4, P % 4) : P;
+    hipLaunchKernelGGL(frames_pack_u8_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, as_stream(stream), src, layout, vec, P,
+                       plane, rgbx);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_roi_sample_u8(const uint8_t* rgbx, const float* tp, const float* yxhw, int B, int H, int W, int dtype,
+                                   void* roi, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(rgbx && tp && yxhw && roi, "null pointer");
+    IVOSW_REQUIRE((reinterpret_cast<uintptr_t>(rgbx) & 3) == 0, "rgbx must be 4-byte aligned");
+    IVOSW_REQUIRE(B > 0 && H > 1 && W > 1, "B must be positive and H, W > 1");
+    IVOSW_REQUIRE((long)H * W <= INT_MAX && B <= (1 << 24), "frame or batch too large (H * W <= INT_MAX, B <= 2^24)");
+    IVOSW_REQUIRE(dtype == IVOSW_F32 || dtype == IVOSW_BF16 || dtype == IVOSW_F32X3, "dtype must be IVOSW_F32, IVOSW_BF16 or IVOSW_F32X3");
+    IVOSW_ON_DEVICE_OF(roi);
+    RoiNorm nrm{{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}, nullptr};  // Encoder.mean/std (assessment.py:41-44)
+    launch_roi_sample(FrameSrc{rgbx, 1}, tp, yxhw, 0, B, H, W, dtype, SampleMap{B, (long)H * W, 0}, nrm, roi, as_stream(stream));
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }

@@ -16,7 +16,13 @@ struct SampleMap {
     int n_frames;
     long stride_frame, stride_obj;
 };
+// Where the sampler reads its colours: fp32 planes [n,3,H,W] in 0..1 (u8 = 0), or RGBX8 bytes [n,H,W,4] (u8 = 1, 4-byte aligned:
+// include/ivosw.h).  It travels with the frames through the chunk loop, the two-stream split and the SampleMap indirection.
+struct FrameSrc {
+    const void* p;
+    int u8;
+};
 void launch_mask_bbox(const float* tp, int b0, int B, int H, int W, const SampleMap& sm, float* yxhw, int32_t* scratch, hipStream_t st);
-void launch_roi_sample(const float* tf, const float* tp, const float* yxhw, int b0, int B, int H, int W, int dtype,
+void launch_roi_sample(const FrameSrc& fs, const float* tp, const float* yxhw, int b0, int B, int H, int W, int dtype,
                        const SampleMap& sm, const RoiNorm& nrm, void* roi, hipStream_t st);
 }  // namespace ivosw

@@ -56,6 +56,9 @@ DEFAULTS = dict(
     vos_adapter="",                    # module on PYTHONPATH that wraps the VOS backbone for the real stack (default ivosw_vos_<backbone>)
     synthetic=-1,                      # -1 auto (synthetic when the real stack is missing), 0 real stack only, 1 synthetic
     precision="bf16",                  # AssessNet mode: bf16 throughput (scores within 4e-3) / bf16x3 fast parity (1e-4) / fp32 exact parity
+    frames="float32",                  # how the assessment path holds a video: "float32" [n,3,H,W] in 0..1 (the reference's all_F), or "uint8":
+                                       # the decoded bytes packed as RGBX8 on the device (a quarter of the memory and of the upload; same scores
+                                       # on the real stack, whose floats are bytes / 255)
     report_save_dir="results",
     eval_max_nb_interactions=8,        # the eval scripts fix 8 interactions on the val subset (eval_agent_manet.py:64-65)
     data=dict(num_workers=0, root_dir_davis="data/DAVIS", root_dir_scribble_youtube_vos="data/Scribble_Youtube_VOS",
@@ -76,6 +79,17 @@ DEFAULTS = dict(
                                    # averaging with tau after every step) or "periodic" (hard sync every target_period-th step), on the device
     synth=dict(n_sequences=3, n_frames=30, height=120, width=216, max_objects=3, baseline_runs=30),
 )
+
+
+FRAME_MODES = ("float32", "uint8")
+
+
+def frames_option(cfg):
+    """cfg.frames (absent: "float32"), refused unless it is one of FRAME_MODES."""
+    mode = cfg.get("frames", "float32")
+    if not isinstance(mode, str) or mode not in FRAME_MODES:
+        raise ValueError(f"frames must be 'float32' or 'uint8', got {mode!r}")
+    return mode
 
 
 def _coerce(text):
@@ -115,6 +129,10 @@ def parse_cli(argv, **overrides):
                 raise SystemExit(f"unknown config section {p!r} in {key!r}")
             node = node[p]
         node[parts[-1]] = _coerce(val)
+    try:
+        frames_option(cfg)
+    except ValueError as e:
+        raise SystemExit(f"[ivos-w] {e}")
     return _attr(cfg)
 
 
@@ -184,6 +202,7 @@ class SyntheticDavis:
                                       col=rs.uniform(0.2, 1.0, (n_obj + 1, 3)), seed=int(rs.randint(1 << 30)))
         self.sets = {cfg.data.subset: list(self.dataset)}
         self._cache = {}
+        self.frames = frames_option(cfg)
 
     def _render(self, name):
         if name in self._cache:
@@ -208,7 +227,12 @@ class SyntheticDavis:
         return self._cache[name]
 
     def load_frames(self, name):
-        return self._render(name)[0]
+        """float32 [n,3,H,W] on the host; under frames=uint8 the same frames quantised with round(f * 255), packed on the device."""
+        frames = self._render(name)[0]
+        if self.frames == "uint8":
+            from .utils import utils_agent
+            return utils_agent.pack_video((frames * 255.0).round().to(torch.uint8), self.device, layout="chw")
+        return frames
 
     def load_annotations(self, name):
         return self._render(name)[1]                                  # uint8 [n,H,W] on the device (the J/F kernels read it there)
@@ -331,6 +355,7 @@ def run_eval(cfg, backbone="MANet"):
     """The loop of eval_agent_manet.py:246-480 on the synthetic back end.  Writes <report_save_dir>/summary.json =
     {"auc", "curve": {metric: [...]}} like the reference and returns it."""
     from .utils import misc, utils_agent, utils_manet
+    frames = frames_option(cfg)                                        # (a bad value is refused here, before anything runs)
     cfg.phase = "eval"
     cfg.data.subset = "val"
     if not torch.cuda.is_available():
@@ -338,6 +363,9 @@ def run_eval(cfg, backbone="MANet"):
     device = torch.device(f"cuda:{cfg.gpu_id}")
     if not choose_backend(backbone, cfg):
         return run_eval_real(cfg, backbone, device)
+    if frames == "uint8":
+        print("[ivos-w] frames=uint8: the synthetic frames are quantised with round(f * 255) and packed as RGBX8 on the device, so the "
+              "numbers of this run differ from frames=float32 (on the real stack the decoded frames ARE bytes and the two modes agree)")
     misc.set_random_seed(int(cfg.seed))
     davis = SyntheticDavis(cfg, device)
     needs_assess = cfg.setting == "wild" and cfg.method in ("ours", "worst")
@@ -391,8 +419,9 @@ def run_eval(cfg, backbone="MANet"):
     with open(os.path.join(report_dir, "summary.json"), "w") as fp:
         json.dump(summary, fp)
     print(f"# global_summary: auc:{auc * 100:.4f}  recommend_frame avg {rec_time.avg * 1e3:.2f} ms  frame-cache uploads "
-          f"{utils_agent.frame_cache.uploads}\n# {metric}: " + " ".join(f"{v * 100:.2f}" for v in curve))
+          f"{utils_agent.frame_cache.uploads}  frames: {frames}\n# {metric}: " + " ".join(f"{v * 100:.2f}" for v in curve))
     summary["backend"] = "synthetic"
+    summary["frames"] = frames
     summary["report_dir"] = report_dir
     return summary
 
@@ -409,6 +438,7 @@ def run_eval_real(cfg, backbone, device):
     from davisinteractive.session import DavisInteractiveSession
     from .utils import misc, utils_agent
     adapter_mod = importlib.import_module(adapter_module_name(backbone, cfg))
+    frames = frames_option(cfg)
     misc.set_random_seed(int(cfg.seed))
     root = cfg.data.root_dir_davis
     needs_assess = cfg.setting == "wild" and cfg.method in ("ours", "worst")
@@ -437,13 +467,19 @@ def run_eval_real(cfg, backbone, device):
                 if sequence not in frames_of:                  # decoded once per sequence: also the key of the device frame cache
                     frames_of.clear()                          # davisinteractive serves a sequence's samples consecutively: keep ONE decoded
                                                                # video (0.35 GB of fp32 at 480p), as the reference holds one all_F — not the whole set
+                                                               # (frames=uint8: 0.16 GB of RGBX8 bytes on the device and no host copy)
                     jdir = os.path.join(root, "JPEGImages", "480p", sequence)
-                    frames_of[sequence] = torch.from_numpy(np.ascontiguousarray(np.stack(
-                        [np.asarray(cv2.imread(os.path.join(jdir, f)), dtype=np.float32)[:, :, [2, 1, 0]] / 255. for f in sorted(os.listdir(jdir))],
-                        0).transpose(0, 3, 1, 2)))
+                    if frames == "uint8":                      # cv2's bytes, BGR -> RGB, packed on the device: the same values as below
+                        frames_of[sequence] = utils_agent.pack_video(
+                            np.stack([np.asarray(cv2.imread(os.path.join(jdir, f)), dtype=np.uint8)[:, :, [2, 1, 0]] for f in sorted(os.listdir(jdir))],
+                                     0), device)
+                    else:
+                        frames_of[sequence] = torch.from_numpy(np.ascontiguousarray(np.stack(
+                            [np.asarray(cv2.imread(os.path.join(jdir, f)), dtype=np.float32)[:, :, [2, 1, 0]] / 255. for f in sorted(os.listdir(jdir))],
+                            0).transpose(0, 3, 1, 2)))
                 all_F = frames_of[sequence]
                 n_frame = len(scribbles["scribbles"])
-                h, w = int(all_F.shape[2]), int(all_F.shape[3])
+                h, w = (all_F.H, all_F.W) if frames == "uint8" else (int(all_F.shape[2]), int(all_F.shape[3]))
                 prev_frames = None if cfg.davis_interactive.allow_repeat > 0 else [next_frame]
                 annotated_list = [next_frame]
                 quality_pred = np.zeros(n_frame) if needs_assess else None
@@ -479,9 +515,10 @@ def run_eval_real(cfg, backbone, device):
     summary = {"auc": auc, "curve": {metric: curve}}
     with open(os.path.join(report_dir, "summary.json"), "w") as fp:
         json.dump(summary, fp)
-    print(f"# final avg {metric}: {final_q.avg:.4f}  final avg corr: {corr_all.avg:.4f}\n# global_summary: auc:{auc * 100:.4f}\n# {metric}: "
-          + " ".join(f"{v * 100:.2f}" for v in curve))
+    print(f"# final avg {metric}: {final_q.avg:.4f}  final avg corr: {corr_all.avg:.4f}\n# global_summary: auc:{auc * 100:.4f}  frames: {frames}\n"
+          f"# {metric}: " + " ".join(f"{v * 100:.2f}" for v in curve))
     summary["backend"] = "real"
+    summary["frames"] = frames
     summary["report_dir"] = report_dir
     return summary
 

@@ -18,6 +18,7 @@ import ctypes
 import os
 import math
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -83,6 +84,61 @@ _DTYPES = {"fp32": L.F32, "bf16": L.BF16, "bf16x3": L.F32X3}
 _TAPS = {"roi": (1, (256, 256, 4)), "stem": (2, (128, 128, 64)), "pool": (3, (64, 64, 64)),
          "res2": (4, (64, 64, 256)), "res3": (5, (32, 32, 512)), "res4": (6, (16, 16, 1024)),
          "res5": (7, (8, 8, 2048)), "pooled": (8, (2048,))}
+
+
+_LAYOUTS = {"hwc": (L.U8_HWC3, 3), "chw": (L.U8_CHW3, 1)}      # layout -> (IVOSW_U8_*, the axis that holds the 3 channels)
+
+
+class PackedFrames:
+    """The 8-bit frames of a video on the device in the library's RGBX8 format: ``rgbx`` uint8 [n,H,W,4], bytes R, G, B, 0.  The colour
+    value of byte v is float32(v) / 255, so every AssessNet entry handed a PackedFrames computes bit for bit what it computes on
+    ``to_float()`` - from a quarter of the bytes.  Build one with ``AssessNet.pack_frames`` / ``utils_agent.pack_video``."""
+
+    def __init__(self, rgbx):
+        if not isinstance(rgbx, torch.Tensor) or rgbx.dtype != torch.uint8:
+            raise TypeError("PackedFrames holds a torch.uint8 tensor")
+        if rgbx.dim() != 4 or rgbx.shape[3] != 4 or not rgbx.is_contiguous():
+            raise ValueError(f"PackedFrames holds a contiguous [n,H,W,4] tensor, got {tuple(rgbx.shape)}")
+        self.rgbx = rgbx
+        self.n, self.H, self.W = (int(v) for v in rgbx.shape[:3])
+
+    @property
+    def device(self):
+        return self.rgbx.device
+
+    def __len__(self):
+        return self.n
+
+    def to_float(self):
+        """float32 [n,3,H,W] in 0..1: what the float entry points take.  The 256 values float32(v) / 255 come from a table divided on the
+        host: on the device torch divides a tensor by a scalar as a product with float32(1 / 255), which rounds 95 / 255 (and more)
+        one ulp away from the division that defines the format."""
+        table = torch.from_numpy(np.arange(256, dtype=np.float32) / np.float32(255.)).to(self.rgbx.device)
+        idx = self.rgbx[..., :3].permute(0, 3, 1, 2).contiguous().view(-1).to(torch.int32)
+        return table.index_select(0, idx).view(self.n, 3, self.H, self.W)
+
+
+def pack_frames(u8, device, layout="hwc"):
+    """Decoded 8-bit frames -> PackedFrames on ``device``.  u8: torch.uint8 tensor or numpy uint8 array, [n,H,W,3] (layout "hwc": cv2 /
+    PIL after the channel flip) or [n,3,H,W] ("chw"), on the host or the device.  A host input is uploaded as bytes; the packing is one
+    launch of ivosw_frames_pack_u8 on the device."""
+    if layout not in _LAYOUTS:
+        raise ValueError(f"layout must be 'hwc' or 'chw', got {layout!r}")
+    if isinstance(u8, np.ndarray):
+        if u8.dtype != np.uint8:
+            raise TypeError(f"8-bit frames must be uint8, got {u8.dtype}")
+        u8 = torch.from_numpy(np.ascontiguousarray(u8))
+    if not isinstance(u8, torch.Tensor) or u8.dtype != torch.uint8:
+        raise TypeError(f"8-bit frames must be a torch.uint8 tensor or a numpy uint8 array, got {getattr(u8, 'dtype', type(u8))}")
+    code, axis = _LAYOUTS[layout]
+    if u8.dim() != 4 or u8.shape[axis] != 3 or min(u8.shape) < 1:
+        want = "[n,H,W,3]" if layout == "hwc" else "[n,3,H,W]"
+        raise ValueError(f"layout {layout!r} takes {want}, got {tuple(u8.shape)}")
+    n, H, W = (int(u8.shape[i]) for i in range(4) if i != axis)
+    src = u8.detach().to(device).contiguous()
+    rgbx = torch.empty(n, H, W, 4, dtype=torch.uint8, device=src.device)
+    L.check(L.lib().ivosw_frames_pack_u8(L.dptr(src), code, n, H, W, L.dptr(rgbx), L.stream_ptr(src.device)), "frames_pack_u8")
+    return PackedFrames(rgbx)
 
 
 class AssessNet(nn.Module):
@@ -154,10 +210,16 @@ class AssessNet(nn.Module):
         if self.training:
             raise RuntimeError("AssessNet on the MI355X path is inference-only (eval-mode BatchNorm); call .eval() — "
                                "training AssessNet is outside the hot path")
-        tf = tf.detach().to(torch.float32).contiguous()
+        u8 = isinstance(tf, PackedFrames)                # the 8-bit path is reached through this type only: a plain uint8 tensor is cast
+        if u8:
+            B, H, W = tf.n, tf.H, tf.W
+            tf = tf.rgbx
+        else:
+            tf = tf.detach().to(torch.float32).contiguous()
+            B, C, H, W = tf.shape
+            assert C == 3
         tp = tp.detach().to(torch.float32).contiguous()
-        B, C, H, W = tf.shape
-        assert C == 3 and tuple(tp.shape) == (B, H, W)
+        assert tuple(tp.shape) == (B, H, W)
         dev = tf.device
         packed = self._ensure_packed()
         lib, dt = L.lib(), _DTYPES[self.precision]
@@ -170,27 +232,40 @@ class AssessNet(nn.Module):
             stage, shp = _TAPS[tap]
             tdt = torch.float32 if (tap == "pooled" or self.precision != "bf16") else torch.bfloat16
             tap_t = torch.empty((B,) + shp, dtype=tdt, device=dev)
-        L.check(lib.ivosw_assess_forward(L.dptr(packed), dt, L.dptr(tf), L.dptr(tp), B, H, W, L.dptr(scores), L.dptr(ws),
-                                         nbytes, chunk, stage, L.dptr(tap_t) if tap else None, L.stream_ptr(dev)),
-                "assess_forward")
+        fwd = lib.ivosw_assess_forward_u8 if u8 else lib.ivosw_assess_forward
+        L.check(fwd(L.dptr(packed), dt, L.dptr(tf), L.dptr(tp), B, H, W, L.dptr(scores), L.dptr(ws),
+                    nbytes, chunk, stage, L.dptr(tap_t) if tap else None, L.stream_ptr(dev)),
+                "assess_forward_u8" if u8 else "assess_forward")
         return scores, tap_t
 
     def forward(self, tf, tp):
-        """tf [B,3,H,W] in [0,1], tp [B,H,W] soft mask -> quality [B,1] ((1,) when B == 1, like the
-        reference's ``.squeeze()``, models/assessment.py:179)."""
+        """tf [B,3,H,W] in [0,1] (or a PackedFrames: the 8-bit path), tp [B,H,W] soft mask -> quality [B,1] ((1,) when B == 1, like
+        the reference's ``.squeeze()``, models/assessment.py:179)."""
         scores, _ = self._run(tf, tp)
         return scores if scores.shape[0] == 1 else scores[:, None]
+
+    def pack_frames(self, u8, layout="hwc"):
+        """8-bit frames ([n,H,W,3] or, with layout="chw", [n,3,H,W]; torch or numpy uint8, host or device) -> PackedFrames on this
+        network's device."""
+        return pack_frames(u8, self.fc1.weight.device, layout)
 
     def forward_objects(self, all_F, all_P, n_objects):
         """Scores of every (object, frame) unit of ONE video without replicating the frames: all_F [n,3,H,W] fp32 on the
         device, all_P [n,C,H,W] fp32 on the device (any layout whose [H,W] planes are contiguous, e.g. the object-major
-        ProbStore view), channel i+1 = object i (utils/utils_agent.py:118-119).  Returns [n_objects, n] fp32 on the device."""
+        ProbStore view), channel i+1 = object i (utils/utils_agent.py:118-119).  all_F may be a PackedFrames (the 8-bit path).
+        Returns [n_objects, n] fp32 on the device."""
         if self.training:
             raise RuntimeError("AssessNet on the MI355X path is inference-only; call .eval()")
-        n, C3, H, W = all_F.shape
-        assert C3 == 3 and all_P.shape[0] == n and tuple(all_P.shape[2:]) == (H, W) and all_P.shape[1] > n_objects
-        if all_F.dtype != torch.float32 or not all_F.is_contiguous():
-            all_F = all_F.detach().to(torch.float32).contiguous()
+        u8 = isinstance(all_F, PackedFrames)
+        if u8:
+            n, H, W = all_F.n, all_F.H, all_F.W
+            all_F = all_F.rgbx
+        else:
+            n, C3, H, W = all_F.shape
+            assert C3 == 3
+            if all_F.dtype != torch.float32 or not all_F.is_contiguous():
+                all_F = all_F.detach().to(torch.float32).contiguous()
+        assert all_P.shape[0] == n and tuple(all_P.shape[2:]) == (H, W) and all_P.shape[1] > n_objects
         if all_P.dtype != torch.float32 or all_P.stride(3) != 1 or all_P.stride(2) != W:
             all_P = all_P.detach().to(torch.float32).contiguous()
         dev = all_F.device
@@ -201,9 +276,10 @@ class AssessNet(nn.Module):
         ws = self._ws.get(nbytes, dev)
         scores = torch.empty(n_objects, n, dtype=torch.float32, device=dev)
         masks = all_P[:, 1:]                                # a view: channel 0 is the background
-        L.check(lib.ivosw_assess_forward_objects(L.dptr(packed), dt, L.dptr(all_F), n, ctypes.c_void_p(masks.data_ptr()),
-                                                 all_P.stride(0), all_P.stride(1), n_objects, H, W, L.dptr(scores),
-                                                 L.dptr(ws), nbytes, self.chunk, L.stream_ptr(dev)), "assess_forward_objects")
+        fwd = lib.ivosw_assess_forward_objects_u8 if u8 else lib.ivosw_assess_forward_objects
+        L.check(fwd(L.dptr(packed), dt, L.dptr(all_F), n, ctypes.c_void_p(masks.data_ptr()),
+                    all_P.stride(0), all_P.stride(1), n_objects, H, W, L.dptr(scores),
+                    L.dptr(ws), nbytes, self.chunk, L.stream_ptr(dev)), "assess_forward_objects_u8" if u8 else "assess_forward_objects")
         return scores
 
     def forward_tap(self, tf, tp, tap):

@@ -88,6 +88,8 @@ class _FrameCache:
 
     def get(self, all_F, device):
         device = torch.device(device)
+        if _is_packed(all_F):                    # 8-bit frames already packed on the device (pack_video): handed on unchanged
+            return all_F
         if all_F.is_cuda:
             return all_F if all_F.device == device else all_F.to(device)
         # The cache holds a STRONG reference to the host tensor and compares identity: while the entry is alive the tensor cannot be
@@ -104,6 +106,19 @@ class _FrameCache:
 
     def clear(self):
         self.key, self.src, self.frames = None, None, None
+
+
+def _is_packed(all_F):
+    from ..models.assessment import PackedFrames
+    return isinstance(all_F, PackedFrames)
+
+
+def pack_video(u8, device, layout="hwc"):
+    """The decoded 8-bit frames of a video ([n,H,W,3], or [n,3,H,W] with layout="chw"; torch or numpy uint8, host or device) ->
+    ``models.assessment.PackedFrames`` on ``device``: a quarter of the fp32 video's bytes over PCIe and in HBM.  Hand the result to
+    ``recommend_frame`` / ``assess_all_objects`` / ``AssessNet`` in place of the float all_F; the scores equal those of u8 / 255."""
+    from ..models.assessment import pack_frames
+    return pack_frames(u8, device, layout)
 
 
 frame_cache = _FrameCache()
