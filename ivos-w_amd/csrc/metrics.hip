@@ -125,8 +125,11 @@ __global__ __launch_bounds__(256) void jf_boundary_row_kernel(JfArgs a) {
         for (int r = 0; r <= JF_RPW; ++r) {
             const bool row_ok = y0 + r < a.H;
             const uint32_t m0 = row_ok ? (mask16(g[r], id4) & vm) : 0u, m1 = row_ok ? (mask16(p[r], id4) & vm) : 0u;
-            const uint32_t e0 = lane == 63 ? ((tail && row_ok && tg[r] == id) ? 1u : 0u) : (lane_next(m0) & 1u);
-            const uint32_t e1 = lane == 63 ? ((tail && row_ok && tp[r] == id) ? 1u : 0u) : (lane_next(m1) & 1u);
+            // the shuffle runs in EVERY lane, outside the lane-63 select: inside its `lane != 63` arm lane 63 is switched off, and a DPP
+            // read of a switched-off lane returns 0 - lane 62 then lost the east neighbour of its last pixel (column 1007 | 1008 of a segment)
+            const uint32_t n0 = lane_next(m0) & 1u, n1 = lane_next(m1) & 1u;
+            const uint32_t e0 = lane == 63 ? ((tail && row_ok && tg[r] == id) ? 1u : 0u) : n0;
+            const uint32_t e1 = lane == 63 ? ((tail && row_ok && tp[r] == id) ? 1u : 0u) : n1;
             mg[r] = m0 | (e0 << 16);
             mp[r] = m1 | (e1 << 16);
         }
