@@ -376,6 +376,41 @@ int ivosw_assess_forward_u8(const void* packed, int dtype, const uint8_t* rgbx, 
 int ivosw_assess_forward_objects_u8(const void* packed, int dtype, const uint8_t* rgbx, int n_frames, const float* masks,
                                     long mask_stride_frame, long mask_stride_obj, int n_obj, int H, int W, float* scores,
                                     void* ws, size_t ws_bytes, int chunk, ivosw_stream_t stream);
+/* Several videos in ONE pass: the front end reads every unit through a table of per-video descriptors, the tower behind it sees 256 x 256
+ * tiles and does not care where one came from, so K sessions fill one full-size pass instead of K small ones.
+ * `videos` is a HOST array of n_videos (1 .. IVOSW_MAX_VIDEOS) descriptors with DEVICE pointers; it is read during the call only and
+ * travels to the kernels inside their arguments (no allocation, no copy: capture-safe like the entries above).  Per video: frames
+ * (fp32 planes or RGBX8, see frames_kind), masks and the two mask strides exactly as ivosw_assess_forward_objects takes them, n_frames,
+ * n_obj, H, W - each video its own.
+ * UNIT ORDER: video-major, then object-major inside a video: u = first_unit[v] + obj * n_frames[v] + frame, with first_unit[v] = the
+ * sum of n_frames * n_obj over the videos before v.  scores / yxhw / roi rows are in unit order.
+ * Per unit the arithmetic is that of the single-video entries, operation for operation: results are bit-identical to running
+ * ivosw_mask_bbox / ivosw_roi_sample(_u8) / ivosw_assess_forward_objects(_u8) per video and concatenating.
+ * ivosw_assess_videos_units: host only; the total number of units, or < 0 (IVOSW_ERR_ARG) if the array would be refused.
+ * ivosw_mask_bbox_videos: yxhw [units,4]; scratch units * 4 int32.   ivosw_roi_sample_videos: roi [units,256,256,4] in `dtype`.
+ * ivosw_assess_forward_videos: scores [units]; chunking, the two-stream split and the taps (B = units <= chunk) as in
+ * ivosw_assess_forward - a chunk or a stream half may begin and end inside a video.  Workspace: ivosw_assess_ws_bytes with B = units;
+ * that query does not look at H and W beyond their sign (the workspace holds 256 x 256 tiles and tower activations only), so any
+ * positive H, W serves for a mixed-size call.
+ * Refused (IVOSW_ERR_ARG) before anything is launched, the message names the video's index: a NULL pointer, n_videos outside
+ * [1, IVOSW_MAX_VIDEOS], an unknown frames_kind or dtype, n_frames or n_obj < 1, H or W <= 1, H * W > INT_MAX, a negative stride,
+ * overlapping consecutive mask planes (mask_stride_frame < H * W with n_frames > 1), an RGBX8 pointer that is not 4-byte aligned,
+ * 2^30 or more units in total, an arena packed for another dtype.                                                                     */
+#define IVOSW_MAX_VIDEOS 32
+#define IVOSW_FRAMES_F32 0      /* float32 [n_frames,3,H,W] in 0..1 */
+#define IVOSW_FRAMES_RGBX8 1    /* uint8 [n_frames,H,W,4], 4-byte aligned (ivosw_frames_pack_u8) */
+typedef struct ivosw_video {
+    const void* frames;                          /* device */
+    const float* masks;                          /* device */
+    long mask_stride_frame, mask_stride_obj;     /* elements, as in ivosw_assess_forward_objects */
+    int frames_kind, n_frames, n_obj, H, W;
+} ivosw_video_t;
+long ivosw_assess_videos_units(const ivosw_video_t* videos, int n_videos);
+int ivosw_mask_bbox_videos(const ivosw_video_t* videos, int n_videos, float* yxhw, int32_t* scratch, ivosw_stream_t stream);
+int ivosw_roi_sample_videos(const ivosw_video_t* videos, int n_videos, const float* yxhw, int dtype, void* roi,
+                            ivosw_stream_t stream);
+int ivosw_assess_forward_videos(const void* packed, int dtype, const ivosw_video_t* videos, int n_videos, float* scores,
+                                void* ws, size_t ws_bytes, int chunk, int tap_stage, void* tap_out, ivosw_stream_t stream);
 /* Replaces `mask_quality[:] = pred.mean(1); state = np.stack([mask_quality, counts], 1)` (utils/utils_agent.py:120-121) on
  * the device: scores [n_obj][n_frames] fp32 (as ivosw_assess_forward_objects writes them), counts [n_frames] fp32 ->
  * quality [n_frames] float64 (numpy's float64 mean of the float32 predictions, same summation order) and

@@ -20,6 +20,15 @@ BRAIN_NPARAMS = 180993
 ASSESS_NTENSORS = 326
 
 _p, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
+MAX_VIDEOS = 32                                      # IVOSW_MAX_VIDEOS
+FRAMES_F32, FRAMES_RGBX8 = 0, 1                      # IVOSW_FRAMES_*
+
+
+class Video(C.Structure):
+    """ivosw_video_t: one video of a multi-video assessment call (device pointers, mask strides in elements)."""
+    _fields_ = [("frames", C.c_void_p), ("masks", C.c_void_p), ("mask_stride_frame", C.c_long), ("mask_stride_obj", C.c_long),
+                ("frames_kind", C.c_int), ("n_frames", C.c_int), ("n_obj", C.c_int), ("H", C.c_int), ("W", C.c_int)]
+
 
 SIGNATURES = {
     "ivosw_last_error": (C.c_char_p, []),
@@ -79,6 +88,10 @@ SIGNATURES = {
     "ivosw_assess_forward_objects": (_i, [_p, _i, _p, _i, _p, C.c_long, C.c_long, _i, _i, _i, _p, _p, _sz, _i, _p]),
     "ivosw_assess_forward_u8": (_i, [_p, _i, _p, _p, _i, _i, _i, _p, _p, _sz, _i, _i, _p, _p]),
     "ivosw_assess_forward_objects_u8": (_i, [_p, _i, _p, _i, _p, C.c_long, C.c_long, _i, _i, _i, _p, _p, _sz, _i, _p]),
+    "ivosw_assess_videos_units": (C.c_long, [_p, _i]),
+    "ivosw_mask_bbox_videos": (_i, [_p, _i, _p, _p, _p]),
+    "ivosw_roi_sample_videos": (_i, [_p, _i, _p, _i, _p, _p]),
+    "ivosw_assess_forward_videos": (_i, [_p, _i, _p, _i, _p, _p, _sz, _i, _i, _p, _p]),
     "ivosw_quality_state": (_i, [_p, _i, _i, _p, _p, _p, _p]),
     "ivosw_assess_dominant_kernel": (C.c_char_p, [_i]),
     "ivosw_jf_ws_bytes": (_sz, [_i, _i, _i, _i]),

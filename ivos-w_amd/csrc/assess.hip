@@ -323,9 +323,10 @@ extern "C" const char* ivosw_assess_dominant_kernel(int dtype) {
     return dtype == IVOSW_BF16 ? "conv_igemm*|conv1x1_wide*|conv3x3_patch*|bneck*|res2_stage*|res2_chain_kernel*|gemm_8phase*|stage_first*|stem_pool*" : dtype == IVOSW_F32X3 ? "conv_igemm*|stem_pool_x3*" : "conv_igemm*";   // the tower's contraction kernels (one family)
 }
 
+// vt != NULL: the units are those of a video table (front.h) and fs / tp / sm / H / W are not looked at
 static int assess_forward_impl(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int B, int H, int W,
                                float* scores, void* ws, size_t ws_bytes, int chunk, int tap_stage, void* tap_out,
-                               ivosw_stream_t stream);
+                               ivosw_stream_t stream, const VideoTable* vt = nullptr);
 
 extern "C" int ivosw_assess_forward(const void* packed, int dtype, const float* tf, const float* tp, int B, int H, int W,
                                     float* scores, void* ws, size_t ws_bytes, int chunk, int tap_stage, void* tap_out,
@@ -367,9 +368,22 @@ extern "C" int ivosw_assess_forward_objects_u8(const void* packed, int dtype, co
                                        scores, ws, ws_bytes, chunk, stream);
 }
 
+// Several videos in one pass (include/ivosw.h): the table is validated and built on the host, then the chunk loop, the two-stream split
+// and the workspace are those of the single-video entries with B = the table's units - a chunk or a stream half may begin and end inside
+// a video and span several, the front-end launches find each unit's video themselves.  (H = W = 2 below only keeps the workspace query of
+// the "workspace too small" message answerable; nothing else reads them.)
+extern "C" int ivosw_assess_forward_videos(const void* packed, int dtype, const ivosw_video_t* videos, int n_videos, float* scores, void* ws,
+                                           size_t ws_bytes, int chunk, int tap_stage, void* tap_out, ivosw_stream_t stream) {
+    VideoTable vt;
+    if (const int rc = video_table_build(videos, n_videos, __func__, &vt)) return rc;
+    return assess_forward_impl(packed, dtype, FrameSrc{nullptr, 0}, nullptr, SampleMap{1, 0, 0}, vt.units, 2, 2, scores, ws, ws_bytes, chunk,
+                               tap_stage, tap_out, stream, &vt);
+}
+
 // units [u0, u0 + B) of the batch on stream st with their own workspace; `slot` = which of the (up to two) concurrent profiler spans
 static void assess_forward_range(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int u0, int B,
-                                 int H, int W, float* scores, void* ws, int chunk, int tap_stage, void* tap_out, int slot, hipStream_t st);
+                                 int H, int W, float* scores, void* ws, int chunk, int tap_stage, void* tap_out, int slot, hipStream_t st,
+                                 const VideoTable* vt);
 
 // One helper stream + two events per device for the two-stream split (created on first use, all-or-nothing; the call holds
 // the device's mutex while it enqueues so two host threads cannot interleave their fork / join pairs).
@@ -405,13 +419,13 @@ Side2* side2_for_current_device() {
 
 static int assess_forward_impl(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int B, int H, int W,
                                float* scores, void* ws, size_t ws_bytes, int chunk, int tap_stage, void* tap_out,
-                               ivosw_stream_t stream) {
-    IVOSW_REQUIRE(packed && fs.p && tp && scores && ws, "null pointer");
-    IVOSW_REQUIRE(!fs.u8 || (reinterpret_cast<uintptr_t>(fs.p) & 3) == 0, "rgbx must be 4-byte aligned");
+                               ivosw_stream_t stream, const VideoTable* vt) {
+    IVOSW_REQUIRE(packed && (vt || (fs.p && tp)) && scores && ws, "null pointer");
+    IVOSW_REQUIRE(vt || !fs.u8 || (reinterpret_cast<uintptr_t>(fs.p) & 3) == 0, "rgbx must be 4-byte aligned");
     IVOSW_ON_DEVICE_OF(scores);
     IVOSW_REQUIRE(dtype == IVOSW_F32 || dtype == IVOSW_BF16 || dtype == IVOSW_F32X3, "dtype must be IVOSW_F32, IVOSW_BF16 or IVOSW_F32X3");
-    IVOSW_REQUIRE(B > 0 && H > 1 && W > 1, "B must be positive and H, W > 1");
-    IVOSW_REQUIRE((long)H * W <= INT_MAX, "frame too large (H * W <= INT_MAX)");
+    IVOSW_REQUIRE(vt || (B > 0 && H > 1 && W > 1), "B must be positive and H, W > 1");      // (a table's videos were checked when it was built)
+    IVOSW_REQUIRE(vt || (long)H * W <= INT_MAX, "frame too large (H * W <= INT_MAX)");
     IVOSW_REQUIRE(tap_stage >= 0 && tap_stage <= 8, "tap_stage out of range");
     IVOSW_REQUIRE(tap_stage == 0 || tap_out, "tap_out is null");
     {
@@ -435,8 +449,8 @@ static int assess_forward_impl(const void* packed, int dtype, const FrameSrc& fs
         bool ok = hipEventRecord(sd->ev[0], st) == hipSuccess && hipStreamWaitEvent(sd->stream, sd->ev[0], 0) == hipSuccess;
         if (ok) {
             span_group_begin();
-            assess_forward_range(packed, dtype, fs, tp, sm, 0, B0, H, W, scores, ws, std::min(default_chunk(dtype), B0), 0, nullptr, 0, st);
-            assess_forward_range(packed, dtype, fs, tp, sm, B0, B1, H, W, scores + B0, ws1, std::min(default_chunk(dtype), B1), 0, nullptr, 1, sd->stream);
+            assess_forward_range(packed, dtype, fs, tp, sm, 0, B0, H, W, scores, ws, std::min(default_chunk(dtype), B0), 0, nullptr, 0, st, vt);
+            assess_forward_range(packed, dtype, fs, tp, sm, B0, B1, H, W, scores + B0, ws1, std::min(default_chunk(dtype), B1), 0, nullptr, 1, sd->stream, vt);
             span_group_end();
             ok = hipEventRecord(sd->ev[1], sd->stream) == hipSuccess && hipStreamWaitEvent(st, sd->ev[1], 0) == hipSuccess;
             if (!ok) {
@@ -449,13 +463,14 @@ static int assess_forward_impl(const void* packed, int dtype, const FrameSrc& fs
         }
         (void)hipGetLastError();        // the fork failed before anything was enqueued on the side stream: run on one stream
     }
-    assess_forward_range(packed, dtype, fs, tp, sm, 0, B, H, W, scores, ws, chunk, tap_stage, tap_out, 0, st);
+    assess_forward_range(packed, dtype, fs, tp, sm, 0, B, H, W, scores, ws, chunk, tap_stage, tap_out, 0, st, vt);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }
 
 static void assess_forward_range(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int u0, int B,
-                                 int H, int W, float* scores, void* ws, int chunk, int tap_stage, void* tap_out, int slot, hipStream_t st) {
+                                 int H, int W, float* scores, void* ws, int chunk, int tap_stage, void* tap_out, int slot, hipStream_t st,
+                                 const VideoTable* vt) {
     const Plan& P = plan_for(dtype);
     const size_t es = (dtype == IVOSW_BF16) ? 2 : 4;
     const char* base = static_cast<const char*>(packed);
@@ -470,7 +485,8 @@ static void assess_forward_range(const void* packed, int dtype, const FrameSrc& 
     };
 
     // K1/K2: mask -> (y,x,h,w) for the whole batch, on device
-    launch_mask_bbox(tp, u0, B, H, W, sm, bf.yxhw, bf.box, st);
+    if (vt) launch_mask_bbox_multi(*vt, u0, B, bf.yxhw, bf.box, st);
+    else launch_mask_bbox(tp, u0, B, H, W, sm, bf.yxhw, bf.box, st);
     // Encoder.mean/std come from the checkpoint: the sampler reads them from the packed arena
     RoiNorm nrm{{0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}, reinterpret_cast<const float*>(base + P.norm_off)};
 
@@ -716,7 +732,8 @@ static void assess_forward_range(const void* packed, int dtype, const FrameSrc& 
                     const int nb = std::min(cs[0], f1 + n1 - f0);
                     // K3: ROI crop-resize + normalise -> NHWC4
                     span_close(st, slot);
-                    launch_roi_sample(fs, tp, bf.yxhw + (size_t)f0 * 4, u0 + f0, nb, H, W, dtype, sm, nrm, bf.roi, st);
+                    if (vt) launch_roi_sample_multi(*vt, bf.yxhw + (size_t)f0 * 4, u0 + f0, nb, dtype, nrm, bf.roi, st);
+                    else launch_roi_sample(fs, tp, bf.yxhw + (size_t)f0 * 4, u0 + f0, nb, H, W, dtype, sm, nrm, bf.roi, st);
                     tap(1, bf.roi, nb * E_ROI * es);
                     // K4: stem 7x7/2 (RGB|P) + BN + ReLU, then 3x3/2 max pool (bf16: one fused kernel unless the stem tap is wanted)
                     span_open(st, slot);

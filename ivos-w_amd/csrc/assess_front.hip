@@ -405,6 +405,280 @@ void launch_roi_sample(const FrameSrc& fs, const float* tp, const float* yxhw, i
         hipLaunchKernelGGL(roi_sample_kernel<bf16_t>, grid, block, 0, st, tf, tp, yxhw, b0, sm, H, W, nrm, static_cast<bf16_t*>(roi));
 }
 
+// ---------------------------------------------------------------- several videos in one launch (front.h: VideoTable)
+// The video of unit u: how many videos start at or before u, minus one.  No loop-carried load: the compares run on two scalar loads.
+__device__ __forceinline__ int video_of_unit(const VideoTable& vt, int u) {
+    int v = 0;
+#pragma unroll
+    for (int i = 1; i < IVOSW_MAX_VIDEOS; ++i) v += (u >= vt.first[i]) ? 1 : 0;
+    return v;
+}
+
+// bbox_scan_kernel over the units [b0, b0 + gridDim.y) of a video table.  grid (S, B) with S sized for the LARGEST plane of the range:
+// a workgroup whose chunk lies behind its own video's plane leaves before the barrier (the whole workgroup: the test is uniform).
+// Integer min / max: the box does not depend on how the plane is cut into chunks.
+__global__ __launch_bounds__(256) void bbox_scan_multi_kernel(const VideoTable vt, int b0, int chunk, int32_t* __restrict__ box) {
+    const int b = blockIdx.y;
+    const int u = b0 + b, vi = video_of_unit(vt, u);
+    const VideoDesc& d = vt.v[vi];
+    const int W = d.W;
+    const size_t plane = (size_t)d.H * W;
+    const size_t beg = (size_t)blockIdx.x * chunk;
+    if (beg >= plane) return;
+    const int lu = u - vt.first[vi], nf = d.n_frames;
+    const float* p = d.masks + (size_t)(lu / nf) * d.stride_obj + (size_t)(lu % nf) * d.stride_frame;
+    const size_t end = min(plane, beg + (size_t)chunk);
+    int ymin = INT_MAX, ymax = -1, xmin = INT_MAX, xmax = -1;
+    if (d.vec_ok) {  // this video: plane % 4 == 0, base and strides 16-B aligned (chunk % 1024 == 0 for every video)
+        size_t i = beg + (size_t)threadIdx.x * 4;
+        int y = (int)(i / W), x = (int)(i - (size_t)y * W);
+        const int sy = 1024 / W, sx = 1024 % W;
+        auto visit = [&](const float4& v, int yy, int xx) {
+            if (fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)) > 0.5f) {
+                const float e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (e[j] > 0.5f) {
+                        ymin = min(ymin, yy); ymax = max(ymax, yy);
+                        xmin = min(xmin, xx); xmax = max(xmax, xx);
+                    }
+                    if (++xx == W) { xx = 0; ++yy; }
+                }
+            }
+        };
+        auto step = [&](int& yy, int& xx) { yy += sy; xx += sx; if (xx >= W) { xx -= W; ++yy; } };
+        for (; i + 3 * 1024 < end; i += 4 * 1024) {
+            const float4 v0 = *reinterpret_cast<const float4*>(p + i), v1 = *reinterpret_cast<const float4*>(p + i + 1024);
+            const float4 v2 = *reinterpret_cast<const float4*>(p + i + 2048), v3 = *reinterpret_cast<const float4*>(p + i + 3072);
+            visit(v0, y, x); step(y, x);
+            visit(v1, y, x); step(y, x);
+            visit(v2, y, x); step(y, x);
+            visit(v3, y, x); step(y, x);
+        }
+        for (; i < end; i += 1024) {
+            visit(*reinterpret_cast<const float4*>(p + i), y, x);
+            step(y, x);
+        }
+    } else {
+        for (size_t i = beg + threadIdx.x; i < end; i += 256) {
+            if (p[i] > 0.5f) {
+                const int y = (int)(i / W), x = (int)(i - (size_t)y * W);
+                ymin = min(ymin, y); ymax = max(ymax, y);
+                xmin = min(xmin, x); xmax = max(xmax, x);
+            }
+        }
+    }
+    ymin = wave_min(ymin); ymax = wave_max(ymax);
+    xmin = wave_min(xmin); xmax = wave_max(xmax);
+    __shared__ int red[4][4];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0) { red[wave][0] = ymin; red[wave][1] = ymax; red[wave][2] = xmin; red[wave][3] = xmax; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) {
+            ymin = min(ymin, red[w][0]); ymax = max(ymax, red[w][1]);
+            xmin = min(xmin, red[w][2]); xmax = max(xmax, red[w][3]);
+        }
+        if (ymax >= 0) {
+            atomicMin(&box[b * 4 + 0], ymin); atomicMax(&box[b * 4 + 1], ymax);
+            atomicMin(&box[b * 4 + 2], xmin); atomicMax(&box[b * 4 + 3], xmax);
+        }
+    }
+}
+
+// bbox_finalize_kernel with the H, W of the unit's own video (a per-thread lookup: neighbouring units may belong to different videos)
+__global__ void bbox_finalize_multi_kernel(const int32_t* __restrict__ box, const VideoTable vt, int b0, int B, float* __restrict__ yxhw) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int vi = video_of_unit(vt, b0 + b);
+    const int H = vt.v[vi].H, W = vt.v[vi].W;
+    int y0 = box[b * 4 + 0], y1 = box[b * 4 + 1], x0 = box[b * 4 + 2], x1 = box[b * 4 + 3];
+    if (y1 < 0) { y0 = 0; y1 = H; x0 = 0; x1 = W; }
+    if (y1 - y0 < 128) { const int half = (int)((128.0 - (double)(y1 - y0)) / 2.0); y0 -= half; y1 += half; }
+    if (x1 - x0 < 128) { const int half = (int)((128.0 - (double)(x1 - x0)) / 2.0); x0 -= half; x1 += half; }
+    const double oh = (double)(y1 - y0 + 1), ow = (double)(x1 - x0 + 1);
+    const double k = (1.5 - 1.0) / 2.0;
+    const double fy0 = fmax(-5.0, (double)y0 - k * oh), fy1 = fmin((double)H + 5.0, (double)y1 + k * oh);
+    const double fx0 = fmax(-5.0, (double)x0 - k * ow), fx1 = fmin((double)W + 5.0, (double)x1 + k * ow);
+    yxhw[b * 4 + 0] = (float)((fy1 + fy0) / 2.0);
+    yxhw[b * 4 + 1] = (float)((fx1 + fx0) / 2.0);
+    yxhw[b * 4 + 2] = (float)(fy1 - fy0 + 1.0);
+    yxhw[b * 4 + 3] = (float)(fx1 - fx0 + 1.0);
+}
+
+void launch_mask_bbox_multi(const VideoTable& vt, int b0, int B, float* yxhw, int32_t* scratch, hipStream_t st) {
+    hipLaunchKernelGGL(bbox_init_kernel, dim3((B + 63) / 64), dim3(64), 0, st, scratch, B);
+    size_t plane = 0;                                              // the largest plane among the videos of [b0, b0 + B)
+    for (int i = 0; i < vt.n; ++i) {
+        const long lo = vt.first[i], hi = lo + (long)vt.v[i].n_frames * vt.v[i].n_obj;
+        if (hi > b0 && lo < (long)b0 + B) plane = max(plane, (size_t)vt.v[i].H * vt.v[i].W);
+    }
+    int S = (int)max((size_t)1, min((size_t)64, (size_t)2048 / (size_t)B));
+    size_t chunk = (plane + S - 1) / S;
+    chunk = (chunk + 1023) / 1024 * 1024;
+    S = (int)((plane + chunk - 1) / chunk);
+    hipLaunchKernelGGL(bbox_scan_multi_kernel, dim3(S, B), dim3(256), 0, st, vt, b0, (int)chunk, scratch);
+    hipLaunchKernelGGL(bbox_finalize_multi_kernel, dim3((B + 63) / 64), dim3(64), 0, st, scratch, vt, b0, B, yxhw);
+}
+
+// One unit's ROI_R output rows: the body of roi_sample_kernel (U8 = false) / roi_sample_u8_kernel (U8 = true) behind their pointer
+// setup - the same theta, taps, weights, clamped pair loads, zero weights, product-sums and (f - mean) / std, in the same order.  The
+// four product-sums are written as the FMA chain that both single-video kernels compile to (see roi_sample_u8_kernel).
+template <typename T, bool U8>
+__device__ __forceinline__ void roi_unit_rows(const void* __restrict__ frame, const float* __restrict__ srcp, const float* __restrict__ yx,
+                                              int H, int W, const RoiNorm& nrm, int i0, int j, T* __restrict__ dst) {
+    const float ry = yx[0], rx = yx[1], rh = yx[2], rw = yx[3];
+    const float ymin = __fsub_rn(ry, rh / 2.0f), ymax = __fadd_rn(ry, rh / 2.0f);
+    const float xmin = __fsub_rn(rx, rw / 2.0f), xmax = __fadd_rn(rx, rw / 2.0f);
+    const float wm = (float)(W - 1), hm = (float)(H - 1);
+    const float t00 = __fsub_rn(xmax, xmin) / wm, t02 = __fsub_rn(__fadd_rn(xmin, xmax), wm) / wm;
+    const float t11 = __fsub_rn(ymax, ymin) / hm, t12 = __fsub_rn(__fadd_rn(ymin, ymax), hm) / hm;
+    const float gx = __fadd_rn(__fmul_rn(lin_m1_1(j, 256), t00), t02);
+    const float sx = __fmul_rn(__fmul_rn(__fadd_rn(gx, 1.0f), 0.5f), wm);
+    const float x0f = floorf(sx);
+    const int x0 = (int)x0f;
+    const float wx1 = __fsub_rn(sx, x0f), wx0 = __fsub_rn(__fadd_rn(x0f, 1.0f), sx);
+    const bool vx0 = x0 >= 0 && x0 < W, vx1 = x0 + 1 >= 0 && x0 + 1 < W;
+    const int xb = min(max(x0, 0), W - 2);
+    const bool t0_hi = x0 >= W - 1, t1_lo = x0 < 0;
+    const size_t plane = (size_t)H * W;
+    float mu[3], sd[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        mu[c] = nrm.dev ? nrm.dev[c] : nrm.mean[c];
+        sd[c] = nrm.dev ? nrm.dev[3 + c] : nrm.std[c];
+    }
+#pragma unroll 1
+    for (int r0 = 0; r0 < ROI_R; r0 += 2) {
+        float v[2][4][4], k[2][4];                                 // [row][channel][tap: nw, ne, sw, se]
+        uint32_t px[2][4];                                         // U8: the four taps' pixel words
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+            const int i = i0 + r0 + rr;
+            const float gy = __fadd_rn(__fmul_rn(lin_m1_1(i, 256), t11), t12);
+            const float sy = __fmul_rn(__fmul_rn(__fadd_rn(gy, 1.0f), 0.5f), hm);
+            const float y0f = floorf(sy);
+            const int y0 = (int)y0f;
+            const float wy1 = __fsub_rn(sy, y0f), wy0 = __fsub_rn(__fadd_rn(y0f, 1.0f), sy);
+            const bool vy0 = y0 >= 0 && y0 < H, vy1 = y0 + 1 >= 0 && y0 + 1 < H;
+            const int yc0 = min(max(y0, 0), H - 1), yc1 = min(max(y0 + 1, 0), H - 1);
+            const int o0 = yc0 * W + xb, o1 = yc1 * W + xb;        // pixels o0, o0 + 1 < H * W <= INT_MAX (checked by the host)
+            const float w_nw = __fmul_rn(wx0, wy0), w_ne = __fmul_rn(wx1, wy0), w_sw = __fmul_rn(wx0, wy1), w_se = __fmul_rn(wx1, wy1);
+            k[rr][0] = (vy0 && vx0) ? w_nw : 0.f; k[rr][1] = (vy0 && vx1) ? w_ne : 0.f;
+            k[rr][2] = (vy1 && vx0) ? w_sw : 0.f; k[rr][3] = (vy1 && vx1) ? w_se : 0.f;
+            if constexpr (U8) {
+                const uint8_t* srcf = static_cast<const uint8_t*>(frame);
+                const uint2 c0 = ld_pair_u32(srcf + (size_t)o0 * 4), c1 = ld_pair_u32(srcf + (size_t)o1 * 4);
+                px[rr][0] = t0_hi ? c0.y : c0.x; px[rr][1] = t1_lo ? c0.x : c0.y;
+                px[rr][2] = t0_hi ? c1.y : c1.x; px[rr][3] = t1_lo ? c1.x : c1.y;
+            }
+#pragma unroll
+            for (int c = U8 ? 3 : 0; c < 4; ++c) {
+                const float* s = c < 3 ? static_cast<const float*>(frame) + (size_t)c * plane : srcp;
+                const float2 p0 = ld_pair(s + o0), p1 = ld_pair(s + o1);
+                v[rr][c][0] = t0_hi ? p0.y : p0.x; v[rr][c][1] = t1_lo ? p0.x : p0.y;
+                v[rr][c][2] = t0_hi ? p1.y : p1.x; v[rr][c][3] = t1_lo ? p1.x : p1.y;
+            }
+        }
+#pragma unroll
+        for (int rr = 0; rr < 2; ++rr) {
+            float out[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                float t[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    if constexpr (U8) t[q] = c < 3 ? u8_unit(px[rr][q], c) : v[rr][3][q];
+                    else t[q] = v[rr][c][q];
+                }
+                float acc = 0.f;
+                acc = __builtin_fmaf(t[0], k[rr][0], acc);
+                acc = __builtin_fmaf(t[1], k[rr][1], acc);
+                acc = __builtin_fmaf(t[2], k[rr][2], acc);
+                acc = __builtin_fmaf(t[3], k[rr][3], acc);
+                if (c < 3) acc = __fsub_rn(acc, mu[c]) / sd[c];
+                out[c] = acc;
+            }
+            T* d = dst + (size_t)(r0 + rr) * 256 * 4;
+            if constexpr (sizeof(T) == 4) {
+                *reinterpret_cast<float4*>(d) = make_float4(out[0], out[1], out[2], out[3]);
+            } else {
+                *reinterpret_cast<uint2*>(d) = make_uint2(pack2_bf16(out[0], out[1]), pack2_bf16(out[2], out[3]));
+            }
+        }
+    }
+}
+
+// roi_sample_kernel / roi_sample_u8_kernel over the units [b0, b0 + B) of a video table: grid B * 256 / ROI_R, block 256, thread j =
+// output column j of ROI_R rows of one unit.  The workgroup resolves its unit's video once (uniform), then runs that video's sampler.
+template <typename T>
+__global__ __launch_bounds__(256) void roi_sample_multi_kernel(const VideoTable vt, const float* __restrict__ yxhw, int b0, RoiNorm nrm,
+                                                               T* __restrict__ roi) {
+    constexpr int GPS = 256 / ROI_R;
+    const int b = blockIdx.x / GPS, i0 = (blockIdx.x % GPS) * ROI_R, j = threadIdx.x;
+    const int u = b0 + b, vi = video_of_unit(vt, u);
+    const VideoDesc& d = vt.v[vi];
+    const int H = d.H, W = d.W, nf = d.n_frames;
+    const int lu = u - vt.first[vi], fr = lu % nf;
+    const float* srcp = d.masks + (size_t)(lu / nf) * d.stride_obj + (size_t)fr * d.stride_frame;
+    T* dst = roi + (((size_t)b * 256 + i0) * 256 + j) * 4;
+    if (d.u8) {
+        const uint8_t* srcf = static_cast<const uint8_t*>(d.frames) + (size_t)fr * H * W * 4;
+        roi_unit_rows<T, true>(srcf, srcp, yxhw + b * 4, H, W, nrm, i0, j, dst);
+    } else {
+        const float* srcf = static_cast<const float*>(d.frames) + (size_t)fr * 3 * H * W;
+        roi_unit_rows<T, false>(srcf, srcp, yxhw + b * 4, H, W, nrm, i0, j, dst);
+    }
+}
+
+void launch_roi_sample_multi(const VideoTable& vt, const float* yxhw, int b0, int B, int dtype, const RoiNorm& nrm, void* roi, hipStream_t st) {
+    const dim3 grid(B * (256 / ROI_R)), block(256);
+    if (dtype != IVOSW_BF16)
+        hipLaunchKernelGGL(roi_sample_multi_kernel<float>, grid, block, 0, st, vt, yxhw, b0, nrm, static_cast<float*>(roi));
+    else
+        hipLaunchKernelGGL(roi_sample_multi_kernel<bf16_t>, grid, block, 0, st, vt, yxhw, b0, nrm, static_cast<bf16_t*>(roi));
+}
+
+static void set_video_error(const char* who, int i, const char* msg) { set_error("%s: video %d: %s", who, i, msg); }
+
+int video_table_build(const ivosw_video_t* videos, int n_videos, const char* who, VideoTable* out) {
+    if (!videos) { set_error("%s: null pointer (videos)", who); return IVOSW_ERR_ARG; }
+    if (n_videos < 1 || n_videos > IVOSW_MAX_VIDEOS) {
+        set_error("%s: n_videos = %d is outside [1, %d]", who, n_videos, IVOSW_MAX_VIDEOS);
+        return IVOSW_ERR_ARG;
+    }
+    VideoTable t{};
+    long units = 0;
+    for (int i = 0; i < IVOSW_MAX_VIDEOS; ++i) t.first[i] = INT_MAX;
+    for (int i = 0; i < n_videos; ++i) {
+        const ivosw_video_t& s = videos[i];
+#define VIDEO_REQUIRE(cond, msg) do { if (!(cond)) { set_video_error(who, i, msg); return IVOSW_ERR_ARG; } } while (0)
+        VIDEO_REQUIRE(s.frames && s.masks, "null pointer");
+        VIDEO_REQUIRE(s.frames_kind == IVOSW_FRAMES_F32 || s.frames_kind == IVOSW_FRAMES_RGBX8, "frames_kind must be IVOSW_FRAMES_F32 or IVOSW_FRAMES_RGBX8");
+        VIDEO_REQUIRE(s.n_frames > 0 && s.n_obj > 0, "n_frames and n_obj must be positive");
+        VIDEO_REQUIRE(s.H > 1 && s.W > 1, "H, W > 1 wanted");
+        VIDEO_REQUIRE((long)s.H * s.W <= INT_MAX, "frame too large (H * W <= INT_MAX)");
+        VIDEO_REQUIRE(s.mask_stride_obj >= 0 && s.mask_stride_frame >= 0, "negative mask stride");
+        VIDEO_REQUIRE(s.mask_stride_frame >= (long)s.H * s.W || s.n_frames == 1, "mask planes of consecutive frames overlap");
+        VIDEO_REQUIRE(s.frames_kind != IVOSW_FRAMES_RGBX8 || (reinterpret_cast<uintptr_t>(s.frames) & 3) == 0, "rgbx must be 4-byte aligned");
+        units += (long)s.n_frames * s.n_obj;
+        VIDEO_REQUIRE(units < (1L << 30), "too many (frame, object) units for one call (2^30 or more up to this video)");
+#undef VIDEO_REQUIRE
+        VideoDesc& d = t.v[i];
+        d.frames = s.frames; d.masks = s.masks;
+        d.stride_frame = s.mask_stride_frame; d.stride_obj = s.mask_stride_obj;
+        d.n_frames = s.n_frames; d.n_obj = s.n_obj; d.H = s.H; d.W = s.W;
+        d.u8 = s.frames_kind == IVOSW_FRAMES_RGBX8;
+        d.vec_ok = ((size_t)s.H * s.W) % 4 == 0 && (reinterpret_cast<uintptr_t>(s.masks) & 15) == 0 && s.mask_stride_frame % 4 == 0 &&
+                   s.mask_stride_obj % 4 == 0;
+        t.first[i] = (int)(units - (long)s.n_frames * s.n_obj);
+    }
+    t.n = n_videos;
+    t.units = (int)units;
+    if (out) *out = t;
+    return IVOSW_OK;
+}
+
 }  // namespace ivosw
 
 using namespace ivosw;
@@ -459,6 +733,36 @@ extern "C" int ivosw_roi_sample_u8(const uint8_t* rgbx, const float* tp, const f
     IVOSW_ON_DEVICE_OF(roi);
     RoiNorm nrm{{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}, nullptr};  // Encoder.mean/std (assessment.py:41-44)
     launch_roi_sample(FrameSrc{rgbx, 1}, tp, yxhw, 0, B, H, W, dtype, SampleMap{B, (long)H * W, 0}, nrm, roi, as_stream(stream));
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" long ivosw_assess_videos_units(const ivosw_video_t* videos, int n_videos) {
+    VideoTable vt;
+    const int rc = video_table_build(videos, n_videos, __func__, &vt);
+    return rc == IVOSW_OK ? (long)vt.units : (long)rc;
+}
+
+extern "C" int ivosw_mask_bbox_videos(const ivosw_video_t* videos, int n_videos, float* yxhw, int32_t* scratch, ivosw_stream_t stream) {
+    VideoTable vt;
+    if (const int rc = video_table_build(videos, n_videos, __func__, &vt)) return rc;
+    IVOSW_REQUIRE(yxhw && scratch, "null pointer");
+    IVOSW_ON_DEVICE_OF(yxhw);
+    launch_mask_bbox_multi(vt, 0, vt.units, yxhw, scratch, as_stream(stream));
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_roi_sample_videos(const ivosw_video_t* videos, int n_videos, const float* yxhw, int dtype, void* roi,
+                                       ivosw_stream_t stream) {
+    VideoTable vt;
+    if (const int rc = video_table_build(videos, n_videos, __func__, &vt)) return rc;
+    IVOSW_REQUIRE(yxhw && roi, "null pointer");
+    IVOSW_REQUIRE(vt.units <= (1 << 24), "batch too large (units <= 2^24)");
+    IVOSW_REQUIRE(dtype == IVOSW_F32 || dtype == IVOSW_BF16 || dtype == IVOSW_F32X3, "dtype must be IVOSW_F32, IVOSW_BF16 or IVOSW_F32X3");
+    IVOSW_ON_DEVICE_OF(roi);
+    RoiNorm nrm{{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}, nullptr};  // Encoder.mean/std (assessment.py:41-44)
+    launch_roi_sample_multi(vt, yxhw, 0, vt.units, dtype, nrm, roi, as_stream(stream));
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }

@@ -22,6 +22,27 @@ struct FrameSrc {
     const void* p;
     int u8;
 };
+// Several videos in one launch.  Units are numbered video-major, then object-major inside a video: u = first[v] + obj * n_frames[v] +
+// frame.  The table travels BY VALUE in the kernel arguments (under 2 KB for IVOSW_MAX_VIDEOS = 32): no allocation and no copy, so the
+// multi-video entries stay capture-safe.  A workgroup finds the video of its unit with a branch-free count over first[] (entries behind
+// the last video hold INT_MAX) - scalar loads and compares, uniform per workgroup - and reads that video's row through scalar loads.
+struct VideoDesc {
+    const void* frames;                  // fp32 [n,3,H,W] or RGBX8 [n,H,W,4] (u8)
+    const float* masks;
+    long stride_frame, stride_obj;       // of the mask planes, in elements
+    int n_frames, n_obj, H, W;
+    int u8;                              // frame source: 0 fp32 planes, 1 RGBX8
+    int vec_ok;                          // the scan may use 16-byte loads on this video's planes (what launch_mask_bbox derives)
+};
+struct VideoTable {
+    VideoDesc v[IVOSW_MAX_VIDEOS];
+    int first[IVOSW_MAX_VIDEOS];         // first unit of video i; INT_MAX for i >= n
+    int n, units;
+};
+// Validates the caller's array (every refusal of include/ivosw.h, the message names the video) and fills the table.
+int video_table_build(const ivosw_video_t* videos, int n_videos, const char* who, VideoTable* out);
+void launch_mask_bbox_multi(const VideoTable& vt, int b0, int B, float* yxhw, int32_t* scratch, hipStream_t st);
+void launch_roi_sample_multi(const VideoTable& vt, const float* yxhw, int b0, int B, int dtype, const RoiNorm& nrm, void* roi, hipStream_t st);
 void launch_mask_bbox(const float* tp, int b0, int B, int H, int W, const SampleMap& sm, float* yxhw, int32_t* scratch, hipStream_t st);
 void launch_roi_sample(const FrameSrc& fs, const float* tp, const float* yxhw, int b0, int B, int H, int W, int dtype,
                        const SampleMap& sm, const RoiNorm& nrm, void* roi, hipStream_t st);

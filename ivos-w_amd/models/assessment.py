@@ -282,6 +282,69 @@ class AssessNet(nn.Module):
                     L.dptr(ws), nbytes, self.chunk, L.stream_ptr(dev)), "assess_forward_objects_u8" if u8 else "assess_forward_objects")
         return scores
 
+    def _video_entry(self, k, video, keep):
+        """One (all_F | PackedFrames, all_P, n_objects) of forward_videos -> (L.Video, n), normalised by forward_objects' rules; tensors the
+        descriptor points into are appended to `keep`."""
+        all_F, all_P, n_objects = video
+        n_objects = int(n_objects)
+        u8 = isinstance(all_F, PackedFrames)
+        if u8:
+            n, H, W = all_F.n, all_F.H, all_F.W
+            all_F = all_F.rgbx
+        else:
+            n, C3, H, W = all_F.shape
+            assert C3 == 3, f"video {k}: all_F must be [n,3,H,W]"
+            if all_F.dtype != torch.float32 or not all_F.is_contiguous():
+                all_F = all_F.detach().to(torch.float32).contiguous()
+        assert all_P.shape[0] == n and tuple(all_P.shape[2:]) == (H, W) and all_P.shape[1] > n_objects >= 1, f"video {k}: all_P shape"
+        if all_P.dtype != torch.float32 or all_P.stride(3) != 1 or all_P.stride(2) != W:
+            all_P = all_P.detach().to(torch.float32).contiguous()
+        if not all_P.is_cuda or all_P.device != all_F.device:
+            raise RuntimeError(f"ivos_w_amd: video {k}: all_P must live on the frames' GPU (there is no CPU fallback)")
+        masks = all_P[:, 1:]                                # a view: channel 0 is the background
+        keep += [all_F, all_P]
+        return L.Video(L.dptr(all_F).value, masks.data_ptr(), all_P.stride(0), all_P.stride(1),
+                       L.FRAMES_RGBX8 if u8 else L.FRAMES_F32, n, n_objects, H, W), n
+
+    def forward_videos(self, videos):
+        """Scores of every (object, frame) unit of SEVERAL videos in one pass (ivosw_assess_forward_videos): ``videos`` is a sequence of
+        (all_F | PackedFrames, all_P, n_objects), each as ``forward_objects`` takes them - every video its own length, frame size, frame
+        format and all_P layout, all on this network's device.  Returns a list with one [n_objects, n] fp32 view per video, in the order
+        given, all views of one flat score tensor in unit order (video-major, then object-major).  Each score is bit for bit what
+        ``forward_objects`` gives for that video alone.  More than 32 videos run in groups of 32."""
+        if self.training:
+            raise RuntimeError("AssessNet on the MI355X path is inference-only; call .eval()")
+        videos = list(videos)
+        if not videos:
+            return []
+        keep, descs, shapes = [], [], []
+        for k, video in enumerate(videos):
+            d, n = self._video_entry(k, video, keep)
+            descs.append(d)
+            shapes.append((d.n_obj, n))
+        dev = keep[0].device
+        packed = self._ensure_packed()
+        lib, dt = L.lib(), _DTYPES[self.precision]
+        scores = torch.empty(sum(o * n for o, n in shapes), dtype=torch.float32, device=dev)
+        off = 0
+        for g in range(0, len(descs), L.MAX_VIDEOS):
+            group = descs[g:g + L.MAX_VIDEOS]
+            arr = (L.Video * len(group))(*group)
+            units = int(lib.ivosw_assess_videos_units(arr, len(group)))
+            if units < 0:
+                L.check(units, "assess_videos_units")
+            nbytes = lib.ivosw_assess_ws_bytes(dt, units, group[0].H, group[0].W, self.chunk)     # (H, W are not looked at)
+            ws = self._ws.get(nbytes, dev)
+            out = scores[off:off + units]
+            L.check(lib.ivosw_assess_forward_videos(L.dptr(packed), dt, arr, len(group), L.dptr(out), L.dptr(ws), nbytes, self.chunk,
+                                                    0, None, L.stream_ptr(dev)), "assess_forward_videos")
+            off += units
+        views, off = [], 0
+        for o, n in shapes:
+            views.append(scores[off:off + o * n].view(o, n))
+            off += o * n
+        return views
+
     def forward_tap(self, tf, tp, tap):
         """Debug/test hook: also returns one intermediate (NHWC; see ``_TAPS``)."""
         return self._run(tf, tp, tap)

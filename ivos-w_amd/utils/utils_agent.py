@@ -168,6 +168,72 @@ def _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, cou
     return picked if picked is not None else np.int64(host[n:].view(torch.int64)[0].item())
 
 
+def assess_videos_device(assess_net, videos, device):
+    """Quality predictions of SEVERAL videos from one assessment pass (AssessNet.forward_videos): ``videos`` is a sequence of
+    (all_F | PackedFrames, all_P, n_objects); returns one [n_objects, n_frame] device tensor per video, each bit for bit what
+    ``assess_all_objects_device`` gives for that video alone.  Host-resident tensors are uploaded for this call only: the single-entry
+    ``frame_cache`` is neither read nor written (several videos would evict each other on every call) - multi-session callers keep
+    their videos on the device (``pack_video``, or ``all_F.to(device)`` once per sequence)."""
+    device = torch.device(device)
+    on_dev = []
+    for all_F, all_P, n_objects in videos:
+        if not _is_packed(all_F) and not (all_F.is_cuda and all_F.device == device):
+            all_F = all_F.to(device=device, dtype=torch.float32)
+        if not (all_P.is_cuda and all_P.device == device):
+            all_P = all_P.to(device)
+        on_dev.append((all_F, all_P, n_objects))
+    return assess_net.forward_videos(on_dev)
+
+
+def recommend_frames(cfg_yl, assess_net, agent, device, requests):
+    """``recommend_frame`` for several sessions at once: ``requests`` is a sequence of dicts, each the keyword arguments of
+    ``recommend_frame`` behind ``device`` (n_frame, n_objects, all_F, all_P, new_masks_quality, prev_frames, annotated_frames_list,
+    mask_quality, first_frame, max_nb_interactions).  Returns the recommended indices in request order.
+
+    Under wild/ours and wild/worst all requests share ONE assessment pass (assess_videos_device: K short videos fill one full-size pass
+    instead of K small ones); then, per request in request order, quality -> state -> Brain -> first-max argmax runs on the device
+    (``agent.action`` is called once per request, so ``steps_done`` and the host RNG move exactly as under sequential
+    ``recommend_frame`` calls), ONE device-to-host copy brings back every quality vector and index, and each request's
+    ``mask_quality`` is filled in place.  Indices and quality vectors equal those of ``recommend_frame`` per request.  Every other
+    setting / method is ``recommend_frame`` per request.
+
+    Keep the videos on the device (``pack_video`` or ``all_F.to(device)`` once per sequence): host-resident frames are uploaded on
+    every call here, and the single-entry ``frame_cache`` of ``recommend_frame`` is left alone."""
+    requests = list(requests)
+    if not (cfg_yl.setting == "wild" and cfg_yl.method in ("worst", "ours")):
+        return [recommend_frame(cfg_yl, assess_net, agent, device, **r) for r in requests]
+    if not requests:
+        return []
+    from .. import _lib as L
+    method = cfg_yl.method
+    with torch.no_grad():
+        scores = assess_videos_device(assess_net, [(r["all_F"], r["all_P"], r["n_objects"]) for r in requests], device)
+        dev = scores[0].device
+        ns = [int(s.shape[1]) for s in scores]
+        offs = np.concatenate([[0], np.cumsum([n + 1 for n in ns])])
+        out = torch.zeros(int(offs[-1]), dtype=torch.float64, device=dev)   # per request [quality (n) | recommended index (int64 bits)]
+        counts = [_annotation_counts(len(r["new_masks_quality"]), r["annotated_frames_list"]) for r in requests]
+        cnt = torch.as_tensor(np.concatenate(counts).astype(np.float32)).to(dev, non_blocking=True)      # one upload for all requests
+        picked, c0 = [], 0
+        for r, s, n, o in zip(requests, scores, ns, offs[:-1]):
+            o = int(o)
+            state = torch.empty(n, 2, dtype=torch.float32, device=dev)
+            L.check(L.lib().ivosw_quality_state(L.dptr(s), int(r["n_objects"]), n, L.dptr(cnt[c0:c0 + n]), L.dptr(out[o:o + n]),
+                                                L.dptr(state), L.stream_ptr(dev)), "quality_state")
+            c0 += n
+            picked.append(agent.action(state, device_out=out[o + n:o + n + 1].view(torch.int64)) if method == "ours" else None)
+        host = out.cpu()                                                    # the one D2H copy of the call
+    result = []
+    for r, n, o, pk in zip(requests, ns, offs[:-1], picked):
+        o = int(o)
+        r["mask_quality"][:] = host[o:o + n].numpy()                        # in place: the caller logs corr/diff from this array
+        if method == "worst":
+            result.append(select_next_frame(r["mask_quality"], metric="worst", prev_frames=r["prev_frames"]))
+        else:
+            result.append(pk if pk is not None else np.int64(host[o + n:o + n + 1].view(torch.int64)[0].item()))
+    return result
+
+
 def recommend_frame(cfg_yl, assess_net, agent, device, n_frame, n_objects, all_F, all_P, new_masks_quality, prev_frames,
                     annotated_frames_list, mask_quality, first_frame, max_nb_interactions):
     setting, method = cfg_yl.setting, cfg_yl.method
