@@ -17,8 +17,7 @@
 #include "gemm_f32.h"
 #include "brain_fused.h"
 #include "brain_bwd.h"
-#include "sgd.h"
-#include "target.h"
+#include "dqn_update.h"
 
 namespace ivosw {
 
@@ -1599,122 +1598,49 @@ extern "C" int ivosw_dqn_loss_grad(const float* policy, const float* target, con
                                   grads, loss, ws, ws_bytes, stream);
 }
 
-// Clamp + Adam (clamp_adam_dev_kernel's expressions: same bits) with the step's split-K slab reduction folded in: an element of
-// a slabbed tensor is summed from its slabs ON LOAD in splitk_reduce_group_kernel's order (four interleaved partial sums over
-// z, eight loads in flight, (s0 + s1) + (s2 + s3)) and written to the gradient arena on the way, so the arena holds what the
-// separate reduction would have left there.  off[k] = element offset of slab set k in the arena.
-struct ReduceOffsets { int off[REDUCE_MAX]; };
-
-// The gradient of arena element i as the update tails see it: an element of a slabbed tensor is summed from its slabs here (and
-// written to g[i]), any other element is read from the arena.  Shared by clamp_adam_dev_reduce_kernel and clamp_sgd_reduce_kernel.
-__device__ __forceinline__ float reduce_on_load(float* __restrict__ g, const ReduceGroup& rg, const ReduceOffsets& ro, int i) {
-    int w = -1;
-#pragma unroll
-    for (int k = 0; k < REDUCE_MAX; ++k)
-        if (rg.nslab[k] > 0 && i >= ro.off[k] && i < ro.off[k] + rg.n[k]) w = k;
-    if (w < 0) return g[i];
-    const float* sl = rg.slabs[w] + (i - ro.off[w]);
-    const size_t nn = rg.n[w];
-    const int ns = rg.nslab[w];
-    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-    int z = 0;
-    for (; z + 8 <= ns; z += 8) {
-        float q[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) q[u] = sl[(size_t)(z + u) * nn];
-        s0 += q[0]; s1 += q[1]; s2 += q[2]; s3 += q[3];
-        s0 += q[4]; s1 += q[5]; s2 += q[6]; s3 += q[7];
-    }
-    for (; z < ns; ++z) s0 += sl[(size_t)z * nn];
-    const float gi = (s0 + s1) + (s2 + s3);
-    g[i] = gi;
-    return gi;
-}
-
-// One element per lane, 177 workgroups: the slabs (13.5 MB at B = 128, T = 25, fresh in L2) are pulled by the whole chip — with the
-// 45 workgroups of the 16-byte form the launch took 11 us, more than the reduction + update launches it replaces (5.3 + 5.1).
-// The body is shared with clamp_adam_dev_reduce_sched_kernel, which only picks lr differently.
-__device__ __forceinline__ void clamp_adam_dev_reduce_apply(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                            float* __restrict__ v, int n, AdamDevState* __restrict__ st, const ReduceGroup& rg,
-                                                            const ReduceOffsets& ro, float lr, float beta1, float beta2, float eps, float wd,
-                                                            float clampv, float gscale) {
-    const int step = st->step + 1;
-    const double b1t = ipow((double)beta1, step), b2t = ipow((double)beta2, step);
-    const float step_size = (float)((double)lr / (1.0 - b1t)), bc2_sqrt = (float)sqrt(1.0 - b2t);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const float gi = reduce_on_load(g, rg, ro, i);
-        float mi = m[i], vi = v[i];
-        p[i] = clamp_adam_elem(gi, p[i], mi, vi, step_size, bc2_sqrt, beta1, beta2, eps, wd, clampv, gscale);
-        m[i] = mi; v[i] = vi;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (atomicAdd(&st->ticket, 1u) == gridDim.x - 1) {
-            st->b1t = b1t; st->b2t = b2t; st->step = step; st->step_size = step_size; st->bc2_sqrt = bc2_sqrt;
-            atomicExch(&st->ticket, 0u);
-        }
-    }
-}
+// The one-call step's tails: clamp_update (dqn_update.h) with the step's split-K slab reduction folded into the gradient load (SlabGrad:
+// reduce_on_load), one wrapper per combination of rule, lr source and target; the stand-alone kernels of dqn.hip are the same body over
+// ArenaGrad, so both give the same bits.  One element per lane, 177 workgroups: the slabs (13.5 MB at B = 128, T = 25, fresh in L2) are
+// pulled by the whole chip — with the 45 workgroups of the 16-byte form the launch took 11 us, more than the reduction + update launches
+// it replaces (5.3 + 5.1).
+struct ReduceOffsets { int off[REDUCE_MAX]; };       // off[k] = element offset of slab set k in the gradient arena
 
 __global__ __launch_bounds__(1024) void clamp_adam_dev_reduce_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                                      float* __restrict__ v, int n, AdamDevState* __restrict__ st, ReduceGroup rg,
                                                                      ReduceOffsets ro, float lr, float beta1, float beta2, float eps, float wd,
                                                                      float clampv, float gscale) {
-    clamp_adam_dev_reduce_apply(p, g, m, v, n, st, rg, ro, lr, beta1, beta2, eps, wd, clampv, gscale);
+    clamp_update<false>(p, n, AdamRule{m, v, st, beta1, beta2, eps, wd, clampv, gscale}, SlabGrad{g, rg, ro.off}, Lr<false>{lr}, NoTarget{});
 }
 
-// The scheduled one-call tail (cfg.agent.lr_schedule = "poly"): lr = lr_table[min(k, lr_steps)] with k the counter left by the previous
-// step (clamp_adam_dev_sched_kernel's choice), the rest clamp_adam_dev_reduce_kernel's.
+// cfg.agent.lr_schedule = "poly"
 __global__ __launch_bounds__(1024) void clamp_adam_dev_reduce_sched_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                                            float* __restrict__ v, int n, AdamDevState* __restrict__ st,
                                                                            ReduceGroup rg, ReduceOffsets ro, const float* __restrict__ lr_table,
                                                                            int lr_steps, float beta1, float beta2, float eps, float wd,
                                                                            float clampv, float gscale) {
-    clamp_adam_dev_reduce_apply(p, g, m, v, n, st, rg, ro, sched_lr(lr_table, lr_steps, st->step), beta1, beta2, eps, wd, clampv, gscale);
+    clamp_update<false>(p, n, AdamRule{m, v, st, beta1, beta2, eps, wd, clampv, gscale}, SlabGrad{g, rg, ro.off}, Lr<true>{0.f, lr_table, lr_steps},
+                        NoTarget{});
 }
 
-// Clamp + SGD (clamp_sgd_elem: the expressions of clamp_sgd_kernel) with the same slab reduction folded in on load.  No step counter, so
-// no ticket: the launch simply repeats under a captured graph.
+// cfg.agent.optimizer = "sgd": no step counter, so no ticket; on the schedule the SGD state's
 __global__ __launch_bounds__(1024) void clamp_sgd_reduce_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf, int n,
                                                                 ReduceGroup rg, ReduceOffsets ro, float lr, float mu, float wd, int nesterov,
                                                                 float clampv, float gscale) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float gi = reduce_on_load(g, rg, ro, i);
-    float bi = buf[i];
-    p[i] = clamp_sgd_elem(gi, p[i], bi, lr, mu, wd, nesterov, clampv, gscale);
-    buf[i] = bi;
+    clamp_update<false>(p, n, SgdRule{buf, nullptr, mu, wd, nesterov, clampv, gscale}, SlabGrad{g, rg, ro.off}, Lr<false>{lr}, NoTarget{});
 }
 
-// The scheduled form: lr = lr_table[min(k, lr_steps)] with k = st->step, the update of clamp_sgd_reduce_kernel, and the device step counter
-// advanced by the last workgroup (clamp_sgd_sched_kernel's ticket).
 __global__ __launch_bounds__(1024) void clamp_sgd_reduce_sched_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf,
                                                                       int n, SgdDevState* __restrict__ st, ReduceGroup rg, ReduceOffsets ro,
                                                                       const float* __restrict__ lr_table, int lr_steps, float mu, float wd,
                                                                       int nesterov, float clampv, float gscale) {
-    const int k = st->step;
-    const float lr = sched_lr(lr_table, lr_steps, k);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const float gi = reduce_on_load(g, rg, ro, i);
-        float bi = buf[i];
-        p[i] = clamp_sgd_elem(gi, p[i], bi, lr, mu, wd, nesterov, clampv, gscale);
-        buf[i] = bi;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (atomicAdd(&st->ticket, 1u) == gridDim.x - 1) {
-            st->step = k + 1;
-            atomicExch(&st->ticket, 0u);
-        }
-    }
+    clamp_update<false>(p, n, SgdRule{buf, st, mu, wd, nesterov, clampv, gscale}, SlabGrad{g, rg, ro.off}, Lr<true>{0.f, lr_table, lr_steps},
+                        NoTarget{});
 }
 
-// The one-call tails with the target-network rule fused in (cfg.agent.target_update = "soft" | "periodic", target.h): the thread that
-// has just produced p_new also writes the target element, so the step keeps its eight launches.  The target arena was last read by the
-// head kernel, earlier in the stream.  The update is clamp_adam_dev_reduce[_sched]_kernel's, expression by expression (same bits); both
-// counters are read by every workgroup before the last one (the Adam state's ticket) advances them.
+// The tails with the target-network rule fused in (cfg.agent.target_update = "soft" | "periodic", target.h): the thread that has just
+// produced p_new also writes the target element, so the step keeps its eight launches.  The target arena was last read by the head
+// kernel, earlier in the stream.  Both counters advance under one ticket: the Adam state's, the SGD state's on the schedule, and the
+// target state's for the constant-lr SGD update, which has no counter of its own.
 struct TargetArgs {
     float* t;
     TargetDevState* st;
@@ -1729,184 +1655,35 @@ __global__ __launch_bounds__(1024) void adam_tail_tgt_kernel(float* __restrict__
                                                              ReduceOffsets ro, float lr_const, const float* __restrict__ lr_table, int lr_steps,
                                                              float beta1, float beta2, float eps, float wd, float clampv, float gscale,
                                                              TargetArgs ta) {
-    const float lr = SCHED ? sched_lr(lr_table, lr_steps, st->step) : lr_const;
-    const int k = ta.st->step;
-    const bool fires = target_fires(k, ta.period);
-    const int step = st->step + 1;
-    const double b1t = ipow((double)beta1, step), b2t = ipow((double)beta2, step);
-    const float step_size = (float)((double)lr / (1.0 - b1t)), bc2_sqrt = (float)sqrt(1.0 - b2t);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const float gi = reduce_on_load(g, rg, ro, i);
-        float mi = m[i], vi = v[i];
-        const float pn = clamp_adam_elem(gi, p[i], mi, vi, step_size, bc2_sqrt, beta1, beta2, eps, wd, clampv, gscale);
-        p[i] = pn;
-        m[i] = mi; v[i] = vi;
-        target_elem(ta.t, i, pn, ta.mode, ta.tau, fires);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (atomicAdd(&st->ticket, 1u) == gridDim.x - 1) {
-            st->b1t = b1t; st->b2t = b2t; st->step = step; st->step_size = step_size; st->bc2_sqrt = bc2_sqrt;
-            ta.st->step = k + 1;
-            atomicExch(&st->ticket, 0u);
-        }
-    }
+    clamp_update<false>(p, n, AdamRule{m, v, st, beta1, beta2, eps, wd, clampv, gscale}, SlabGrad{g, rg, ro.off},
+                        Lr<SCHED>{lr_const, lr_table, lr_steps}, ta);
 }
 
-// The SGD tails (clamp_sgd_reduce[_sched]_kernel's update) with the rule fused in.  The constant-lr update has no counter of its own: the
-// ticket is the target state's; the scheduled one advances both counters under the SGD state's.
 template <bool SCHED>
 __global__ __launch_bounds__(1024) void sgd_tail_tgt_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf, int n,
                                                             SgdDevState* __restrict__ st, ReduceGroup rg, ReduceOffsets ro, float lr_const,
                                                             const float* __restrict__ lr_table, int lr_steps, float mu, float wd, int nesterov,
                                                             float clampv, float gscale, TargetArgs ta) {
-    const int ks = SCHED ? st->step : 0;
-    const float lr = SCHED ? sched_lr(lr_table, lr_steps, ks) : lr_const;
-    const int k = ta.st->step;
-    const bool fires = target_fires(k, ta.period);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const float gi = reduce_on_load(g, rg, ro, i);
-        float bi = buf[i];
-        const float pn = clamp_sgd_elem(gi, p[i], bi, lr, mu, wd, nesterov, clampv, gscale);
-        p[i] = pn;
-        buf[i] = bi;
-        target_elem(ta.t, i, pn, ta.mode, ta.tau, fires);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned* ticket = SCHED ? &st->ticket : &ta.st->ticket;
-        if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
-            if (SCHED) st->step = ks + 1;
-            ta.st->step = k + 1;
-            atomicExch(ticket, 0u);
-        }
-    }
+    clamp_update<false>(p, n, SgdRule{buf, st, mu, wd, nesterov, clampv, gscale}, SlabGrad{g, rg, ro.off}, Lr<SCHED>{lr_const, lr_table, lr_steps},
+                        ta);
 }
 
-extern "C" int ivosw_replay_draw_gather(const float* old_iou, const float* new_iou, const float* annotated, const float* next_annotated,
-                                        const int64_t* action, const float* reward_step, const float* reward_done, void* draw_state, int n,
-                                        int B, int T, int64_t* idx_out, float* state, float* new_state, int64_t* action_out,
-                                        float* reward_step_out, float* reward_done_out, ivosw_stream_t stream);
-extern "C" int ivosw_clamp_adam_dev(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int n, void* adam_state, float lr,
-                                    float beta1, float beta2, float eps, float weight_decay, float clamp, float grad_scale,
-                                    ivosw_stream_t stream);
-extern "C" int ivosw_clamp_sgd(float* params, const float* grads, float* momentum_buf, int n, float lr, float momentum, float weight_decay,
-                               int nesterov, float clamp, float grad_scale, ivosw_stream_t stream);
-extern "C" int ivosw_clamp_adam_dev_sched(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int n, void* adam_state,
-                                          const float* lr_table, int lr_steps, float beta1, float beta2, float eps, float weight_decay,
-                                          float clamp, float grad_scale, ivosw_stream_t stream);
-extern "C" int ivosw_clamp_sgd_dev_sched(float* params, const float* grads, float* momentum_buf, int n, void* sgd_state, const float* lr_table,
-                                         int lr_steps, float momentum, float weight_decay, int nesterov, float clamp, float grad_scale,
-                                         ivosw_stream_t stream);
-extern "C" int ivosw_target_update(float* target, const float* policy, int n, int mode, float tau, int period, void* target_state,
-                                   ivosw_stream_t stream);
-
-extern "C" int ivosw_dqn_step_drawn_ex(float* policy, const float* target, const float* old_iou, const float* new_iou, const float* annotated,
-                                       const float* next_annotated, const int64_t* action, const float* reward_step, const float* reward_done,
-                                       void* draw_state, int n, int B, int T, float gamma, int loss_kind, float huber_delta, int64_t* idx_out,
-                                       float* state, float* new_state, int64_t* action_out, float* reward_step_out, float* reward_done_out,
-                                       float* grads, float* loss, void* ws, size_t ws_bytes, float* exp_avg, float* exp_avg_sq, void* adam_state,
-                                       float lr, float beta1, float beta2, float eps, float weight_decay, float clamp, float grad_scale,
-                                       ivosw_stream_t stream) {
-    IVOSW_REQUIRE(policy && target && old_iou && new_iou && annotated && next_annotated && action && reward_step && reward_done && draw_state &&
-                      idx_out && state && new_state && action_out && reward_step_out && reward_done_out && grads && loss && ws && exp_avg &&
-                      exp_avg_sq && adam_state,
-                  "null pointer");
-    IVOSW_ON_DEVICE_OF(grads);
-    IVOSW_REQUIRE(n > 0 && B > 0 && T > 0, "n, B and T must be positive");
-    // refused before anything is launched (the un-folded sequence below would otherwise advance the draw counter first)
-    if (const int rc = check_dqn_loss("ivosw_dqn_step_drawn", loss_kind, huber_delta)) return rc;
-    const bool aligned = ((reinterpret_cast<uintptr_t>(policy) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(exp_avg) |
-                           reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0;
-    bool folded = false;
-    if (aligned && tune_get("DQN_ONECALL", 1)) {
-        const EncDraw dr{old_iou, new_iou, annotated, next_annotated, action, reward_step, reward_done, static_cast<DrawState*>(draw_state), n, B, T,
-                         idx_out, state, new_state, action_out, reward_step_out, reward_done_out};
-        ReduceGroup rg{};
-        const int rc = dqn_loss_grad_impl(policy, target, state, new_state, action_out, reward_step_out, reward_done_out, B, T, gamma, loss_kind,
-                                          huber_delta, grads, loss, ws, ws_bytes, stream, &dr, &rg, &folded);
-        if (rc != IVOSW_OK) return rc;
-        if (folded) {
-            ReduceOffsets ro{};
-            for (int k = 0; k < REDUCE_MAX; ++k) ro.off[k] = rg.out[k] ? (int)(rg.out[k] - grads) : 0;
-            const int nprm = IVOSW_BRAIN_NPARAMS;
-            hipLaunchKernelGGL(clamp_adam_dev_reduce_kernel, dim3((nprm + 1023) / 1024), dim3(1024), 0, as_stream(stream), policy, grads,
-                               exp_avg, exp_avg_sq, nprm, static_cast<AdamDevState*>(adam_state), rg, ro, lr, beta1, beta2, eps, weight_decay,
-                               clamp, grad_scale);
-            IVOSW_CHECK_LAUNCH();
-            return IVOSW_OK;
-        }
-    }
-    // the un-folded sequence (a tunable moved the step off the fused launch chain): the same three entries the caller would have made
-    int rc = ivosw_replay_draw_gather(old_iou, new_iou, annotated, next_annotated, action, reward_step, reward_done, draw_state, n, B, T, idx_out,
-                                      state, new_state, action_out, reward_step_out, reward_done_out, stream);
-    if (rc == IVOSW_OK)
-        rc = ivosw_dqn_loss_grad_ex(policy, target, state, new_state, action_out, reward_step_out, reward_done_out, B, T, gamma, loss_kind,
-                                    huber_delta, grads, loss, ws, ws_bytes, stream);
-    if (rc == IVOSW_OK)
-        rc = ivosw_clamp_adam_dev(policy, grads, exp_avg, exp_avg_sq, IVOSW_BRAIN_NPARAMS, adam_state, lr, beta1, beta2, eps, weight_decay, clamp,
-                                  grad_scale, stream);
-    return rc;
+// the tails' geometry: IVOSW_BRAIN_NPARAMS lanes in workgroups of 1024
+template <class... Params, class... Args>
+static void launch_tail(void (*kernel)(Params...), ivosw_stream_t stream, Args... args) {
+    hipLaunchKernelGGL(kernel, dim3((IVOSW_BRAIN_NPARAMS + 1023) / 1024), dim3(1024), 0, as_stream(stream), args...);
 }
 
-// ivosw_dqn_step_drawn_ex with clamp + SGD in place of clamp + Adam: the same eight launches, the last one clamp_sgd_reduce_kernel.
-extern "C" int ivosw_dqn_step_drawn_sgd(float* policy, const float* target, const float* old_iou, const float* new_iou, const float* annotated,
-                                        const float* next_annotated, const int64_t* action, const float* reward_step, const float* reward_done,
-                                        void* draw_state, int n, int B, int T, float gamma, int loss_kind, float huber_delta, int64_t* idx_out,
-                                        float* state, float* new_state, int64_t* action_out, float* reward_step_out, float* reward_done_out,
-                                        float* grads, float* loss, void* ws, size_t ws_bytes, float* momentum_buf, float lr, float momentum,
-                                        float weight_decay, int nesterov, float clamp, float grad_scale, ivosw_stream_t stream) {
-    IVOSW_REQUIRE(policy && target && old_iou && new_iou && annotated && next_annotated && action && reward_step && reward_done && draw_state &&
-                      idx_out && state && new_state && action_out && reward_step_out && reward_done_out && grads && loss && ws && momentum_buf,
-                  "null pointer");
-    IVOSW_REQUIRE(n > 0 && B > 0 && T > 0, "n, B and T must be positive");
-    // refused before anything is launched (the un-folded sequence below would otherwise advance the draw counter first)
-    if (const int rc = check_dqn_loss("ivosw_dqn_step_drawn_sgd", loss_kind, huber_delta)) return rc;
-    if (const int rc = check_sgd("ivosw_dqn_step_drawn_sgd", lr, momentum, weight_decay, nesterov)) return rc;
-    IVOSW_ON_DEVICE_OF(grads);
-    const bool aligned = ((reinterpret_cast<uintptr_t>(policy) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(momentum_buf)) &
-                          15) == 0;
-    bool folded = false;
-    if (aligned && tune_get("DQN_ONECALL", 1)) {
-        const EncDraw dr{old_iou, new_iou, annotated, next_annotated, action, reward_step, reward_done, static_cast<DrawState*>(draw_state), n, B, T,
-                         idx_out, state, new_state, action_out, reward_step_out, reward_done_out};
-        ReduceGroup rg{};
-        const int rc = dqn_loss_grad_impl(policy, target, state, new_state, action_out, reward_step_out, reward_done_out, B, T, gamma, loss_kind,
-                                          huber_delta, grads, loss, ws, ws_bytes, stream, &dr, &rg, &folded);
-        if (rc != IVOSW_OK) return rc;
-        if (folded) {
-            ReduceOffsets ro{};
-            for (int k = 0; k < REDUCE_MAX; ++k) ro.off[k] = rg.out[k] ? (int)(rg.out[k] - grads) : 0;
-            const int nprm = IVOSW_BRAIN_NPARAMS;
-            hipLaunchKernelGGL(clamp_sgd_reduce_kernel, dim3((nprm + 1023) / 1024), dim3(1024), 0, as_stream(stream), policy, grads, momentum_buf,
-                               nprm, rg, ro, lr, momentum, weight_decay, nesterov, clamp, grad_scale);
-            IVOSW_CHECK_LAUNCH();
-            return IVOSW_OK;
-        }
-    }
-    // the un-folded sequence (a tunable moved the step off the fused launch chain): the same three entries the caller would have made
-    int rc = ivosw_replay_draw_gather(old_iou, new_iou, annotated, next_annotated, action, reward_step, reward_done, draw_state, n, B, T, idx_out,
-                                      state, new_state, action_out, reward_step_out, reward_done_out, stream);
-    if (rc == IVOSW_OK)
-        rc = ivosw_dqn_loss_grad_ex(policy, target, state, new_state, action_out, reward_step_out, reward_done_out, B, T, gamma, loss_kind,
-                                    huber_delta, grads, loss, ws, ws_bytes, stream);
-    if (rc == IVOSW_OK)
-        rc = ivosw_clamp_sgd(policy, grads, momentum_buf, IVOSW_BRAIN_NPARAMS, lr, momentum, weight_decay, nesterov, clamp, grad_scale, stream);
-    return rc;
-}
-
-// The common part of the two scheduled one-call steps (the caller has checked its arguments): the fused chain with the draw + gather in
-// the encoder launch, then fold(rg, ro) launches the update with the slab reduction folded in; or, off the fused chain, the draw + gather
-// and loss + gradient entries followed by unfold(), the update's own entry.
+// The one path of every one-call step (the entry `who` has checked its arguments; `aligned`: its arenas are 16-byte aligned): the fused
+// chain with the draw + gather in the encoder launch, then fold(rg, ro) launches the entry's tail; or, off the fused chain (a tunable
+// moved the step off it), the same entries the caller would have made: draw + gather, loss + gradient, then unfold(), the update's own.
 template <class Fold, class Unfold>
-static int dqn_step_drawn_sched_run(const char* who, bool aligned, float* policy, const float* target, const float* old_iou, const float* new_iou,
-                                    const float* annotated, const float* next_annotated, const int64_t* action, const float* reward_step,
-                                    const float* reward_done, void* draw_state, int n, int B, int T, float gamma, int loss_kind, float huber_delta,
-                                    int64_t* idx_out, float* state, float* new_state, int64_t* action_out, float* reward_step_out,
-                                    float* reward_done_out, float* grads, float* loss, void* ws, size_t ws_bytes, ivosw_stream_t stream, Fold fold,
-                                    Unfold unfold) {
+static int dqn_step_drawn_run(const char* who, bool aligned, float* policy, const float* target, const float* old_iou, const float* new_iou,
+                              const float* annotated, const float* next_annotated, const int64_t* action, const float* reward_step,
+                              const float* reward_done, void* draw_state, int n, int B, int T, float gamma, int loss_kind, float huber_delta,
+                              int64_t* idx_out, float* state, float* new_state, int64_t* action_out, float* reward_step_out,
+                              float* reward_done_out, float* grads, float* loss, void* ws, size_t ws_bytes, ivosw_stream_t stream, Fold fold,
+                              Unfold unfold) {
     bool folded = false;
     if (aligned && tune_get("DQN_ONECALL", 1)) {
         const EncDraw dr{old_iou, new_iou, annotated, next_annotated, action, reward_step, reward_done, static_cast<DrawState*>(draw_state), n, B, T,
@@ -1936,6 +1713,62 @@ static int dqn_step_drawn_sched_run(const char* who, bool aligned, float* policy
     return rc;
 }
 
+// Every entry below refuses bad arguments before anything is launched (the un-folded sequence would otherwise advance the draw counter first).
+extern "C" int ivosw_dqn_step_drawn_ex(float* policy, const float* target, const float* old_iou, const float* new_iou, const float* annotated,
+                                       const float* next_annotated, const int64_t* action, const float* reward_step, const float* reward_done,
+                                       void* draw_state, int n, int B, int T, float gamma, int loss_kind, float huber_delta, int64_t* idx_out,
+                                       float* state, float* new_state, int64_t* action_out, float* reward_step_out, float* reward_done_out,
+                                       float* grads, float* loss, void* ws, size_t ws_bytes, float* exp_avg, float* exp_avg_sq, void* adam_state,
+                                       float lr, float beta1, float beta2, float eps, float weight_decay, float clamp, float grad_scale,
+                                       ivosw_stream_t stream) {
+    IVOSW_REQUIRE(policy && target && old_iou && new_iou && annotated && next_annotated && action && reward_step && reward_done && draw_state &&
+                      idx_out && state && new_state && action_out && reward_step_out && reward_done_out && grads && loss && ws && exp_avg &&
+                      exp_avg_sq && adam_state,
+                  "null pointer");
+    IVOSW_ON_DEVICE_OF(grads);
+    IVOSW_REQUIRE(n > 0 && B > 0 && T > 0, "n, B and T must be positive");
+    if (const int rc = check_dqn_loss("ivosw_dqn_step_drawn", loss_kind, huber_delta)) return rc;
+    const int nprm = IVOSW_BRAIN_NPARAMS;
+    return dqn_step_drawn_run(
+        __func__, aligned16({policy, grads, exp_avg, exp_avg_sq}), policy, target, old_iou, new_iou, annotated, next_annotated, action, reward_step,
+        reward_done, draw_state, n, B, T, gamma, loss_kind, huber_delta, idx_out, state, new_state, action_out, reward_step_out, reward_done_out,
+        grads, loss, ws, ws_bytes, stream,
+        [&](const ReduceGroup& rg, const ReduceOffsets& ro) {
+            launch_tail(clamp_adam_dev_reduce_kernel, stream, policy, grads, exp_avg, exp_avg_sq, nprm, static_cast<AdamDevState*>(adam_state), rg, ro,
+                        lr, beta1, beta2, eps, weight_decay, clamp, grad_scale);
+        },
+        [&] {
+            return ivosw_clamp_adam_dev(policy, grads, exp_avg, exp_avg_sq, nprm, adam_state, lr, beta1, beta2, eps, weight_decay, clamp, grad_scale,
+                                        stream);
+        });
+}
+
+// ivosw_dqn_step_drawn_ex with clamp + SGD in place of clamp + Adam: the same eight launches, the last one clamp_sgd_reduce_kernel.
+extern "C" int ivosw_dqn_step_drawn_sgd(float* policy, const float* target, const float* old_iou, const float* new_iou, const float* annotated,
+                                        const float* next_annotated, const int64_t* action, const float* reward_step, const float* reward_done,
+                                        void* draw_state, int n, int B, int T, float gamma, int loss_kind, float huber_delta, int64_t* idx_out,
+                                        float* state, float* new_state, int64_t* action_out, float* reward_step_out, float* reward_done_out,
+                                        float* grads, float* loss, void* ws, size_t ws_bytes, float* momentum_buf, float lr, float momentum,
+                                        float weight_decay, int nesterov, float clamp, float grad_scale, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(policy && target && old_iou && new_iou && annotated && next_annotated && action && reward_step && reward_done && draw_state &&
+                      idx_out && state && new_state && action_out && reward_step_out && reward_done_out && grads && loss && ws && momentum_buf,
+                  "null pointer");
+    IVOSW_REQUIRE(n > 0 && B > 0 && T > 0, "n, B and T must be positive");
+    if (const int rc = check_dqn_loss(__func__, loss_kind, huber_delta)) return rc;
+    if (const int rc = check_sgd(__func__, lr, momentum, weight_decay, nesterov)) return rc;
+    IVOSW_ON_DEVICE_OF(grads);
+    const int nprm = IVOSW_BRAIN_NPARAMS;
+    return dqn_step_drawn_run(
+        __func__, aligned16({policy, grads, momentum_buf}), policy, target, old_iou, new_iou, annotated, next_annotated, action, reward_step,
+        reward_done, draw_state, n, B, T, gamma, loss_kind, huber_delta, idx_out, state, new_state, action_out, reward_step_out, reward_done_out,
+        grads, loss, ws, ws_bytes, stream,
+        [&](const ReduceGroup& rg, const ReduceOffsets& ro) {
+            launch_tail(clamp_sgd_reduce_kernel, stream, policy, grads, momentum_buf, nprm, rg, ro, lr, momentum, weight_decay, nesterov, clamp,
+                        grad_scale);
+        },
+        [&] { return ivosw_clamp_sgd(policy, grads, momentum_buf, nprm, lr, momentum, weight_decay, nesterov, clamp, grad_scale, stream); });
+}
+
 // ivosw_dqn_step_drawn_ex with the poly learning-rate schedule: the same eight launches, the last one clamp_adam_dev_reduce_sched_kernel.
 extern "C" int ivosw_dqn_step_drawn_sched(float* policy, const float* target, const float* old_iou, const float* new_iou, const float* annotated,
                                           const float* next_annotated, const int64_t* action, const float* reward_step, const float* reward_done,
@@ -1949,22 +1782,18 @@ extern "C" int ivosw_dqn_step_drawn_sched(float* policy, const float* target, co
                       exp_avg_sq && adam_state,
                   "null pointer");
     IVOSW_REQUIRE(n > 0 && B > 0 && T > 0, "n, B and T must be positive");
-    // refused before anything is launched (the un-folded sequence would otherwise advance the draw counter first)
-    static const char* who = "ivosw_dqn_step_drawn_sched";
-    if (const int rc = check_dqn_loss(who, loss_kind, huber_delta)) return rc;
-    if (const int rc = check_lr_table(who, lr_table, lr_steps)) return rc;
-    if (const int rc = check_adam(who, beta1, beta2, eps, weight_decay)) return rc;
+    if (const int rc = check_dqn_loss(__func__, loss_kind, huber_delta)) return rc;
+    if (const int rc = check_lr_table(__func__, lr_table, lr_steps)) return rc;
+    if (const int rc = check_adam(__func__, beta1, beta2, eps, weight_decay)) return rc;
     IVOSW_ON_DEVICE_OF(grads);
-    const bool aligned = ((reinterpret_cast<uintptr_t>(policy) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(exp_avg) |
-                           reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0;
-    AdamDevState* sd = static_cast<AdamDevState*>(adam_state);
     const int nprm = IVOSW_BRAIN_NPARAMS;
-    return dqn_step_drawn_sched_run(
-        who, aligned, policy, target, old_iou, new_iou, annotated, next_annotated, action, reward_step, reward_done, draw_state, n, B, T, gamma,
-        loss_kind, huber_delta, idx_out, state, new_state, action_out, reward_step_out, reward_done_out, grads, loss, ws, ws_bytes, stream,
+    return dqn_step_drawn_run(
+        __func__, aligned16({policy, grads, exp_avg, exp_avg_sq}), policy, target, old_iou, new_iou, annotated, next_annotated, action, reward_step,
+        reward_done, draw_state, n, B, T, gamma, loss_kind, huber_delta, idx_out, state, new_state, action_out, reward_step_out, reward_done_out,
+        grads, loss, ws, ws_bytes, stream,
         [&](const ReduceGroup& rg, const ReduceOffsets& ro) {
-            hipLaunchKernelGGL(clamp_adam_dev_reduce_sched_kernel, dim3((nprm + 1023) / 1024), dim3(1024), 0, as_stream(stream), policy, grads,
-                               exp_avg, exp_avg_sq, nprm, sd, rg, ro, lr_table, lr_steps, beta1, beta2, eps, weight_decay, clamp, grad_scale);
+            launch_tail(clamp_adam_dev_reduce_sched_kernel, stream, policy, grads, exp_avg, exp_avg_sq, nprm, static_cast<AdamDevState*>(adam_state),
+                        rg, ro, lr_table, lr_steps, beta1, beta2, eps, weight_decay, clamp, grad_scale);
         },
         [&] {
             return ivosw_clamp_adam_dev_sched(policy, grads, exp_avg, exp_avg_sq, nprm, adam_state, lr_table, lr_steps, beta1, beta2, eps,
@@ -1985,21 +1814,18 @@ extern "C" int ivosw_dqn_step_drawn_sgd_sched(float* policy, const float* target
                       sgd_state,
                   "null pointer");
     IVOSW_REQUIRE(n > 0 && B > 0 && T > 0, "n, B and T must be positive");
-    static const char* who = "ivosw_dqn_step_drawn_sgd_sched";
-    if (const int rc = check_dqn_loss(who, loss_kind, huber_delta)) return rc;
-    if (const int rc = check_lr_table(who, lr_table, lr_steps)) return rc;
-    if (const int rc = check_sgd(who, 0.f, momentum, weight_decay, nesterov)) return rc;
+    if (const int rc = check_dqn_loss(__func__, loss_kind, huber_delta)) return rc;
+    if (const int rc = check_lr_table(__func__, lr_table, lr_steps)) return rc;
+    if (const int rc = check_sgd(__func__, 0.f, momentum, weight_decay, nesterov)) return rc;
     IVOSW_ON_DEVICE_OF(grads);
-    const bool aligned = ((reinterpret_cast<uintptr_t>(policy) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(momentum_buf)) &
-                          15) == 0;
-    SgdDevState* sd = static_cast<SgdDevState*>(sgd_state);
     const int nprm = IVOSW_BRAIN_NPARAMS;
-    return dqn_step_drawn_sched_run(
-        who, aligned, policy, target, old_iou, new_iou, annotated, next_annotated, action, reward_step, reward_done, draw_state, n, B, T, gamma,
-        loss_kind, huber_delta, idx_out, state, new_state, action_out, reward_step_out, reward_done_out, grads, loss, ws, ws_bytes, stream,
+    return dqn_step_drawn_run(
+        __func__, aligned16({policy, grads, momentum_buf}), policy, target, old_iou, new_iou, annotated, next_annotated, action, reward_step,
+        reward_done, draw_state, n, B, T, gamma, loss_kind, huber_delta, idx_out, state, new_state, action_out, reward_step_out, reward_done_out,
+        grads, loss, ws, ws_bytes, stream,
         [&](const ReduceGroup& rg, const ReduceOffsets& ro) {
-            hipLaunchKernelGGL(clamp_sgd_reduce_sched_kernel, dim3((nprm + 1023) / 1024), dim3(1024), 0, as_stream(stream), policy, grads,
-                               momentum_buf, nprm, sd, rg, ro, lr_table, lr_steps, momentum, weight_decay, nesterov, clamp, grad_scale);
+            launch_tail(clamp_sgd_reduce_sched_kernel, stream, policy, grads, momentum_buf, nprm, static_cast<SgdDevState*>(sgd_state), rg, ro,
+                        lr_table, lr_steps, momentum, weight_decay, nesterov, clamp, grad_scale);
         },
         [&] {
             return ivosw_clamp_sgd_dev_sched(policy, grads, momentum_buf, nprm, sgd_state, lr_table, lr_steps, momentum, weight_decay, nesterov,
@@ -2022,7 +1848,6 @@ extern "C" int ivosw_dqn_step_drawn_tgt(float* policy, float* target, const floa
                                         float momentum, int nesterov, float weight_decay, float clamp, float grad_scale, int target_mode,
                                         float tau, int target_period, void* target_state, ivosw_stream_t stream) {
     static const char* who = "ivosw_dqn_step_drawn_tgt";
-    // everything is refused before anything is launched (the un-folded sequence would otherwise advance the draw counter first)
     if (const int rc = check_target(who, target_state, target_mode, tau, target_period)) return rc;
     IVOSW_REQUIRE(optimizer == IVOSW_OPT_ADAM || optimizer == IVOSW_OPT_SGD, "unknown optimizer (IVOSW_OPT_ADAM or IVOSW_OPT_SGD)");
     const bool adam = optimizer == IVOSW_OPT_ADAM, sched = lr_table != nullptr;
@@ -2042,34 +1867,22 @@ extern "C" int ivosw_dqn_step_drawn_tgt(float* policy, float* target, const floa
         if (const int rc = check_sgd(who, sched ? 0.f : lr, momentum, weight_decay, nesterov)) return rc;
     }
     IVOSW_ON_DEVICE_OF(grads);
-    const bool aligned = ((reinterpret_cast<uintptr_t>(policy) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(opt_buf0) |
-                           (adam ? reinterpret_cast<uintptr_t>(opt_buf1) : 0)) & 15) == 0;
+    const bool aligned = aligned16({policy, grads, opt_buf0, adam ? opt_buf1 : nullptr});
     if (target_mode == TARGET_SOFT) target_period = 1;      // not looked at under soft; keeps any value off the kernel's modulo
     const TargetArgs ta{target, static_cast<TargetDevState*>(target_state), target_mode, tau, target_period};
     const int nprm = IVOSW_BRAIN_NPARAMS;
-    const dim3 grid((nprm + 1023) / 1024), block(1024);
-    hipStream_t hs = as_stream(stream);
-    return dqn_step_drawn_sched_run(
+    return dqn_step_drawn_run(
         who, aligned, policy, target, old_iou, new_iou, annotated, next_annotated, action, reward_step, reward_done, draw_state, n, B, T, gamma,
         loss_kind, huber_delta, idx_out, state, new_state, action_out, reward_step_out, reward_done_out, grads, loss, ws, ws_bytes, stream,
         [&](const ReduceGroup& rg, const ReduceOffsets& ro) {
-            if (adam) {
-                AdamDevState* sd = static_cast<AdamDevState*>(opt_state);
-                if (sched)
-                    hipLaunchKernelGGL(adam_tail_tgt_kernel<true>, grid, block, 0, hs, policy, grads, opt_buf0, opt_buf1, nprm, sd, rg, ro, lr, lr_table,
-                                       lr_steps, beta1, beta2, eps, weight_decay, clamp, grad_scale, ta);
-                else
-                    hipLaunchKernelGGL(adam_tail_tgt_kernel<false>, grid, block, 0, hs, policy, grads, opt_buf0, opt_buf1, nprm, sd, rg, ro, lr, lr_table,
-                                       lr_steps, beta1, beta2, eps, weight_decay, clamp, grad_scale, ta);
-            } else {
-                SgdDevState* sd = static_cast<SgdDevState*>(opt_state);
-                if (sched)
-                    hipLaunchKernelGGL(sgd_tail_tgt_kernel<true>, grid, block, 0, hs, policy, grads, opt_buf0, nprm, sd, rg, ro, lr, lr_table, lr_steps,
-                                       momentum, weight_decay, nesterov, clamp, grad_scale, ta);
-                else
-                    hipLaunchKernelGGL(sgd_tail_tgt_kernel<false>, grid, block, 0, hs, policy, grads, opt_buf0, nprm, sd, rg, ro, lr, lr_table, lr_steps,
-                                       momentum, weight_decay, nesterov, clamp, grad_scale, ta);
-            }
+            if (adam)
+                launch_tail(sched ? adam_tail_tgt_kernel<true> : adam_tail_tgt_kernel<false>, stream, policy, grads, opt_buf0, opt_buf1, nprm,
+                            static_cast<AdamDevState*>(opt_state), rg, ro, lr, lr_table, lr_steps, beta1, beta2, eps, weight_decay, clamp, grad_scale,
+                            ta);
+            else
+                launch_tail(sched ? sgd_tail_tgt_kernel<true> : sgd_tail_tgt_kernel<false>, stream, policy, grads, opt_buf0, nprm,
+                            static_cast<SgdDevState*>(opt_state), rg, ro, lr, lr_table, lr_steps, momentum, weight_decay, nesterov, clamp,
+                            grad_scale, ta);
         },
         [&] {
             int rc;

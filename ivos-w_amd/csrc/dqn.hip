@@ -1,9 +1,7 @@
 // Fused clamp + Adam over the flat parameter arena (K9; clamp + SGD with momentum beside it), hard target sync (K10), replay gather (K11).
 // Reference: models/agent.py:157-165 (clamp, optim.Adam(lr, weight_decay) step, target sync),
 // datasets/agent_dataset.py:71-115 + train_agent.py:177-182 (minibatch assembly).
-#include "adam.h"
-#include "sgd.h"
-#include "target.h"
+#include "dqn_update.h"
 
 namespace ivosw {
 
@@ -21,6 +19,19 @@ __global__ void clamp_adam_kernel(float* __restrict__ p, const float* __restrict
     v[i] = vi;
 }
 
+// Row `src` of the replay into slot b of the minibatch: the (iou, annotated) pairs of its T steps, by the whole workgroup.
+__device__ __forceinline__ void replay_copy_row(const float* __restrict__ old_iou, const float* __restrict__ new_iou,
+                                                const float* __restrict__ ann, const float* __restrict__ nann, int64_t src, int b, int T,
+                                                float* __restrict__ state, float* __restrict__ new_state) {
+    for (int t = threadIdx.x; t < T; t += blockDim.x) {
+        const size_t s = (size_t)src * T + t, d = ((size_t)b * T + t) * 2;
+        state[d] = old_iou[s];
+        state[d + 1] = ann[s];
+        new_state[d] = new_iou[s];
+        new_state[d + 1] = nann[s];
+    }
+}
+
 __global__ void replay_gather_kernel(const float* __restrict__ old_iou, const float* __restrict__ new_iou,
                                      const float* __restrict__ ann, const float* __restrict__ nann,
                                      const int64_t* __restrict__ action, const float* __restrict__ rstep,
@@ -30,13 +41,7 @@ __global__ void replay_gather_kernel(const float* __restrict__ old_iou, const fl
                                      float* __restrict__ rdone_out) {
     const int b = blockIdx.x;
     const int64_t src = idx[b];
-    for (int t = threadIdx.x; t < T; t += blockDim.x) {
-        const size_t s = (size_t)src * T + t, d = ((size_t)b * T + t) * 2;
-        state[d] = old_iou[s];
-        state[d + 1] = ann[s];
-        new_state[d] = new_iou[s];
-        new_state[d + 1] = nann[s];
-    }
+    replay_copy_row(old_iou, new_iou, ann, nann, src, b, T, state, new_state);
     if (threadIdx.x == 0) {
         action_out[b] = action[src];
         rstep_out[b] = rstep[src];
@@ -47,7 +52,7 @@ __global__ void replay_gather_kernel(const float* __restrict__ old_iou, const fl
 // The minibatch draw on the device (uniform with replacement, what torch.randint gave the eager loop): the index of slot b
 // of draw number c is a splitmix64 finaliser of (seed, c, b) scaled to [0, n) by a 64 x 64 -> high-64 multiply — integer
 // arithmetic only, so tests/ and a host mirror (ivos_w_amd.models.momory_pool.draw_indices) reproduce it bit for bit.  The
-// draw counter lives on the device and is advanced by the LAST workgroup of the launch (a ticket, as in clamp_adam_dev), so a
+// draw counter lives on the device and is advanced by the LAST workgroup of the launch (last_workgroup, dqn_update.h), so a
 // captured HIP graph replays a fresh minibatch each time with no host-side RNG launch in front of it (that launch and the
 // bubble it left before the graph cost ~9.5 us of a 204 us step).
 __global__ void replay_draw_gather_kernel(const float* __restrict__ old_iou, const float* __restrict__ new_iou,
@@ -60,24 +65,14 @@ __global__ void replay_draw_gather_kernel(const float* __restrict__ old_iou, con
     const int b = blockIdx.x;
     const unsigned counter = ds->counter;
     const int64_t src = (int64_t)__umul64hi(draw_mix(ds->seed, counter, (unsigned)b), (unsigned long long)n);
-    for (int t = threadIdx.x; t < T; t += blockDim.x) {
-        const size_t s = (size_t)src * T + t, d = ((size_t)b * T + t) * 2;
-        state[d] = old_iou[s];
-        state[d + 1] = ann[s];
-        new_state[d] = new_iou[s];
-        new_state[d + 1] = nann[s];
-    }
-    __syncthreads();
+    replay_copy_row(old_iou, new_iou, ann, nann, src, b, T, state, new_state);
     if (threadIdx.x == 0) {
         idx_out[b] = src;
         action_out[b] = action[src];
         rstep_out[b] = rstep[src];
         rdone_out[b] = rdone[src];
-        if (atomicAdd(&ds->ticket, 1u) == gridDim.x - 1) {
-            ds->counter = counter + 1;
-            atomicExch(&ds->ticket, 0u);
-        }
     }
+    last_workgroup(&ds->ticket, [&] { ds->counter = counter + 1; });
 }
 
 // mask_quality[:] = pred.mean(1); state = stack([mask_quality, counts], 1) (utils/utils_agent.py:120-121) without leaving the
@@ -108,159 +103,55 @@ __global__ void quality_state_kernel(const float* __restrict__ scores, int n_obj
     state[2 * f + 1] = counts[f];
 }
 
-// Clamp + Adam with the step counter advanced by the SAME launch (a one-thread tick kernel in front of it cost a link of the
-// step's launch chain, ~5 us): every thread reads the counter k left by the previous launch and evaluates step k+1's bias
-// corrections itself (the float64 expressions of ivosw_clamp_adam: identical bits); the LAST workgroup to finish — a
-// device-scope ticket, taken after the workgroup's own reads and writes — publishes k+1.  No other workgroup can still
-// be reading the state at that point, and nothing but the ticket crosses workgroups, so no fence is needed.
-// The body is shared with clamp_adam_dev_sched_kernel, which only picks lr differently.
-template <bool VEC>
-__device__ __forceinline__ void clamp_adam_dev_apply(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                     float* __restrict__ v, int n, AdamDevState* __restrict__ st, float lr, float beta1,
-                                                     float beta2, float eps, float wd, float clampv, float gscale) {
-    const int step = st->step + 1;
-    const double b1t = ipow((double)beta1, step), b2t = ipow((double)beta2, step);
-    const float step_size = (float)((double)lr / (1.0 - b1t)), bc2_sqrt = (float)sqrt(1.0 - b2t);
-    auto upd = [&](float gi, float pi, float& mi, float& vi) {
-        return clamp_adam_elem(gi, pi, mi, vi, step_size, bc2_sqrt, beta1, beta2, eps, wd, clampv, gscale);
-    };
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (VEC) {      // 16 bytes per lane and array; the n % 4 tail elements go to the first threads
-        const int n4 = n >> 2;
-        if (t < n4) {
-            const float4 g4 = reinterpret_cast<const float4*>(g)[t];
-            float4 p4 = reinterpret_cast<float4*>(p)[t], m4 = reinterpret_cast<float4*>(m)[t], v4 = reinterpret_cast<float4*>(v)[t];
-            p4.x = upd(g4.x, p4.x, m4.x, v4.x); p4.y = upd(g4.y, p4.y, m4.y, v4.y);
-            p4.z = upd(g4.z, p4.z, m4.z, v4.z); p4.w = upd(g4.w, p4.w, m4.w, v4.w);
-            reinterpret_cast<float4*>(m)[t] = m4; reinterpret_cast<float4*>(v)[t] = v4; reinterpret_cast<float4*>(p)[t] = p4;
-        } else if (t - n4 < (n & 3)) {
-            const int i = 4 * n4 + (t - n4);
-            float mi = m[i], vi = v[i];
-            p[i] = upd(g[i], p[i], mi, vi);
-            m[i] = mi; v[i] = vi;
-        }
-    } else if (t < n) {
-        float mi = m[t], vi = v[t];
-        p[t] = upd(g[t], p[t], mi, vi);
-        m[t] = mi; v[t] = vi;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (atomicAdd(&st->ticket, 1u) == gridDim.x - 1) {
-            st->b1t = b1t; st->b2t = b2t; st->step = step; st->step_size = step_size; st->bc2_sqrt = bc2_sqrt;
-            atomicExch(&st->ticket, 0u);
-        }
-    }
-}
-
+// The update kernels: thin wrappers of clamp_update (dqn_update.h), which documents the body, the ticket and the traversal.  VEC: 16 bytes
+// per lane and array.  clamp_adam_dev_kernel: clamp + Adam with the step counter advanced by the SAME launch (a one-thread tick kernel
+// in front of it cost a link of the step's launch chain, ~5 us).
 template <bool VEC>
 __global__ __launch_bounds__(1024) void clamp_adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                               float* __restrict__ v, int n, AdamDevState* __restrict__ st, float lr, float beta1,
                                                               float beta2, float eps, float wd, float clampv, float gscale) {
-    clamp_adam_dev_apply<VEC>(p, g, m, v, n, st, lr, beta1, beta2, eps, wd, clampv, gscale);
+    clamp_update<VEC>(p, n, AdamRule{m, v, st, beta1, beta2, eps, wd, clampv, gscale}, ArenaGrad{g}, Lr<false>{lr}, NoTarget{});
 }
 
-// The scheduled form (cfg.agent.lr_schedule = "poly"): lr = lr_table[min(k, lr_steps)] with k the counter left by the previous launch,
-// one scalar load per wave in place of the lr argument; everything else is clamp_adam_dev_kernel's, ticket and publish included.
+// The scheduled form (cfg.agent.lr_schedule = "poly"): lr = lr_table[min(k, lr_steps)] with k the counter left by the previous launch.
 template <bool VEC>
 __global__ __launch_bounds__(1024) void clamp_adam_dev_sched_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                                     float* __restrict__ v, int n, AdamDevState* __restrict__ st,
                                                                     const float* __restrict__ lr_table, int lr_steps, float beta1, float beta2,
                                                                     float eps, float wd, float clampv, float gscale) {
-    clamp_adam_dev_apply<VEC>(p, g, m, v, n, st, sched_lr(lr_table, lr_steps, st->step), beta1, beta2, eps, wd, clampv, gscale);
+    clamp_update<VEC>(p, n, AdamRule{m, v, st, beta1, beta2, eps, wd, clampv, gscale}, ArenaGrad{g}, Lr<true>{0.f, lr_table, lr_steps}, NoTarget{});
 }
 
-// Clamp + SGD (clamp_sgd_elem) over the flat arena.  Nothing but the momentum buffer carries over from one step to the next, so
-// the launch is capture-safe as it stands: no step counter, no ticket.  VEC: 16 bytes per lane and array, the n % 4 tail elements
-// go to the first threads past the vector part (clamp_adam_dev_kernel's layout).
-// The body is shared with clamp_sgd_sched_kernel.
-template <bool VEC>
-__device__ __forceinline__ void clamp_sgd_apply(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int n, float lr,
-                                                float mu, float wd, int nesterov, float clampv, float gscale) {
-    auto upd = [&](float gi, float pi, float& bi) { return clamp_sgd_elem(gi, pi, bi, lr, mu, wd, nesterov, clampv, gscale); };
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (VEC) {
-        const int n4 = n >> 2;
-        if (t < n4) {
-            const float4 g4 = reinterpret_cast<const float4*>(g)[t];
-            float4 p4 = reinterpret_cast<float4*>(p)[t], b4 = reinterpret_cast<float4*>(buf)[t];
-            p4.x = upd(g4.x, p4.x, b4.x); p4.y = upd(g4.y, p4.y, b4.y);
-            p4.z = upd(g4.z, p4.z, b4.z); p4.w = upd(g4.w, p4.w, b4.w);
-            reinterpret_cast<float4*>(buf)[t] = b4; reinterpret_cast<float4*>(p)[t] = p4;
-        } else if (t - n4 < (n & 3)) {
-            const int i = 4 * n4 + (t - n4);
-            float bi = buf[i];
-            p[i] = upd(g[i], p[i], bi);
-            buf[i] = bi;
-        }
-    } else if (t < n) {
-        float bi = buf[t];
-        p[t] = upd(g[t], p[t], bi);
-        buf[t] = bi;
-    }
-}
-
+// Clamp + SGD: capture-safe as it stands, no step counter, no ticket (256-lane workgroups: there is nothing to serialise).
 template <bool VEC>
 __global__ __launch_bounds__(256) void clamp_sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, int n,
                                                         float lr, float mu, float wd, int nesterov, float clampv, float gscale) {
-    clamp_sgd_apply<VEC>(p, g, buf, n, lr, mu, wd, nesterov, clampv, gscale);
+    clamp_update<VEC>(p, n, SgdRule{buf, nullptr, mu, wd, nesterov, clampv, gscale}, ArenaGrad{g}, Lr<false>{lr}, NoTarget{});
 }
 
-// The scheduled form: lr = lr_table[min(k, lr_steps)] with k = st->step, then clamp_sgd_kernel's update, then the last workgroup
-// publishes k + 1 (clamp_adam_dev_kernel's ticket).  1024-lane workgroups, as clamp_adam_dev_kernel: the tickets of one launch serialise
-// on one address, so the launch keeps few of them (45 at n = 180 993).
+// The scheduled form: the SGD state's counter picks lr and is advanced under its ticket.  1024-lane workgroups, as clamp_adam_dev_kernel
+// (45 tickets at n = 180 993).
 template <bool VEC>
 __global__ __launch_bounds__(1024) void clamp_sgd_sched_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf,
                                                                int n, SgdDevState* __restrict__ st, const float* __restrict__ lr_table,
                                                                int lr_steps, float mu, float wd, int nesterov, float clampv, float gscale) {
-    const int k = st->step;
-    clamp_sgd_apply<VEC>(p, g, buf, n, sched_lr(lr_table, lr_steps, k), mu, wd, nesterov, clampv, gscale);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (atomicAdd(&st->ticket, 1u) == gridDim.x - 1) {
-            st->step = k + 1;
-            atomicExch(&st->ticket, 0u);
-        }
-    }
+    clamp_update<VEC>(p, n, SgdRule{buf, st, mu, wd, nesterov, clampv, gscale}, ArenaGrad{g}, Lr<true>{0.f, lr_table, lr_steps}, NoTarget{});
 }
 
-// The target-network rule as a launch of its own (target.h: soft = t += tau * (p - t) in one fma, periodic = copy every period-th step),
-// for every chain that does not end in the one-call step's fused tail.  Every workgroup reads the counter, the last one to finish
-// publishes counter + 1 (clamp_sgd_sched_kernel's ticket; 1024-lane workgroups for the same reason).  VEC: 16 bytes per lane and array,
-// the n % 4 tail elements go to the first threads past the vector part.
+// The target-network rule as a launch of its own (target_group: soft = t += tau * (p - t) in one fma, periodic = copy every period-th
+// step), for every chain that does not end in the one-call step's fused tail.  Every workgroup reads the counter, the last one to
+// finish publishes counter + 1 (1024-lane workgroups for the ticket's sake).  A periodic step that does not fire loads nothing.
 template <bool VEC>
 __global__ __launch_bounds__(1024) void target_update_kernel(float* __restrict__ t, const float* __restrict__ p, int n, int mode, float tau,
                                                              int period, TargetDevState* __restrict__ st) {
     const int k = st->step;
     const bool fires = target_fires(k, period);
-    const int id = blockIdx.x * blockDim.x + threadIdx.x;
-    if (mode == TARGET_SOFT || fires) {
-        if (VEC) {
-            const int n4 = n >> 2;
-            if (id < n4) {
-                const float4 p4 = reinterpret_cast<const float4*>(p)[id];
-                float4 t4 = p4;
-                if (mode == TARGET_SOFT) {
-                    t4 = reinterpret_cast<float4*>(t)[id];
-                    t4.x = fmaf(tau, p4.x - t4.x, t4.x); t4.y = fmaf(tau, p4.y - t4.y, t4.y);
-                    t4.z = fmaf(tau, p4.z - t4.z, t4.z); t4.w = fmaf(tau, p4.w - t4.w, t4.w);
-                }
-                reinterpret_cast<float4*>(t)[id] = t4;
-            } else if (id - n4 < (n & 3)) {
-                const int i = 4 * n4 + (id - n4);
-                target_elem(t, i, p[i], mode, tau, fires);
-            }
-        } else if (id < n) {
-            target_elem(t, id, p[id], mode, tau, fires);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (atomicAdd(&st->ticket, 1u) == gridDim.x - 1) {
-            st->step = k + 1;
-            atomicExch(&st->ticket, 0u);
-        }
-    }
+    if (mode == TARGET_SOFT || fires)
+        for_each_group<VEC>(n, [&](int i, auto w) {
+            constexpr int W = decltype(w)::value;
+            target_group<W>(t, i, load_group<W>(p, i), mode, tau, fires);
+        });
+    last_workgroup(&st->ticket, [&] { st->step = k + 1; });
 }
 
 // ---------------------------------------------------------------- prioritized replay (cfg.agent.replay = "prioritized")
@@ -580,13 +471,8 @@ extern "C" int ivosw_clamp_sgd(float* params, const float* grads, float* momentu
     IVOSW_REQUIRE(n > 0, "n must be positive");
     if (const int rc = check_sgd("ivosw_clamp_sgd", lr, momentum, weight_decay, nesterov)) return rc;
     IVOSW_ON_DEVICE_OF(params);
-    const bool vec = ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(momentum_buf)) & 15) == 0;
-    if (vec)
-        hipLaunchKernelGGL(clamp_sgd_kernel<true>, dim3((n / 4 + 3 + 255) / 256), dim3(256), 0, as_stream(stream), params, grads, momentum_buf,
-                           n, lr, momentum, weight_decay, nesterov, clamp, grad_scale);
-    else
-        hipLaunchKernelGGL(clamp_sgd_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, as_stream(stream), params, grads, momentum_buf, n, lr,
-                           momentum, weight_decay, nesterov, clamp, grad_scale);
+    launch_traversal(clamp_sgd_kernel<true>, clamp_sgd_kernel<false>, {params, grads, momentum_buf}, n, 256, as_stream(stream), params, grads,
+                     momentum_buf, n, lr, momentum, weight_decay, nesterov, clamp, grad_scale);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }
@@ -601,14 +487,9 @@ extern "C" int ivosw_clamp_sgd_dev_sched(float* params, const float* grads, floa
     if (const int rc = check_lr_table("ivosw_clamp_sgd_dev_sched", lr_table, lr_steps)) return rc;
     if (const int rc = check_sgd("ivosw_clamp_sgd_dev_sched", 0.f, momentum, weight_decay, nesterov)) return rc;
     IVOSW_ON_DEVICE_OF(params);
-    SgdDevState* sd = static_cast<SgdDevState*>(sgd_state);
-    const bool vec = ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(momentum_buf)) & 15) == 0;
-    if (vec)
-        hipLaunchKernelGGL(clamp_sgd_sched_kernel<true>, dim3((n / 4 + 3 + 1023) / 1024), dim3(1024), 0, as_stream(stream), params, grads,
-                           momentum_buf, n, sd, lr_table, lr_steps, momentum, weight_decay, nesterov, clamp, grad_scale);
-    else
-        hipLaunchKernelGGL(clamp_sgd_sched_kernel<false>, dim3((n + 1023) / 1024), dim3(1024), 0, as_stream(stream), params, grads, momentum_buf,
-                           n, sd, lr_table, lr_steps, momentum, weight_decay, nesterov, clamp, grad_scale);
+    launch_traversal(clamp_sgd_sched_kernel<true>, clamp_sgd_sched_kernel<false>, {params, grads, momentum_buf}, n, 1024, as_stream(stream),
+                     params, grads, momentum_buf, n, static_cast<SgdDevState*>(sgd_state), lr_table, lr_steps, momentum, weight_decay, nesterov,
+                     clamp, grad_scale);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }
@@ -623,15 +504,9 @@ extern "C" int ivosw_clamp_adam_dev_sched(float* params, const float* grads, flo
     if (const int rc = check_lr_table("ivosw_clamp_adam_dev_sched", lr_table, lr_steps)) return rc;
     if (const int rc = check_adam("ivosw_clamp_adam_dev_sched", beta1, beta2, eps, weight_decay)) return rc;
     IVOSW_ON_DEVICE_OF(params);
-    AdamDevState* sd = static_cast<AdamDevState*>(adam_state);
-    const bool vec = ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(exp_avg) |
-                       reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0;
-    if (vec)
-        hipLaunchKernelGGL(clamp_adam_dev_sched_kernel<true>, dim3((n / 4 + 3 + 1023) / 1024), dim3(1024), 0, as_stream(stream), params, grads,
-                           exp_avg, exp_avg_sq, n, sd, lr_table, lr_steps, beta1, beta2, eps, weight_decay, clamp, grad_scale);
-    else
-        hipLaunchKernelGGL(clamp_adam_dev_sched_kernel<false>, dim3((n + 1023) / 1024), dim3(1024), 0, as_stream(stream), params, grads,
-                           exp_avg, exp_avg_sq, n, sd, lr_table, lr_steps, beta1, beta2, eps, weight_decay, clamp, grad_scale);
+    launch_traversal(clamp_adam_dev_sched_kernel<true>, clamp_adam_dev_sched_kernel<false>, {params, grads, exp_avg, exp_avg_sq}, n, 1024,
+                     as_stream(stream), params, grads, exp_avg, exp_avg_sq, n, static_cast<AdamDevState*>(adam_state), lr_table, lr_steps, beta1,
+                     beta2, eps, weight_decay, clamp, grad_scale);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }
@@ -642,16 +517,9 @@ extern "C" int ivosw_clamp_adam_dev(float* params, const float* grads, float* ex
     IVOSW_REQUIRE(params && grads && exp_avg && exp_avg_sq && adam_state, "null pointer");
     IVOSW_ON_DEVICE_OF(params);
     IVOSW_REQUIRE(n > 0, "n must be positive");
-    AdamDevState* sd = static_cast<AdamDevState*>(adam_state);
-    // few, large workgroups: the tickets of one launch serialise on one address (708 of them took longer than the update)
-    const bool vec = ((reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) | reinterpret_cast<uintptr_t>(exp_avg) |
-                       reinterpret_cast<uintptr_t>(exp_avg_sq)) & 15) == 0;
-    if (vec)
-        hipLaunchKernelGGL(clamp_adam_dev_kernel<true>, dim3((n / 4 + 3 + 1023) / 1024), dim3(1024), 0, as_stream(stream), params, grads,
-                           exp_avg, exp_avg_sq, n, sd, lr, beta1, beta2, eps, weight_decay, clamp, grad_scale);
-    else
-        hipLaunchKernelGGL(clamp_adam_dev_kernel<false>, dim3((n + 1023) / 1024), dim3(1024), 0, as_stream(stream), params, grads,
-                           exp_avg, exp_avg_sq, n, sd, lr, beta1, beta2, eps, weight_decay, clamp, grad_scale);
+    launch_traversal(clamp_adam_dev_kernel<true>, clamp_adam_dev_kernel<false>, {params, grads, exp_avg, exp_avg_sq}, n, 1024, as_stream(stream),
+                     params, grads, exp_avg, exp_avg_sq, n, static_cast<AdamDevState*>(adam_state), lr, beta1, beta2, eps, weight_decay, clamp,
+                     grad_scale);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }
@@ -705,14 +573,8 @@ extern "C" int ivosw_target_update(float* target, const float* policy, int n, in
     IVOSW_REQUIRE(n > 0, "n must be positive");
     IVOSW_ON_DEVICE_OF(target);
     if (mode == TARGET_SOFT) period = 1;         // not looked at under soft: any value is accepted, none reaches the kernel's modulo
-    TargetDevState* sd = static_cast<TargetDevState*>(target_state);
-    const bool vec = ((reinterpret_cast<uintptr_t>(target) | reinterpret_cast<uintptr_t>(policy)) & 15) == 0;
-    if (vec)
-        hipLaunchKernelGGL(target_update_kernel<true>, dim3((n / 4 + 3 + 1023) / 1024), dim3(1024), 0, as_stream(stream), target, policy, n, mode,
-                           tau, period, sd);
-    else
-        hipLaunchKernelGGL(target_update_kernel<false>, dim3((n + 1023) / 1024), dim3(1024), 0, as_stream(stream), target, policy, n, mode, tau,
-                           period, sd);
+    launch_traversal(target_update_kernel<true>, target_update_kernel<false>, {target, policy}, n, 1024, as_stream(stream), target, policy, n, mode,
+                     tau, period, static_cast<TargetDevState*>(target_state));
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }

@@ -28,7 +28,7 @@ __device__ __forceinline__ float clamp_sgd_elem(float g, float pi, float& bi, fl
 }
 
 // The step counter of a scheduled SGD update (cfg.agent.lr_schedule = "poly"), on the device so that a captured graph replays the
-// schedule: the update reads lr_table[min(step, N)], and the last workgroup of the launch (the ticket, as in clamp_adam_dev_kernel)
+// schedule: the update reads lr_table[min(step, N)], and the last workgroup of the launch (the ticket: last_workgroup, dqn_update.h)
 // publishes step + 1.  Layout (8 bytes): the counter is the int32 at byte 0; a caller resumes from host step k by writing k there.
 // The constant-lr update keeps no counter.
 struct SgdDevState {

@@ -1,5 +1,6 @@
-// The target-network rule of the DQN step (cfg.agent.target_update = "soft" | "periodic"), shared by ivosw_target_update (dqn.hip) and the
-// one-call step's fused tails (brain.hip) so that both evaluate the same expression.  After the policy update of a step, per element:
+// The target-network rule of the DQN step (cfg.agent.target_update = "soft" | "periodic").  ivosw_target_update (dqn.hip) and the one-call
+// step's fused tails (brain.hip) both apply it through target_group (dqn_update.h), so both evaluate the same expression.  After the
+// policy update of a step, per element:
 //   soft:      t = fmaf(tau, p_new - t, t)          (one rounding of the product-sum: torch.Tensor.lerp_(p, tau) on the CPU for tau < 0.5)
 //   periodic:  t = p_new when k % period == 0, k = the number of steps since the counter was last written, this one included
 // "coin", the reference's host coin flip, never reaches these kernels.
@@ -13,7 +14,7 @@ namespace ivosw {
 constexpr int TARGET_SOFT = 1, TARGET_PERIODIC = 2;          // IVOSW_TARGET_* (include/ivosw.h)
 
 // The step counter of the rule, on the device so that a captured graph replays it: every workgroup reads `step` (the steps before this
-// one), the last workgroup of the launch (the ticket, as in clamp_adam_dev_kernel) publishes step + 1.  The fused tails of an optimizer
+// one), the last workgroup of the launch (the ticket: last_workgroup, dqn_update.h) publishes step + 1.  The fused tails of an optimizer
 // that has a ticket of its own advance `step` under that one.  Layout (16 bytes): the counter is the int32 at byte 0; a caller resumes
 // from host step k by writing k there.
 struct TargetDevState {
@@ -25,16 +26,6 @@ static_assert(sizeof(TargetDevState) == 16, "TargetDevState layout (step at byte
 
 // Does the step that follows k earlier ones copy the policy?  (soft: not looked at)
 __device__ __forceinline__ bool target_fires(int k, int period) { return ((unsigned)k + 1u) % (unsigned)period == 0u; }
-
-// The rule on element i, in the thread that holds p_new.  A periodic step that does not fire touches nothing.
-__device__ __forceinline__ void target_elem(float* __restrict__ t, int i, float p_new, int mode, float tau, bool fires) {
-    if (mode == TARGET_SOFT) {
-        const float ti = t[i];
-        t[i] = fmaf(tau, p_new - ti, ti);
-    } else if (fires) {
-        t[i] = p_new;
-    }
-}
 
 // What every entry that takes the rule refuses (IVOSW_ERR_ARG) before it launches anything.
 inline int check_target(const char* who, const void* target_state, int mode, float tau, int period) {
