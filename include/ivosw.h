@@ -60,6 +60,23 @@ int ivosw_brain_forward(const float* params, const float* x, int N, int T, float
                         void* ws, size_t ws_bytes, ivosw_stream_t stream);
 /* Replaces Q.argmax() in Agent.action (models/agent.py:187-188): first maximum per row -> idx[N]. */
 int ivosw_brain_argmax(const float* q, int N, int T, int64_t* idx, ivosw_stream_t stream);
+/* Ragged forward: n_seqs (1 .. IVOSW_MAX_SEQS) sequences, each of its OWN length, in one launch chain.  `lengths` is a HOST array, read
+ * during the call only; the sequence table (row offsets) travels to the kernels inside their arguments (no allocation, no copy, no
+ * synchronisation: capture-safe).  x [R,2] and q [R] are flat over the sequences in the order given, R = sum of lengths; sequence k owns
+ * the rows [row_off[k], row_off[k] + lengths[k]).  Each sequence gets, bit for bit, what ivosw_brain_forward(N = 1, T = lengths[k])
+ * computes on its slice: the encoder and the decoder are row-wise over the R flat rows, and the recurrence runs one workgroup per
+ * (sequence, direction) with that sequence's own trip count - the backward direction starts at the sequence's own last frame, nothing
+ * is padded.  Three launches; with DQN_FUSED or LSTM_QUAD switched off, the N = 1 path of ivosw_brain_forward per sequence.
+ * ivosw_brain_ragged_rows: host only; R, or < 0 (IVOSW_ERR_ARG) if the call would be refused.
+ * ivosw_brain_argmax_ragged: the first maximum of every sequence's slice of q (index inside the slice) -> idx[n_seqs]; one launch.
+ * Refused (IVOSW_ERR_ARG) before anything is launched, the message names the sequence's index: a NULL pointer, n_seqs outside
+ * [1, IVOSW_MAX_SEQS], a length < 1, R > 2^20.  A workspace below ivosw_brain_ragged_ws_bytes(R): IVOSW_ERR_WS.                     */
+#define IVOSW_MAX_SEQS 128
+long ivosw_brain_ragged_rows(const int* lengths, int n_seqs);
+size_t ivosw_brain_ragged_ws_bytes(long rows);
+int ivosw_brain_forward_ragged(const float* params, const float* x, const int* lengths, int n_seqs,
+                               float* q, void* ws, size_t ws_bytes, ivosw_stream_t stream);
+int ivosw_brain_argmax_ragged(const float* q, const int* lengths, int n_seqs, int64_t* idx, ivosw_stream_t stream);
 
 /* ------------------------------------------------------------------ agent: DQN step (K8-K10) -- */
 /* Replaces the arithmetic of Agent.update_agent (models/agent.py:128-155):
@@ -417,6 +434,13 @@ int ivosw_assess_forward_videos(const void* packed, int dtype, const ivosw_video
  * state [n_frames,2] fp32 = (float32(quality), counts), the Brain's input.                                              */
 int ivosw_quality_state(const float* scores, int n_obj, int n_frames, const float* counts, double* quality,
                         float* state, ivosw_stream_t stream);
+/* ivosw_quality_state for n_seqs (1 .. IVOSW_MAX_SEQS) videos in ONE launch: `scores` is the flat score buffer of
+ * ivosw_assess_forward_videos (unit order: video k's [n_obj[k]][lengths[k]] block starts at the sum of n_obj * lengths over the videos
+ * before it), counts [R], quality [R] and state [R,2] are flat over the videos, R = sum of lengths.  n_obj and lengths are HOST arrays
+ * (they travel inside the kernel's arguments).  Per video the float64 summation order is ivosw_quality_state's: results are bit-identical.
+ * Refused (IVOSW_ERR_ARG) before the launch, naming the video's index: what ivosw_brain_ragged_rows refuses, and an n_obj < 1.       */
+int ivosw_quality_state_ragged(const float* scores, const int* n_obj, const int* lengths, int n_seqs,
+                               const float* counts, double* quality, float* state, ivosw_stream_t stream);
 /* Kernel-name patterns of the dominant kernel family (the tower's contraction kernels) for profiling. */
 const char* ivosw_assess_dominant_kernel(int dtype);
 

@@ -21,6 +21,7 @@ ASSESS_NTENSORS = 326
 
 _p, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 MAX_VIDEOS = 32                                      # IVOSW_MAX_VIDEOS
+MAX_SEQS = 128                                       # IVOSW_MAX_SEQS
 FRAMES_F32, FRAMES_RGBX8 = 0, 1                      # IVOSW_FRAMES_*
 
 
@@ -36,6 +37,10 @@ SIGNATURES = {
     "ivosw_brain_ws_bytes": (_sz, [_i, _i]),
     "ivosw_brain_forward": (_i, [_p, _p, _i, _i, _p, _p, _sz, _p]),
     "ivosw_brain_argmax": (_i, [_p, _i, _i, _p, _p]),
+    "ivosw_brain_ragged_rows": (C.c_long, [_p, _i]),
+    "ivosw_brain_ragged_ws_bytes": (_sz, [C.c_long]),
+    "ivosw_brain_forward_ragged": (_i, [_p, _p, _p, _i, _p, _p, _sz, _p]),
+    "ivosw_brain_argmax_ragged": (_i, [_p, _p, _i, _p, _p]),
     "ivosw_dqn_ws_bytes": (_sz, [_i, _i]),
     "ivosw_dqn_loss_grad": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _p, _p, _p, _sz, _p]),
     "ivosw_dqn_loss_grad_ex": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _i, _f, _p, _p, _p, _sz, _p]),
@@ -93,6 +98,7 @@ SIGNATURES = {
     "ivosw_roi_sample_videos": (_i, [_p, _i, _p, _i, _p, _p]),
     "ivosw_assess_forward_videos": (_i, [_p, _i, _p, _i, _p, _p, _sz, _i, _i, _p, _p]),
     "ivosw_quality_state": (_i, [_p, _i, _i, _p, _p, _p, _p]),
+    "ivosw_quality_state_ragged": (_i, [_p, _p, _p, _i, _p, _p, _p, _p]),
     "ivosw_assess_dominant_kernel": (C.c_char_p, [_i]),
     "ivosw_jf_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "ivosw_jf_counts": (_i, [_p, _p, _i, _i, _i, C.c_char_p, _i, _i, _p, _p, _sz, _p]),
@@ -194,6 +200,12 @@ def dptr(t, dtype=None):
     if not t.is_contiguous():
         raise ValueError("tensor must be contiguous")
     return C.c_void_p(t.data_ptr())
+
+
+def int_array(values):
+    """A host int array as the ragged entries take their lengths / n_obj (read during the call only)."""
+    values = [int(v) for v in values]
+    return (C.c_int * len(values))(*values)
 
 
 def stream_ptr(device=None):

@@ -270,15 +270,65 @@ struct QuadDpp {
     }
 };
 
+// Where the rows of a quad workgroup live.  lstm_fwd_quad_body below is the recurrence; an addressing says how many steps the workgroup
+// runs, which frame step s consumes, where that frame's input-side gates and its h are, and whether the backward pass's buffers are
+// kept.  Two instances: the [N,T] batch (R rows per workgroup, training and inference) and the sequence table of the ragged
+// forward (one row per workgroup, its own length).
 template <int R>
-__global__ __launch_bounds__(512) void lstm_fwd_quad_kernel(LstmFwd p) {
+struct QuadBatchRows {
+    static constexpr bool KEEPS = true;
+    const LstmFwd& p;
+    int Nk;
+    int dd[R], nn[R];
+    bool ok[R], keep[R];
+    __device__ __forceinline__ explicit QuadBatchRows(const LstmFwd& p_) : p(p_) {
+        Nk = p.N - p.keep_from;
+        const int row0 = blockIdx.x * R;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int row = row0 + r;
+            ok[r] = row < 2 * p.N;
+            const int rc = ok[r] ? row : 2 * p.N - 1;
+            dd[r] = rc / p.N;
+            nn[r] = rc - dd[r] * p.N;
+            keep[r] = ok[r] && p.gates && nn[r] >= p.keep_from;
+        }
+    }
+    __device__ __forceinline__ int steps() const { return p.T; }
+    __device__ __forceinline__ int frame(int r, int s) const { return dd[r] ? p.T - 1 - s : s; }
+    __device__ __forceinline__ const float* gx(int r, int t) const { return p.gx + ((size_t)nn[r] * p.T + t) * 512; }
+    __device__ __forceinline__ float* hs(int r, int t) const { return p.hs + ((size_t)nn[r] * p.T + t) * 256 + dd[r] * HD; }
+    __device__ __forceinline__ size_t kept(int r, int t) const { return ((size_t)dd[r] * Nk + (nn[r] - p.keep_from)) * p.T + t; }
+};
+
+struct QuadRaggedRow {                     // R = 1: workgroup 2k + d runs direction d of sequence k
+    static constexpr bool KEEPS = false;   // inference only: no gates / cs / hprev
+    const float* gx_;                      // [rows,512]
+    float* hs_;                            // [rows,256]
+    int row0, T, d;
+    bool ok[1] = {true}, keep[1] = {false};
+    __device__ __forceinline__ QuadRaggedRow(const float* gx, float* hs, const SeqTable& tab) : gx_(gx), hs_(hs) {
+        const int k = blockIdx.x >> 1;
+        d = blockIdx.x & 1;
+        row0 = tab.row_off[k];
+        T = tab.row_off[k + 1] - row0;
+    }
+    __device__ __forceinline__ int steps() const { return T; }
+    __device__ __forceinline__ int frame(int, int s) const { return d ? T - 1 - s : s; }
+    __device__ __forceinline__ const float* gx(int, int t) const { return gx_ + (size_t)(row0 + t) * 512; }
+    __device__ __forceinline__ float* hs(int, int t) const { return hs_ + (size_t)(row0 + t) * 256 + d * HD; }
+    __device__ __forceinline__ size_t kept(int, int) const { return 0; }
+};
+
+template <int R, class Rows>
+__device__ __forceinline__ void lstm_fwd_quad_body(const float* whh, float* gates, float* cs, float* hprev, const Rows& rows) {
     constexpr int HQ = 36;                                   // a K-quarter of h: 32 floats + 4 of padding (the four quarters of a
     __shared__ __attribute__((aligned(16))) float h_s[2][R][4 * HQ];   // wave's reads fall on disjoint banks)
     const int tid = threadIdx.x, j = tid >> 2, q = tid & 3;
     float w[4][32];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
-        const float4* wp = reinterpret_cast<const float4*>(p.whh + (size_t)(g * HD + j) * HD + 32 * q);
+        const float4* wp = reinterpret_cast<const float4*>(whh + (size_t)(g * HD + j) * HD + 32 * q);
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const float4 v = wp[i];
@@ -288,39 +338,25 @@ __global__ __launch_bounds__(512) void lstm_fwd_quad_kernel(LstmFwd p) {
     for (int i = tid; i < R * 4 * HQ; i += 512) (&h_s[0][0][0])[i] = 0.f;
     __syncthreads();
     const float gk = (q == 2) ? 2.0f : 1.0f;                  // tanh(x) = 2*sigmoid(2x) - 1: one branch-free exp path for all gates
-    const int Nk = p.N - p.keep_from;
-    const int row0 = blockIdx.x * R;
-    int dd[R], nn[R];
-    bool ok[R], keep[R];
+    const int T = rows.steps();
     float c[R];
 #pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const int row = row0 + r;
-        ok[r] = row < 2 * p.N;
-        const int rc = ok[r] ? row : 2 * p.N - 1;
-        dd[r] = rc / p.N;
-        nn[r] = rc - dd[r] * p.N;
-        keep[r] = ok[r] && p.gates && nn[r] >= p.keep_from;
-        c[r] = 0.f;
-    }
+    for (int r = 0; r < R; ++r) c[r] = 0.f;
     float a_nx[R];
     auto gx_fetch = [&](int s) {                              // lane q fetches the input-side term of gate q
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int t = dd[r] ? p.T - 1 - s : s;
-            a_nx[r] = p.gx[((size_t)nn[r] * p.T + t) * 512 + q * HD + j];
-        }
+        for (int r = 0; r < R; ++r) a_nx[r] = rows.gx(r, rows.frame(r, s))[q * HD + j];
     };
     gx_fetch(0);
-    for (int s = 0; s < p.T; ++s) {
+    for (int s = 0; s < T; ++s) {
         const int cur = s & 1;
         float a_cur[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) a_cur[r] = a_nx[r];
-        if (s + 1 < p.T) gx_fetch(s + 1);
+        if (s + 1 < T) gx_fetch(s + 1);
 #pragma unroll
         for (int r = 0; r < R; ++r) {
-            const int t = dd[r] ? p.T - 1 - s : s;
+            const int t = rows.frame(r, s);
             float acc[4] = {0.f, 0.f, 0.f, 0.f};
             const float* hq = &h_s[cur][r][q * HQ];
 #pragma unroll
@@ -348,21 +384,35 @@ __global__ __launch_bounds__(512) void lstm_fwd_quad_kernel(LstmFwd p) {
             const float cn = fmaf(gf, c[r], gi * gg);
             const float h = go * fast_tanh(cn);
             c[r] = cn;
-            if (ok[r]) {
+            if (rows.ok[r]) {
                 if (q == 0) {
                     h_s[cur ^ 1][r][(j >> 5) * HQ + (j & 31)] = h;
-                    p.hs[((size_t)nn[r] * p.T + t) * 256 + dd[r] * HD + j] = h;
+                    rows.hs(r, t)[j] = h;
                 }
-                if (keep[r]) {
-                    const size_t base = ((size_t)dd[r] * Nk + (nn[r] - p.keep_from)) * p.T + t;
-                    p.gates[base * 512 + q * HD + j] = act;
-                    if (q == 1) p.hprev[base * HD + j] = h_s[cur][r][(j >> 5) * HQ + (j & 31)];   // h before this frame
-                    if (q == 2) p.cs[base * HD + j] = cn;
+                if constexpr (Rows::KEEPS) {
+                    if (rows.keep[r]) {
+                        const size_t base = rows.kept(r, t);
+                        gates[base * 512 + q * HD + j] = act;
+                        if (q == 1) hprev[base * HD + j] = h_s[cur][r][(j >> 5) * HQ + (j & 31)];   // h before this frame
+                        if (q == 2) cs[base * HD + j] = cn;
+                    }
                 }
             }
         }
         __syncthreads();                                      // h of step s+1 is complete; buffer `cur` is free for step s+2
     }
+}
+
+template <int R>
+__global__ __launch_bounds__(512) void lstm_fwd_quad_kernel(LstmFwd p) {
+    lstm_fwd_quad_body<R>(p.whh, p.gates, p.cs, p.hprev, QuadBatchRows<R>(p));
+}
+
+// The ragged forward's recurrence (ivosw_brain_forward_ragged): grid = 2 n_seqs, workgroup 2k + d = direction d of sequence k over ITS
+// rows of the flat gx / hs and ITS number of steps - the arithmetic of lstm_fwd_quad_kernel<1> on that slice (the same body).
+__global__ __launch_bounds__(512) void lstm_fwd_quad_ragged_kernel(const float* __restrict__ whh, const float* __restrict__ gx,
+                                                                   float* __restrict__ hs, SeqTable tab) {
+    lstm_fwd_quad_body<1>(whh, nullptr, nullptr, nullptr, QuadRaggedRow(gx, hs, tab));
 }
 
 // ---------------------------------------------------------------- forward recurrence on the 4x4x1 matrix instruction
@@ -1292,6 +1342,88 @@ extern "C" int ivosw_brain_argmax(const float* q, int N, int T, int64_t* idx, iv
     IVOSW_ON_DEVICE_OF(idx);
     IVOSW_REQUIRE(N > 0 && T > 0, "N and T must be positive");
     hipLaunchKernelGGL(argmax_rows_kernel, dim3(N), dim3(64), 0, as_stream(stream), q, N, T, idx);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+// ---------------------------------------------------------------- ragged forward: K sequences, each of its own length
+extern "C" long ivosw_brain_ragged_rows(const int* lengths, int n_seqs) {
+    IVOSW_REQUIRE(lengths, "null pointer");
+    return ragged_rows(__func__, lengths, n_seqs, nullptr);
+}
+
+extern "C" size_t ivosw_brain_ragged_ws_bytes(long rows) {
+    if (rows <= 0 || rows > RAGGED_MAX_ROWS) return 0;
+    return fwd_bufs_floats(1, (int)rows, 0) * sizeof(float);
+}
+
+extern "C" int ivosw_brain_forward_ragged(const float* params, const float* x, const int* lengths, int n_seqs, float* q, void* ws,
+                                          size_t ws_bytes, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(params && x && lengths && q && ws, "null pointer");
+    SeqTable tab;
+    const long rows = ragged_rows(__func__, lengths, n_seqs, &tab);
+    if (rows < 0) return IVOSW_ERR_ARG;
+    IVOSW_ON_DEVICE_OF(q);
+    if (ws_bytes < ivosw_brain_ragged_ws_bytes(rows)) {
+        set_error("ivosw_brain_forward_ragged: workspace %zu < %zu", ws_bytes, ivosw_brain_ragged_ws_bytes(rows));
+        return IVOSW_ERR_WS;
+    }
+    hipStream_t st = as_stream(stream);
+    Arena ar(ws);
+    FwdBufs b = carve_fwd(ar, 1, (int)rows, -1);          // the flat rows are one [1, R] batch to the row-wise encoder and decoder
+    b.q = q;
+    const FwdPass fp{params, x, nullptr, 1, 0, &b};
+    if (fused_forward_ok(&fp, 1)) {
+        const int R = (int)rows, tiles = (R + FM - 1) / FM;
+        EncGroup eg{};
+        DecGroup dg{};
+        eg.j[0] = EncJob{params, x, x, b.gx, b.a1, b.e, R, R, R};
+        dg.j[0] = DecJob{params, b.hs, b.d1, q, R, R};
+        eg.first1 = dg.first1 = tiles;
+        hipLaunchKernelGGL(enc_fused_kernel, dim3(tiles), dim3(256), 0, st, eg, O_W1, O_B1, O_W2, O_B2, O_WIH);
+        hipLaunchKernelGGL(lstm_fwd_quad_ragged_kernel, dim3(2 * n_seqs), dim3(512), 0, st, params + O_WHH, b.gx, b.hs, tab);
+        hipLaunchKernelGGL(dec_fused_kernel, dim3(tiles), dim3(256), 0, st, dg, O_W3, O_B3, O_W4, O_B4);
+    } else {
+        // DQN_FUSED or LSTM_QUAD switched off: the N = 1 path of ivosw_brain_forward per sequence, on that sequence's slices
+        for (int k = 0; k < n_seqs; ++k) {
+            const size_t r0 = (size_t)tab.row_off[k];
+            FwdBufs bk = b;
+            bk.a1 += r0 * 128; bk.e += r0 * 128; bk.gx += r0 * 512; bk.hs += r0 * 256; bk.d1 += r0 * 128; bk.q += r0;
+            const FwdPass fk{params, x + r0 * 2, nullptr, 1, 0, &bk};
+            if (fused_forward_ok(&fk, 1)) brain_forward_fused(&fk, 1, lengths[k], st);
+            else brain_forward_internal(params, x + r0 * 2, 1, lengths[k], bk, st);
+        }
+    }
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+// argmax_rows_kernel over a sequence table: one wave per sequence, the same scan and the same tie rule (the lower index wins)
+__global__ __launch_bounds__(64) void argmax_ragged_kernel(const float* __restrict__ q, SeqTable tab, int64_t* __restrict__ idx) {
+    const int k = blockIdx.x, lane = threadIdx.x;
+    const int r0 = tab.row_off[k], T = tab.row_off[k + 1] - r0;
+    const float* r = q + r0;
+    float best = -INFINITY;
+    int am = 0x7fffffff;
+    for (int t = lane; t < T; t += 64) {
+        const float v = r[t];
+        if (v > best || am == 0x7fffffff) { best = v; am = t; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o, 64);
+        const int oa = __shfl_xor(am, o, 64);
+        if (oa != 0x7fffffff && (am == 0x7fffffff || ob > best || (ob == best && oa < am))) { best = ob; am = oa; }
+    }
+    if (lane == 0) idx[k] = am;
+}
+
+extern "C" int ivosw_brain_argmax_ragged(const float* q, const int* lengths, int n_seqs, int64_t* idx, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(q && lengths && idx, "null pointer");
+    SeqTable tab;
+    if (ragged_rows(__func__, lengths, n_seqs, &tab) < 0) return IVOSW_ERR_ARG;
+    IVOSW_ON_DEVICE_OF(idx);
+    hipLaunchKernelGGL(argmax_ragged_kernel, dim3(n_seqs), dim3(64), 0, as_stream(stream), q, tab, idx);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }

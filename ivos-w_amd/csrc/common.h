@@ -77,6 +77,37 @@ struct Arena {
     }
 };
 
+// The sequence table of the ragged entries (ivosw_brain_forward_ragged and its kin): it travels inside the kernel arguments.
+struct SeqTable {
+    int row_off[IVOSW_MAX_SEQS + 1];      // sequence k owns the flat rows [row_off[k], row_off[k + 1])
+};
+constexpr long RAGGED_MAX_ROWS = 1L << 20;
+
+// Host-side check of a ragged call's lengths (the caller has checked the pointer and names itself): the total number of rows with
+// tab (nullable) filled, or IVOSW_ERR_ARG with the message set.
+inline long ragged_rows(const char* who, const int* lengths, int n_seqs, SeqTable* tab) {
+    if (n_seqs < 1 || n_seqs > IVOSW_MAX_SEQS) {
+        set_error("%s: n_seqs %d outside [1, %d]", who, n_seqs, IVOSW_MAX_SEQS);
+        return IVOSW_ERR_ARG;
+    }
+    long rows = 0;
+    for (int k = 0; k < n_seqs; ++k) {
+        if (lengths[k] < 1) {
+            set_error("%s: sequence %d: length %d must be positive", who, k, lengths[k]);
+            return IVOSW_ERR_ARG;
+        }
+        if (tab) tab->row_off[k] = (int)rows;
+        rows += lengths[k];
+        if (rows > RAGGED_MAX_ROWS) {
+            set_error("%s: sequence %d: too many rows (more than 2^20 in total)", who, k);
+            return IVOSW_ERR_ARG;
+        }
+    }
+    if (tab)
+        for (int k = n_seqs; k <= IVOSW_MAX_SEQS; ++k) tab->row_off[k] = (int)rows;
+    return rows;
+}
+
 // ---------------------------------------------------------------- device helpers
 typedef uint16_t bf16_t;  // raw bfloat16 bits
 

@@ -79,11 +79,10 @@ __global__ void replay_draw_gather_kernel(const float* __restrict__ old_iou, con
 // device.  pred is a float64 [n_frames, n_obj] array filled with the float32 scores, so the mean is a float64 sum in numpy's
 // order (add.reduce along the contiguous axis: sequential below 8 elements, else 8 interleaved partial sums combined
 // pairwise plus a sequential tail) divided by n_obj; the Brain then sees float32(mean) (torch.Tensor(state), agent.py:176).
-__global__ void quality_state_kernel(const float* __restrict__ scores, int n_obj, int n_frames, const float* __restrict__ counts,
-                                     double* __restrict__ quality, float* __restrict__ state) {
-    const int f = blockIdx.x * blockDim.x + threadIdx.x;
-    if (f >= n_frames) return;
-    auto at = [&](int o) { return (double)scores[(size_t)o * n_frames + f]; };
+// One frame of it: `col` points at the frame's score of object 0, the objects are `stride` floats apart.
+__device__ __forceinline__ void quality_state_row(const float* __restrict__ col, int n_obj, size_t stride, float count,
+                                                  double* __restrict__ quality, float* __restrict__ state) {
+    auto at = [&](int o) { return (double)col[(size_t)o * stride]; };
     double sum;
     if (n_obj < 8) {
         sum = at(0);        // numpy's reduce starts from the first element (no 0.0 + x)
@@ -98,9 +97,37 @@ __global__ void quality_state_kernel(const float* __restrict__ scores, int n_obj
         for (; i < n_obj; ++i) sum += at(i);
     }
     const double q = sum / (double)n_obj;
-    quality[f] = q;
-    state[2 * f] = (float)q;
-    state[2 * f + 1] = counts[f];
+    *quality = q;
+    state[0] = (float)q;
+    state[1] = count;
+}
+
+__global__ void quality_state_kernel(const float* __restrict__ scores, int n_obj, int n_frames, const float* __restrict__ counts,
+                                     double* __restrict__ quality, float* __restrict__ state) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= n_frames) return;
+    quality_state_row(scores + f, n_obj, (size_t)n_frames, counts[f], quality + f, state + 2 * (size_t)f);
+}
+
+// The same for several videos in one launch (ivosw_quality_state_ragged): one thread per flat row; the row's video is found in the
+// table (row_off is ascending: the last k with row_off[k] <= row), whose scores are the [n_obj[k], T_k] block at unit_off[k].
+struct QualityTable {
+    SeqTable seq;
+    int n_obj[IVOSW_MAX_SEQS];
+    long long unit_off[IVOSW_MAX_SEQS];
+};
+__global__ void quality_state_ragged_kernel(const float* __restrict__ scores, QualityTable tab, int n_seqs, int rows,
+                                            const float* __restrict__ counts, double* __restrict__ quality, float* __restrict__ state) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= rows) return;
+    int lo = 0, hi = n_seqs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab.seq.row_off[mid] <= f) lo = mid;
+        else hi = mid - 1;
+    }
+    const int r0 = tab.seq.row_off[lo], T = tab.seq.row_off[lo + 1] - r0;
+    quality_state_row(scores + tab.unit_off[lo] + (f - r0), tab.n_obj[lo], (size_t)T, counts[f], quality + f, state + 2 * (size_t)f);
 }
 
 // The update kernels: thin wrappers of clamp_update (dqn_update.h), which documents the body, the ticket and the traversal.  VEC: 16 bytes
@@ -531,6 +558,30 @@ extern "C" int ivosw_quality_state(const float* scores, int n_obj, int n_frames,
     IVOSW_REQUIRE(n_obj > 0 && n_frames > 0, "n_obj and n_frames must be positive");
     hipLaunchKernelGGL(quality_state_kernel, dim3((n_frames + 63) / 64), dim3(64), 0, as_stream(stream), scores, n_obj, n_frames,
                        counts, quality, state);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_quality_state_ragged(const float* scores, const int* n_obj, const int* lengths, int n_seqs, const float* counts,
+                                          double* quality, float* state, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(scores && n_obj && lengths && counts && quality && state, "null pointer");
+    QualityTable tab;
+    const long rows = ragged_rows(__func__, lengths, n_seqs, &tab.seq);
+    if (rows < 0) return IVOSW_ERR_ARG;
+    long long units = 0;
+    for (int k = 0; k < IVOSW_MAX_SEQS; ++k) {
+        tab.n_obj[k] = k < n_seqs ? n_obj[k] : 1;
+        tab.unit_off[k] = units;
+        if (k >= n_seqs) continue;
+        if (n_obj[k] < 1) {
+            set_error("%s: sequence %d: n_obj %d must be positive", __func__, k, n_obj[k]);
+            return IVOSW_ERR_ARG;
+        }
+        units += (long long)n_obj[k] * lengths[k];
+    }
+    IVOSW_ON_DEVICE_OF(state);
+    hipLaunchKernelGGL(quality_state_ragged_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, as_stream(stream), scores, tab, n_seqs,
+                       (int)rows, counts, quality, state);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }

@@ -13,6 +13,7 @@ arithmetic replaced by libivosw_hip.so:
                           ivosw_copy_f32         (hard target sync on the reference's host coin, cfg.agent.target_update = "coin";
                           ivosw_target_update     "soft" / "periodic": the rule on the device, fused into the one-call step's last launch)
   Agent.action         -> ivosw_brain_forward + ivosw_brain_argmax (first max, like numpy)
+  Agent.actions        -> ivosw_brain_forward_ragged + ivosw_brain_argmax_ragged (several states of different lengths, one launch chain)
 
 torch modules (nn.Linear / nn.LSTMCell) are used only as parameter containers so that ``state_dict()`` keys,
 shapes and default initialisation are the reference's; their ``forward`` is never called.  All ten tensors are
@@ -31,6 +32,23 @@ from .momory_pool import PrioritizedReplay, ReplayMemory, per_params
 _ORDER = ("encoder_fc1.weight", "encoder_fc1.bias", "encoder_fc2.weight", "encoder_fc2.bias",
           "lstm_cell.weight_ih", "lstm_cell.weight_hh", "decoder_fc1.weight", "decoder_fc1.bias",
           "decoder_fc2.weight", "decoder_fc2.bias")
+
+
+def _adjacent_rows(states):
+    """The flat [R,2] tensor behind ``states`` when they are consecutive row slices of ONE contiguous fp32 [*,2] tensor, else None."""
+    base = states[0]._base if torch.is_tensor(states[0]) else None
+    if base is None or base.dim() != 2 or base.shape[1] != 2 or base.dtype != torch.float32 or not base.is_contiguous():
+        return None
+    first = states[0].storage_offset() - base.storage_offset()
+    want = first
+    for s in states:
+        if not torch.is_tensor(s) or s._base is not base or s.dim() != 2 or s.shape[1] != 2 or not s.is_contiguous() \
+                or s.storage_offset() - base.storage_offset() != want:
+            return None
+        want += 2 * s.shape[0]
+    if first % 2:
+        return None
+    return base[first // 2:want // 2]
 
 
 class Brain(nn.Module):
@@ -88,6 +106,49 @@ class Brain(nn.Module):
         ws = self._ws.get(nbytes, x.device)
         L.check(lib.ivosw_brain_forward(L.dptr(self.flat), L.dptr(x), N, T, L.dptr(q), L.dptr(ws), nbytes,
                                         L.stream_ptr(x.device)), "brain_forward")
+        return q
+
+    def forward_ragged(self, states, lengths=None):
+        """Q of SEVERAL sequences, each of its own length, in one launch chain (ivosw_brain_forward_ragged).  ``states`` is a sequence of
+        [T_k,2] fp32 tensors on this network's device, or ONE flat [R,2] tensor with ``lengths`` (R = their sum).  Returns (q, views): the
+        flat Q [R] and one [T_k] view of it per sequence.  Each view holds, bit for bit, ``forward(state[None])[0]`` of its sequence:
+        nothing is padded, the backward direction of every sequence starts at its own last frame.  More than 128 sequences run in
+        groups of 128."""
+        if lengths is None:
+            states = list(states)
+            lengths = [int(s.shape[0]) for s in states]
+            if not states:
+                raise ValueError("forward_ragged needs at least one sequence")
+            x = _adjacent_rows(states)                        # slices of one flat [R,2] tensor, in order: read in place
+            if x is None:
+                x = states[0] if len(states) == 1 else torch.cat([s.detach().to(dtype=torch.float32) for s in states], 0)
+        else:
+            x, lengths = states, [int(n) for n in lengths]
+        x = x.detach().to(dtype=torch.float32).contiguous()
+        if x.dim() != 2 or x.shape[1] != 2 or not lengths or min(lengths) < 1 or sum(lengths) != x.shape[0]:
+            raise ValueError(f"forward_ragged: states must be [R,2] with positive lengths that sum to R, got {tuple(x.shape)} and {lengths}")
+        q = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
+        self.forward_ragged_into(x, lengths, q)
+        views, off = [], 0
+        for n in lengths:
+            views.append(q[off:off + n])
+            off += n
+        return q, views
+
+    def forward_ragged_into(self, x, lengths, q):
+        """forward_ragged on a flat contiguous fp32 x [R,2] into a preallocated q [R] (no allocation beyond the grow-only workspace)."""
+        lib, off = L.lib(), 0
+        for g in range(0, len(lengths), L.MAX_SEQS):
+            group = lengths[g:g + L.MAX_SEQS]
+            arr = L.int_array(group)
+            rows = int(lib.ivosw_brain_ragged_rows(arr, len(group)))
+            if rows < 0:
+                L.check(rows, "brain_ragged_rows")
+            nbytes = lib.ivosw_brain_ragged_ws_bytes(rows)
+            ws = self._ws.get(nbytes, x.device)
+            L.check(lib.ivosw_brain_forward_ragged(L.dptr(self.flat), L.dptr(x[off:off + rows]), arr, len(group), L.dptr(q[off:off + rows]),
+                                                   L.dptr(ws), nbytes, L.stream_ptr(x.device)), "brain_forward_ragged")
+            off += rows
         return q
 
 
@@ -715,26 +776,71 @@ class Agent(nn.Module):
         utils_agent's device-resident chain: `state` may be a [T,2] fp32 CUDA tensor, and with `device_out` (int64 [1] on
         the device) the greedy index is left THERE and None is returned, so the caller can fetch it together with its
         other results in one D2H copy (the epsilon branch still returns a host integer)."""
+        pick = self._host_pick(state, verbose)
+        if pick is not None:
+            return pick
+        on_device = torch.is_tensor(state) and state.is_cuda       # [T,2] fp32 already on the GPU (utils_agent's device chain)
+        st = state if on_device else torch.as_tensor(np.asarray(state), dtype=torch.float32).to(self.device)
+        if device_out is not None:
+            self.greedy_index_device(st, out=device_out)
+            return None
+        return np.int64(self.greedy_index_device(st).item())
+
+    def _host_pick(self, state, verbose):
+        """The host half of one action (agent.py:168-185): steps_done, the epsilon threshold, the random.random() draw and the log line;
+        on the random branch the random.choice pick, on the greedy branch None."""
         self.steps_done += 1
         if self.cfg.phase != "train":
             eps_threshold = 0
         else:
             eps_threshold = self.EPS_END + (self.EPS_START - self.EPS_END) * \
                 math.exp(-0.5 * self.steps_done / self.EPS_DECAY)
-        on_device = torch.is_tensor(state) and state.is_cuda       # [T,2] fp32 already on the GPU (utils_agent's device chain)
+        on_device = torch.is_tensor(state) and state.is_cuda
         n_frames = state.shape[0] if on_device else np.asarray(state).shape[0]
         rand_flag = random.random()
         greedy = rand_flag > eps_threshold
         if verbose:
             print(f"step:{self.steps_done}, rand_flag:{rand_flag:.4f}, eps_threshold:{eps_threshold:.4f}, "
                   f"frame index was selected {'by agent' if greedy else 'randomly'}")
-        if not greedy:
-            return random.choice(np.array(range(n_frames)))
-        st = state if on_device else torch.as_tensor(np.asarray(state), dtype=torch.float32).to(self.device)
+        return None if greedy else random.choice(np.array(range(n_frames)))
+
+    def actions(self, states, verbose=True, device_out=None):
+        """``action`` for several states: per state, in order, exactly the host work of ``action`` (steps_done, the epsilon threshold,
+        random.random(), the log line, random.choice on the random branch), then ONE ragged forward + ONE ragged argmax over all states
+        (``greedy_indices_device``).  Returns a list with one entry per state: the host integer of a random pick, otherwise the greedy
+        index - or None when ``device_out`` (int64 [K] on the device) is given: entry k of it then holds state k's greedy index (also
+        for random-branch states, whose entry the caller ignores).  The host RNG streams and ``steps_done`` end where K sequential
+        ``action`` calls leave them."""
+        states = list(states)
+        picks = [self._host_pick(state, verbose) for state in states]
+        if all(p is not None for p in picks):                 # (also: no state at all) nothing is greedy: no forward, as under `action`
+            return picks
+        idx = self.greedy_indices_device(states, out=device_out)
         if device_out is not None:
-            self.greedy_index_device(st, out=device_out)
-            return None
-        return np.int64(self.greedy_index_device(st).item())
+            return picks
+        host = idx.cpu().numpy()
+        return [p if p is not None else np.int64(host[k]) for k, p in enumerate(picks)]
+
+    def greedy_indices_device(self, states, out=None):
+        """argmax_t Q(state_k)[t] for several states ([T_k,2]; host arrays are uploaded), left on the device (int64 [K], or written to
+        `out`): one Brain.forward_ragged and one ivosw_brain_argmax_ragged per 128 states."""
+        dev = self.policy_net.flat.device
+        sts = [s if (torch.is_tensor(s) and s.is_cuda) else torch.as_tensor(np.asarray(s), dtype=torch.float32).to(dev) for s in states]
+        lengths = [int(s.shape[0]) for s in sts]
+        q, _ = self.policy_net.forward_ragged(sts)
+        return self.argmax_ragged(q, lengths, out=out)
+
+    def argmax_ragged(self, q, lengths, out=None):
+        """The first maximum of every sequence's slice of the flat q -> int64 [K] on the device (or `out`)."""
+        idx = out if out is not None else torch.empty(len(lengths), dtype=torch.int64, device=q.device)
+        lib, off = L.lib(), 0
+        for g in range(0, len(lengths), L.MAX_SEQS):
+            group = lengths[g:g + L.MAX_SEQS]
+            rows = sum(group)
+            L.check(lib.ivosw_brain_argmax_ragged(L.dptr(q[off:off + rows]), L.int_array(group), len(group), L.dptr(idx[g:g + len(group)]),
+                                                  L.stream_ptr(q.device)), "argmax_ragged")
+            off += rows
+        return idx
 
     def greedy_index_device(self, state, out=None):
         """argmax_t Q(state)[t] for a device state [T,2] fp32, result left on the device (int64 [1], or written to `out`)."""

@@ -185,17 +185,26 @@ def assess_videos_device(assess_net, videos, device):
     return assess_net.forward_videos(on_dev)
 
 
+# recommend_frames runs quality -> state -> Brain -> argmax as ONE ragged chain from this many requests on, and per request below it.
+# tools/ragged_brain_probe.py times both chains (profiles/ragged_brain_probe.txt): at 2 requests of 30 frames 170 us per request against
+# 117 us ragged with a run-to-run spread of 3 us (100 frames: 261 against 159, spread 23), and the gap grows with every request.
+RAGGED_MIN_REQUESTS = 2
+
+
 def recommend_frames(cfg_yl, assess_net, agent, device, requests):
     """``recommend_frame`` for several sessions at once: ``requests`` is a sequence of dicts, each the keyword arguments of
     ``recommend_frame`` behind ``device`` (n_frame, n_objects, all_F, all_P, new_masks_quality, prev_frames, annotated_frames_list,
     mask_quality, first_frame, max_nb_interactions).  Returns the recommended indices in request order.
 
     Under wild/ours and wild/worst all requests share ONE assessment pass (assess_videos_device: K short videos fill one full-size pass
-    instead of K small ones); then, per request in request order, quality -> state -> Brain -> first-max argmax runs on the device
-    (``agent.action`` is called once per request, so ``steps_done`` and the host RNG move exactly as under sequential
-    ``recommend_frame`` calls), ONE device-to-host copy brings back every quality vector and index, and each request's
-    ``mask_quality`` is filled in place.  Indices and quality vectors equal those of ``recommend_frame`` per request.  Every other
-    setting / method is ``recommend_frame`` per request.
+    instead of K small ones) and, from RAGGED_MIN_REQUESTS requests on, ONE chain behind it whatever K is: one upload of the concatenated
+    counts, ivosw_quality_state_ragged over the flat scores of that pass (every request's float64 quality and fp32 state in one launch),
+    ``agent.actions`` (the host work of ``agent.action`` per request in request order - ``steps_done`` and the host RNG move exactly as
+    under sequential ``recommend_frame`` calls - then ONE ragged Brain forward over all sessions, each of its own length, and ONE ragged
+    first-max argmax: five launches where the per-request loop needed 5 K, and the K recurrences run side by side instead of one behind
+    the other), and ONE device-to-host copy of [quality (R) float64 | index (K) int64] that fills each request's ``mask_quality`` in
+    place.  A single request keeps the per-request chain.  Indices and quality vectors equal those of ``recommend_frame`` per request,
+    bit for bit.  Every other setting / method is ``recommend_frame`` per request.
 
     Keep the videos on the device (``pack_video`` or ``all_F.to(device)`` once per sequence): host-resident frames are uploaded on
     every call here, and the single-entry ``frame_cache`` of ``recommend_frame`` is left alone."""
@@ -206,31 +215,50 @@ def recommend_frames(cfg_yl, assess_net, agent, device, requests):
         return []
     from .. import _lib as L
     method = cfg_yl.method
+    K = len(requests)
     with torch.no_grad():
         scores = assess_videos_device(assess_net, [(r["all_F"], r["all_P"], r["n_objects"]) for r in requests], device)
         dev = scores[0].device
         ns = [int(s.shape[1]) for s in scores]
-        offs = np.concatenate([[0], np.cumsum([n + 1 for n in ns])])
-        out = torch.zeros(int(offs[-1]), dtype=torch.float64, device=dev)   # per request [quality (n) | recommended index (int64 bits)]
         counts = [_annotation_counts(len(r["new_masks_quality"]), r["annotated_frames_list"]) for r in requests]
         cnt = torch.as_tensor(np.concatenate(counts).astype(np.float32)).to(dev, non_blocking=True)      # one upload for all requests
-        picked, c0 = [], 0
-        for r, s, n, o in zip(requests, scores, ns, offs[:-1]):
-            o = int(o)
-            state = torch.empty(n, 2, dtype=torch.float32, device=dev)
-            L.check(L.lib().ivosw_quality_state(L.dptr(s), int(r["n_objects"]), n, L.dptr(cnt[c0:c0 + n]), L.dptr(out[o:o + n]),
-                                                L.dptr(state), L.stream_ptr(dev)), "quality_state")
-            c0 += n
-            picked.append(agent.action(state, device_out=out[o + n:o + n + 1].view(torch.int64)) if method == "ours" else None)
+        if K < RAGGED_MIN_REQUESTS:
+            qoffs = np.concatenate([[0], np.cumsum([n + 1 for n in ns])])[:-1]   # per request [quality (n) | recommended index (int64 bits)]
+            ioffs = [int(o) + n for o, n in zip(qoffs, ns)]
+            out = torch.zeros(sum(ns) + K, dtype=torch.float64, device=dev)
+            picked, c0 = [], 0
+            for r, s, n, o in zip(requests, scores, ns, qoffs):
+                o = int(o)
+                state = torch.empty(n, 2, dtype=torch.float32, device=dev)
+                L.check(L.lib().ivosw_quality_state(L.dptr(s), int(r["n_objects"]), n, L.dptr(cnt[c0:c0 + n]), L.dptr(out[o:o + n]),
+                                                    L.dptr(state), L.stream_ptr(dev)), "quality_state")
+                c0 += n
+                picked.append(agent.action(state, device_out=out[o + n:o + n + 1].view(torch.int64)) if method == "ours" else None)
+        else:
+            R = sum(ns)
+            qoffs = np.concatenate([[0], np.cumsum(ns)])[:-1]                    # [quality of every request (R) | the K indices (int64 bits)]
+            ioffs = [R + k for k in range(K)]
+            out = torch.zeros(R + K, dtype=torch.float64, device=dev)
+            state = torch.empty(R, 2, dtype=torch.float32, device=dev)
+            for g in range(0, K, L.MAX_SEQS):                                    # (one launch per 128 requests)
+                o, n_g = int(qoffs[g]), sum(ns[g:g + L.MAX_SEQS])
+                L.check(L.lib().ivosw_quality_state_ragged(
+                    L.dptr(scores[g]), L.int_array(int(s.shape[0]) for s in scores[g:g + L.MAX_SEQS]), L.int_array(ns[g:g + L.MAX_SEQS]),
+                    len(ns[g:g + L.MAX_SEQS]), L.dptr(cnt[o:o + n_g]), L.dptr(out[o:o + n_g]), L.dptr(state[o:o + n_g]), L.stream_ptr(dev)),
+                    "quality_state_ragged")
+            picked = [None] * K
+            if method == "ours":
+                picked = agent.actions([state[int(o):int(o) + n] for o, n in zip(qoffs, ns)], device_out=out[R:].view(torch.int64))
         host = out.cpu()                                                    # the one D2H copy of the call
+    quality, index = host.numpy(), host.view(torch.int64).numpy()
     result = []
-    for r, n, o, pk in zip(requests, ns, offs[:-1], picked):
+    for r, n, o, i, pk in zip(requests, ns, qoffs, ioffs, picked):
         o = int(o)
-        r["mask_quality"][:] = host[o:o + n].numpy()                        # in place: the caller logs corr/diff from this array
+        r["mask_quality"][:] = quality[o:o + n]                             # in place: the caller logs corr/diff from this array
         if method == "worst":
             result.append(select_next_frame(r["mask_quality"], metric="worst", prev_frames=r["prev_frames"]))
         else:
-            result.append(pk if pk is not None else np.int64(host[o + n:o + n + 1].view(torch.int64)[0].item()))
+            result.append(pk if pk is not None else np.int64(index[i]))
     return result
 
 
