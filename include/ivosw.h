@@ -77,6 +77,22 @@ size_t ivosw_brain_ragged_ws_bytes(long rows);
 int ivosw_brain_forward_ragged(const float* params, const float* x, const int* lengths, int n_seqs,
                                float* q, void* ws, size_t ws_bytes, ivosw_stream_t stream);
 int ivosw_brain_argmax_ragged(const float* q, const int* lengths, int n_seqs, int64_t* idx, ivosw_stream_t stream);
+/* Ragged, masked top-k: the k (1 .. IVOSW_MAX_CANDIDATES) strongest frames of every sequence's slice of q, in the place of the single
+ * Q.argmax() of Agent.action (models/agent.py:168-196), with select_next_frame's rule for annotated frames (utils_agent.py:38-74) on the
+ * device.  The frames of a sequence are ranked by this total order, the strongest first:
+ *   1. the tier: with skip_annotated != 0, frames whose annotation count state[(r0 + t) * 2 + 1] is 0 come before all others (when
+ *      every frame is annotated the ranking falls through to them, as select_next_frame does); with skip_annotated == 0 there is one
+ *      tier, and `state` (the [R,2] state ivosw_quality_state[_ragged] writes) may be NULL;
+ *   2. inside a tier the larger q first: -0 and +0 are equal, +inf and -inf are ordinary values, NaN ranks below every number;
+ *   3. then the lower index first.
+ * idx[s * k + j] = the j-th frame of sequence s in that order (index inside the slice, as ivosw_brain_argmax_ragged returns it), -1
+ * for j >= lengths[s]; qv (nullable) [n_seqs, k] = the bits of q at that frame, 0.0f for a -1 slot.  With k = 1 and skip_annotated = 0
+ * idx equals ivosw_brain_argmax_ragged on any NaN-free q.  One launch, one wave per sequence, no workspace; capture-safe.
+ * Refused (IVOSW_ERR_ARG) before anything is launched, the message names the argument: a NULL q, lengths or idx, k outside
+ * [1, IVOSW_MAX_CANDIDATES], skip_annotated != 0 with a NULL state, and what ivosw_brain_ragged_rows refuses.                          */
+#define IVOSW_MAX_CANDIDATES 16
+int ivosw_brain_topk_ragged(const float* q, const float* state, const int* lengths, int n_seqs, int k, int skip_annotated,
+                            int64_t* idx, float* qv, ivosw_stream_t stream);
 
 /* ------------------------------------------------------------------ agent: DQN step (K8-K10) -- */
 /* Replaces the arithmetic of Agent.update_agent (models/agent.py:128-155):

@@ -22,6 +22,7 @@ ASSESS_NTENSORS = 326
 _p, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 MAX_VIDEOS = 32                                      # IVOSW_MAX_VIDEOS
 MAX_SEQS = 128                                       # IVOSW_MAX_SEQS
+MAX_CANDIDATES = 16                                  # IVOSW_MAX_CANDIDATES
 FRAMES_F32, FRAMES_RGBX8 = 0, 1                      # IVOSW_FRAMES_*
 
 
@@ -41,6 +42,7 @@ SIGNATURES = {
     "ivosw_brain_ragged_ws_bytes": (_sz, [C.c_long]),
     "ivosw_brain_forward_ragged": (_i, [_p, _p, _p, _i, _p, _p, _sz, _p]),
     "ivosw_brain_argmax_ragged": (_i, [_p, _p, _i, _p, _p]),
+    "ivosw_brain_topk_ragged": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p]),
     "ivosw_dqn_ws_bytes": (_sz, [_i, _i]),
     "ivosw_dqn_loss_grad": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _p, _p, _p, _sz, _p]),
     "ivosw_dqn_loss_grad_ex": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _i, _f, _p, _p, _p, _sz, _p]),

@@ -1428,6 +1428,101 @@ extern "C" int ivosw_brain_argmax_ragged(const float* q, const int* lengths, int
     return IVOSW_OK;
 }
 
+// ---------------------------------------------------------------- ragged masked top-k: the k strongest frames of every sequence
+// One 64-bit key per frame, larger = stronger, unique inside a sequence:
+//   bit 53      always set (0 is "no frame")
+//   bit 52      the tier: set for a frame that is not annotated when annotated frames are to come last
+//   bits 51-20  the float as an order-preserving uint32: -0 canonicalised to +0, NaN mapped to 0 (below -inf, which maps to 0x007fffff)
+//   bits 19-0   2^20 - 1 - t (RAGGED_MAX_ROWS = 2^20): among equal values the lower index wins
+__device__ __forceinline__ uint64_t topk_key(float v, bool strong, int t) {
+    uint32_t u = __float_as_uint(v);
+    if ((u & 0x7fffffffu) > 0x7f800000u) {
+        u = 0;
+    } else {
+        if (u == 0x80000000u) u = 0;
+        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    }
+    return (1ull << 53) | ((uint64_t)strong << 52) | ((uint64_t)u << 20) | (uint64_t)(0xfffff - t);
+}
+
+__device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)v, o, 64);
+        const uint32_t hi = (uint32_t)__shfl_xor((int)(uint32_t)(v >> 32), o, 64);
+        const uint64_t other = ((uint64_t)hi << 32) | lo;
+        v = other > v ? other : v;
+    }
+    return v;
+}
+
+// One wave per sequence.  Round j finds the largest key strictly below round j - 1's winner (lanes stride the frames, then a 64-lane
+// butterfly on the key): the keys are unique, so nothing is marked as taken, and there is no LDS and no atomic.  A sequence of up to
+// 64 TOPK_TRIPS frames keeps its keys in registers over the rounds (q and state are read once); a longer one rebuilds them from memory
+// every round.  Lane j keeps round j's winner; at the end the first k lanes store their slot (and fetch its q).
+constexpr int TOPK_TRIPS = 4;
+__global__ __launch_bounds__(64) void topk_ragged_kernel(const float* __restrict__ q, const float* __restrict__ state, SeqTable tab, int k,
+                                                         int skip, int64_t* __restrict__ idx, float* __restrict__ qv) {
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int r0 = tab.row_off[s], T = tab.row_off[s + 1] - r0;
+    const float* r = q + r0;
+    const float* c = skip ? state + (size_t)r0 * 2 + 1 : nullptr;           // column 1 of the state: how often the frame was annotated
+    uint64_t bound = ~0ull, mine = 0;
+    if (T <= 64 * TOPK_TRIPS) {
+        uint64_t key[TOPK_TRIPS];
+#pragma unroll
+        for (int i = 0; i < TOPK_TRIPS; ++i) {
+            const int t = lane + 64 * i;
+            key[i] = t < T ? topk_key(r[t], skip && c[2 * t] == 0.f, t) : 0;
+        }
+        for (int j = 0; j < k; ++j) {
+            uint64_t best = 0;
+#pragma unroll
+            for (int i = 0; i < TOPK_TRIPS; ++i)
+                if (key[i] < bound && key[i] > best) best = key[i];
+            best = wave_max_u64(best);
+            if (best == 0) break;                                           // (wave-uniform) every frame is ranked: the rest stays -1
+            if (lane == j) mine = best;
+            bound = best;
+        }
+    } else {
+        for (int j = 0; j < k; ++j) {
+            uint64_t best = 0;
+            for (int t = lane; t < T; t += 64) {
+                const uint64_t key = topk_key(r[t], skip && c[2 * t] == 0.f, t);
+                if (key < bound && key > best) best = key;
+            }
+            best = wave_max_u64(best);
+            if (best == 0) break;
+            if (lane == j) mine = best;
+            bound = best;
+        }
+    }
+    if (lane < k) {
+        const int t = mine ? 0xfffff - (int)(mine & 0xfffff) : -1;
+        idx[(size_t)s * k + lane] = t;
+        if (qv) qv[(size_t)s * k + lane] = t >= 0 ? r[t] : 0.f;
+    }
+}
+
+extern "C" int ivosw_brain_topk_ragged(const float* q, const float* state, const int* lengths, int n_seqs, int k, int skip_annotated,
+                                       int64_t* idx, float* qv, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(q, "q is a null pointer");
+    IVOSW_REQUIRE(lengths, "lengths is a null pointer");
+    IVOSW_REQUIRE(idx, "idx is a null pointer");
+    if (k < 1 || k > IVOSW_MAX_CANDIDATES) {
+        set_error("%s: k %d outside [1, %d]", __func__, k, IVOSW_MAX_CANDIDATES);
+        return IVOSW_ERR_ARG;
+    }
+    IVOSW_REQUIRE(!skip_annotated || state, "skip_annotated needs state, which is a null pointer");
+    SeqTable tab;
+    if (ragged_rows(__func__, lengths, n_seqs, &tab) < 0) return IVOSW_ERR_ARG;
+    IVOSW_ON_DEVICE_OF(idx);
+    hipLaunchKernelGGL(topk_ragged_kernel, dim3(n_seqs), dim3(64), 0, as_stream(stream), q, state, tab, k, skip_annotated ? 1 : 0, idx, qv);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
 extern "C" size_t ivosw_dqn_ws_bytes(int B, int T) {
     if (B <= 0 || T <= 0) return 0;
     return dqn_ws_floats(B, T) * sizeof(float);

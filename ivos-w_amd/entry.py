@@ -74,9 +74,12 @@ DEFAULTS = dict(
                replay="uniform", per_alpha=0.6, per_beta=0.4, per_beta_steps=0, per_eps=1e-6,
                                    # minibatches: uniform (the reference's shuffle), or "prioritized": PER with priority exponent per_alpha,
                                    # IS exponent per_beta annealed to 1 over per_beta_steps draws (0: constant), per_eps added to |TD|
-               target_update="coin", tau=0.005, target_period=20),
+               target_update="coin", tau=0.005, target_period=20,
                                    # target net: "coin" (the reference's hard sync with probability update_rate per step), "soft" (Polyak
                                    # averaging with tau after every step) or "periodic" (hard sync every target_period-th step), on the device
+               candidates=1, skip_annotated=False),
+                                   # recommendation: how many ranked frames the agent proposes per interaction (1: the reference's argmax; up
+                                   # to 16), and whether frames that were annotated before rank behind all others (select_next_frame's rule)
     synth=dict(n_sequences=3, n_frames=30, height=120, width=216, max_objects=3, baseline_runs=30),
 )
 
@@ -398,18 +401,19 @@ def run_eval(cfg, backbone="MANet"):
             labels, all_P = _segment(vos, davis, sequence, n_objects, annotated, store)
             quality = misc.sequence_metric(metric, davis.load_annotations(sequence), labels, n_objects)
             tic = time.time()
-            next_frame = utils_agent.recommend_frame(
-                cfg, assess_net, agent, device, n_frame=n_frame, n_objects=n_objects, all_F=all_F, all_P=all_P,
+            candidates = [int(i) for i in utils_agent.recommend_candidates(cfg, assess_net, agent, device, [dict(
+                n_frame=n_frame, n_objects=n_objects, all_F=all_F, all_P=all_P,
                 new_masks_quality=quality, prev_frames=prev_frames, annotated_frames_list=copy.deepcopy(annotated),
-                mask_quality=quality_pred, first_frame=first_frame, max_nb_interactions=max_nb)
-            next_frame = int(next_frame)
+                mask_quality=quality_pred, first_frame=first_frame, max_nb_interactions=max_nb)])[0]]
+            next_frame = candidates[0]                                # the session annotates the first candidate
             if prev_frames is not None:
                 prev_frames.append(next_frame)
             rec_time.update(time.time() - tic)
-            sess.submit_masks(labels, next_scribble_frame_candidates=[next_frame])
+            sess.submit_masks(labels, next_scribble_frame_candidates=candidates)
             corr = float(np.corrcoef([quality, quality_pred])[0, 1]) if quality_pred is not None else float("nan")
             corr_all.update(0.0 if np.isnan(corr) else corr)
             print(f"avg_{metric}: {quality.mean() * 100:.2f} rec_time:{rec_time.val * 1e3:.1f} ms next_frame: {next_frame:2d} "
+                  + (f"candidates: {candidates} " if len(candidates) > 1 else "") +
                   f"[{int((quality < quality[next_frame]).sum()) + 1:2d}/{n_frame:2d}] corr: {corr:.2f} "
                   f"seq: {sequence}_{seen_seq[sequence]} [{n_interaction:2d}/{max_nb:2d}]")
         gs = sess.get_global_summary()
@@ -432,6 +436,9 @@ def run_eval_real(cfg, backbone, device):
     DAVIS frames from disk, the caller's VOS adapter for the segmentation, and this build's hot path for everything the reference
     owns in that loop: ``sequence_metric`` (J / F), ``recommend_frame`` (AssessNet + agent), the checkpoint loaders.  Writes
     <report_save_dir>/<backbone>/<setting>/<dataset>/<method>/summary.json like the reference (eval_agent_manet.py:470-480)."""
+    if cfg.agent.get("candidates", 1) != 1:
+        raise ValueError(f"agent.candidates = {cfg.agent.get('candidates')!r} is not supported on the real stack: its loop takes the "
+                         "recommended frame for the annotated one, and davisinteractive's robot may pick any candidate (use 1)")
     import cv2
     from davisinteractive import utils as interactive_utils
     from davisinteractive.dataset import Davis

@@ -14,6 +14,7 @@ arithmetic replaced by libivosw_hip.so:
                           ivosw_target_update     "soft" / "periodic": the rule on the device, fused into the one-call step's last launch)
   Agent.action         -> ivosw_brain_forward + ivosw_brain_argmax (first max, like numpy)
   Agent.actions        -> ivosw_brain_forward_ragged + ivosw_brain_argmax_ragged (several states of different lengths, one launch chain)
+  cfg.agent.candidates / skip_annotated -> ivosw_brain_topk_ragged in the argmax's place (k ranked frames per state, annotated ones last)
 
 torch modules (nn.Linear / nn.LSTMCell) are used only as parameter containers so that ``state_dict()`` keys,
 shapes and default initialisation are the reference's; their ``forward`` is never called.  All ten tensors are
@@ -515,6 +516,26 @@ class FusedClampSGD(_LrSchedule):
         self.state["momentum_buffer"].copy_(st["momentum_buffer"])
 
 
+def candidates_option(candidates=1, skip_annotated=False):
+    """(k, skip), checked: cfg.agent.candidates an int in [1, L.MAX_CANDIDATES] and cfg.agent.skip_annotated a bool.  Anything else is a
+    ValueError that names the key."""
+    if isinstance(candidates, bool) or not isinstance(candidates, int) or not 1 <= candidates <= L.MAX_CANDIDATES:
+        raise ValueError(f"agent.candidates must be an int in [1, {L.MAX_CANDIDATES}], got {candidates!r}")
+    if not isinstance(skip_annotated, bool):
+        raise ValueError(f"agent.skip_annotated must be true or false, got {skip_annotated!r}")
+    return candidates, skip_annotated
+
+
+def merge_candidates(pick, ranking, k):
+    """The candidate list of one state as a host np.int64 array: the device ranking (its -1 slots cut off), cut to k.  With a random
+    pick of the epsilon branch (``pick`` not None) the pick comes first and the ranking follows with that frame removed."""
+    rank = np.asarray(ranking, dtype=np.int64).reshape(-1)
+    rank = rank[rank >= 0]
+    if pick is not None:
+        rank = np.concatenate([np.array([int(pick)], dtype=np.int64), rank[rank != int(pick)]])
+    return rank[:k]
+
+
 class Agent(nn.Module):
     def __init__(self, device, cfg):
         super().__init__()
@@ -528,6 +549,7 @@ class Agent(nn.Module):
         self.replay_kind, self.per_alpha, self.per_beta, self.per_beta_steps, self.per_eps = self._replay_option(a)
         self.per_replay = None                      # the PrioritizedReplay of the episode loop (utils_agent._device_update_loop)
         self.target_update, self.tau, self.target_period = self._target_option(a)
+        self.candidates, self.skip_annotated = self._candidates_option(a)
         self.target_steps = 0                       # steps the device rule has seen (soft / periodic); resumed by load_target_state
         self._target_dev, self._target_dev_step = None, 0
         self.EPS_START, self.EPS_END, self.EPS_DECAY = a.eps_start, a.eps_end, a.eps_decay
@@ -611,6 +633,13 @@ class Agent(nn.Module):
         with .get, so a config without the keys keeps the coin; tau and target_period are only checked under their mode
         (target_update_option), before anything is allocated.  update_rate is only read under "coin"."""
         return target_update_option(a.get("target_update", "coin"), a.get("tau", 0.005), a.get("target_period", 20))
+
+    @staticmethod
+    def _candidates_option(a):
+        """cfg.agent.candidates (1, the reference's single frame and the default: how many ranked frames action / actions return per
+        state) and cfg.agent.skip_annotated (False: frames that were annotated before rank behind all others, select_next_frame's rule):
+        read with .get, so a config without the keys acts as before; checked by candidates_option, before anything is allocated."""
+        return candidates_option(a.get("candidates", 1), a.get("skip_annotated", False))
 
     def prioritized_replay(self, soa, device, seed):
         """A PrioritizedReplay over `soa` with this agent's PER options."""
@@ -775,16 +804,28 @@ class Agent(nn.Module):
         """Reference surface: action(state [T,2] numpy, verbose) -> frame index (agent.py:168-196).  Extensions used by
         utils_agent's device-resident chain: `state` may be a [T,2] fp32 CUDA tensor, and with `device_out` (int64 [1] on
         the device) the greedy index is left THERE and None is returned, so the caller can fetch it together with its
-        other results in one D2H copy (the epsilon branch still returns a host integer)."""
+        other results in one D2H copy (the epsilon branch still returns a host integer).
+
+        With agent.skip_annotated the greedy index is slot 0 of the masked ranking (``candidates_device``): same types, same host work.
+        With agent.candidates = k > 1 the return is an np.int64 array of min(k, T) frames: the ranking on the greedy branch; on the epsilon
+        branch the random pick, then the ranking with that frame removed (``merge_candidates``).  `device_out` is then int64 [k]: the
+        ranking is left there on either branch and the caller merges (None, or the random pick, is returned)."""
         pick = self._host_pick(state, verbose)
-        if pick is not None:
+        k, skip = candidates_option(self.candidates, self.skip_annotated)
+        if pick is not None and k == 1:
             return pick
         on_device = torch.is_tensor(state) and state.is_cuda       # [T,2] fp32 already on the GPU (utils_agent's device chain)
         st = state if on_device else torch.as_tensor(np.asarray(state), dtype=torch.float32).to(self.device)
+        if k == 1 and not skip:
+            if device_out is not None:
+                self.greedy_index_device(st, out=device_out)
+                return None
+            return np.int64(self.greedy_index_device(st).item())
+        rank = self.candidates_device([st], k, skip, out=device_out)
         if device_out is not None:
-            self.greedy_index_device(st, out=device_out)
-            return None
-        return np.int64(self.greedy_index_device(st).item())
+            return pick
+        host = rank.cpu().numpy()
+        return np.int64(host[0, 0]) if k == 1 else merge_candidates(pick, host[0], k)
 
     def _host_pick(self, state, verbose):
         """The host half of one action (agent.py:168-185): steps_done, the epsilon threshold, the random.random() draw and the log line;
@@ -810,16 +851,70 @@ class Agent(nn.Module):
         (``greedy_indices_device``).  Returns a list with one entry per state: the host integer of a random pick, otherwise the greedy
         index - or None when ``device_out`` (int64 [K] on the device) is given: entry k of it then holds state k's greedy index (also
         for random-branch states, whose entry the caller ignores).  The host RNG streams and ``steps_done`` end where K sequential
-        ``action`` calls leave them."""
+        ``action`` calls leave them.
+
+        With agent.skip_annotated / agent.candidates = k the argmax is the ragged masked top-k (``candidates_device``) and the entries are
+        what ``action`` returns in that mode; ``device_out`` is int64 [K, k] and holds every state's ranking."""
         states = list(states)
         picks = [self._host_pick(state, verbose) for state in states]
-        if all(p is not None for p in picks):                 # (also: no state at all) nothing is greedy: no forward, as under `action`
+        k, skip = candidates_option(self.candidates, self.skip_annotated)
+        if not states or (k == 1 and all(p is not None for p in picks)):      # nothing is greedy: no forward, as under `action`
             return picks
-        idx = self.greedy_indices_device(states, out=device_out)
+        if k == 1 and not skip:
+            idx = self.greedy_indices_device(states, out=device_out)
+            if device_out is not None:
+                return picks
+            host = idx.cpu().numpy()
+            return [p if p is not None else np.int64(host[i]) for i, p in enumerate(picks)]
+        rank = self.candidates_device(states, k, skip, out=device_out)
         if device_out is not None:
             return picks
-        host = idx.cpu().numpy()
-        return [p if p is not None else np.int64(host[k]) for k, p in enumerate(picks)]
+        host = rank.cpu().numpy()
+        if k == 1:
+            return [p if p is not None else np.int64(host[i, 0]) for i, p in enumerate(picks)]
+        return [merge_candidates(p, host[i], k) for i, p in enumerate(picks)]
+
+    def candidates_device(self, states, k=None, skip_annotated=None, out=None):
+        """The k strongest frames of every state ([T_k,2]; host arrays are uploaded) by Q, annotated frames last under skip_annotated
+        (ivosw_brain_topk_ragged's order), left on the device: int64 [K, k] (or written to `out`, K k int64 values), -1 behind a state's
+        last frame.  k and skip_annotated default to the agent's options.  One Brain.forward_ragged and one top-k launch per 128 states;
+        a single state runs Brain.forward and the same entry with one sequence."""
+        k, skip = candidates_option(self.candidates if k is None else k, self.skip_annotated if skip_annotated is None else skip_annotated)
+        dev = self.policy_net.flat.device
+        sts = [s if (torch.is_tensor(s) and s.is_cuda) else torch.as_tensor(np.asarray(s), dtype=torch.float32).to(dev) for s in states]
+        if not sts:
+            raise ValueError("candidates_device needs at least one state")
+        lengths = [int(s.shape[0]) for s in sts]
+        if len(sts) == 1:
+            x = sts[0].detach().to(dtype=torch.float32).contiguous()
+            q = self.policy_net(x[None]).view(-1)
+        else:
+            x = _adjacent_rows(sts)                           # slices of one flat [R,2] tensor, in order: read in place
+            if x is None:
+                x = torch.cat([s.detach().to(dtype=torch.float32) for s in sts], 0)
+            x = x.detach().to(dtype=torch.float32).contiguous()
+            q, _ = self.policy_net.forward_ragged(x, lengths)
+        return self.topk_ragged(q, x, lengths, k, skip, out=out)
+
+    def topk_ragged(self, q, states, lengths, k, skip, out=None, qv=None):
+        """ivosw_brain_topk_ragged over the flat q [R] of sequences of `lengths`: int64 [K, k] on the device (or `out`), the j-th
+        strongest frame of every sequence, -1 from its length on.  `states` is the flat [R,2] fp32 state whose column 1 holds the
+        annotation counts, or None (only with `skip` false); `qv` (float32 [K, k], optional) receives the Q values of the slots."""
+        K = len(lengths)
+        idx = out.view(K, k) if out is not None else torch.empty(K, k, dtype=torch.int64, device=q.device)
+        if qv is not None:
+            qv = qv.view(K, k)
+        lib, off = L.lib(), 0
+        for g in range(0, K, L.MAX_SEQS):
+            group = lengths[g:g + L.MAX_SEQS]
+            rows = sum(group)
+            L.check(lib.ivosw_brain_topk_ragged(L.dptr(q[off:off + rows], torch.float32),
+                                                L.dptr(states[off:off + rows], torch.float32) if states is not None else None,
+                                                L.int_array(group), len(group), int(k), int(bool(skip)), L.dptr(idx[g:g + len(group)], torch.int64),
+                                                L.dptr(qv[g:g + len(group)], torch.float32) if qv is not None else None,
+                                                L.stream_ptr(q.device)), "topk_ragged")
+            off += rows
+        return idx
 
     def greedy_indices_device(self, states, out=None):
         """argmax_t Q(state_k)[t] for several states ([T_k,2]; host arrays are uploaded), left on the device (int64 [K], or written to

@@ -77,6 +77,37 @@ def _annotation_counts(n, annotated_frames_list):
     return counts
 
 
+def _topk_options(cfg_yl, agent):
+    """(k, skip_annotated): the agent's checked options; without an agent (method "worst" needs none) cfg.agent's keys, defaults 1 / False."""
+    from ..models.agent import candidates_option
+    if agent is not None and hasattr(agent, "candidates"):
+        return candidates_option(agent.candidates, agent.skip_annotated)
+    a = cfg_yl.get("agent") if hasattr(cfg_yl, "get") else None
+    if a is None:
+        return 1, False
+    return candidates_option(a.get("candidates", 1), a.get("skip_annotated", False))
+
+
+def worst_candidates(frame_value, k, prev_frames=None):
+    """The first k frames of the order select_next_frame(frame_value, "worst", prev_frames) walks: its pick, then the other frames that are
+    not in prev_frames by rising value, then (when those run out) the frames of prev_frames by rising value.  np.int64 [min(k, n)]."""
+    first = int(select_next_frame(frame_value, metric="worst", prev_frames=prev_frames))
+    order = [int(i) for i in np.asarray(frame_value).argsort() if int(i) != first]
+    if prev_frames is not None:
+        order = [i for i in order if i not in prev_frames] + [i for i in order if i in prev_frames]
+    return np.array([first] + order, dtype=np.int64)[:k]
+
+
+def _candidate_list(pick, k):
+    """What a k = 1 recommendation returns (one index) or a k > 1 one (an array), as the np.int64 array recommend_candidates returns."""
+    return np.atleast_1d(np.asarray(pick, dtype=np.int64))[:k]
+
+
+def _first(pick):
+    """Candidate 0 of what Agent.action returns: the index itself with agent.candidates = 1, else the first entry of its array."""
+    return pick[0] if np.ndim(pick) else pick
+
+
 class _FrameCache:
     """The video of the current sequence, resident on the GPU across interactions.  The reference uploads all_F (and all_P)
     on EVERY interaction (utils/utils_agent.py:114-115: 100 frames x 480p fp32 = 0.5 GB, ~10 ms of PCIe per call); the entry
@@ -144,16 +175,18 @@ def assess_all_objects(assess_net, all_F, all_P, n_objects, device):
     return assess_all_objects_device(assess_net, all_F, all_P, n_objects, device).transpose(0, 1).cpu().numpy()
 
 
-def _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, counts, mask_quality, prev_frames):
+def _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, counts, mask_quality, prev_frames, k=1, as_list=False):
     """wild/worst and wild/ours (utils/utils_agent.py:111-122) with the chain quality -> state -> Brain -> argmax on the
     device: per-object scores are averaged into mask_quality (float64, numpy's summation order) and stacked with the
     annotation counts by ivosw_quality_state, the Brain and its first-max argmax read that state in place, and ONE D2H copy
-    brings back the n quality values the caller's array wants plus the recommended index."""
+    brings back the n quality values the caller's array wants plus the recommended index.  With agent.candidates = k /
+    agent.skip_annotated the argmax is the masked top-k and the buffer holds k indices; `as_list`: return all candidates (an array)."""
     from .. import _lib as L
+    from ..models.agent import merge_candidates
     scores = assess_all_objects_device(assess_net, all_F, all_P, n_objects, device)
     n = scores.shape[1]
     dev = scores.device
-    out = torch.empty(n + 1, dtype=torch.float64, device=dev)          # [quality (n) | recommended index (int64 bits)]
+    out = torch.empty(n + k, dtype=torch.float64, device=dev)          # [quality (n) | k recommended indices (int64 bits)]
     state = torch.empty(n, 2, dtype=torch.float32, device=dev)
     cnt = torch.as_tensor(np.asarray(counts, dtype=np.float32)).to(dev, non_blocking=True)
     L.check(L.lib().ivosw_quality_state(L.dptr(scores), n_objects, n, L.dptr(cnt), L.dptr(out), L.dptr(state),
@@ -164,8 +197,14 @@ def _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, cou
     host = out.cpu()                                                    # the one D2H copy of the interaction
     mask_quality[:] = host[:n].numpy()          # in place: the caller logs corr/diff from this array
     if method == "worst":
+        if as_list:
+            return worst_candidates(mask_quality, k, prev_frames)
         return select_next_frame(mask_quality, metric="worst", prev_frames=prev_frames)
-    return picked if picked is not None else np.int64(host[n:].view(torch.int64)[0].item())
+    if k > 1:
+        cand = merge_candidates(picked, host[n:].view(torch.int64).numpy(), k)
+        return cand if as_list else cand[0]
+    pick = picked if picked is not None else np.int64(host[n:].view(torch.int64)[0].item())
+    return _candidate_list(pick, 1) if as_list else pick
 
 
 def assess_videos_device(assess_net, videos, device):
@@ -206,14 +245,37 @@ def recommend_frames(cfg_yl, assess_net, agent, device, requests):
     place.  A single request keeps the per-request chain.  Indices and quality vectors equal those of ``recommend_frame`` per request,
     bit for bit.  Every other setting / method is ``recommend_frame`` per request.
 
+    With agent.candidates = k / agent.skip_annotated the chain ends in the ragged masked top-k instead of the argmax (still five launches
+    and one copy, of [quality (R) | K k indices]); the index returned per request is candidate 0 (``recommend_candidates`` returns all).
+
     Keep the videos on the device (``pack_video`` or ``all_F.to(device)`` once per sequence): host-resident frames are uploaded on
     every call here, and the single-entry ``frame_cache`` of ``recommend_frame`` is left alone."""
+    return _recommend_many(cfg_yl, assess_net, agent, device, requests, as_list=False)
+
+
+def recommend_candidates(cfg_yl, assess_net, agent, device, requests):
+    """``recommend_frames`` with every candidate returned: one np.int64 array of min(agent.candidates, n_frame) frame indices per request,
+    the strongest first (entry 0 is what ``recommend_frames`` returns), and the same in-place ``mask_quality`` side effect.  One request
+    or many: the same chains as ``recommend_frames`` (a single request takes the per-request chain with a one-sequence top-k).  wild/ours
+    and oracle/ours: Agent.action's candidates (the ranking by Q, annotated frames last under agent.skip_annotated; on the epsilon branch
+    the random pick first); oracle/ours runs on the host state.  "worst": the first k frames of the order select_next_frame walks
+    (``worst_candidates``).  "random" / "linspace": their single pick."""
+    return _recommend_many(cfg_yl, assess_net, agent, device, requests, as_list=True)
+
+
+def _recommend_many(cfg_yl, assess_net, agent, device, requests, as_list):
     requests = list(requests)
+    k, _ = _topk_options(cfg_yl, agent)
     if not (cfg_yl.setting == "wild" and cfg_yl.method in ("worst", "ours")):
+        if as_list:
+            return [_recommend_one(cfg_yl, assess_net, agent, device, k=k, as_list=True, **r) for r in requests]
         return [recommend_frame(cfg_yl, assess_net, agent, device, **r) for r in requests]
+    if as_list and len(requests) == 1:           # one session: recommend_frame's chain (its frame cache, a one-sequence top-k)
+        return [_recommend_one(cfg_yl, assess_net, agent, device, k=k, as_list=True, **requests[0])]
     if not requests:
         return []
     from .. import _lib as L
+    from ..models.agent import merge_candidates
     method = cfg_yl.method
     K = len(requests)
     with torch.no_grad():
@@ -223,9 +285,9 @@ def recommend_frames(cfg_yl, assess_net, agent, device, requests):
         counts = [_annotation_counts(len(r["new_masks_quality"]), r["annotated_frames_list"]) for r in requests]
         cnt = torch.as_tensor(np.concatenate(counts).astype(np.float32)).to(dev, non_blocking=True)      # one upload for all requests
         if K < RAGGED_MIN_REQUESTS:
-            qoffs = np.concatenate([[0], np.cumsum([n + 1 for n in ns])])[:-1]   # per request [quality (n) | recommended index (int64 bits)]
+            qoffs = np.concatenate([[0], np.cumsum([n + k for n in ns])])[:-1]   # per request [quality (n) | k recommended indices (int64 bits)]
             ioffs = [int(o) + n for o, n in zip(qoffs, ns)]
-            out = torch.zeros(sum(ns) + K, dtype=torch.float64, device=dev)
+            out = torch.zeros(sum(ns) + K * k, dtype=torch.float64, device=dev)
             picked, c0 = [], 0
             for r, s, n, o in zip(requests, scores, ns, qoffs):
                 o = int(o)
@@ -233,12 +295,12 @@ def recommend_frames(cfg_yl, assess_net, agent, device, requests):
                 L.check(L.lib().ivosw_quality_state(L.dptr(s), int(r["n_objects"]), n, L.dptr(cnt[c0:c0 + n]), L.dptr(out[o:o + n]),
                                                     L.dptr(state), L.stream_ptr(dev)), "quality_state")
                 c0 += n
-                picked.append(agent.action(state, device_out=out[o + n:o + n + 1].view(torch.int64)) if method == "ours" else None)
+                picked.append(agent.action(state, device_out=out[o + n:o + n + k].view(torch.int64)) if method == "ours" else None)
         else:
             R = sum(ns)
-            qoffs = np.concatenate([[0], np.cumsum(ns)])[:-1]                    # [quality of every request (R) | the K indices (int64 bits)]
-            ioffs = [R + k for k in range(K)]
-            out = torch.zeros(R + K, dtype=torch.float64, device=dev)
+            qoffs = np.concatenate([[0], np.cumsum(ns)])[:-1]                    # [quality of every request (R) | the K k indices (int64 bits)]
+            ioffs = [R + j * k for j in range(K)]
+            out = torch.zeros(R + K * k, dtype=torch.float64, device=dev)
             state = torch.empty(R, 2, dtype=torch.float32, device=dev)
             for g in range(0, K, L.MAX_SEQS):                                    # (one launch per 128 requests)
                 o, n_g = int(qoffs[g]), sum(ns[g:g + L.MAX_SEQS])
@@ -256,34 +318,50 @@ def recommend_frames(cfg_yl, assess_net, agent, device, requests):
         o = int(o)
         r["mask_quality"][:] = quality[o:o + n]                             # in place: the caller logs corr/diff from this array
         if method == "worst":
-            result.append(select_next_frame(r["mask_quality"], metric="worst", prev_frames=r["prev_frames"]))
+            result.append(worst_candidates(r["mask_quality"], k, r["prev_frames"]) if as_list else
+                          select_next_frame(r["mask_quality"], metric="worst", prev_frames=r["prev_frames"]))
+        elif k > 1:
+            cand = merge_candidates(pk, index[i:i + k], k)
+            result.append(cand if as_list else cand[0])
         else:
-            result.append(pk if pk is not None else np.int64(index[i]))
+            pick = pk if pk is not None else np.int64(index[i])
+            result.append(_candidate_list(pick, 1) if as_list else pick)
     return result
 
 
 def recommend_frame(cfg_yl, assess_net, agent, device, n_frame, n_objects, all_F, all_P, new_masks_quality, prev_frames,
                     annotated_frames_list, mask_quality, first_frame, max_nb_interactions):
+    k, _ = _topk_options(cfg_yl, agent)
+    return _recommend_one(cfg_yl, assess_net, agent, device, n_frame, n_objects, all_F, all_P, new_masks_quality, prev_frames,
+                          annotated_frames_list, mask_quality, first_frame, max_nb_interactions, k=k, as_list=False)
+
+
+def _recommend_one(cfg_yl, assess_net, agent, device, n_frame, n_objects, all_F, all_P, new_masks_quality, prev_frames,
+                   annotated_frames_list, mask_quality, first_frame, max_nb_interactions, k=1, as_list=False):
+    """recommend_frame (the reference's index: candidate 0), or with `as_list` the candidates of recommend_candidates."""
     setting, method = cfg_yl.setting, cfg_yl.method
+    one = (lambda pick: _candidate_list(pick, k)) if as_list else _first
     if setting == "oracle":
         if method == "worst":
+            if as_list:
+                return worst_candidates(new_masks_quality, k, prev_frames)
             return select_next_frame(new_masks_quality, metric="worst", prev_frames=prev_frames)
         if method == "ours":
             state = np.stack([new_masks_quality, _annotation_counts(len(new_masks_quality), annotated_frames_list)], 1)
             with torch.no_grad():
-                return agent.action(state)
+                return one(agent.action(state))
         raise NotImplementedError
     if setting == "wild":
         if method == "random":
-            return select_next_frame(new_masks_quality, metric="random")
+            return one(select_next_frame(new_masks_quality, metric="random"))
         if method == "linspace":
             subseq = gen_subseq(first_frame, n_frame, min(max_nb_interactions, n_frame), "equal")
-            return next((i for i in subseq if i not in prev_frames), prev_frames[0])
+            return one(next((i for i in subseq if i not in prev_frames), prev_frames[0]))
         if method in ("worst", "ours"):
             counts = _annotation_counts(len(new_masks_quality), annotated_frames_list)
             with torch.no_grad():
                 return _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, counts, mask_quality,
-                                    prev_frames)
+                                    prev_frames, k=k, as_list=as_list)
         raise NotImplementedError
     raise NotImplementedError
 
