@@ -444,6 +444,36 @@ int ivosw_roi_sample_videos(const ivosw_video_t* videos, int n_videos, const flo
                             ivosw_stream_t stream);
 int ivosw_assess_forward_videos(const void* packed, int dtype, const ivosw_video_t* videos, int n_videos, float* scores,
                                 void* ws, size_t ws_bytes, int chunk, int tap_stage, void* tap_out, ivosw_stream_t stream);
+/* Incremental assessment: re-score only the (frame, object) units whose mask planes changed since the session was last scored.
+ * `videos` is the descriptor array of ivosw_assess_forward_videos - the same unit order, the same refusals.
+ * ivosw_mask_delta_videos compares every unit's plane with the session's copy of the planes it was last scored on and brings that copy
+ * up to date.  cache[v] (DEVICE buffer, 4-byte aligned; dense [n_obj][n_frames][H*W] fp32, unit order inside the video) and cold[v] are
+ * HOST arrays of n_videos entries, read during the call only (the pointers travel in the kernel arguments like the table).  A unit is
+ * DIRTY when any 32-bit pattern of its plane differs from the cached plane - compared as integers: +0 against -0 is dirty, a NaN with the
+ * same bits is clean; clean means the tower would see the same bits.  cold[v] != 0: the cache content is undefined, every unit of v is
+ * dirty and its planes are copied without comparing.  On return (stream order) cache[v] equals the planes bit for bit; only elements
+ * (16-byte vectors on the vector path) that differ are stored, so an unchanged session writes nothing.  flags: [units] int32 scratch
+ * (zeroed by the call's own init launch).  unit_ids [units] int32: entries [0, *n_dirty) are the dirty units in ascending order, the rest
+ * is unspecified; n_dirty: one int32 on the device.  Three launches (init, compare, compaction), no allocation, no atomics:
+ * capture-safe and deterministic.  16-byte loads when the video's planes allow them (H * W % 4 == 0, 16-byte aligned masks and strides)
+ * and cache[v] is 16-byte aligned; else the scalar path.
+ * ivosw_mask_bbox_units / ivosw_roi_sample_units / ivosw_assess_forward_units: the *_videos entries over a unit LIST.  unit_ids is a
+ * DEVICE array of n_ids units of the table (what ivosw_mask_delta_videos wrote); row i of yxhw [n_ids,4] / roi [n_ids,256,256,4]
+ * belongs to unit unit_ids[i]; scratch n_ids * 4 int32.  Per unit the arithmetic is that of the *_videos entries, operation for operation.
+ * ivosw_assess_forward_units: `scores` is the session's FULL [units] table; only scores[unit_ids[i]] is written.  Chunking and the
+ * two-stream split work on list positions (B = n_ids).  Workspace: ivosw_assess_units_ws_bytes(dtype, n_ids, chunk) (0 for n_ids <= 0).
+ * n_ids == 0 returns IVOSW_OK and launches nothing.  Refused before any launch: what the *_videos entries refuse, n_ids < 0, n_ids above
+ * the table's units, a NULL list with n_ids > 0.  A row whose id lies outside [0, units) is skipped (an all-zero yxhw row / roi tile, no
+ * score stored): no address is ever formed from such an id.                                                                            */
+int ivosw_mask_delta_videos(const ivosw_video_t* videos, int n_videos, float* const* cache, const int* cold,
+                            int32_t* flags, int32_t* unit_ids, int32_t* n_dirty, ivosw_stream_t stream);
+int ivosw_mask_bbox_units(const ivosw_video_t* videos, int n_videos, const int32_t* unit_ids, int n_ids, float* yxhw,
+                          int32_t* scratch, ivosw_stream_t stream);
+int ivosw_roi_sample_units(const ivosw_video_t* videos, int n_videos, const int32_t* unit_ids, int n_ids, const float* yxhw,
+                           int dtype, void* roi, ivosw_stream_t stream);
+size_t ivosw_assess_units_ws_bytes(int dtype, int n_ids, int chunk);
+int ivosw_assess_forward_units(const void* packed, int dtype, const ivosw_video_t* videos, int n_videos, const int32_t* unit_ids,
+                               int n_ids, float* scores, void* ws, size_t ws_bytes, int chunk, ivosw_stream_t stream);
 /* Replaces `mask_quality[:] = pred.mean(1); state = np.stack([mask_quality, counts], 1)` (utils/utils_agent.py:120-121) on
  * the device: scores [n_obj][n_frames] fp32 (as ivosw_assess_forward_objects writes them), counts [n_frames] fp32 ->
  * quality [n_frames] float64 (numpy's float64 mean of the float32 predictions, same summation order) and

@@ -99,6 +99,11 @@ SIGNATURES = {
     "ivosw_mask_bbox_videos": (_i, [_p, _i, _p, _p, _p]),
     "ivosw_roi_sample_videos": (_i, [_p, _i, _p, _i, _p, _p]),
     "ivosw_assess_forward_videos": (_i, [_p, _i, _p, _i, _p, _p, _sz, _i, _i, _p, _p]),
+    "ivosw_mask_delta_videos": (_i, [_p, _i, _p, _p, _p, _p, _p, _p]),
+    "ivosw_mask_bbox_units": (_i, [_p, _i, _p, _i, _p, _p, _p]),
+    "ivosw_roi_sample_units": (_i, [_p, _i, _p, _i, _p, _i, _p, _p]),
+    "ivosw_assess_units_ws_bytes": (_sz, [_i, _i, _i]),
+    "ivosw_assess_forward_units": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _sz, _i, _p]),
     "ivosw_quality_state": (_i, [_p, _i, _i, _p, _p, _p, _p]),
     "ivosw_quality_state_ragged": (_i, [_p, _p, _p, _i, _p, _p, _p, _p]),
     "ivosw_assess_dominant_kernel": (C.c_char_p, [_i]),

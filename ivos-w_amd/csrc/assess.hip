@@ -324,9 +324,10 @@ extern "C" const char* ivosw_assess_dominant_kernel(int dtype) {
 }
 
 // vt != NULL: the units are those of a video table (front.h) and fs / tp / sm / H / W are not looked at
+// ids != NULL (with vt): the B rows of the pass are the entries of a unit list, row i = unit ids[i]; chunks and stream halves cut the LIST
 static int assess_forward_impl(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int B, int H, int W,
                                float* scores, void* ws, size_t ws_bytes, int chunk, int tap_stage, void* tap_out,
-                               ivosw_stream_t stream, const VideoTable* vt = nullptr);
+                               ivosw_stream_t stream, const VideoTable* vt = nullptr, const int32_t* ids = nullptr);
 
 extern "C" int ivosw_assess_forward(const void* packed, int dtype, const float* tf, const float* tp, int B, int H, int W,
                                     float* scores, void* ws, size_t ws_bytes, int chunk, int tap_stage, void* tap_out,
@@ -380,10 +381,46 @@ extern "C" int ivosw_assess_forward_videos(const void* packed, int dtype, const 
                                tap_stage, tap_out, stream, &vt);
 }
 
+// The same pass over a unit LIST (include/ivosw.h): row i of the pass is unit unit_ids[i] of the table, so B = n_ids and the chunk loop,
+// the two-stream split and the workspace are those of a pass of n_ids units.  The tower writes its scores into a compact [n_ids] buffer
+// at the head of the workspace; one scatter launch behind the join stores them at scores[unit_ids[i]] and touches nothing else.
+static size_t units_head_bytes(int n_ids) { return align_up((size_t)n_ids * sizeof(float), 256); }
+
+extern "C" size_t ivosw_assess_units_ws_bytes(int dtype, int n_ids, int chunk) {
+    if (n_ids <= 0) return 0;
+    const size_t body = ivosw_assess_ws_bytes(dtype, n_ids, 2, 2, chunk);
+    return body ? units_head_bytes(n_ids) + body : 0;
+}
+
+extern "C" int ivosw_assess_forward_units(const void* packed, int dtype, const ivosw_video_t* videos, int n_videos, const int32_t* unit_ids,
+                                          int n_ids, float* scores, void* ws, size_t ws_bytes, int chunk, ivosw_stream_t stream) {
+    VideoTable vt;
+    if (const int rc = video_table_build(videos, n_videos, __func__, &vt)) return rc;
+    IVOSW_REQUIRE(n_ids >= 0, "n_ids is negative");
+    IVOSW_REQUIRE(n_ids <= vt.units, "n_ids is above the table's units");
+    IVOSW_REQUIRE(n_ids == 0 || unit_ids, "null pointer (unit_ids)");
+    IVOSW_REQUIRE(dtype == IVOSW_F32 || dtype == IVOSW_BF16 || dtype == IVOSW_F32X3, "dtype must be IVOSW_F32, IVOSW_BF16 or IVOSW_F32X3");
+    if (n_ids == 0) return IVOSW_OK;
+    IVOSW_REQUIRE(packed && scores && ws, "null pointer");
+    IVOSW_ON_DEVICE_OF(scores);
+    const size_t head = units_head_bytes(n_ids);
+    if (ws_bytes < head) {
+        set_error("ivosw_assess_forward_units: workspace %zu < %zu", ws_bytes, ivosw_assess_units_ws_bytes(dtype, n_ids, chunk));
+        return IVOSW_ERR_WS;
+    }
+    float* compact = static_cast<float*>(ws);
+    if (const int rc = assess_forward_impl(packed, dtype, FrameSrc{nullptr, 0}, nullptr, SampleMap{1, 0, 0}, n_ids, 2, 2, compact,
+                                           static_cast<char*>(ws) + head, ws_bytes - head, chunk, 0, nullptr, stream, &vt, unit_ids))
+        return rc;
+    launch_scatter_units(compact, unit_ids, n_ids, vt.units, scores, as_stream(stream));
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
 // units [u0, u0 + B) of the batch on stream st with their own workspace; `slot` = which of the (up to two) concurrent profiler spans
 static void assess_forward_range(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int u0, int B,
                                  int H, int W, float* scores, void* ws, int chunk, int tap_stage, void* tap_out, int slot, hipStream_t st,
-                                 const VideoTable* vt);
+                                 const VideoTable* vt, const int32_t* ids);
 
 // One helper stream + two events per device for the two-stream split (created on first use, all-or-nothing; the call holds
 // the device's mutex while it enqueues so two host threads cannot interleave their fork / join pairs).
@@ -419,7 +456,7 @@ Side2* side2_for_current_device() {
 
 static int assess_forward_impl(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int B, int H, int W,
                                float* scores, void* ws, size_t ws_bytes, int chunk, int tap_stage, void* tap_out,
-                               ivosw_stream_t stream, const VideoTable* vt) {
+                               ivosw_stream_t stream, const VideoTable* vt, const int32_t* ids) {
     IVOSW_REQUIRE(packed && (vt || (fs.p && tp)) && scores && ws, "null pointer");
     IVOSW_REQUIRE(vt || !fs.u8 || (reinterpret_cast<uintptr_t>(fs.p) & 3) == 0, "rgbx must be 4-byte aligned");
     IVOSW_ON_DEVICE_OF(scores);
@@ -449,8 +486,8 @@ static int assess_forward_impl(const void* packed, int dtype, const FrameSrc& fs
         bool ok = hipEventRecord(sd->ev[0], st) == hipSuccess && hipStreamWaitEvent(sd->stream, sd->ev[0], 0) == hipSuccess;
         if (ok) {
             span_group_begin();
-            assess_forward_range(packed, dtype, fs, tp, sm, 0, B0, H, W, scores, ws, std::min(default_chunk(dtype), B0), 0, nullptr, 0, st, vt);
-            assess_forward_range(packed, dtype, fs, tp, sm, B0, B1, H, W, scores + B0, ws1, std::min(default_chunk(dtype), B1), 0, nullptr, 1, sd->stream, vt);
+            assess_forward_range(packed, dtype, fs, tp, sm, 0, B0, H, W, scores, ws, std::min(default_chunk(dtype), B0), 0, nullptr, 0, st, vt, ids);
+            assess_forward_range(packed, dtype, fs, tp, sm, B0, B1, H, W, scores + B0, ws1, std::min(default_chunk(dtype), B1), 0, nullptr, 1, sd->stream, vt, ids);
             span_group_end();
             ok = hipEventRecord(sd->ev[1], sd->stream) == hipSuccess && hipStreamWaitEvent(st, sd->ev[1], 0) == hipSuccess;
             if (!ok) {
@@ -463,14 +500,14 @@ static int assess_forward_impl(const void* packed, int dtype, const FrameSrc& fs
         }
         (void)hipGetLastError();        // the fork failed before anything was enqueued on the side stream: run on one stream
     }
-    assess_forward_range(packed, dtype, fs, tp, sm, 0, B, H, W, scores, ws, chunk, tap_stage, tap_out, 0, st, vt);
+    assess_forward_range(packed, dtype, fs, tp, sm, 0, B, H, W, scores, ws, chunk, tap_stage, tap_out, 0, st, vt, ids);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }
 
 static void assess_forward_range(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int u0, int B,
                                  int H, int W, float* scores, void* ws, int chunk, int tap_stage, void* tap_out, int slot, hipStream_t st,
-                                 const VideoTable* vt) {
+                                 const VideoTable* vt, const int32_t* ids) {
     const Plan& P = plan_for(dtype);
     const size_t es = (dtype == IVOSW_BF16) ? 2 : 4;
     const char* base = static_cast<const char*>(packed);
@@ -485,7 +522,7 @@ static void assess_forward_range(const void* packed, int dtype, const FrameSrc& 
     };
 
     // K1/K2: mask -> (y,x,h,w) for the whole batch, on device
-    if (vt) launch_mask_bbox_multi(*vt, u0, B, bf.yxhw, bf.box, st);
+    if (vt) launch_mask_bbox_multi(*vt, u0, B, bf.yxhw, bf.box, st, ids);
     else launch_mask_bbox(tp, u0, B, H, W, sm, bf.yxhw, bf.box, st);
     // Encoder.mean/std come from the checkpoint: the sampler reads them from the packed arena
     RoiNorm nrm{{0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}, reinterpret_cast<const float*>(base + P.norm_off)};
@@ -732,7 +769,7 @@ static void assess_forward_range(const void* packed, int dtype, const FrameSrc& 
                     const int nb = std::min(cs[0], f1 + n1 - f0);
                     // K3: ROI crop-resize + normalise -> NHWC4
                     span_close(st, slot);
-                    if (vt) launch_roi_sample_multi(*vt, bf.yxhw + (size_t)f0 * 4, u0 + f0, nb, dtype, nrm, bf.roi, st);
+                    if (vt) launch_roi_sample_multi(*vt, bf.yxhw + (size_t)f0 * 4, u0 + f0, nb, dtype, nrm, bf.roi, st, ids);
                     else launch_roi_sample(fs, tp, bf.yxhw + (size_t)f0 * 4, u0 + f0, nb, H, W, dtype, sm, nrm, bf.roi, st);
                     tap(1, bf.roi, nb * E_ROI * es);
                     // K4: stem 7x7/2 (RGB|P) + BN + ReLU, then 3x3/2 max pool (bf16: one fused kernel unless the stem tap is wanted)

@@ -414,12 +414,31 @@ __device__ __forceinline__ int video_of_unit(const VideoTable& vt, int u) {
     return v;
 }
 
+// Which unit row b of a launch works on: the b-th unit of a range (unit = b0 + b: what the *_videos entries launch), or the b-th entry of
+// a unit list (unit = ids[b0 + b]: the *_units entries; ids is a device array).  The kernels below take either one as their `Units`
+// template parameter, so both variants come from one body.  A list entry outside [0, units) is never turned into an address: valid()
+// is false and the row is skipped (the box stays empty, the tile is zero).
+struct UnitRange {
+    int b0;
+    __device__ __forceinline__ int at(int b) const { return b0 + b; }
+    __device__ __forceinline__ bool valid(int, int) const { return true; }
+};
+struct UnitList {
+    const int32_t* ids;
+    int b0;
+    __device__ __forceinline__ int at(int b) const { return ids[b0 + b]; }
+    __device__ __forceinline__ bool valid(int u, int units) const { return (unsigned)u < (unsigned)units; }
+};
+
 // bbox_scan_kernel over the units [b0, b0 + gridDim.y) of a video table.  grid (S, B) with S sized for the LARGEST plane of the range:
 // a workgroup whose chunk lies behind its own video's plane leaves before the barrier (the whole workgroup: the test is uniform).
 // Integer min / max: the box does not depend on how the plane is cut into chunks.
-__global__ __launch_bounds__(256) void bbox_scan_multi_kernel(const VideoTable vt, int b0, int chunk, int32_t* __restrict__ box) {
+template <typename Units>
+__global__ __launch_bounds__(256) void bbox_scan_multi_kernel(const VideoTable vt, Units un, int chunk, int32_t* __restrict__ box) {
     const int b = blockIdx.y;
-    const int u = b0 + b, vi = video_of_unit(vt, u);
+    const int u = un.at(b);
+    if (!un.valid(u, vt.units)) return;                            // (uniform: the whole workgroup leaves)
+    const int vi = video_of_unit(vt, u);
     const VideoDesc& d = vt.v[vi];
     const int W = d.W;
     const size_t plane = (size_t)d.H * W;
@@ -487,10 +506,16 @@ __global__ __launch_bounds__(256) void bbox_scan_multi_kernel(const VideoTable v
 }
 
 // bbox_finalize_kernel with the H, W of the unit's own video (a per-thread lookup: neighbouring units may belong to different videos)
-__global__ void bbox_finalize_multi_kernel(const int32_t* __restrict__ box, const VideoTable vt, int b0, int B, float* __restrict__ yxhw) {
+template <typename Units>
+__global__ void bbox_finalize_multi_kernel(const int32_t* __restrict__ box, const VideoTable vt, Units un, int B, float* __restrict__ yxhw) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const int vi = video_of_unit(vt, b0 + b);
+    const int u = un.at(b);
+    if (!un.valid(u, vt.units)) {
+        yxhw[b * 4 + 0] = 0.f; yxhw[b * 4 + 1] = 0.f; yxhw[b * 4 + 2] = 0.f; yxhw[b * 4 + 3] = 0.f;
+        return;
+    }
+    const int vi = video_of_unit(vt, u);
     const int H = vt.v[vi].H, W = vt.v[vi].W;
     int y0 = box[b * 4 + 0], y1 = box[b * 4 + 1], x0 = box[b * 4 + 2], x1 = box[b * 4 + 3];
     if (y1 < 0) { y0 = 0; y1 = H; x0 = 0; x1 = W; }
@@ -506,19 +531,24 @@ __global__ void bbox_finalize_multi_kernel(const int32_t* __restrict__ box, cons
     yxhw[b * 4 + 3] = (float)(fx1 - fx0 + 1.0);
 }
 
-void launch_mask_bbox_multi(const VideoTable& vt, int b0, int B, float* yxhw, int32_t* scratch, hipStream_t st) {
+void launch_mask_bbox_multi(const VideoTable& vt, int b0, int B, float* yxhw, int32_t* scratch, hipStream_t st, const int32_t* ids) {
     hipLaunchKernelGGL(bbox_init_kernel, dim3((B + 63) / 64), dim3(64), 0, st, scratch, B);
     size_t plane = 0;                                              // the largest plane among the videos of [b0, b0 + B)
-    for (int i = 0; i < vt.n; ++i) {
+    for (int i = 0; i < vt.n; ++i) {                               // (a list: of all videos - the host does not know which ones it names)
         const long lo = vt.first[i], hi = lo + (long)vt.v[i].n_frames * vt.v[i].n_obj;
-        if (hi > b0 && lo < (long)b0 + B) plane = max(plane, (size_t)vt.v[i].H * vt.v[i].W);
+        if (ids || (hi > b0 && lo < (long)b0 + B)) plane = max(plane, (size_t)vt.v[i].H * vt.v[i].W);
     }
     int S = (int)max((size_t)1, min((size_t)64, (size_t)2048 / (size_t)B));
     size_t chunk = (plane + S - 1) / S;
     chunk = (chunk + 1023) / 1024 * 1024;
     S = (int)((plane + chunk - 1) / chunk);
-    hipLaunchKernelGGL(bbox_scan_multi_kernel, dim3(S, B), dim3(256), 0, st, vt, b0, (int)chunk, scratch);
-    hipLaunchKernelGGL(bbox_finalize_multi_kernel, dim3((B + 63) / 64), dim3(64), 0, st, scratch, vt, b0, B, yxhw);
+    if (ids) {
+        hipLaunchKernelGGL(bbox_scan_multi_kernel<UnitList>, dim3(S, B), dim3(256), 0, st, vt, UnitList{ids, b0}, (int)chunk, scratch);
+        hipLaunchKernelGGL(bbox_finalize_multi_kernel<UnitList>, dim3((B + 63) / 64), dim3(64), 0, st, scratch, vt, UnitList{ids, b0}, B, yxhw);
+        return;
+    }
+    hipLaunchKernelGGL(bbox_scan_multi_kernel<UnitRange>, dim3(S, B), dim3(256), 0, st, vt, UnitRange{b0}, (int)chunk, scratch);
+    hipLaunchKernelGGL(bbox_finalize_multi_kernel<UnitRange>, dim3((B + 63) / 64), dim3(64), 0, st, scratch, vt, UnitRange{b0}, B, yxhw);
 }
 
 // One unit's ROI_R output rows: the body of roi_sample_kernel (U8 = false) / roi_sample_u8_kernel (U8 = true) behind their pointer
@@ -611,17 +641,26 @@ __device__ __forceinline__ void roi_unit_rows(const void* __restrict__ frame, co
 
 // roi_sample_kernel / roi_sample_u8_kernel over the units [b0, b0 + B) of a video table: grid B * 256 / ROI_R, block 256, thread j =
 // output column j of ROI_R rows of one unit.  The workgroup resolves its unit's video once (uniform), then runs that video's sampler.
-template <typename T>
-__global__ __launch_bounds__(256) void roi_sample_multi_kernel(const VideoTable vt, const float* __restrict__ yxhw, int b0, RoiNorm nrm,
+template <typename T, typename Units>
+__global__ __launch_bounds__(256) void roi_sample_multi_kernel(const VideoTable vt, const float* __restrict__ yxhw, Units un, RoiNorm nrm,
                                                                T* __restrict__ roi) {
     constexpr int GPS = 256 / ROI_R;
     const int b = blockIdx.x / GPS, i0 = (blockIdx.x % GPS) * ROI_R, j = threadIdx.x;
-    const int u = b0 + b, vi = video_of_unit(vt, u);
+    const int u = un.at(b);
+    T* dst = roi + (((size_t)b * 256 + i0) * 256 + j) * 4;
+    if (!un.valid(u, vt.units)) {                                  // (uniform) a zero tile
+        for (int r = 0; r < ROI_R; ++r) {
+            T* d0 = dst + (size_t)r * 256 * 4;
+            if constexpr (sizeof(T) == 4) *reinterpret_cast<float4*>(d0) = make_float4(0.f, 0.f, 0.f, 0.f);
+            else *reinterpret_cast<uint2*>(d0) = make_uint2(0u, 0u);
+        }
+        return;
+    }
+    const int vi = video_of_unit(vt, u);
     const VideoDesc& d = vt.v[vi];
     const int H = d.H, W = d.W, nf = d.n_frames;
     const int lu = u - vt.first[vi], fr = lu % nf;
     const float* srcp = d.masks + (size_t)(lu / nf) * d.stride_obj + (size_t)fr * d.stride_frame;
-    T* dst = roi + (((size_t)b * 256 + i0) * 256 + j) * 4;
     if (d.u8) {
         const uint8_t* srcf = static_cast<const uint8_t*>(d.frames) + (size_t)fr * H * W * 4;
         roi_unit_rows<T, true>(srcf, srcp, yxhw + b * 4, H, W, nrm, i0, j, dst);
@@ -631,12 +670,22 @@ __global__ __launch_bounds__(256) void roi_sample_multi_kernel(const VideoTable 
     }
 }
 
-void launch_roi_sample_multi(const VideoTable& vt, const float* yxhw, int b0, int B, int dtype, const RoiNorm& nrm, void* roi, hipStream_t st) {
+void launch_roi_sample_multi(const VideoTable& vt, const float* yxhw, int b0, int B, int dtype, const RoiNorm& nrm, void* roi, hipStream_t st,
+                             const int32_t* ids) {
     const dim3 grid(B * (256 / ROI_R)), block(256);
+    if (ids) {
+        const UnitList un{ids, b0};
+        if (dtype != IVOSW_BF16)
+            hipLaunchKernelGGL((roi_sample_multi_kernel<float, UnitList>), grid, block, 0, st, vt, yxhw, un, nrm, static_cast<float*>(roi));
+        else
+            hipLaunchKernelGGL((roi_sample_multi_kernel<bf16_t, UnitList>), grid, block, 0, st, vt, yxhw, un, nrm, static_cast<bf16_t*>(roi));
+        return;
+    }
+    const UnitRange un{b0};
     if (dtype != IVOSW_BF16)
-        hipLaunchKernelGGL(roi_sample_multi_kernel<float>, grid, block, 0, st, vt, yxhw, b0, nrm, static_cast<float*>(roi));
+        hipLaunchKernelGGL((roi_sample_multi_kernel<float, UnitRange>), grid, block, 0, st, vt, yxhw, un, nrm, static_cast<float*>(roi));
     else
-        hipLaunchKernelGGL(roi_sample_multi_kernel<bf16_t>, grid, block, 0, st, vt, yxhw, b0, nrm, static_cast<bf16_t*>(roi));
+        hipLaunchKernelGGL((roi_sample_multi_kernel<bf16_t, UnitRange>), grid, block, 0, st, vt, yxhw, un, nrm, static_cast<bf16_t*>(roi));
 }
 
 static void set_video_error(const char* who, int i, const char* msg) { set_error("%s: video %d: %s", who, i, msg); }
@@ -677,6 +726,113 @@ int video_table_build(const ivosw_video_t* videos, int n_videos, const char* who
     t.units = (int)units;
     if (out) *out = t;
     return IVOSW_OK;
+}
+
+
+// ---------------------------------------------------------------- which units changed (incremental assessment)
+// The session's copy of the planes it was last scored on against the planes of now: a pure streaming pass, two 16-byte loads per lane
+// and a store only where the bit patterns differ (per 16-byte vector when any lane differs; per element on the scalar path), so a session
+// whose masks did not change writes nothing.  Bytes per unit: 2 x 4 x H x W read (4 x H x W when the video is cold: the cache is not
+// looked at), up to 4 x H x W written.  cache[v] is dense [n_obj][n_frames][H*W] in unit order.  The pointers travel in the kernel
+// arguments like the table.
+struct DeltaArgs {
+    float* cache[IVOSW_MAX_VIDEOS];
+    int cold[IVOSW_MAX_VIDEOS];
+    int vec[IVOSW_MAX_VIDEOS];           // 16-byte path: the video's vec_ok and a 16-byte aligned cache
+};
+constexpr int DELTA_CHUNK = 8192;        // elements of a plane per workgroup: two rounds of four 16-byte loads per lane and side
+
+__global__ void delta_init_kernel(int32_t* __restrict__ flags, int n) {
+    const int u = blockIdx.x * blockDim.x + threadIdx.x;
+    if (u < n) flags[u] = 0;
+}
+
+__device__ __forceinline__ bool differs(const uint4& a, const uint4& b) { return ((a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w)) != 0u; }
+
+// grid units * S (S = slices of the largest plane), block 256: workgroup (u, s) compares elements [s * DELTA_CHUNK, (s + 1) * DELTA_CHUNK)
+// of unit u's plane.  A workgroup whose slice lies behind its own video's plane leaves before the barrier (uniform).  Every workgroup that
+// finds a difference stores the same 1 into flags[u]: no atomics.
+__global__ __launch_bounds__(256) void mask_delta_kernel(const VideoTable vt, const DeltaArgs da, int S, int32_t* __restrict__ flags) {
+    const int u = blockIdx.x / S, s = blockIdx.x % S;
+    const int vi = video_of_unit(vt, u);
+    const VideoDesc& d = vt.v[vi];
+    const size_t plane = (size_t)d.H * d.W;
+    const size_t beg = (size_t)s * DELTA_CHUNK;
+    if (beg >= plane) return;
+    const size_t end = min(plane, beg + (size_t)DELTA_CHUNK);
+    const int lu = u - vt.first[vi], nf = d.n_frames;
+    const uint32_t* p = reinterpret_cast<const uint32_t*>(d.masks + (size_t)(lu / nf) * d.stride_obj + (size_t)(lu % nf) * d.stride_frame);
+    uint32_t* c = reinterpret_cast<uint32_t*>(da.cache[vi]) + (size_t)lu * plane;
+    const bool cold = da.cold[vi] != 0;
+    int dirty = cold ? 1 : 0;
+    if (da.vec[vi]) {                     // plane % 4 == 0: end is a multiple of 4 and every vector lies inside the plane
+        size_t i = beg + (size_t)threadIdx.x * 4;
+        if (cold) {
+            for (; i < end; i += 1024) *reinterpret_cast<uint4*>(c + i) = *reinterpret_cast<const uint4*>(p + i);
+        } else {
+            for (; i + 3 * 1024 < end; i += 4 * 1024) {            // eight 16-byte loads in flight per lane
+                uint4 a[4], b[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) a[k] = *reinterpret_cast<const uint4*>(p + i + k * 1024);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) b[k] = *reinterpret_cast<const uint4*>(c + i + k * 1024);
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (differs(a[k], b[k])) { *reinterpret_cast<uint4*>(c + i + k * 1024) = a[k]; dirty = 1; }
+            }
+            for (; i < end; i += 1024) {
+                const uint4 a = *reinterpret_cast<const uint4*>(p + i), b = *reinterpret_cast<const uint4*>(c + i);
+                if (differs(a, b)) { *reinterpret_cast<uint4*>(c + i) = a; dirty = 1; }
+            }
+        }
+    } else {
+        for (size_t i = beg + threadIdx.x; i < end; i += 256) {
+            const uint32_t a = p[i];
+            if (cold || a != c[i]) { c[i] = a; dirty = 1; }
+        }
+    }
+    if (__syncthreads_or(dirty) && threadIdx.x == 0) flags[u] = 1;
+}
+
+// flags [n] -> the set entries' indices in ascending order, and their number: one workgroup walks the flags 1024 at a time, a ballot gives
+// every wave its count and every lane its rank inside the wave, the 16 wave counts are summed through LDS.
+__global__ __launch_bounds__(1024) void delta_compact_kernel(const int32_t* __restrict__ flags, int n, int32_t* __restrict__ ids,
+                                                             int32_t* __restrict__ n_out) {
+    __shared__ int wsum[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int total = 0;
+    for (int base = 0; base < n; base += 1024) {
+        const int u = base + (int)threadIdx.x;
+        const bool f = u < n && flags[u] != 0;
+        const unsigned long long m = __ballot(f);
+        const int rank = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wsum[wave] = __popcll(m);
+        __syncthreads();
+        int before = 0, all = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) {
+            const int c = wsum[w];
+            before += w < wave ? c : 0;
+            all += c;
+        }
+        if (f) ids[total + before + rank] = u;
+        total += all;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *n_out = total;
+}
+
+// scores[ids[i]] = compact[i]: the last launch of a forward over a unit list.  An id outside [0, units) is dropped.
+__global__ void scatter_units_kernel(const float* __restrict__ compact, const int32_t* __restrict__ ids, int n, int units,
+                                     float* __restrict__ scores) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int u = ids[i];
+    if ((unsigned)u < (unsigned)units) scores[u] = compact[i];
+}
+
+void launch_scatter_units(const float* compact, const int32_t* ids, int n, int units, float* scores, hipStream_t st) {
+    hipLaunchKernelGGL(scatter_units_kernel, dim3((n + 255) / 256), dim3(256), 0, st, compact, ids, n, units, scores);
 }
 
 }  // namespace ivosw
@@ -763,6 +919,69 @@ extern "C" int ivosw_roi_sample_videos(const ivosw_video_t* videos, int n_videos
     IVOSW_ON_DEVICE_OF(roi);
     RoiNorm nrm{{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}, nullptr};  // Encoder.mean/std (assessment.py:41-44)
     launch_roi_sample_multi(vt, yxhw, 0, vt.units, dtype, nrm, roi, as_stream(stream));
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_mask_delta_videos(const ivosw_video_t* videos, int n_videos, float* const* cache, const int* cold, int32_t* flags,
+                                       int32_t* unit_ids, int32_t* n_dirty, ivosw_stream_t stream) {
+    VideoTable vt;
+    if (const int rc = video_table_build(videos, n_videos, __func__, &vt)) return rc;
+    IVOSW_REQUIRE(cache && cold && flags && unit_ids && n_dirty, "null pointer");
+    DeltaArgs da{};
+    size_t plane = 0;
+    for (int i = 0; i < vt.n; ++i) {
+        if (!cache[i]) { set_video_error(__func__, i, "null pointer (cache)"); return IVOSW_ERR_ARG; }
+        if (reinterpret_cast<uintptr_t>(cache[i]) & 3) { set_video_error(__func__, i, "cache must be 4-byte aligned"); return IVOSW_ERR_ARG; }
+        da.cache[i] = cache[i];
+        da.cold[i] = cold[i] != 0;
+        da.vec[i] = vt.v[i].vec_ok && (reinterpret_cast<uintptr_t>(cache[i]) & 15) == 0;
+        plane = std::max(plane, (size_t)vt.v[i].H * vt.v[i].W);
+    }
+    IVOSW_ON_DEVICE_OF(flags);
+    const int S = (int)((plane + DELTA_CHUNK - 1) / DELTA_CHUNK);
+    IVOSW_REQUIRE((long)vt.units * S <= INT_MAX, "too many (unit, plane slice) workgroups for one launch");
+    hipStream_t st = as_stream(stream);
+    hipLaunchKernelGGL(delta_init_kernel, dim3((vt.units + 255) / 256), dim3(256), 0, st, flags, vt.units);
+    hipLaunchKernelGGL(mask_delta_kernel, dim3((unsigned)(vt.units * S)), dim3(256), 0, st, vt, da, S, flags);
+    hipLaunchKernelGGL(delta_compact_kernel, dim3(1), dim3(1024), 0, st, flags, vt.units, unit_ids, n_dirty);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+// what the *_units entries refuse about their list, before any launch
+static int unit_list_check(const char* who, const VideoTable& vt, const int32_t* unit_ids, int n_ids) {
+    if (n_ids < 0) { set_error("%s: n_ids = %d is negative", who, n_ids); return IVOSW_ERR_ARG; }
+    if (n_ids > vt.units) { set_error("%s: n_ids = %d is above the table's %d units", who, n_ids, vt.units); return IVOSW_ERR_ARG; }
+    if (n_ids > 0 && !unit_ids) { set_error("%s: null pointer (unit_ids)", who); return IVOSW_ERR_ARG; }
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_mask_bbox_units(const ivosw_video_t* videos, int n_videos, const int32_t* unit_ids, int n_ids, float* yxhw,
+                                     int32_t* scratch, ivosw_stream_t stream) {
+    VideoTable vt;
+    if (const int rc = video_table_build(videos, n_videos, __func__, &vt)) return rc;
+    if (const int rc = unit_list_check(__func__, vt, unit_ids, n_ids)) return rc;
+    if (n_ids == 0) return IVOSW_OK;
+    IVOSW_REQUIRE(yxhw && scratch, "null pointer");
+    IVOSW_ON_DEVICE_OF(yxhw);
+    launch_mask_bbox_multi(vt, 0, n_ids, yxhw, scratch, as_stream(stream), unit_ids);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_roi_sample_units(const ivosw_video_t* videos, int n_videos, const int32_t* unit_ids, int n_ids, const float* yxhw,
+                                      int dtype, void* roi, ivosw_stream_t stream) {
+    VideoTable vt;
+    if (const int rc = video_table_build(videos, n_videos, __func__, &vt)) return rc;
+    if (const int rc = unit_list_check(__func__, vt, unit_ids, n_ids)) return rc;
+    IVOSW_REQUIRE(dtype == IVOSW_F32 || dtype == IVOSW_BF16 || dtype == IVOSW_F32X3, "dtype must be IVOSW_F32, IVOSW_BF16 or IVOSW_F32X3");
+    if (n_ids == 0) return IVOSW_OK;
+    IVOSW_REQUIRE(yxhw && roi, "null pointer");
+    IVOSW_REQUIRE(n_ids <= (1 << 24), "batch too large (n_ids <= 2^24)");
+    IVOSW_ON_DEVICE_OF(roi);
+    RoiNorm nrm{{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}, nullptr};  // Encoder.mean/std (assessment.py:41-44)
+    launch_roi_sample_multi(vt, yxhw, 0, n_ids, dtype, nrm, roi, as_stream(stream), unit_ids);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }

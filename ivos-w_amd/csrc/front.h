@@ -41,8 +41,12 @@ struct VideoTable {
 };
 // Validates the caller's array (every refusal of include/ivosw.h, the message names the video) and fills the table.
 int video_table_build(const ivosw_video_t* videos, int n_videos, const char* who, VideoTable* out);
-void launch_mask_bbox_multi(const VideoTable& vt, int b0, int B, float* yxhw, int32_t* scratch, hipStream_t st);
-void launch_roi_sample_multi(const VideoTable& vt, const float* yxhw, int b0, int B, int dtype, const RoiNorm& nrm, void* roi, hipStream_t st);
+// ids != NULL: rows [b0, b0 + B) of a unit list (a device array) instead of the units [b0, b0 + B): row b works on unit ids[b0 + b]
+void launch_mask_bbox_multi(const VideoTable& vt, int b0, int B, float* yxhw, int32_t* scratch, hipStream_t st, const int32_t* ids = nullptr);
+void launch_roi_sample_multi(const VideoTable& vt, const float* yxhw, int b0, int B, int dtype, const RoiNorm& nrm, void* roi, hipStream_t st,
+                             const int32_t* ids = nullptr);
+// scores[ids[i]] = compact[i], i < n (ids outside [0, units) are dropped)
+void launch_scatter_units(const float* compact, const int32_t* ids, int n, int units, float* scores, hipStream_t st);
 void launch_mask_bbox(const float* tp, int b0, int B, int H, int W, const SampleMap& sm, float* yxhw, int32_t* scratch, hipStream_t st);
 void launch_roi_sample(const FrameSrc& fs, const float* tp, const float* yxhw, int b0, int B, int H, int W, int dtype,
                        const SampleMap& sm, const RoiNorm& nrm, void* roi, hipStream_t st);

@@ -59,6 +59,9 @@ DEFAULTS = dict(
     frames="float32",                  # how the assessment path holds a video: "float32" [n,3,H,W] in 0..1 (the reference's all_F), or "uint8":
                                        # the decoded bytes packed as RGBX8 on the device (a quarter of the memory and of the upload; same scores
                                        # on the real stack, whose floats are bytes / 255)
+    rescore="all",                     # the assessment pass of an interaction scores "all" (frame, object) units, or only the "changed" ones:
+                                       # the device compares every mask plane with the session's copy of the planes it was last scored on and
+                                       # the tower sees the units that differ (same scores; utils_agent.score_cache holds the copies)
     report_save_dir="results",
     eval_max_nb_interactions=8,        # the eval scripts fix 8 interactions on the val subset (eval_agent_manet.py:64-65)
     data=dict(num_workers=0, root_dir_davis="data/DAVIS", root_dir_scribble_youtube_vos="data/Scribble_Youtube_VOS",
@@ -93,6 +96,12 @@ def frames_option(cfg):
     if not isinstance(mode, str) or mode not in FRAME_MODES:
         raise ValueError(f"frames must be 'float32' or 'uint8', got {mode!r}")
     return mode
+
+
+def rescore_option(cfg):
+    """cfg.rescore (absent: "all"), refused unless it is "all" or "changed" (utils_agent.RESCORE_MODES)."""
+    from .utils import utils_agent
+    return utils_agent.rescore_option(cfg)
 
 
 def _coerce(text):
@@ -134,6 +143,7 @@ def parse_cli(argv, **overrides):
         node[parts[-1]] = _coerce(val)
     try:
         frames_option(cfg)
+        rescore_option(cfg)
     except ValueError as e:
         raise SystemExit(f"[ivos-w] {e}")
     return _attr(cfg)
@@ -353,12 +363,22 @@ def _segment(vos, davis, seq, n_objects, annotated, store):
     return store.labels_u8, store.all_P
 
 
+def _print_rescored(rescore, needs_assess):
+    """rescore=changed only: the share of (frame, object) units the assessment passes of the run scored again."""
+    if rescore != "changed" or not needs_assess:
+        return
+    from .utils import utils_agent
+    units, again = utils_agent.score_cache.stats()
+    print(f"# rescore: changed  rescored {again} of {units} units ({100.0 * again / max(units, 1):.1f} %)")
+
+
 # ------------------------------------------------------------------------------------------ eval_agent_*  (synthetic back end)
 def run_eval(cfg, backbone="MANet"):
     """The loop of eval_agent_manet.py:246-480 on the synthetic back end.  Writes <report_save_dir>/summary.json =
     {"auc", "curve": {metric: [...]}} like the reference and returns it."""
     from .utils import misc, utils_agent, utils_manet
     frames = frames_option(cfg)                                        # (a bad value is refused here, before anything runs)
+    rescore = rescore_option(cfg)
     cfg.phase = "eval"
     cfg.data.subset = "val"
     if not torch.cuda.is_available():
@@ -424,6 +444,7 @@ def run_eval(cfg, backbone="MANet"):
         json.dump(summary, fp)
     print(f"# global_summary: auc:{auc * 100:.4f}  recommend_frame avg {rec_time.avg * 1e3:.2f} ms  frame-cache uploads "
           f"{utils_agent.frame_cache.uploads}  frames: {frames}\n# {metric}: " + " ".join(f"{v * 100:.2f}" for v in curve))
+    _print_rescored(rescore, needs_assess)
     summary["backend"] = "synthetic"
     summary["frames"] = frames
     summary["report_dir"] = report_dir
@@ -446,6 +467,7 @@ def run_eval_real(cfg, backbone, device):
     from .utils import misc, utils_agent
     adapter_mod = importlib.import_module(adapter_module_name(backbone, cfg))
     frames = frames_option(cfg)
+    rescore = rescore_option(cfg)
     misc.set_random_seed(int(cfg.seed))
     root = cfg.data.root_dir_davis
     needs_assess = cfg.setting == "wild" and cfg.method in ("ours", "worst")
@@ -524,6 +546,7 @@ def run_eval_real(cfg, backbone, device):
         json.dump(summary, fp)
     print(f"# final avg {metric}: {final_q.avg:.4f}  final avg corr: {corr_all.avg:.4f}\n# global_summary: auc:{auc * 100:.4f}  frames: {frames}\n"
           f"# {metric}: " + " ".join(f"{v * 100:.2f}" for v in curve))
+    _print_rescored(rescore, needs_assess)
     summary["backend"] = "real"
     summary["frames"] = frames
     summary["report_dir"] = report_dir

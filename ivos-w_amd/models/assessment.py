@@ -141,6 +141,61 @@ def pack_frames(u8, device, layout="hwc"):
     return PackedFrames(rgbx)
 
 
+class ScoreCache:
+    """What one video's session keeps between interactions for the incremental forward (``AssessNet.forward_videos_incremental``): the
+    planes it was last scored on (``planes``: dense [n_obj, n_frames, H*W] fp32 on the device, unit order), the score table
+    (``scores`` [n_obj, n_frames]) and a key - the identity of the frames object (held by a STRONG reference, as utils_agent._FrameCache
+    holds its host tensor, so the allocator cannot hand its address to another video while the entry lives), n_frames, n_obj, H, W, and
+    the net's precision and ``_weights_key()``.  Any mismatch makes the cache cold: every unit is scored again.  The key guards what the
+    device comparison cannot see (other frames, other weights); the masks are compared bit for bit against whatever planes the cache
+    holds, so a wrong guess about "same session" costs time, never results.  Frames rewritten in place behind an unchanged tensor
+    object (through numpy, or .data) are not seen: drop the cache then (``utils_agent.clear_score_cache``).
+    ``units`` / ``rescored``: the video's units and how many of them the last call scored again."""
+
+    def __init__(self):
+        self.planes, self.scores, self.key, self.src = None, None, None, None
+        self.units, self._rescored = 0, 0
+
+    @staticmethod
+    def make_key(net, frames, n_frames, n_obj, H, W):
+        """(key, src): src is the object whose identity stands for the frames."""
+        src = frames
+        t = frames.rgbx if isinstance(frames, PackedFrames) else frames
+        ident = (t.data_ptr(), t._version) if isinstance(t, torch.Tensor) else ()
+        return (id(src), ident, int(n_frames), int(n_obj), int(H), int(W), net.precision, net._weights_key()), src
+
+    @staticmethod
+    def nbytes_for(n_frames, n_obj, H, W):
+        return 4 * int(n_frames) * int(n_obj) * (int(H) * int(W) + 1)
+
+    @property
+    def nbytes(self):
+        return 0 if self.key is None else self.nbytes_for(*self.key[2:6])
+
+    @property
+    def rescored(self):
+        if isinstance(self._rescored, torch.Tensor):                # a multi-video call: counted on the device, fetched when asked for
+            self._rescored = int(self._rescored.item())
+        return self._rescored
+
+    def bind(self, net, frames, n_frames, n_obj, H, W, device):
+        """Make the cache one for this video; returns True when it is cold (its planes and scores are undefined)."""
+        key, src = self.make_key(net, frames, n_frames, n_obj, H, W)
+        device = torch.device(device)
+        warm = (self.key == key and self.src is src and self.planes is not None and self.planes.device == device)
+        if not warm:
+            if self.planes is None or self.planes.device != device or self.planes.numel() != n_obj * n_frames * H * W:
+                self.planes = torch.empty(n_obj * n_frames * H * W, dtype=torch.float32, device=device)
+            self.scores = torch.empty(n_obj, n_frames, dtype=torch.float32, device=device)
+            self.key, self.src = key, src
+        self.units = n_obj * n_frames
+        return not warm
+
+    def clear(self):
+        self.planes, self.scores, self.key, self.src = None, None, None, None
+        self.units, self._rescored = 0, 0
+
+
 class AssessNet(nn.Module):
     def __init__(self, precision="fp32", chunk=0):
         super().__init__()
@@ -338,6 +393,69 @@ class AssessNet(nn.Module):
             out = scores[off:off + units]
             L.check(lib.ivosw_assess_forward_videos(L.dptr(packed), dt, arr, len(group), L.dptr(out), L.dptr(ws), nbytes, self.chunk,
                                                     0, None, L.stream_ptr(dev)), "assess_forward_videos")
+            off += units
+        views, off = [], 0
+        for o, n in shapes:
+            views.append(scores[off:off + o * n].view(o, n))
+            off += o * n
+        return views
+
+    def forward_videos_incremental(self, videos, caches, sources=None):
+        """``forward_videos`` that scores only the units whose mask planes changed since ``caches`` were last scored: ``caches`` holds one
+        ``ScoreCache`` per video (distinct objects), ``sources`` optionally the object whose identity stands for each video's frames in
+        the cache key (default: the all_F given; a caller that uploads a host video per call names the host tensor here).  Per group of
+        up to 32 videos: ivosw_mask_delta_videos compares every plane with the cached one on the device and updates the cache, ONE
+        4-byte device-to-host copy brings the number of dirty units - the one synchronisation this path adds to ``forward_videos`` -
+        and ivosw_assess_forward_units scores those units into the full table.  Returns what ``forward_videos`` returns, bit for bit: one
+        [n_objects, n] view per video of one flat score tensor in unit order.  ``cache.units`` / ``cache.rescored`` tell what the call
+        did per video.  The masks may be rewritten in place between calls (ProbStore): the comparison is against the cache's own copy."""
+        if self.training:
+            raise RuntimeError("AssessNet on the MI355X path is inference-only; call .eval()")
+        videos, caches = list(videos), list(caches)
+        if len(videos) != len(caches) or len({id(c) for c in caches}) != len(caches):
+            raise ValueError("forward_videos_incremental takes one distinct ScoreCache per video")
+        sources = [v[0] for v in videos] if sources is None else list(sources)
+        if not videos:
+            return []
+        keep, descs, shapes = [], [], []
+        for k, video in enumerate(videos):
+            d, n = self._video_entry(k, video, keep)
+            descs.append(d)
+            shapes.append((d.n_obj, n))
+        dev = keep[0].device
+        packed = self._ensure_packed()
+        lib, dt, st = L.lib(), _DTYPES[self.precision], L.stream_ptr(dev)
+        scores = torch.empty(sum(o * n for o, n in shapes), dtype=torch.float32, device=dev)
+        off = 0
+        for g in range(0, len(descs), L.MAX_VIDEOS):
+            group, gc = descs[g:g + L.MAX_VIDEOS], caches[g:g + L.MAX_VIDEOS]
+            arr = (L.Video * len(group))(*group)
+            units = int(lib.ivosw_assess_videos_units(arr, len(group)))
+            if units < 0:
+                L.check(units, "assess_videos_units")
+            out = scores[off:off + units]
+            cold, o = [], 0
+            for d, c, src in zip(group, gc, sources[g:g + L.MAX_VIDEOS]):
+                cold.append(c.bind(self, src, d.n_frames, d.n_obj, d.H, d.W, dev))
+                if not cold[-1]:
+                    out[o:o + c.units].copy_(c.scores.view(-1))      # the table of the last call; the dirty entries are overwritten below
+                o += c.units
+            ptrs = (ctypes.c_void_p * len(group))(*[c.planes.data_ptr() for c in gc])
+            meta = torch.empty(2 * units + 1, dtype=torch.int32, device=dev)       # [flags (units) | unit ids (units) | n_dirty]
+            flags, ids, n_dirty = meta[:units], meta[units:2 * units], meta[2 * units:]
+            L.check(lib.ivosw_mask_delta_videos(arr, len(group), ptrs, L.int_array(cold), L.dptr(flags), L.dptr(ids), L.dptr(n_dirty), st),
+                    "mask_delta_videos")
+            n_ids = int(n_dirty.item())                                 # the one synchronisation of the incremental path
+            if n_ids:
+                nbytes = lib.ivosw_assess_units_ws_bytes(dt, n_ids, self.chunk)
+                ws = self._ws.get(nbytes, dev)
+                L.check(lib.ivosw_assess_forward_units(L.dptr(packed), dt, arr, len(group), L.dptr(ids), n_ids, L.dptr(out), L.dptr(ws),
+                                                       nbytes, self.chunk, st), "assess_forward_units")
+            o = 0
+            for c, was_cold in zip(gc, cold):
+                c.scores.view(-1).copy_(out[o:o + c.units])
+                c._rescored = n_ids if len(gc) == 1 else c.units if was_cold else flags[o:o + c.units].sum()
+                o += c.units
             off += units
         views, off = [], 0
         for o, n in shapes:

@@ -161,21 +161,132 @@ def clear_frame_cache():
     frame_cache.clear()
 
 
-def assess_all_objects_device(assess_net, all_F, all_P, n_objects, device):
+RESCORE_MODES = ("all", "changed")
+# score_cache keeps the sessions' plane copies and score tables up to this many bytes (least recently used first out).  One 100-frame,
+# 3-object 480p session costs 0.49 GB (300 planes of 480 x 854 fp32).
+SCORE_CACHE_BYTES = 8 << 30
+
+
+def rescore_option(cfg):
+    """cfg.rescore (absent: "all"), refused unless it is one of RESCORE_MODES.  "changed": the assessment pass scores only the (frame,
+    object) units whose masks changed since the session was last scored (AssessNet.forward_videos_incremental); same results."""
+    mode = (cfg.get("rescore", "all") if hasattr(cfg, "get") else getattr(cfg, "rescore", "all")) if cfg is not None else "all"
+    if not isinstance(mode, str) or mode not in RESCORE_MODES:
+        raise ValueError(f"rescore must be 'all' or 'changed', got {mode!r}")
+    return mode
+
+
+def _video_dims(all_F):
+    """(n_frames, H, W) of a float all_F or a PackedFrames."""
+    if _is_packed(all_F):
+        return all_F.n, all_F.H, all_F.W
+    return int(all_F.shape[0]), int(all_F.shape[2]), int(all_F.shape[3])
+
+
+class _ScoreCacheLRU:
+    """The sessions' ScoreCaches under rescore=changed, least recently used first out, bounded by SCORE_CACHE_BYTES.  Keyed like a
+    ScoreCache - the frames object's identity (the entry's ScoreCache holds the strong reference once it was used), n_frames, n_obj, H,
+    W, the net's precision and weights key - plus the video's rank among the videos of one call that share that key (two requests on one
+    frames object get a cache each; which one a request meets decides how much is scored again, never what comes out).
+    ``units`` / ``rescored``: totals over all calls (``stats()`` brings them up to date)."""
+
+    def __init__(self):
+        from collections import OrderedDict
+        self.entries = OrderedDict()
+        self.units, self._rescored, self._pending = 0, 0, []
+
+    def get_many(self, assess_net, videos):
+        """One ScoreCache per (all_F, all_P, n_objects) of a call, made on first sight; the ones handed out become the most recent."""
+        from ..models.assessment import ScoreCache
+        out, seen = [], {}
+        for all_F, _, n_objects in videos:
+            n, H, W = _video_dims(all_F)
+            key, _ = ScoreCache.make_key(assess_net, all_F, n, int(n_objects), H, W)
+            rank = seen[key] = seen.get(key, -1) + 1
+            entry = self.entries.get((key, rank))
+            if entry is None or (entry[0].src is not None and entry[0].src is not all_F):
+                entry = (ScoreCache(), ScoreCache.nbytes_for(n, int(n_objects), H, W))
+            self.entries[(key, rank)] = entry
+            self.entries.move_to_end((key, rank))
+            out.append(entry[0])
+        return out
+
+    def nbytes(self):
+        return sum(b for _, b in self.entries.values())
+
+    def trim(self, limit=None):
+        """Evict least recently used entries until the rest fits `limit` bytes (default SCORE_CACHE_BYTES)."""
+        limit = SCORE_CACHE_BYTES if limit is None else limit
+        while self.entries and self.nbytes() > limit:
+            _, (cache, _) = self.entries.popitem(last=False)
+            cache.clear()
+
+    def account(self, caches):
+        for c in caches:
+            self.units += c.units
+            if isinstance(c._rescored, torch.Tensor):
+                self._pending.append(c._rescored)            # counted on the device: fetched by stats(), not here (no extra sync)
+            else:
+                self._rescored += c._rescored
+        if len(self._pending) > 256:
+            self._pending = [torch.stack(self._pending).sum()]
+        self.trim()
+
+    def stats(self):
+        """(units seen, units scored again) over all calls so far."""
+        for t in self._pending:
+            self._rescored += int(t.item())
+        self._pending = []
+        return self.units, self._rescored
+
+    @property
+    def rescored(self):
+        return self.stats()[1]
+
+    def clear(self):
+        for cache, _ in self.entries.values():
+            cache.clear()
+        self.entries.clear()
+        self.units, self._rescored, self._pending = 0, 0, []
+
+
+score_cache = _ScoreCacheLRU()
+
+
+def clear_score_cache():
+    """Drop every cached score table and plane copy (rescore=changed).  Call when a video's frames are rewritten IN PLACE behind an
+    unchanged tensor object - through numpy or .data, which do not bump the tensor version the key watches: the masks are compared on the
+    device on every call, the frames are not.  (The same caveat as clear_frame_cache.)"""
+    score_cache.clear()
+
+
+def _forward_changed(assess_net, on_dev, sources):
+    """forward_videos through the score caches: on_dev = the device-resident (frames, probs, n_objects), sources = the callers' all_F."""
+    caches = score_cache.get_many(assess_net, [(src, None, v[2]) for src, v in zip(sources, on_dev)])
+    out = assess_net.forward_videos_incremental(on_dev, caches, sources=sources)
+    score_cache.account(caches)
+    return out
+
+
+def assess_all_objects_device(assess_net, all_F, all_P, n_objects, device, rescore="all"):
     """[n_objects, n_frame] quality predictions ON the device from one launch sequence: every object's masks are read in
     place from all_P (channel i+1 = object i) and all objects share one device copy of the frames (frame-index
-    indirection inside ivosw_assess_forward_objects) - nothing is repeated, transposed or copied."""
+    indirection inside ivosw_assess_forward_objects) - nothing is repeated, transposed or copied.
+    rescore="changed": only the units whose masks changed since this video was last scored are scored again (score_cache); same values."""
     frames = frame_cache.get(all_F, device)
     probs = all_P if (all_P.is_cuda and all_P.device == torch.device(device)) else all_P.to(device)
+    if rescore == "changed":
+        return _forward_changed(assess_net, [(frames, probs, n_objects)], [all_F])[0]
     return assess_net.forward_objects(frames, probs, n_objects)
 
 
-def assess_all_objects(assess_net, all_F, all_P, n_objects, device):
+def assess_all_objects(assess_net, all_F, all_P, n_objects, device, rescore="all"):
     """[n_frame, n_objects] quality predictions as a host array (one small D2H copy)."""
-    return assess_all_objects_device(assess_net, all_F, all_P, n_objects, device).transpose(0, 1).cpu().numpy()
+    return assess_all_objects_device(assess_net, all_F, all_P, n_objects, device, rescore).transpose(0, 1).cpu().numpy()
 
 
-def _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, counts, mask_quality, prev_frames, k=1, as_list=False):
+def _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, counts, mask_quality, prev_frames, k=1, as_list=False,
+                 rescore="all"):
     """wild/worst and wild/ours (utils/utils_agent.py:111-122) with the chain quality -> state -> Brain -> argmax on the
     device: per-object scores are averaged into mask_quality (float64, numpy's summation order) and stacked with the
     annotation counts by ivosw_quality_state, the Brain and its first-max argmax read that state in place, and ONE D2H copy
@@ -183,7 +294,7 @@ def _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, cou
     agent.skip_annotated the argmax is the masked top-k and the buffer holds k indices; `as_list`: return all candidates (an array)."""
     from .. import _lib as L
     from ..models.agent import merge_candidates
-    scores = assess_all_objects_device(assess_net, all_F, all_P, n_objects, device)
+    scores = assess_all_objects_device(assess_net, all_F, all_P, n_objects, device, rescore)
     n = scores.shape[1]
     dev = scores.device
     out = torch.empty(n + k, dtype=torch.float64, device=dev)          # [quality (n) | k recommended indices (int64 bits)]
@@ -207,20 +318,25 @@ def _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, cou
     return _candidate_list(pick, 1) if as_list else pick
 
 
-def assess_videos_device(assess_net, videos, device):
+def assess_videos_device(assess_net, videos, device, rescore="all"):
     """Quality predictions of SEVERAL videos from one assessment pass (AssessNet.forward_videos): ``videos`` is a sequence of
     (all_F | PackedFrames, all_P, n_objects); returns one [n_objects, n_frame] device tensor per video, each bit for bit what
     ``assess_all_objects_device`` gives for that video alone.  Host-resident tensors are uploaded for this call only: the single-entry
     ``frame_cache`` is neither read nor written (several videos would evict each other on every call) - multi-session callers keep
-    their videos on the device (``pack_video``, or ``all_F.to(device)`` once per sequence)."""
+    their videos on the device (``pack_video``, or ``all_F.to(device)`` once per sequence).
+    rescore="changed": only the units whose masks changed since each video was last scored are scored again (score_cache, keyed by the
+    all_F object the caller hands in); same values."""
     device = torch.device(device)
-    on_dev = []
+    on_dev, sources = [], []
     for all_F, all_P, n_objects in videos:
+        sources.append(all_F)
         if not _is_packed(all_F) and not (all_F.is_cuda and all_F.device == device):
             all_F = all_F.to(device=device, dtype=torch.float32)
         if not (all_P.is_cuda and all_P.device == device):
             all_P = all_P.to(device)
         on_dev.append((all_F, all_P, n_objects))
+    if rescore == "changed":
+        return _forward_changed(assess_net, on_dev, sources)
     return assess_net.forward_videos(on_dev)
 
 
@@ -279,7 +395,7 @@ def _recommend_many(cfg_yl, assess_net, agent, device, requests, as_list):
     method = cfg_yl.method
     K = len(requests)
     with torch.no_grad():
-        scores = assess_videos_device(assess_net, [(r["all_F"], r["all_P"], r["n_objects"]) for r in requests], device)
+        scores = assess_videos_device(assess_net, [(r["all_F"], r["all_P"], r["n_objects"]) for r in requests], device, rescore_option(cfg_yl))
         dev = scores[0].device
         ns = [int(s.shape[1]) for s in scores]
         counts = [_annotation_counts(len(r["new_masks_quality"]), r["annotated_frames_list"]) for r in requests]
@@ -361,7 +477,7 @@ def _recommend_one(cfg_yl, assess_net, agent, device, n_frame, n_objects, all_F,
             counts = _annotation_counts(len(new_masks_quality), annotated_frames_list)
             with torch.no_grad():
                 return _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, counts, mask_quality,
-                                    prev_frames, k=k, as_list=as_list)
+                                    prev_frames, k=k, as_list=as_list, rescore=rescore_option(cfg_yl))
         raise NotImplementedError
     raise NotImplementedError
 
