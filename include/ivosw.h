@@ -94,6 +94,22 @@ int ivosw_brain_argmax_ragged(const float* q, const int* lengths, int n_seqs, in
 int ivosw_brain_topk_ragged(const float* q, const float* state, const int* lengths, int n_seqs, int k, int skip_annotated,
                             int64_t* idx, float* qv, ivosw_stream_t stream);
 
+/* The same ranking with its k frames spread in time (agent.candidate_gap): Q sits on a bidirectional LSTM over the frame axis and is
+ * smooth along it, so the k strongest frames are usually one peak and its neighbours.  The frames of a sequence are walked in the total
+ * order of ivosw_brain_topk_ragged (tier, larger q, lower index) and a frame t is accepted if and only if |t - w| >= gap for every frame w
+ * accepted so far; the walk stops after k accepted frames.  gap = 1 is ivosw_brain_topk_ragged, bit for bit.  Only accepted frames
+ * suppress: annotated frames by themselves suppress nothing, and under skip_annotated the walk falls through to the annotated tier as
+ * before, under the same distance rule.  When fewer than k frames can be accepted the remaining slots are -1 (nothing suppressed comes
+ * back).  first (HOST memory, n_seqs ints, NULL = all -1): first[s] >= 0 is the forced first candidate of sequence s (the epsilon
+ * branch's random pick): it is slot 0 whatever its q or tier, counts as accepted, and the walk fills slots 1 .. k - 1.  It is read
+ * during the call and travels inside the kernel arguments, as lengths does: no allocation, no copy, no synchronisation.  idx and qv as
+ * for ivosw_brain_topk_ragged (qv: the bits of q at each slot, 0.0f at a -1 slot).  One launch, one wave per sequence, no workspace;
+ * capture-safe.  Refused (IVOSW_ERR_ARG) before anything is launched, the message names the argument: what ivosw_brain_topk_ragged
+ * refuses, gap outside [1, IVOSW_MAX_CANDIDATE_GAP], and a first[s] outside [-1, lengths[s]) (the message names s).                    */
+#define IVOSW_MAX_CANDIDATE_GAP (1 << 20)
+int ivosw_brain_topk_spread_ragged(const float* q, const float* state, const int* lengths, int n_seqs, int k, int skip_annotated, int gap,
+                                   const int* first, int64_t* idx, float* qv, ivosw_stream_t stream);
+
 /* ------------------------------------------------------------------ agent: DQN step (K8-K10) -- */
 /* Replaces the arithmetic of Agent.update_agent (models/agent.py:128-155):
  *   a* = argmax policy(s'); Qn = target(s')[a*]; y1 = gamma*Qn + 0.1*r_step; y2 = 0.1*r_done;

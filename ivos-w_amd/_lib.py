@@ -43,6 +43,7 @@ SIGNATURES = {
     "ivosw_brain_forward_ragged": (_i, [_p, _p, _p, _i, _p, _p, _sz, _p]),
     "ivosw_brain_argmax_ragged": (_i, [_p, _p, _i, _p, _p]),
     "ivosw_brain_topk_ragged": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p]),
+    "ivosw_brain_topk_spread_ragged": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p]),
     "ivosw_dqn_ws_bytes": (_sz, [_i, _i]),
     "ivosw_dqn_loss_grad": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _p, _p, _p, _sz, _p]),
     "ivosw_dqn_loss_grad_ex": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _f, _i, _f, _p, _p, _p, _sz, _p]),

@@ -1460,42 +1460,95 @@ __device__ __forceinline__ uint64_t wave_max_u64(uint64_t v) {
 // butterfly on the key): the keys are unique, so nothing is marked as taken, and there is no LDS and no atomic.  A sequence of up to
 // 64 TOPK_TRIPS frames keeps its keys in registers over the rounds (q and state are read once); a longer one rebuilds them from memory
 // every round.  Lane j keeps round j's winner; at the end the first k lanes store their slot (and fetch its q).
+//
+// SPREAD (ivosw_brain_topk_spread_ragged): the same order walked greedily, a frame accepted only if it lies `gap` or more frames from every
+// frame accepted before it.  What is accepted only ever suppresses more, so the next frame of the walk is the largest key that is not
+// suppressed yet, and a round stays one scan and one butterfly; a winner suppresses itself, so there is no bound.  In registers a
+// suppressed key is zeroed in place.  On the rescan path lane j also keeps round j's frame index (TOPK_FAR while it has none), the rounds
+// read the IVOSW_MAX_CANDIDATES lanes back with v_readlane at constant lane numbers (wave-uniform, no array that is indexed at run time)
+// and test every rebuilt key against them.  `first` >= 0 is accepted before the walk as slot 0, whatever its key.
 constexpr int TOPK_TRIPS = 4;
+constexpr int TOPK_FAR = -(1 << 22);                                        // further than any gap (at most 2^20) from every frame
+// What the spread instantiation takes besides: the gap and the forced first candidates, like the sequence table inside the kernel arguments.
+template <bool SPREAD> struct SpreadArgs {};
+template <> struct SpreadArgs<true> {
+    int gap;
+    int first[IVOSW_MAX_SEQS];
+};
+template <bool SPREAD>
 __global__ __launch_bounds__(64) void topk_ragged_kernel(const float* __restrict__ q, const float* __restrict__ state, SeqTable tab, int k,
-                                                         int skip, int64_t* __restrict__ idx, float* __restrict__ qv) {
+                                                         int skip, int64_t* __restrict__ idx, float* __restrict__ qv, SpreadArgs<SPREAD> sp) {
     const int s = blockIdx.x, lane = threadIdx.x;
     const int r0 = tab.row_off[s], T = tab.row_off[s + 1] - r0;
     const float* r = q + r0;
     const float* c = skip ? state + (size_t)r0 * 2 + 1 : nullptr;           // column 1 of the state: how often the frame was annotated
     uint64_t bound = ~0ull, mine = 0;
+    int gap = 1, first = -1, j0 = 0;
+    if constexpr (SPREAD) {
+        gap = sp.gap;
+        first = sp.first[s];
+        if (first >= 0) {                                                   // (wave-uniform) slot 0 is given
+            if (lane == 0) mine = (1ull << 53) | (uint64_t)(0xfffff - first);
+            j0 = 1;
+        }
+    }
     if (T <= 64 * TOPK_TRIPS) {
         uint64_t key[TOPK_TRIPS];
 #pragma unroll
         for (int i = 0; i < TOPK_TRIPS; ++i) {
             const int t = lane + 64 * i;
             key[i] = t < T ? topk_key(r[t], skip && c[2 * t] == 0.f, t) : 0;
+            if constexpr (SPREAD)
+                if (first >= 0 && abs(t - first) < gap) key[i] = 0;
         }
-        for (int j = 0; j < k; ++j) {
+        for (int j = j0; j < k; ++j) {
             uint64_t best = 0;
 #pragma unroll
             for (int i = 0; i < TOPK_TRIPS; ++i)
-                if (key[i] < bound && key[i] > best) best = key[i];
+                if ((SPREAD || key[i] < bound) && key[i] > best) best = key[i];
             best = wave_max_u64(best);
             if (best == 0) break;                                           // (wave-uniform) every frame is ranked: the rest stays -1
             if (lane == j) mine = best;
-            bound = best;
+            if constexpr (SPREAD) {
+                const int w = 0xfffff - (int)(best & 0xfffff);
+#pragma unroll
+                for (int i = 0; i < TOPK_TRIPS; ++i)
+                    if (abs(lane + 64 * i - w) < gap) key[i] = 0;
+            } else {
+                bound = best;
+            }
         }
     } else {
-        for (int j = 0; j < k; ++j) {
+        int taken = TOPK_FAR;                                               // SPREAD: lane j holds the frame of slot j
+        if constexpr (SPREAD)
+            if (first >= 0 && lane == 0) taken = first;
+        for (int j = j0; j < k; ++j) {
             uint64_t best = 0;
-            for (int t = lane; t < T; t += 64) {
-                const uint64_t key = topk_key(r[t], skip && c[2 * t] == 0.f, t);
-                if (key < bound && key > best) best = key;
+            if constexpr (SPREAD) {
+                int w[IVOSW_MAX_CANDIDATES];
+#pragma unroll
+                for (int a = 0; a < IVOSW_MAX_CANDIDATES; ++a) w[a] = __builtin_amdgcn_readlane(taken, a);
+                for (int t = lane; t < T; t += 64) {
+                    const uint64_t key = topk_key(r[t], skip && c[2 * t] == 0.f, t);
+                    bool open = true;
+#pragma unroll
+                    for (int a = 0; a < IVOSW_MAX_CANDIDATES; ++a) open = open && abs(t - w[a]) >= gap;
+                    if (open && key > best) best = key;
+                }
+            } else {
+                for (int t = lane; t < T; t += 64) {
+                    const uint64_t key = topk_key(r[t], skip && c[2 * t] == 0.f, t);
+                    if (key < bound && key > best) best = key;
+                }
             }
             best = wave_max_u64(best);
             if (best == 0) break;
             if (lane == j) mine = best;
-            bound = best;
+            if constexpr (SPREAD) {
+                if (lane == j) taken = 0xfffff - (int)(best & 0xfffff);
+            } else {
+                bound = best;
+            }
         }
     }
     if (lane < k) {
@@ -1518,7 +1571,41 @@ extern "C" int ivosw_brain_topk_ragged(const float* q, const float* state, const
     SeqTable tab;
     if (ragged_rows(__func__, lengths, n_seqs, &tab) < 0) return IVOSW_ERR_ARG;
     IVOSW_ON_DEVICE_OF(idx);
-    hipLaunchKernelGGL(topk_ragged_kernel, dim3(n_seqs), dim3(64), 0, as_stream(stream), q, state, tab, k, skip_annotated ? 1 : 0, idx, qv);
+    hipLaunchKernelGGL(topk_ragged_kernel<false>, dim3(n_seqs), dim3(64), 0, as_stream(stream), q, state, tab, k, skip_annotated ? 1 : 0, idx, qv,
+                       SpreadArgs<false>{});
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_brain_topk_spread_ragged(const float* q, const float* state, const int* lengths, int n_seqs, int k, int skip_annotated,
+                                              int gap, const int* first, int64_t* idx, float* qv, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(q, "q is a null pointer");
+    IVOSW_REQUIRE(lengths, "lengths is a null pointer");
+    IVOSW_REQUIRE(idx, "idx is a null pointer");
+    if (k < 1 || k > IVOSW_MAX_CANDIDATES) {
+        set_error("%s: k %d outside [1, %d]", __func__, k, IVOSW_MAX_CANDIDATES);
+        return IVOSW_ERR_ARG;
+    }
+    IVOSW_REQUIRE(!skip_annotated || state, "skip_annotated needs state, which is a null pointer");
+    if (gap < 1 || gap > IVOSW_MAX_CANDIDATE_GAP) {
+        set_error("%s: gap %d outside [1, 2^20]", __func__, gap);
+        return IVOSW_ERR_ARG;
+    }
+    SeqTable tab;
+    if (ragged_rows(__func__, lengths, n_seqs, &tab) < 0) return IVOSW_ERR_ARG;
+    SpreadArgs<true> forced;
+    forced.gap = gap;
+    for (int s = 0; s < IVOSW_MAX_SEQS; ++s) forced.first[s] = -1;
+    for (int s = 0; first && s < n_seqs; ++s) {
+        if (first[s] < -1 || first[s] >= lengths[s]) {
+            set_error("%s: first[%d] = %d outside [-1, %d), the frames of sequence %d", __func__, s, first[s], lengths[s], s);
+            return IVOSW_ERR_ARG;
+        }
+        forced.first[s] = first[s];
+    }
+    IVOSW_ON_DEVICE_OF(idx);
+    hipLaunchKernelGGL(topk_ragged_kernel<true>, dim3(n_seqs), dim3(64), 0, as_stream(stream), q, state, tab, k, skip_annotated ? 1 : 0, idx, qv,
+                       forced);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }

@@ -80,9 +80,10 @@ DEFAULTS = dict(
                target_update="coin", tau=0.005, target_period=20,
                                    # target net: "coin" (the reference's hard sync with probability update_rate per step), "soft" (Polyak
                                    # averaging with tau after every step) or "periodic" (hard sync every target_period-th step), on the device
-               candidates=1, skip_annotated=False),
+               candidates=1, skip_annotated=False, candidate_gap=1),
                                    # recommendation: how many ranked frames the agent proposes per interaction (1: the reference's argmax; up
-                                   # to 16), and whether frames that were annotated before rank behind all others (select_next_frame's rule)
+                                   # to 16), whether frames that were annotated before rank behind all others (select_next_frame's rule), and
+                                   # the least distance in frames between any two of the candidates (1: the plain ranking)
     synth=dict(n_sequences=3, n_frames=30, height=120, width=216, max_objects=3, baseline_runs=30),
 )
 

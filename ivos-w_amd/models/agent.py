@@ -15,6 +15,7 @@ arithmetic replaced by libivosw_hip.so:
   Agent.action         -> ivosw_brain_forward + ivosw_brain_argmax (first max, like numpy)
   Agent.actions        -> ivosw_brain_forward_ragged + ivosw_brain_argmax_ragged (several states of different lengths, one launch chain)
   cfg.agent.candidates / skip_annotated -> ivosw_brain_topk_ragged in the argmax's place (k ranked frames per state, annotated ones last)
+  cfg.agent.candidate_gap > 1 -> ivosw_brain_topk_spread_ragged in its place (the k frames at least that many frames apart, greedily)
 
 torch modules (nn.Linear / nn.LSTMCell) are used only as parameter containers so that ``state_dict()`` keys,
 shapes and default initialisation are the reference's; their ``forward`` is never called.  All ten tensors are
@@ -526,6 +527,24 @@ def candidates_option(candidates=1, skip_annotated=False):
     return candidates, skip_annotated
 
 
+MAX_CANDIDATE_GAP = 1 << 20                 # RAGGED_MAX_ROWS: a larger distance than any sequence is long says nothing more
+
+
+def candidate_gap_option(candidate_gap=1):
+    """gap, checked: cfg.agent.candidate_gap an int in [1, 2^20] (1: the plain ranking).  Anything else, a bool included, is a ValueError
+    that names the key."""
+    if isinstance(candidate_gap, bool) or not isinstance(candidate_gap, int) or not 1 <= candidate_gap <= MAX_CANDIDATE_GAP:
+        raise ValueError(f"agent.candidate_gap must be an int in [1, {MAX_CANDIDATE_GAP}], got {candidate_gap!r}")
+    return candidate_gap
+
+
+def spread_candidates(ranking):
+    """The candidate list of one state from a ranking that ivosw_brain_topk_spread_ragged wrote (the forced first candidate already in
+    slot 0, every slot at least the gap from the others): its -1 slots cut off, as a host np.int64 array.  Nothing is spliced in."""
+    rank = np.asarray(ranking, dtype=np.int64).reshape(-1)
+    return rank[rank >= 0]
+
+
 def merge_candidates(pick, ranking, k):
     """The candidate list of one state as a host np.int64 array: the device ranking (its -1 slots cut off), cut to k.  With a random
     pick of the epsilon branch (``pick`` not None) the pick comes first and the ranking follows with that frame removed."""
@@ -550,6 +569,7 @@ class Agent(nn.Module):
         self.per_replay = None                      # the PrioritizedReplay of the episode loop (utils_agent._device_update_loop)
         self.target_update, self.tau, self.target_period = self._target_option(a)
         self.candidates, self.skip_annotated = self._candidates_option(a)
+        self.candidate_gap = self._candidate_gap_option(a)
         self.target_steps = 0                       # steps the device rule has seen (soft / periodic); resumed by load_target_state
         self._target_dev, self._target_dev_step = None, 0
         self.EPS_START, self.EPS_END, self.EPS_DECAY = a.eps_start, a.eps_end, a.eps_decay
@@ -640,6 +660,18 @@ class Agent(nn.Module):
         state) and cfg.agent.skip_annotated (False: frames that were annotated before rank behind all others, select_next_frame's rule):
         read with .get, so a config without the keys acts as before; checked by candidates_option, before anything is allocated."""
         return candidates_option(a.get("candidates", 1), a.get("skip_annotated", False))
+
+    @staticmethod
+    def _candidate_gap_option(a):
+        """cfg.agent.candidate_gap (1, the plain ranking and the default: the least distance in frames between any two of the k candidates
+        of a state, ivosw_brain_topk_spread_ragged's greedy rule): read with .get, so a config without the key acts as before; checked
+        by candidate_gap_option, before anything is allocated.  Without effect at candidates = 1."""
+        return candidate_gap_option(a.get("candidate_gap", 1))
+
+    def _spread_gap(self, k):
+        """The gap the device ranking of k candidates runs under: 1 (the plain ranking, today's calls) unless k > 1 and a gap is set."""
+        gap = candidate_gap_option(getattr(self, "candidate_gap", 1))
+        return gap if k > 1 else 1
 
     def prioritized_replay(self, soa, device, seed):
         """A PrioritizedReplay over `soa` with this agent's PER options."""
@@ -809,7 +841,11 @@ class Agent(nn.Module):
         With agent.skip_annotated the greedy index is slot 0 of the masked ranking (``candidates_device``): same types, same host work.
         With agent.candidates = k > 1 the return is an np.int64 array of min(k, T) frames: the ranking on the greedy branch; on the epsilon
         branch the random pick, then the ranking with that frame removed (``merge_candidates``).  `device_out` is then int64 [k]: the
-        ranking is left there on either branch and the caller merges (None, or the random pick, is returned)."""
+        ranking is left there on either branch and the caller merges (None, or the random pick, is returned).
+
+        With agent.candidate_gap = g > 1 (and k > 1) the candidates are at least g frames apart (ivosw_brain_topk_spread_ragged): the random
+        pick goes to the device as the forced first candidate, so the ranking that comes back is the candidate list as it stands (its -1
+        slots cut off: it may be shorter than k) and nothing is merged, by this method or, with `device_out`, by the caller."""
         pick = self._host_pick(state, verbose)
         k, skip = candidates_option(self.candidates, self.skip_annotated)
         if pick is not None and k == 1:
@@ -821,6 +857,10 @@ class Agent(nn.Module):
                 self.greedy_index_device(st, out=device_out)
                 return None
             return np.int64(self.greedy_index_device(st).item())
+        gap = self._spread_gap(k)
+        if gap > 1:
+            rank = self.candidates_device([st], k, skip, out=device_out, gap=gap, first=[-1 if pick is None else int(pick)])
+            return pick if device_out is not None else spread_candidates(rank.cpu().numpy()[0])
         rank = self.candidates_device([st], k, skip, out=device_out)
         if device_out is not None:
             return pick
@@ -854,7 +894,8 @@ class Agent(nn.Module):
         ``action`` calls leave them.
 
         With agent.skip_annotated / agent.candidates = k the argmax is the ragged masked top-k (``candidates_device``) and the entries are
-        what ``action`` returns in that mode; ``device_out`` is int64 [K, k] and holds every state's ranking."""
+        what ``action`` returns in that mode; ``device_out`` is int64 [K, k] and holds every state's ranking.  With agent.candidate_gap > 1
+        the random picks are the forced first candidates of that ranking, which is then final (see ``action``)."""
         states = list(states)
         picks = [self._host_pick(state, verbose) for state in states]
         k, skip = candidates_option(self.candidates, self.skip_annotated)
@@ -866,6 +907,13 @@ class Agent(nn.Module):
                 return picks
             host = idx.cpu().numpy()
             return [p if p is not None else np.int64(host[i]) for i, p in enumerate(picks)]
+        gap = self._spread_gap(k)
+        if gap > 1:
+            rank = self.candidates_device(states, k, skip, out=device_out, gap=gap, first=[-1 if p is None else int(p) for p in picks])
+            if device_out is not None:
+                return picks
+            host = rank.cpu().numpy()
+            return [spread_candidates(host[i]) for i in range(len(states))]
         rank = self.candidates_device(states, k, skip, out=device_out)
         if device_out is not None:
             return picks
@@ -874,11 +922,12 @@ class Agent(nn.Module):
             return [p if p is not None else np.int64(host[i, 0]) for i, p in enumerate(picks)]
         return [merge_candidates(p, host[i], k) for i, p in enumerate(picks)]
 
-    def candidates_device(self, states, k=None, skip_annotated=None, out=None):
+    def candidates_device(self, states, k=None, skip_annotated=None, out=None, gap=1, first=None):
         """The k strongest frames of every state ([T_k,2]; host arrays are uploaded) by Q, annotated frames last under skip_annotated
         (ivosw_brain_topk_ragged's order), left on the device: int64 [K, k] (or written to `out`, K k int64 values), -1 behind a state's
         last frame.  k and skip_annotated default to the agent's options.  One Brain.forward_ragged and one top-k launch per 128 states;
-        a single state runs Brain.forward and the same entry with one sequence."""
+        a single state runs Brain.forward and the same entry with one sequence.  `gap` > 1 / `first` (one forced first candidate per
+        state, -1 for none): ``topk_ragged``'s spread ranking."""
         k, skip = candidates_option(self.candidates if k is None else k, self.skip_annotated if skip_annotated is None else skip_annotated)
         dev = self.policy_net.flat.device
         sts = [s if (torch.is_tensor(s) and s.is_cuda) else torch.as_tensor(np.asarray(s), dtype=torch.float32).to(dev) for s in states]
@@ -894,25 +943,38 @@ class Agent(nn.Module):
                 x = torch.cat([s.detach().to(dtype=torch.float32) for s in sts], 0)
             x = x.detach().to(dtype=torch.float32).contiguous()
             q, _ = self.policy_net.forward_ragged(x, lengths)
-        return self.topk_ragged(q, x, lengths, k, skip, out=out)
+        if gap == 1 and first is None:
+            return self.topk_ragged(q, x, lengths, k, skip, out=out)
+        return self.topk_ragged(q, x, lengths, k, skip, out=out, gap=gap, first=first)
 
-    def topk_ragged(self, q, states, lengths, k, skip, out=None, qv=None):
+    def topk_ragged(self, q, states, lengths, k, skip, out=None, qv=None, gap=1, first=None):
         """ivosw_brain_topk_ragged over the flat q [R] of sequences of `lengths`: int64 [K, k] on the device (or `out`), the j-th
         strongest frame of every sequence, -1 from its length on.  `states` is the flat [R,2] fp32 state whose column 1 holds the
-        annotation counts, or None (only with `skip` false); `qv` (float32 [K, k], optional) receives the Q values of the slots."""
+        annotation counts, or None (only with `skip` false); `qv` (float32 [K, k], optional) receives the Q values of the slots.
+
+        With `gap` > 1 or `first` (K host ints: the forced first candidate of every sequence, -1 for none) the entry is
+        ivosw_brain_topk_spread_ragged: the same order walked greedily, a frame accepted only `gap` or more frames from every accepted one,
+        -1 from the slot on at which nothing more can be accepted."""
         K = len(lengths)
         idx = out.view(K, k) if out is not None else torch.empty(K, k, dtype=torch.int64, device=q.device)
         if qv is not None:
             qv = qv.view(K, k)
+        spread = gap != 1 or first is not None
+        if first is not None and len(first) != K:
+            raise ValueError(f"topk_ragged: {len(first)} forced first candidates for {K} sequences")
         lib, off = L.lib(), 0
         for g in range(0, K, L.MAX_SEQS):
             group = lengths[g:g + L.MAX_SEQS]
             rows = sum(group)
-            L.check(lib.ivosw_brain_topk_ragged(L.dptr(q[off:off + rows], torch.float32),
-                                                L.dptr(states[off:off + rows], torch.float32) if states is not None else None,
-                                                L.int_array(group), len(group), int(k), int(bool(skip)), L.dptr(idx[g:g + len(group)], torch.int64),
-                                                L.dptr(qv[g:g + len(group)], torch.float32) if qv is not None else None,
-                                                L.stream_ptr(q.device)), "topk_ragged")
+            head = (L.dptr(q[off:off + rows], torch.float32), L.dptr(states[off:off + rows], torch.float32) if states is not None else None,
+                    L.int_array(group), len(group), int(k), int(bool(skip)))
+            tail = (L.dptr(idx[g:g + len(group)], torch.int64), L.dptr(qv[g:g + len(group)], torch.float32) if qv is not None else None,
+                    L.stream_ptr(q.device))
+            if spread:
+                L.check(lib.ivosw_brain_topk_spread_ragged(*head, int(gap), L.int_array(first[g:g + len(group)]) if first is not None else None,
+                                                           *tail), "topk_spread_ragged")
+            else:
+                L.check(lib.ivosw_brain_topk_ragged(*head, *tail), "topk_ragged")
             off += rows
         return idx
 

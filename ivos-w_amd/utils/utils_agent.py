@@ -78,23 +78,36 @@ def _annotation_counts(n, annotated_frames_list):
 
 
 def _topk_options(cfg_yl, agent):
-    """(k, skip_annotated): the agent's checked options; without an agent (method "worst" needs none) cfg.agent's keys, defaults 1 / False."""
-    from ..models.agent import candidates_option
+    """(k, skip_annotated, gap): the agent's checked options; without an agent (method "worst" needs none) cfg.agent's keys, defaults
+    1 / False / 1.  The gap (agent.candidate_gap) is the one the k candidates are spread by: 1 with one candidate, where it has no effect."""
+    from ..models.agent import candidate_gap_option, candidates_option
     if agent is not None and hasattr(agent, "candidates"):
-        return candidates_option(agent.candidates, agent.skip_annotated)
-    a = cfg_yl.get("agent") if hasattr(cfg_yl, "get") else None
-    if a is None:
-        return 1, False
-    return candidates_option(a.get("candidates", 1), a.get("skip_annotated", False))
+        k, skip = candidates_option(agent.candidates, agent.skip_annotated)
+        gap = candidate_gap_option(getattr(agent, "candidate_gap", 1))
+    else:
+        a = cfg_yl.get("agent") if hasattr(cfg_yl, "get") else None
+        if a is None:
+            return 1, False, 1
+        k, skip = candidates_option(a.get("candidates", 1), a.get("skip_annotated", False))
+        gap = candidate_gap_option(a.get("candidate_gap", 1))
+    return k, skip, gap if k > 1 else 1
 
 
-def worst_candidates(frame_value, k, prev_frames=None):
+def worst_candidates(frame_value, k, prev_frames=None, gap=1):
     """The first k frames of the order select_next_frame(frame_value, "worst", prev_frames) walks: its pick, then the other frames that are
-    not in prev_frames by rising value, then (when those run out) the frames of prev_frames by rising value.  np.int64 [min(k, n)]."""
+    not in prev_frames by rising value, then (when those run out) the frames of prev_frames by rising value.  np.int64 [min(k, n)].
+    With `gap` > 1 the order is walked greedily (agent.candidate_gap, the rule of ivosw_brain_topk_spread_ragged): a frame is accepted only
+    `gap` or more frames from every accepted one, and the list is shorter than k when no more can be."""
     first = int(select_next_frame(frame_value, metric="worst", prev_frames=prev_frames))
     order = [int(i) for i in np.asarray(frame_value).argsort() if int(i) != first]
     if prev_frames is not None:
         order = [i for i in order if i not in prev_frames] + [i for i in order if i in prev_frames]
+    if gap > 1:
+        taken = []
+        for t in [first] + order:
+            if len(taken) < k and all(abs(t - w) >= gap for w in taken):
+                taken.append(t)
+        return np.array(taken, dtype=np.int64)
     return np.array([first] + order, dtype=np.int64)[:k]
 
 
@@ -286,14 +299,15 @@ def assess_all_objects(assess_net, all_F, all_P, n_objects, device, rescore="all
 
 
 def _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, counts, mask_quality, prev_frames, k=1, as_list=False,
-                 rescore="all"):
+                 rescore="all", gap=1):
     """wild/worst and wild/ours (utils/utils_agent.py:111-122) with the chain quality -> state -> Brain -> argmax on the
     device: per-object scores are averaged into mask_quality (float64, numpy's summation order) and stacked with the
     annotation counts by ivosw_quality_state, the Brain and its first-max argmax read that state in place, and ONE D2H copy
     brings back the n quality values the caller's array wants plus the recommended index.  With agent.candidates = k /
-    agent.skip_annotated the argmax is the masked top-k and the buffer holds k indices; `as_list`: return all candidates (an array)."""
+    agent.skip_annotated the argmax is the masked top-k and the buffer holds k indices; `as_list`: return all candidates (an array).
+    With `gap` > 1 (agent.candidate_gap) the device ranking is the spread one and final: it is not merged with the random pick again."""
     from .. import _lib as L
-    from ..models.agent import merge_candidates
+    from ..models.agent import merge_candidates, spread_candidates
     scores = assess_all_objects_device(assess_net, all_F, all_P, n_objects, device, rescore)
     n = scores.shape[1]
     dev = scores.device
@@ -309,10 +323,11 @@ def _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, cou
     mask_quality[:] = host[:n].numpy()          # in place: the caller logs corr/diff from this array
     if method == "worst":
         if as_list:
-            return worst_candidates(mask_quality, k, prev_frames)
+            return worst_candidates(mask_quality, k, prev_frames, gap)
         return select_next_frame(mask_quality, metric="worst", prev_frames=prev_frames)
     if k > 1:
-        cand = merge_candidates(picked, host[n:].view(torch.int64).numpy(), k)
+        ranking = host[n:].view(torch.int64).numpy()
+        cand = spread_candidates(ranking) if gap > 1 else merge_candidates(picked, ranking, k)
         return cand if as_list else cand[0]
     pick = picked if picked is not None else np.int64(host[n:].view(torch.int64)[0].item())
     return _candidate_list(pick, 1) if as_list else pick
@@ -375,23 +390,27 @@ def recommend_candidates(cfg_yl, assess_net, agent, device, requests):
     or many: the same chains as ``recommend_frames`` (a single request takes the per-request chain with a one-sequence top-k).  wild/ours
     and oracle/ours: Agent.action's candidates (the ranking by Q, annotated frames last under agent.skip_annotated; on the epsilon branch
     the random pick first); oracle/ours runs on the host state.  "worst": the first k frames of the order select_next_frame walks
-    (``worst_candidates``).  "random" / "linspace": their single pick."""
+    (``worst_candidates``).  "random" / "linspace": their single pick.
+
+    With agent.candidate_gap = g > 1 the candidates of a request lie g or more frames apart (the order above walked greedily; on the device
+    ivosw_brain_topk_spread_ragged in the top-k's place, the random pick of the epsilon branch its forced first candidate): the list may
+    be shorter than k, entry 0 is what it is without a gap, and the chains keep their launches and their one copy."""
     return _recommend_many(cfg_yl, assess_net, agent, device, requests, as_list=True)
 
 
 def _recommend_many(cfg_yl, assess_net, agent, device, requests, as_list):
     requests = list(requests)
-    k, _ = _topk_options(cfg_yl, agent)
+    k, _, gap = _topk_options(cfg_yl, agent)
     if not (cfg_yl.setting == "wild" and cfg_yl.method in ("worst", "ours")):
         if as_list:
-            return [_recommend_one(cfg_yl, assess_net, agent, device, k=k, as_list=True, **r) for r in requests]
+            return [_recommend_one(cfg_yl, assess_net, agent, device, k=k, as_list=True, gap=gap, **r) for r in requests]
         return [recommend_frame(cfg_yl, assess_net, agent, device, **r) for r in requests]
     if as_list and len(requests) == 1:           # one session: recommend_frame's chain (its frame cache, a one-sequence top-k)
-        return [_recommend_one(cfg_yl, assess_net, agent, device, k=k, as_list=True, **requests[0])]
+        return [_recommend_one(cfg_yl, assess_net, agent, device, k=k, as_list=True, gap=gap, **requests[0])]
     if not requests:
         return []
     from .. import _lib as L
-    from ..models.agent import merge_candidates
+    from ..models.agent import merge_candidates, spread_candidates
     method = cfg_yl.method
     K = len(requests)
     with torch.no_grad():
@@ -434,10 +453,10 @@ def _recommend_many(cfg_yl, assess_net, agent, device, requests, as_list):
         o = int(o)
         r["mask_quality"][:] = quality[o:o + n]                             # in place: the caller logs corr/diff from this array
         if method == "worst":
-            result.append(worst_candidates(r["mask_quality"], k, r["prev_frames"]) if as_list else
+            result.append(worst_candidates(r["mask_quality"], k, r["prev_frames"], gap) if as_list else
                           select_next_frame(r["mask_quality"], metric="worst", prev_frames=r["prev_frames"]))
-        elif k > 1:
-            cand = merge_candidates(pk, index[i:i + k], k)
+        elif k > 1:                                                         # (a spread ranking is final: the pick is its slot 0 already)
+            cand = spread_candidates(index[i:i + k]) if gap > 1 else merge_candidates(pk, index[i:i + k], k)
             result.append(cand if as_list else cand[0])
         else:
             pick = pk if pk is not None else np.int64(index[i])
@@ -447,20 +466,20 @@ def _recommend_many(cfg_yl, assess_net, agent, device, requests, as_list):
 
 def recommend_frame(cfg_yl, assess_net, agent, device, n_frame, n_objects, all_F, all_P, new_masks_quality, prev_frames,
                     annotated_frames_list, mask_quality, first_frame, max_nb_interactions):
-    k, _ = _topk_options(cfg_yl, agent)
+    k, _, gap = _topk_options(cfg_yl, agent)
     return _recommend_one(cfg_yl, assess_net, agent, device, n_frame, n_objects, all_F, all_P, new_masks_quality, prev_frames,
-                          annotated_frames_list, mask_quality, first_frame, max_nb_interactions, k=k, as_list=False)
+                          annotated_frames_list, mask_quality, first_frame, max_nb_interactions, k=k, as_list=False, gap=gap)
 
 
 def _recommend_one(cfg_yl, assess_net, agent, device, n_frame, n_objects, all_F, all_P, new_masks_quality, prev_frames,
-                   annotated_frames_list, mask_quality, first_frame, max_nb_interactions, k=1, as_list=False):
-    """recommend_frame (the reference's index: candidate 0), or with `as_list` the candidates of recommend_candidates."""
+                   annotated_frames_list, mask_quality, first_frame, max_nb_interactions, k=1, as_list=False, gap=1):
+    """recommend_frame (the reference's index: candidate 0), or with `as_list` the candidates of recommend_candidates (`gap` apart)."""
     setting, method = cfg_yl.setting, cfg_yl.method
     one = (lambda pick: _candidate_list(pick, k)) if as_list else _first
     if setting == "oracle":
         if method == "worst":
             if as_list:
-                return worst_candidates(new_masks_quality, k, prev_frames)
+                return worst_candidates(new_masks_quality, k, prev_frames, gap)
             return select_next_frame(new_masks_quality, metric="worst", prev_frames=prev_frames)
         if method == "ours":
             state = np.stack([new_masks_quality, _annotation_counts(len(new_masks_quality), annotated_frames_list)], 1)
@@ -477,7 +496,7 @@ def _recommend_one(cfg_yl, assess_net, agent, device, n_frame, n_objects, all_F,
             counts = _annotation_counts(len(new_masks_quality), annotated_frames_list)
             with torch.no_grad():
                 return _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, counts, mask_quality,
-                                    prev_frames, k=k, as_list=as_list, rescore=rescore_option(cfg_yl))
+                                    prev_frames, k=k, as_list=as_list, rescore=rescore_option(cfg_yl), gap=gap)
         raise NotImplementedError
     raise NotImplementedError
 
