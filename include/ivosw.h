@@ -490,6 +490,48 @@ int ivosw_roi_sample_units(const ivosw_video_t* videos, int n_videos, const int3
 size_t ivosw_assess_units_ws_bytes(int dtype, int n_ids, int chunk);
 int ivosw_assess_forward_units(const void* packed, int dtype, const ivosw_video_t* videos, int n_videos, const int32_t* unit_ids,
                                int n_ids, float* scores, void* ws, size_t ws_bytes, int chunk, ivosw_stream_t stream);
+/* Label-map masks: a video's masks as ONE hard label map, uint8 [n_frames,H,W] (row-major planes, stride_frame elements between frames) -
+ * what ivosw_seg_epilogue writes as label_u8 and ivosw_jf_counts reads - in place of n_obj float planes: 1 byte per pixel and frame
+ * instead of 4 * (n_obj + 1).  Object obj (0-based, obj < n_obj <= 255) owns the value obj + 1; 0 and values above n_obj belong to no
+ * object.  The mask plane of unit (frame, obj) is, by definition, tp[y,x] = (map[frame,y,x] == obj + 1) ? 1.0f : 0.0f, and every _lab
+ * entry computes exactly what its plain twin computes on those planes, operation for operation: boxes, tiles, scores and dirty lists are
+ * bit-identical.  (The bbox test tp > 0.5f becomes byte == obj + 1; the sampler turns its four byte taps into 1.0f / 0.0f before the same
+ * tap selection, weights and FMA chain.)
+ * `labels` is a HOST array of n_videos entries, read during the call only; it travels in the kernel arguments like the table (no
+ * allocation, no copy: capture-safe).  labels[v].map != NULL: video v's masks come from the map, videos[v].masks and its two strides are
+ * not looked at (the pointer may be NULL).  labels[v].map == NULL: video v is a float video exactly as in the plain entry - one call may
+ * mix float and label videos, fp32 and RGBX8 frames.  labels == NULL: the plain entry.  Unit order, chunking, the two-stream split, taps,
+ * the workspaces (ivosw_assess_ws_bytes, ivosw_assess_units_ws_bytes) and every refusal of the plain entries are unchanged.  Refused in
+ * addition, before any launch, the message names the video: n_obj > 255 on a label video, a negative stride_frame, stride_frame < H * W
+ * with n_frames > 1 (overlapping frames), a float video with NULL masks.
+ * The scan reads 16 pixels per lane and load when H * W % 16 == 0 and the map's base and stride_frame are 16-byte aligned, else byte by
+ * byte.  A call without a label video launches the kernels of the plain entry.
+ * ivosw_mask_delta_videos_lab: cache[v] of a label video is a dense uint8 [n_frames][H*W] copy of the map (any alignment; 16-byte aligned
+ * for the vector path), of a float video the fp32 planes as in ivosw_mask_delta_videos.  A cold label video marks every unit dirty and
+ * copies the map; otherwise every pixel whose byte differs (cached a, now b) flags the units (frame, a - 1) and (frame, b - 1) whose labels
+ * lie in 1 .. n_obj - the planes that pixel changed in - and only differing bytes (16-byte vectors on the vector path) are stored: an
+ * unchanged session writes nothing.  One compare pass per FRAME (2 bytes read per pixel) instead of one per unit (8 bytes per pixel and
+ * unit); a call that mixes float and label videos runs two compare launches.  flags, unit_ids and n_dirty as in the plain entry.       */
+typedef struct ivosw_labels {
+    const uint8_t* map;                          /* device; NULL: a float video */
+    long stride_frame;                           /* elements */
+} ivosw_labels_t;
+int ivosw_mask_bbox_videos_lab(const ivosw_video_t* videos, const ivosw_labels_t* labels, int n_videos, float* yxhw, int32_t* scratch,
+                               ivosw_stream_t stream);
+int ivosw_roi_sample_videos_lab(const ivosw_video_t* videos, const ivosw_labels_t* labels, int n_videos, const float* yxhw, int dtype,
+                                void* roi, ivosw_stream_t stream);
+int ivosw_assess_forward_videos_lab(const void* packed, int dtype, const ivosw_video_t* videos, const ivosw_labels_t* labels,
+                                    int n_videos, float* scores, void* ws, size_t ws_bytes, int chunk, int tap_stage, void* tap_out,
+                                    ivosw_stream_t stream);
+int ivosw_mask_delta_videos_lab(const ivosw_video_t* videos, const ivosw_labels_t* labels, int n_videos, void* const* cache,
+                                const int* cold, int32_t* flags, int32_t* unit_ids, int32_t* n_dirty, ivosw_stream_t stream);
+int ivosw_mask_bbox_units_lab(const ivosw_video_t* videos, const ivosw_labels_t* labels, int n_videos, const int32_t* unit_ids,
+                              int n_ids, float* yxhw, int32_t* scratch, ivosw_stream_t stream);
+int ivosw_roi_sample_units_lab(const ivosw_video_t* videos, const ivosw_labels_t* labels, int n_videos, const int32_t* unit_ids,
+                               int n_ids, const float* yxhw, int dtype, void* roi, ivosw_stream_t stream);
+int ivosw_assess_forward_units_lab(const void* packed, int dtype, const ivosw_video_t* videos, const ivosw_labels_t* labels,
+                                   int n_videos, const int32_t* unit_ids, int n_ids, float* scores, void* ws, size_t ws_bytes,
+                                   int chunk, ivosw_stream_t stream);
 /* Replaces `mask_quality[:] = pred.mean(1); state = np.stack([mask_quality, counts], 1)` (utils/utils_agent.py:120-121) on
  * the device: scores [n_obj][n_frames] fp32 (as ivosw_assess_forward_objects writes them), counts [n_frames] fp32 ->
  * quality [n_frames] float64 (numpy's float64 mean of the float32 predictions, same summation order) and

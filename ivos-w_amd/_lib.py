@@ -32,6 +32,11 @@ class Video(C.Structure):
                 ("frames_kind", C.c_int), ("n_frames", C.c_int), ("n_obj", C.c_int), ("H", C.c_int), ("W", C.c_int)]
 
 
+class Labels(C.Structure):
+    """ivosw_labels_t: the label map of one video of a *_lab call (device pointer, frame stride in elements); map = None: a float video."""
+    _fields_ = [("map", C.c_void_p), ("stride_frame", C.c_long)]
+
+
 SIGNATURES = {
     "ivosw_last_error": (C.c_char_p, []),
     "ivosw_version": (_i, []),
@@ -105,6 +110,14 @@ SIGNATURES = {
     "ivosw_roi_sample_units": (_i, [_p, _i, _p, _i, _p, _i, _p, _p]),
     "ivosw_assess_units_ws_bytes": (_sz, [_i, _i, _i]),
     "ivosw_assess_forward_units": (_i, [_p, _i, _p, _i, _p, _i, _p, _p, _sz, _i, _p]),
+    # the *_lab twins: `labels` (a host array of Labels) right behind `videos`, nothing else
+    "ivosw_mask_bbox_videos_lab": (_i, [_p, _p, _i, _p, _p, _p]),
+    "ivosw_roi_sample_videos_lab": (_i, [_p, _p, _i, _p, _i, _p, _p]),
+    "ivosw_assess_forward_videos_lab": (_i, [_p, _i, _p, _p, _i, _p, _p, _sz, _i, _i, _p, _p]),
+    "ivosw_mask_delta_videos_lab": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p]),
+    "ivosw_mask_bbox_units_lab": (_i, [_p, _p, _i, _p, _i, _p, _p, _p]),
+    "ivosw_roi_sample_units_lab": (_i, [_p, _p, _i, _p, _i, _p, _i, _p, _p]),
+    "ivosw_assess_forward_units_lab": (_i, [_p, _i, _p, _p, _i, _p, _i, _p, _p, _sz, _i, _p]),
     "ivosw_quality_state": (_i, [_p, _i, _i, _p, _p, _p, _p]),
     "ivosw_quality_state_ragged": (_i, [_p, _p, _p, _i, _p, _p, _p, _p]),
     "ivosw_assess_dominant_kernel": (C.c_char_p, [_i]),

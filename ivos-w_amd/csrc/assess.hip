@@ -381,6 +381,17 @@ extern "C" int ivosw_assess_forward_videos(const void* packed, int dtype, const 
                                tap_stage, tap_out, stream, &vt);
 }
 
+// ... with label-map masks (include/ivosw.h: ivosw_labels_t): the table carries each label video's map, the front-end launches pick their
+// Lab instantiations, and everything behind the ROI tile is the pass above.
+extern "C" int ivosw_assess_forward_videos_lab(const void* packed, int dtype, const ivosw_video_t* videos, const ivosw_labels_t* labels,
+                                               int n_videos, float* scores, void* ws, size_t ws_bytes, int chunk, int tap_stage, void* tap_out,
+                                               ivosw_stream_t stream) {
+    VideoTable vt;
+    if (const int rc = video_table_build(videos, n_videos, __func__, &vt, labels)) return rc;
+    return assess_forward_impl(packed, dtype, FrameSrc{nullptr, 0}, nullptr, SampleMap{1, 0, 0}, vt.units, 2, 2, scores, ws, ws_bytes, chunk,
+                               tap_stage, tap_out, stream, &vt);
+}
+
 // The same pass over a unit LIST (include/ivosw.h): row i of the pass is unit unit_ids[i] of the table, so B = n_ids and the chunk loop,
 // the two-stream split and the workspace are those of a pass of n_ids units.  The tower writes its scores into a compact [n_ids] buffer
 // at the head of the workspace; one scatter launch behind the join stores them at scores[unit_ids[i]] and touches nothing else.
@@ -392,10 +403,26 @@ extern "C" size_t ivosw_assess_units_ws_bytes(int dtype, int n_ids, int chunk) {
     return body ? units_head_bytes(n_ids) + body : 0;
 }
 
+static int assess_forward_units_impl(const char* who, const void* packed, int dtype, const ivosw_video_t* videos, const ivosw_labels_t* labels,
+                                     int n_videos, const int32_t* unit_ids, int n_ids, float* scores, void* ws, size_t ws_bytes, int chunk,
+                                     ivosw_stream_t stream);
+
 extern "C" int ivosw_assess_forward_units(const void* packed, int dtype, const ivosw_video_t* videos, int n_videos, const int32_t* unit_ids,
                                           int n_ids, float* scores, void* ws, size_t ws_bytes, int chunk, ivosw_stream_t stream) {
+    return assess_forward_units_impl(__func__, packed, dtype, videos, nullptr, n_videos, unit_ids, n_ids, scores, ws, ws_bytes, chunk, stream);
+}
+
+extern "C" int ivosw_assess_forward_units_lab(const void* packed, int dtype, const ivosw_video_t* videos, const ivosw_labels_t* labels,
+                                              int n_videos, const int32_t* unit_ids, int n_ids, float* scores, void* ws, size_t ws_bytes,
+                                              int chunk, ivosw_stream_t stream) {
+    return assess_forward_units_impl(__func__, packed, dtype, videos, labels, n_videos, unit_ids, n_ids, scores, ws, ws_bytes, chunk, stream);
+}
+
+static int assess_forward_units_impl(const char* who, const void* packed, int dtype, const ivosw_video_t* videos, const ivosw_labels_t* labels,
+                                     int n_videos, const int32_t* unit_ids, int n_ids, float* scores, void* ws, size_t ws_bytes, int chunk,
+                                     ivosw_stream_t stream) {
     VideoTable vt;
-    if (const int rc = video_table_build(videos, n_videos, __func__, &vt)) return rc;
+    if (const int rc = video_table_build(videos, n_videos, who, &vt, labels)) return rc;
     IVOSW_REQUIRE(n_ids >= 0, "n_ids is negative");
     IVOSW_REQUIRE(n_ids <= vt.units, "n_ids is above the table's units");
     IVOSW_REQUIRE(n_ids == 0 || unit_ids, "null pointer (unit_ids)");

@@ -9,6 +9,7 @@
 #include <limits.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 #include "front.h"
@@ -433,7 +434,20 @@ struct UnitList {
 // bbox_scan_kernel over the units [b0, b0 + gridDim.y) of a video table.  grid (S, B) with S sized for the LARGEST plane of the range:
 // a workgroup whose chunk lies behind its own video's plane leaves before the barrier (the whole workgroup: the test is uniform).
 // Integer min / max: the box does not depend on how the plane is cut into chunks.
-template <typename Units>
+//
+// Lab (compile time, like Units): the table holds at least one label video (front.h: VideoDesc::lab).  The choice is then made per video,
+// uniform per workgroup; a float-only table runs the Lab = false instantiation, whose code is what it was before label maps existed.
+// A label video's unit (frame, obj) scans the frame's uint8 map for the value obj + 1 - `tp > 0.5f` on the one-hot plane is that test.
+// Vector path: one 16-byte load = 16 pixels per lane (block stride 4096 pixels; chunk % 1024 == 0 and plane % 16 == 0 keep every vector
+// inside the chunk), a vector without a byte equal to the label is skipped by a zero-byte test on the four words XOR the label.
+
+// any byte of w equal to the byte replicated in `rep`?  (the classic zero-byte test on w ^ rep: exact as a yes / no answer)
+__device__ __forceinline__ uint32_t has_byte(uint32_t w, uint32_t rep) {
+    const uint32_t x = w ^ rep;
+    return (x - 0x01010101u) & ~x & 0x80808080u;
+}
+
+template <typename Units, bool Lab>
 __global__ __launch_bounds__(256) void bbox_scan_multi_kernel(const VideoTable vt, Units un, int chunk, int32_t* __restrict__ box) {
     const int b = blockIdx.y;
     const int u = un.at(b);
@@ -448,7 +462,52 @@ __global__ __launch_bounds__(256) void bbox_scan_multi_kernel(const VideoTable v
     const float* p = d.masks + (size_t)(lu / nf) * d.stride_obj + (size_t)(lu % nf) * d.stride_frame;
     const size_t end = min(plane, beg + (size_t)chunk);
     int ymin = INT_MAX, ymax = -1, xmin = INT_MAX, xmax = -1;
-    if (d.vec_ok) {  // this video: plane % 4 == 0, base and strides 16-B aligned (chunk % 1024 == 0 for every video)
+    bool is_lab = false;
+    if constexpr (Lab) is_lab = d.lab != nullptr;                  // (uniform)
+    if (Lab && is_lab) {
+        const uint8_t* q = d.lab + (size_t)(lu % nf) * d.lab_stride;
+        const uint32_t lab = (uint32_t)(lu / nf) + 1u;             // n_obj <= 255 on a label video (checked by the host)
+        if (d.vec_ok) {  // plane % 16 == 0, map base and frame stride 16-B aligned
+            const uint32_t rep = lab * 0x01010101u;
+            size_t i = beg + (size_t)threadIdx.x * 16;
+            int y = (int)(i / W), x = (int)(i - (size_t)y * W);
+            const int sy = 4096 / W, sx = 4096 % W;                // one block stride = 4096 pixels
+            auto visit = [&](const uint4& v, int yy, int xx) {
+                if (has_byte(v.x, rep) | has_byte(v.y, rep) | has_byte(v.z, rep) | has_byte(v.w, rep)) {
+                    const uint32_t e[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) {
+                        if (((e[j >> 2] >> (8 * (j & 3))) & 0xffu) == lab) {
+                            ymin = min(ymin, yy); ymax = max(ymax, yy);
+                            xmin = min(xmin, xx); xmax = max(xmax, xx);
+                        }
+                        if (++xx == W) { xx = 0; ++yy; }
+                    }
+                }
+            };
+            auto step = [&](int& yy, int& xx) { yy += sy; xx += sx; if (xx >= W) { xx -= W; ++yy; } };
+            for (; i + 3 * 4096 < end; i += 4 * 4096) {
+                const uint4 v0 = *reinterpret_cast<const uint4*>(q + i), v1 = *reinterpret_cast<const uint4*>(q + i + 4096);
+                const uint4 v2 = *reinterpret_cast<const uint4*>(q + i + 8192), v3 = *reinterpret_cast<const uint4*>(q + i + 12288);
+                visit(v0, y, x); step(y, x);
+                visit(v1, y, x); step(y, x);
+                visit(v2, y, x); step(y, x);
+                visit(v3, y, x); step(y, x);
+            }
+            for (; i < end; i += 4096) {
+                visit(*reinterpret_cast<const uint4*>(q + i), y, x);
+                step(y, x);
+            }
+        } else {
+            for (size_t i = beg + threadIdx.x; i < end; i += 256) {
+                if (q[i] == lab) {
+                    const int y = (int)(i / W), x = (int)(i - (size_t)y * W);
+                    ymin = min(ymin, y); ymax = max(ymax, y);
+                    xmin = min(xmin, x); xmax = max(xmax, x);
+                }
+            }
+        }
+    } else if (d.vec_ok) {  // this video: plane % 4 == 0, base and strides 16-B aligned (chunk % 1024 == 0 for every video)
         size_t i = beg + (size_t)threadIdx.x * 4;
         int y = (int)(i / W), x = (int)(i - (size_t)y * W);
         const int sy = 1024 / W, sx = 1024 % W;
@@ -543,20 +602,29 @@ void launch_mask_bbox_multi(const VideoTable& vt, int b0, int B, float* yxhw, in
     chunk = (chunk + 1023) / 1024 * 1024;
     S = (int)((plane + chunk - 1) / chunk);
     if (ids) {
-        hipLaunchKernelGGL(bbox_scan_multi_kernel<UnitList>, dim3(S, B), dim3(256), 0, st, vt, UnitList{ids, b0}, (int)chunk, scratch);
+        if (vt.any_lab)
+            hipLaunchKernelGGL((bbox_scan_multi_kernel<UnitList, true>), dim3(S, B), dim3(256), 0, st, vt, UnitList{ids, b0}, (int)chunk, scratch);
+        else
+            hipLaunchKernelGGL((bbox_scan_multi_kernel<UnitList, false>), dim3(S, B), dim3(256), 0, st, vt, UnitList{ids, b0}, (int)chunk, scratch);
         hipLaunchKernelGGL(bbox_finalize_multi_kernel<UnitList>, dim3((B + 63) / 64), dim3(64), 0, st, scratch, vt, UnitList{ids, b0}, B, yxhw);
         return;
     }
-    hipLaunchKernelGGL(bbox_scan_multi_kernel<UnitRange>, dim3(S, B), dim3(256), 0, st, vt, UnitRange{b0}, (int)chunk, scratch);
+    if (vt.any_lab)
+        hipLaunchKernelGGL((bbox_scan_multi_kernel<UnitRange, true>), dim3(S, B), dim3(256), 0, st, vt, UnitRange{b0}, (int)chunk, scratch);
+    else
+        hipLaunchKernelGGL((bbox_scan_multi_kernel<UnitRange, false>), dim3(S, B), dim3(256), 0, st, vt, UnitRange{b0}, (int)chunk, scratch);
     hipLaunchKernelGGL(bbox_finalize_multi_kernel<UnitRange>, dim3((B + 63) / 64), dim3(64), 0, st, scratch, vt, UnitRange{b0}, B, yxhw);
 }
 
 // One unit's ROI_R output rows: the body of roi_sample_kernel (U8 = false) / roi_sample_u8_kernel (U8 = true) behind their pointer
 // setup - the same theta, taps, weights, clamped pair loads, zero weights, product-sums and (f - mean) / std, in the same order.  The
 // four product-sums are written as the FMA chain that both single-video kernels compile to (see roi_sample_u8_kernel).
-template <typename T, bool U8>
-__device__ __forceinline__ void roi_unit_rows(const void* __restrict__ frame, const float* __restrict__ srcp, const float* __restrict__ yx,
-                                              int H, int W, const RoiNorm& nrm, int i0, int j, T* __restrict__ dst) {
+// Lab = true: the P channel comes from a label map (srcp = the frame's uint8 plane, labv = the unit's label): its four taps are BYTE
+// loads at the same clamped offsets o0, o0 + 1, o1, o1 + 1 (no 2-byte load: o0 may be odd), each turned into the one-hot plane's value
+// (byte == labv) ? 1.0f : 0.0f before the same tap selection, weights and FMA chain - bit-identical to the float path on that plane.
+template <typename T, bool U8, bool Lab = false>
+__device__ __forceinline__ void roi_unit_rows(const void* __restrict__ frame, const void* __restrict__ srcp, const float* __restrict__ yx,
+                                              int H, int W, const RoiNorm& nrm, int i0, int j, T* __restrict__ dst, uint32_t labv = 0u) {
     const float ry = yx[0], rx = yx[1], rh = yx[2], rw = yx[3];
     const float ymin = __fsub_rn(ry, rh / 2.0f), ymax = __fadd_rn(ry, rh / 2.0f);
     const float xmin = __fsub_rn(rx, rw / 2.0f), xmax = __fadd_rn(rx, rw / 2.0f);
@@ -604,8 +672,16 @@ __device__ __forceinline__ void roi_unit_rows(const void* __restrict__ frame, co
             }
 #pragma unroll
             for (int c = U8 ? 3 : 0; c < 4; ++c) {
-                const float* s = c < 3 ? static_cast<const float*>(frame) + (size_t)c * plane : srcp;
-                const float2 p0 = ld_pair(s + o0), p1 = ld_pair(s + o1);
+                float2 p0, p1;
+                if (Lab && c == 3) {
+                    const uint8_t* m = static_cast<const uint8_t*>(srcp);
+                    const uint32_t b00 = m[o0], b01 = m[o0 + 1], b10 = m[o1], b11 = m[o1 + 1];
+                    p0 = make_float2(b00 == labv ? 1.0f : 0.0f, b01 == labv ? 1.0f : 0.0f);
+                    p1 = make_float2(b10 == labv ? 1.0f : 0.0f, b11 == labv ? 1.0f : 0.0f);
+                } else {
+                    const float* s = c < 3 ? static_cast<const float*>(frame) + (size_t)c * plane : static_cast<const float*>(srcp);
+                    p0 = ld_pair(s + o0); p1 = ld_pair(s + o1);
+                }
                 v[rr][c][0] = t0_hi ? p0.y : p0.x; v[rr][c][1] = t1_lo ? p0.x : p0.y;
                 v[rr][c][2] = t0_hi ? p1.y : p1.x; v[rr][c][3] = t1_lo ? p1.x : p1.y;
             }
@@ -641,7 +717,8 @@ __device__ __forceinline__ void roi_unit_rows(const void* __restrict__ frame, co
 
 // roi_sample_kernel / roi_sample_u8_kernel over the units [b0, b0 + B) of a video table: grid B * 256 / ROI_R, block 256, thread j =
 // output column j of ROI_R rows of one unit.  The workgroup resolves its unit's video once (uniform), then runs that video's sampler.
-template <typename T, typename Units>
+// Lab: as in bbox_scan_multi_kernel - compiled in only for tables with a label video, chosen per video (uniform) inside.
+template <typename T, typename Units, bool Lab>
 __global__ __launch_bounds__(256) void roi_sample_multi_kernel(const VideoTable vt, const float* __restrict__ yxhw, Units un, RoiNorm nrm,
                                                                T* __restrict__ roi) {
     constexpr int GPS = 256 / ROI_R;
@@ -660,6 +737,20 @@ __global__ __launch_bounds__(256) void roi_sample_multi_kernel(const VideoTable 
     const VideoDesc& d = vt.v[vi];
     const int H = d.H, W = d.W, nf = d.n_frames;
     const int lu = u - vt.first[vi], fr = lu % nf;
+    if constexpr (Lab) {
+        if (d.lab) {                                               // (uniform)
+            const uint8_t* srcm = d.lab + (size_t)fr * d.lab_stride;
+            const uint32_t labv = (uint32_t)(lu / nf) + 1u;
+            if (d.u8) {
+                const uint8_t* srcf = static_cast<const uint8_t*>(d.frames) + (size_t)fr * H * W * 4;
+                roi_unit_rows<T, true, true>(srcf, srcm, yxhw + b * 4, H, W, nrm, i0, j, dst, labv);
+            } else {
+                const float* srcf = static_cast<const float*>(d.frames) + (size_t)fr * 3 * H * W;
+                roi_unit_rows<T, false, true>(srcf, srcm, yxhw + b * 4, H, W, nrm, i0, j, dst, labv);
+            }
+            return;
+        }
+    }
     const float* srcp = d.masks + (size_t)(lu / nf) * d.stride_obj + (size_t)fr * d.stride_frame;
     if (d.u8) {
         const uint8_t* srcf = static_cast<const uint8_t*>(d.frames) + (size_t)fr * H * W * 4;
@@ -673,24 +764,26 @@ __global__ __launch_bounds__(256) void roi_sample_multi_kernel(const VideoTable 
 void launch_roi_sample_multi(const VideoTable& vt, const float* yxhw, int b0, int B, int dtype, const RoiNorm& nrm, void* roi, hipStream_t st,
                              const int32_t* ids) {
     const dim3 grid(B * (256 / ROI_R)), block(256);
-    if (ids) {
-        const UnitList un{ids, b0};
+    auto launch = [&](auto un, auto lab) {
+        constexpr bool Lab = decltype(lab)::value;
+        using Units = decltype(un);
         if (dtype != IVOSW_BF16)
-            hipLaunchKernelGGL((roi_sample_multi_kernel<float, UnitList>), grid, block, 0, st, vt, yxhw, un, nrm, static_cast<float*>(roi));
+            hipLaunchKernelGGL((roi_sample_multi_kernel<float, Units, Lab>), grid, block, 0, st, vt, yxhw, un, nrm, static_cast<float*>(roi));
         else
-            hipLaunchKernelGGL((roi_sample_multi_kernel<bf16_t, UnitList>), grid, block, 0, st, vt, yxhw, un, nrm, static_cast<bf16_t*>(roi));
+            hipLaunchKernelGGL((roi_sample_multi_kernel<bf16_t, Units, Lab>), grid, block, 0, st, vt, yxhw, un, nrm, static_cast<bf16_t*>(roi));
+    };
+    if (ids) {
+        if (vt.any_lab) launch(UnitList{ids, b0}, std::true_type{});
+        else launch(UnitList{ids, b0}, std::false_type{});
         return;
     }
-    const UnitRange un{b0};
-    if (dtype != IVOSW_BF16)
-        hipLaunchKernelGGL((roi_sample_multi_kernel<float, UnitRange>), grid, block, 0, st, vt, yxhw, un, nrm, static_cast<float*>(roi));
-    else
-        hipLaunchKernelGGL((roi_sample_multi_kernel<bf16_t, UnitRange>), grid, block, 0, st, vt, yxhw, un, nrm, static_cast<bf16_t*>(roi));
+    if (vt.any_lab) launch(UnitRange{b0}, std::true_type{});
+    else launch(UnitRange{b0}, std::false_type{});
 }
 
 static void set_video_error(const char* who, int i, const char* msg) { set_error("%s: video %d: %s", who, i, msg); }
 
-int video_table_build(const ivosw_video_t* videos, int n_videos, const char* who, VideoTable* out) {
+int video_table_build(const ivosw_video_t* videos, int n_videos, const char* who, VideoTable* out, const ivosw_labels_t* labels) {
     if (!videos) { set_error("%s: null pointer (videos)", who); return IVOSW_ERR_ARG; }
     if (n_videos < 1 || n_videos > IVOSW_MAX_VIDEOS) {
         set_error("%s: n_videos = %d is outside [1, %d]", who, n_videos, IVOSW_MAX_VIDEOS);
@@ -702,24 +795,36 @@ int video_table_build(const ivosw_video_t* videos, int n_videos, const char* who
     for (int i = 0; i < n_videos; ++i) {
         const ivosw_video_t& s = videos[i];
 #define VIDEO_REQUIRE(cond, msg) do { if (!(cond)) { set_video_error(who, i, msg); return IVOSW_ERR_ARG; } } while (0)
-        VIDEO_REQUIRE(s.frames && s.masks, "null pointer");
+        const bool lab = labels && labels[i].map;                   // a label video: masks and its strides are not looked at
+        VIDEO_REQUIRE(s.frames && (lab || s.masks), "null pointer");
         VIDEO_REQUIRE(s.frames_kind == IVOSW_FRAMES_F32 || s.frames_kind == IVOSW_FRAMES_RGBX8, "frames_kind must be IVOSW_FRAMES_F32 or IVOSW_FRAMES_RGBX8");
         VIDEO_REQUIRE(s.n_frames > 0 && s.n_obj > 0, "n_frames and n_obj must be positive");
         VIDEO_REQUIRE(s.H > 1 && s.W > 1, "H, W > 1 wanted");
         VIDEO_REQUIRE((long)s.H * s.W <= INT_MAX, "frame too large (H * W <= INT_MAX)");
-        VIDEO_REQUIRE(s.mask_stride_obj >= 0 && s.mask_stride_frame >= 0, "negative mask stride");
-        VIDEO_REQUIRE(s.mask_stride_frame >= (long)s.H * s.W || s.n_frames == 1, "mask planes of consecutive frames overlap");
+        if (lab) {
+            VIDEO_REQUIRE(s.n_obj <= 255, "a label map holds at most 255 objects (n_obj <= 255)");
+            VIDEO_REQUIRE(labels[i].stride_frame >= 0, "negative label stride");
+            VIDEO_REQUIRE(labels[i].stride_frame >= (long)s.H * s.W || s.n_frames == 1, "label maps of consecutive frames overlap");
+        } else {
+            VIDEO_REQUIRE(s.mask_stride_obj >= 0 && s.mask_stride_frame >= 0, "negative mask stride");
+            VIDEO_REQUIRE(s.mask_stride_frame >= (long)s.H * s.W || s.n_frames == 1, "mask planes of consecutive frames overlap");
+        }
         VIDEO_REQUIRE(s.frames_kind != IVOSW_FRAMES_RGBX8 || (reinterpret_cast<uintptr_t>(s.frames) & 3) == 0, "rgbx must be 4-byte aligned");
         units += (long)s.n_frames * s.n_obj;
         VIDEO_REQUIRE(units < (1L << 30), "too many (frame, object) units for one call (2^30 or more up to this video)");
 #undef VIDEO_REQUIRE
         VideoDesc& d = t.v[i];
-        d.frames = s.frames; d.masks = s.masks;
-        d.stride_frame = s.mask_stride_frame; d.stride_obj = s.mask_stride_obj;
+        d.frames = s.frames;
+        if (!lab) { d.masks = s.masks; d.stride_frame = s.mask_stride_frame; d.stride_obj = s.mask_stride_obj; }
         d.n_frames = s.n_frames; d.n_obj = s.n_obj; d.H = s.H; d.W = s.W;
         d.u8 = s.frames_kind == IVOSW_FRAMES_RGBX8;
         d.vec_ok = ((size_t)s.H * s.W) % 4 == 0 && (reinterpret_cast<uintptr_t>(s.masks) & 15) == 0 && s.mask_stride_frame % 4 == 0 &&
                    s.mask_stride_obj % 4 == 0;
+        if (lab) {
+            d.lab = labels[i].map; d.lab_stride = labels[i].stride_frame;
+            d.vec_ok = ((size_t)s.H * s.W) % 16 == 0 && (reinterpret_cast<uintptr_t>(d.lab) & 15) == 0 && d.lab_stride % 16 == 0;
+            t.any_lab = 1;
+        }
         t.first[i] = (int)(units - (long)s.n_frames * s.n_obj);
     }
     t.n = n_videos;
@@ -752,10 +857,15 @@ __device__ __forceinline__ bool differs(const uint4& a, const uint4& b) { return
 // grid units * S (S = slices of the largest plane), block 256: workgroup (u, s) compares elements [s * DELTA_CHUNK, (s + 1) * DELTA_CHUNK)
 // of unit u's plane.  A workgroup whose slice lies behind its own video's plane leaves before the barrier (uniform).  Every workgroup that
 // finds a difference stores the same 1 into flags[u]: no atomics.
+// Lab (a call that mixes float and label videos): the units of the label videos leave at once - mask_delta_lab_kernel compares those.
+template <bool Lab>
 __global__ __launch_bounds__(256) void mask_delta_kernel(const VideoTable vt, const DeltaArgs da, int S, int32_t* __restrict__ flags) {
     const int u = blockIdx.x / S, s = blockIdx.x % S;
     const int vi = video_of_unit(vt, u);
     const VideoDesc& d = vt.v[vi];
+    if constexpr (Lab) {
+        if (d.lab) return;                                         // (uniform)
+    }
     const size_t plane = (size_t)d.H * d.W;
     const size_t beg = (size_t)s * DELTA_CHUNK;
     if (beg >= plane) return;
@@ -792,6 +902,101 @@ __global__ __launch_bounds__(256) void mask_delta_kernel(const VideoTable vt, co
         }
     }
     if (__syncthreads_or(dirty) && threadIdx.x == 0) flags[u] = 1;
+}
+
+// The same for label videos, one pass per FRAME instead of one per unit: cache[v] is a dense uint8 [n_frames][H*W] copy of the map, and a
+// pixel whose byte went from a to b dirties the units (frame, a - 1) and (frame, b - 1) - the two planes that pixel changed in - when those
+// labels lie in 1 .. n_obj.  Bytes per frame: 2 x H x W read (H x W when cold), against 2 x 4 x H x W per UNIT of the float pass.
+// grid (frames of the label videos) * S, block 256: workgroup (f, s) compares bytes [s * LAB_DELTA_CHUNK, (s + 1) * LAB_DELTA_CHUNK) of
+// frame f.  Vector path (the video's vec_ok and a 16-byte aligned cache): 16-byte loads of both sides, a store only where the vector
+// differs; else byte by byte, a store only where the byte differs.  Every lane collects the labels 1 .. 64 it saw change in a 64-bit mask,
+// OR-reduced over the workgroup; one lane then stores the same 1 per set bit (no atomics).  Labels above 64 are flagged by a plain store
+// where they are met.
+struct LabDeltaArgs {
+    uint8_t* cache[IVOSW_MAX_VIDEOS];
+    int cold[IVOSW_MAX_VIDEOS];
+    int vec[IVOSW_MAX_VIDEOS];
+    int ffirst[IVOSW_MAX_VIDEOS];        // first frame of video i among the frames of the label videos (a float video holds none); INT_MAX for i >= n
+};
+static_assert(sizeof(VideoTable) + sizeof(LabDeltaArgs) + 64 <= 4096, "mask_delta_lab_kernel's arguments no longer fit");
+static_assert(sizeof(VideoTable) + sizeof(DeltaArgs) + 64 <= 4096, "mask_delta_kernel's arguments no longer fit");
+constexpr int LAB_DELTA_CHUNK = 16384;   // bytes of a frame per workgroup: four 16-byte loads per lane and side
+
+__global__ __launch_bounds__(256) void mask_delta_lab_kernel(const VideoTable vt, const LabDeltaArgs da, int S, int32_t* __restrict__ flags) {
+    const int f = blockIdx.x / S, s = blockIdx.x % S;
+    int vi = 0;
+#pragma unroll
+    for (int i = 1; i < IVOSW_MAX_VIDEOS; ++i) vi += (f >= da.ffirst[i]) ? 1 : 0;
+    const VideoDesc& d = vt.v[vi];
+    const size_t plane = (size_t)d.H * d.W;
+    const size_t beg = (size_t)s * LAB_DELTA_CHUNK;
+    if (beg >= plane) return;
+    const size_t end = min(plane, beg + (size_t)LAB_DELTA_CHUNK);
+    const int fr = f - da.ffirst[vi], nf = d.n_frames, n_obj = d.n_obj;
+    const uint8_t* p = d.lab + (size_t)fr * d.lab_stride;
+    uint8_t* c = da.cache[vi] + (size_t)fr * plane;
+    int32_t* fl = flags + vt.first[vi] + fr;                       // unit (fr, obj) of this video: fl[obj * nf]
+    const bool cold = da.cold[vi] != 0;
+    unsigned long long seen = 0ull;                                // bit l - 1: label l changed somewhere in this lane's bytes
+    auto note = [&](uint32_t l) {
+        if (l - 1u < (uint32_t)n_obj) {
+            if (l <= 64u) seen |= 1ull << (l - 1u);
+            else fl[(size_t)(l - 1u) * nf] = 1;
+        }
+    };
+    if (da.vec[vi]) {                     // plane % 16 == 0: end is a multiple of 16 and every vector lies inside the frame
+        size_t i = beg + (size_t)threadIdx.x * 16;
+        if (cold) {
+            for (; i < end; i += 4096) *reinterpret_cast<uint4*>(c + i) = *reinterpret_cast<const uint4*>(p + i);
+        } else {
+            auto visit = [&](const uint4 a, const uint4 b, size_t at) {      // (by value: b may be loaded from c + at, which is stored to)
+                if (differs(a, b)) {
+                    *reinterpret_cast<uint4*>(c + at) = a;
+                    const uint32_t wa[4] = {a.x, a.y, a.z, a.w}, wb[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        if (wa[k] != wb[k]) {
+#pragma unroll
+                            for (int j = 0; j < 4; ++j) {
+                                const uint32_t x = (wa[k] >> (8 * j)) & 0xffu, y = (wb[k] >> (8 * j)) & 0xffu;
+                                if (x != y) { note(x); note(y); }
+                            }
+                        }
+                    }
+                }
+            };
+            for (; i + 3 * 4096 < end; i += 4 * 4096) {            // eight 16-byte loads in flight per lane
+                uint4 a[4], b[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) a[k] = *reinterpret_cast<const uint4*>(p + i + k * 4096);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) b[k] = *reinterpret_cast<const uint4*>(c + i + k * 4096);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) visit(a[k], b[k], i + k * 4096);
+            }
+            for (; i < end; i += 4096) visit(*reinterpret_cast<const uint4*>(p + i), *reinterpret_cast<const uint4*>(c + i), i);
+        }
+    } else {
+        for (size_t i = beg + threadIdx.x; i < end; i += 256) {
+            const uint32_t a = p[i];
+            if (cold) { c[i] = (uint8_t)a; continue; }
+            const uint32_t b = c[i];
+            if (a != b) { c[i] = (uint8_t)a; note(a); note(b); }
+        }
+    }
+    if (cold) {                                                    // every unit of the frame, whatever the map holds (n_obj <= 255 < 256 lanes)
+        if ((int)threadIdx.x < n_obj) fl[(size_t)threadIdx.x * nf] = 1;
+        return;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) seen |= __shfl_xor(seen, o, 64);
+    __shared__ unsigned long long red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = seen;
+    __syncthreads();
+    if (threadIdx.x < 64) {                                        // lane l - 1 stores label l's flag
+        const unsigned long long all = red[0] | red[1] | red[2] | red[3];
+        if ((all >> threadIdx.x) & 1ull) fl[(size_t)threadIdx.x * nf] = 1;
+    }
 }
 
 // flags [n] -> the set entries' indices in ascending order, and their number: one workgroup walks the flags 1024 at a time, a ballot gives
@@ -899,23 +1104,36 @@ extern "C" long ivosw_assess_videos_units(const ivosw_video_t* videos, int n_vid
     return rc == IVOSW_OK ? (long)vt.units : (long)rc;
 }
 
-extern "C" int ivosw_mask_bbox_videos(const ivosw_video_t* videos, int n_videos, float* yxhw, int32_t* scratch, ivosw_stream_t stream) {
+// The table entries and their _lab twins (include/ivosw.h) share one body each: `labels` is NULL for the plain entry.
+// (IVOSW_REQUIRE with the entry's own name in the message instead of the shared body's)
+#define REQUIRE_AS(who, cond, msg) do { if (!(cond)) { ::ivosw::set_error("%s: %s", who, msg); return IVOSW_ERR_ARG; } } while (0)
+static int mask_bbox_videos_impl(const char* who, const ivosw_video_t* videos, const ivosw_labels_t* labels, int n_videos, float* yxhw,
+                                 int32_t* scratch, ivosw_stream_t stream) {
     VideoTable vt;
-    if (const int rc = video_table_build(videos, n_videos, __func__, &vt)) return rc;
-    IVOSW_REQUIRE(yxhw && scratch, "null pointer");
+    if (const int rc = video_table_build(videos, n_videos, who, &vt, labels)) return rc;
+    REQUIRE_AS(who, yxhw && scratch, "null pointer");
     IVOSW_ON_DEVICE_OF(yxhw);
     launch_mask_bbox_multi(vt, 0, vt.units, yxhw, scratch, as_stream(stream));
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }
 
-extern "C" int ivosw_roi_sample_videos(const ivosw_video_t* videos, int n_videos, const float* yxhw, int dtype, void* roi,
-                                       ivosw_stream_t stream) {
+extern "C" int ivosw_mask_bbox_videos(const ivosw_video_t* videos, int n_videos, float* yxhw, int32_t* scratch, ivosw_stream_t stream) {
+    return mask_bbox_videos_impl(__func__, videos, nullptr, n_videos, yxhw, scratch, stream);
+}
+
+extern "C" int ivosw_mask_bbox_videos_lab(const ivosw_video_t* videos, const ivosw_labels_t* labels, int n_videos, float* yxhw,
+                                          int32_t* scratch, ivosw_stream_t stream) {
+    return mask_bbox_videos_impl(__func__, videos, labels, n_videos, yxhw, scratch, stream);
+}
+
+static int roi_sample_videos_impl(const char* who, const ivosw_video_t* videos, const ivosw_labels_t* labels, int n_videos, const float* yxhw,
+                                  int dtype, void* roi, ivosw_stream_t stream) {
     VideoTable vt;
-    if (const int rc = video_table_build(videos, n_videos, __func__, &vt)) return rc;
-    IVOSW_REQUIRE(yxhw && roi, "null pointer");
-    IVOSW_REQUIRE(vt.units <= (1 << 24), "batch too large (units <= 2^24)");
-    IVOSW_REQUIRE(dtype == IVOSW_F32 || dtype == IVOSW_BF16 || dtype == IVOSW_F32X3, "dtype must be IVOSW_F32, IVOSW_BF16 or IVOSW_F32X3");
+    if (const int rc = video_table_build(videos, n_videos, who, &vt, labels)) return rc;
+    REQUIRE_AS(who, yxhw && roi, "null pointer");
+    REQUIRE_AS(who, vt.units <= (1 << 24), "batch too large (units <= 2^24)");
+    REQUIRE_AS(who, dtype == IVOSW_F32 || dtype == IVOSW_BF16 || dtype == IVOSW_F32X3, "dtype must be IVOSW_F32, IVOSW_BF16 or IVOSW_F32X3");
     IVOSW_ON_DEVICE_OF(roi);
     RoiNorm nrm{{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}, nullptr};  // Encoder.mean/std (assessment.py:41-44)
     launch_roi_sample_multi(vt, yxhw, 0, vt.units, dtype, nrm, roi, as_stream(stream));
@@ -923,30 +1141,72 @@ extern "C" int ivosw_roi_sample_videos(const ivosw_video_t* videos, int n_videos
     return IVOSW_OK;
 }
 
-extern "C" int ivosw_mask_delta_videos(const ivosw_video_t* videos, int n_videos, float* const* cache, const int* cold, int32_t* flags,
-                                       int32_t* unit_ids, int32_t* n_dirty, ivosw_stream_t stream) {
+extern "C" int ivosw_roi_sample_videos(const ivosw_video_t* videos, int n_videos, const float* yxhw, int dtype, void* roi,
+                                       ivosw_stream_t stream) {
+    return roi_sample_videos_impl(__func__, videos, nullptr, n_videos, yxhw, dtype, roi, stream);
+}
+
+extern "C" int ivosw_roi_sample_videos_lab(const ivosw_video_t* videos, const ivosw_labels_t* labels, int n_videos, const float* yxhw,
+                                           int dtype, void* roi, ivosw_stream_t stream) {
+    return roi_sample_videos_impl(__func__, videos, labels, n_videos, yxhw, dtype, roi, stream);
+}
+
+static int mask_delta_videos_impl(const char* who, const ivosw_video_t* videos, const ivosw_labels_t* labels, int n_videos,
+                                  void* const* cache, const int* cold, int32_t* flags, int32_t* unit_ids, int32_t* n_dirty,
+                                  ivosw_stream_t stream) {
     VideoTable vt;
-    if (const int rc = video_table_build(videos, n_videos, __func__, &vt)) return rc;
-    IVOSW_REQUIRE(cache && cold && flags && unit_ids && n_dirty, "null pointer");
+    if (const int rc = video_table_build(videos, n_videos, who, &vt, labels)) return rc;
+    REQUIRE_AS(who, cache && cold && flags && unit_ids && n_dirty, "null pointer");
     DeltaArgs da{};
-    size_t plane = 0;
+    LabDeltaArgs la{};
+    size_t plane = 0, lab_plane = 0;
+    long lab_frames = 0;
+    int n_float = 0;
+    for (int i = 0; i < IVOSW_MAX_VIDEOS; ++i) la.ffirst[i] = INT_MAX;
     for (int i = 0; i < vt.n; ++i) {
-        if (!cache[i]) { set_video_error(__func__, i, "null pointer (cache)"); return IVOSW_ERR_ARG; }
-        if (reinterpret_cast<uintptr_t>(cache[i]) & 3) { set_video_error(__func__, i, "cache must be 4-byte aligned"); return IVOSW_ERR_ARG; }
-        da.cache[i] = cache[i];
+        if (!cache[i]) { set_video_error(who, i, "null pointer (cache)"); return IVOSW_ERR_ARG; }
+        la.ffirst[i] = (int)lab_frames;
+        if (vt.v[i].lab) {                                         // a uint8 [n_frames][H*W] copy of the map: any alignment
+            la.cache[i] = static_cast<uint8_t*>(cache[i]);
+            la.cold[i] = cold[i] != 0;
+            la.vec[i] = vt.v[i].vec_ok && (reinterpret_cast<uintptr_t>(cache[i]) & 15) == 0;
+            lab_plane = std::max(lab_plane, (size_t)vt.v[i].H * vt.v[i].W);
+            lab_frames += vt.v[i].n_frames;
+            continue;
+        }
+        if (reinterpret_cast<uintptr_t>(cache[i]) & 3) { set_video_error(who, i, "cache must be 4-byte aligned"); return IVOSW_ERR_ARG; }
+        da.cache[i] = static_cast<float*>(cache[i]);
         da.cold[i] = cold[i] != 0;
         da.vec[i] = vt.v[i].vec_ok && (reinterpret_cast<uintptr_t>(cache[i]) & 15) == 0;
         plane = std::max(plane, (size_t)vt.v[i].H * vt.v[i].W);
+        ++n_float;
     }
     IVOSW_ON_DEVICE_OF(flags);
     const int S = (int)((plane + DELTA_CHUNK - 1) / DELTA_CHUNK);
-    IVOSW_REQUIRE((long)vt.units * S <= INT_MAX, "too many (unit, plane slice) workgroups for one launch");
+    const int SL = (int)((lab_plane + LAB_DELTA_CHUNK - 1) / LAB_DELTA_CHUNK);
+    REQUIRE_AS(who, (long)vt.units * S <= INT_MAX && lab_frames * SL <= INT_MAX, "too many (unit, plane slice) workgroups for one launch");
     hipStream_t st = as_stream(stream);
     hipLaunchKernelGGL(delta_init_kernel, dim3((vt.units + 255) / 256), dim3(256), 0, st, flags, vt.units);
-    hipLaunchKernelGGL(mask_delta_kernel, dim3((unsigned)(vt.units * S)), dim3(256), 0, st, vt, da, S, flags);
+    if (!vt.any_lab) {
+        hipLaunchKernelGGL(mask_delta_kernel<false>, dim3((unsigned)(vt.units * S)), dim3(256), 0, st, vt, da, S, flags);
+    } else {                                                       // up to two compare launches: the float videos' units, the label videos' frames
+        if (n_float) hipLaunchKernelGGL(mask_delta_kernel<true>, dim3((unsigned)(vt.units * S)), dim3(256), 0, st, vt, da, S, flags);
+        hipLaunchKernelGGL(mask_delta_lab_kernel, dim3((unsigned)(lab_frames * SL)), dim3(256), 0, st, vt, la, SL, flags);
+    }
     hipLaunchKernelGGL(delta_compact_kernel, dim3(1), dim3(1024), 0, st, flags, vt.units, unit_ids, n_dirty);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
+}
+
+extern "C" int ivosw_mask_delta_videos(const ivosw_video_t* videos, int n_videos, float* const* cache, const int* cold, int32_t* flags,
+                                       int32_t* unit_ids, int32_t* n_dirty, ivosw_stream_t stream) {
+    return mask_delta_videos_impl(__func__, videos, nullptr, n_videos, reinterpret_cast<void* const*>(cache), cold, flags, unit_ids, n_dirty,
+                                  stream);
+}
+
+extern "C" int ivosw_mask_delta_videos_lab(const ivosw_video_t* videos, const ivosw_labels_t* labels, int n_videos, void* const* cache,
+                                           const int* cold, int32_t* flags, int32_t* unit_ids, int32_t* n_dirty, ivosw_stream_t stream) {
+    return mask_delta_videos_impl(__func__, videos, labels, n_videos, cache, cold, flags, unit_ids, n_dirty, stream);
 }
 
 // what the *_units entries refuse about their list, before any launch
@@ -957,34 +1217,55 @@ static int unit_list_check(const char* who, const VideoTable& vt, const int32_t*
     return IVOSW_OK;
 }
 
-extern "C" int ivosw_mask_bbox_units(const ivosw_video_t* videos, int n_videos, const int32_t* unit_ids, int n_ids, float* yxhw,
-                                     int32_t* scratch, ivosw_stream_t stream) {
+static int mask_bbox_units_impl(const char* who, const ivosw_video_t* videos, const ivosw_labels_t* labels, int n_videos,
+                                const int32_t* unit_ids, int n_ids, float* yxhw, int32_t* scratch, ivosw_stream_t stream) {
     VideoTable vt;
-    if (const int rc = video_table_build(videos, n_videos, __func__, &vt)) return rc;
-    if (const int rc = unit_list_check(__func__, vt, unit_ids, n_ids)) return rc;
+    if (const int rc = video_table_build(videos, n_videos, who, &vt, labels)) return rc;
+    if (const int rc = unit_list_check(who, vt, unit_ids, n_ids)) return rc;
     if (n_ids == 0) return IVOSW_OK;
-    IVOSW_REQUIRE(yxhw && scratch, "null pointer");
+    REQUIRE_AS(who, yxhw && scratch, "null pointer");
     IVOSW_ON_DEVICE_OF(yxhw);
     launch_mask_bbox_multi(vt, 0, n_ids, yxhw, scratch, as_stream(stream), unit_ids);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }
 
-extern "C" int ivosw_roi_sample_units(const ivosw_video_t* videos, int n_videos, const int32_t* unit_ids, int n_ids, const float* yxhw,
-                                      int dtype, void* roi, ivosw_stream_t stream) {
+extern "C" int ivosw_mask_bbox_units(const ivosw_video_t* videos, int n_videos, const int32_t* unit_ids, int n_ids, float* yxhw,
+                                     int32_t* scratch, ivosw_stream_t stream) {
+    return mask_bbox_units_impl(__func__, videos, nullptr, n_videos, unit_ids, n_ids, yxhw, scratch, stream);
+}
+
+extern "C" int ivosw_mask_bbox_units_lab(const ivosw_video_t* videos, const ivosw_labels_t* labels, int n_videos, const int32_t* unit_ids,
+                                         int n_ids, float* yxhw, int32_t* scratch, ivosw_stream_t stream) {
+    return mask_bbox_units_impl(__func__, videos, labels, n_videos, unit_ids, n_ids, yxhw, scratch, stream);
+}
+
+static int roi_sample_units_impl(const char* who, const ivosw_video_t* videos, const ivosw_labels_t* labels, int n_videos,
+                                 const int32_t* unit_ids, int n_ids, const float* yxhw, int dtype, void* roi, ivosw_stream_t stream) {
     VideoTable vt;
-    if (const int rc = video_table_build(videos, n_videos, __func__, &vt)) return rc;
-    if (const int rc = unit_list_check(__func__, vt, unit_ids, n_ids)) return rc;
-    IVOSW_REQUIRE(dtype == IVOSW_F32 || dtype == IVOSW_BF16 || dtype == IVOSW_F32X3, "dtype must be IVOSW_F32, IVOSW_BF16 or IVOSW_F32X3");
+    if (const int rc = video_table_build(videos, n_videos, who, &vt, labels)) return rc;
+    if (const int rc = unit_list_check(who, vt, unit_ids, n_ids)) return rc;
+    REQUIRE_AS(who, dtype == IVOSW_F32 || dtype == IVOSW_BF16 || dtype == IVOSW_F32X3, "dtype must be IVOSW_F32, IVOSW_BF16 or IVOSW_F32X3");
     if (n_ids == 0) return IVOSW_OK;
-    IVOSW_REQUIRE(yxhw && roi, "null pointer");
-    IVOSW_REQUIRE(n_ids <= (1 << 24), "batch too large (n_ids <= 2^24)");
+    REQUIRE_AS(who, yxhw && roi, "null pointer");
+    REQUIRE_AS(who, n_ids <= (1 << 24), "batch too large (n_ids <= 2^24)");
     IVOSW_ON_DEVICE_OF(roi);
     RoiNorm nrm{{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}, nullptr};  // Encoder.mean/std (assessment.py:41-44)
     launch_roi_sample_multi(vt, yxhw, 0, n_ids, dtype, nrm, roi, as_stream(stream), unit_ids);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }
+
+extern "C" int ivosw_roi_sample_units(const ivosw_video_t* videos, int n_videos, const int32_t* unit_ids, int n_ids, const float* yxhw,
+                                      int dtype, void* roi, ivosw_stream_t stream) {
+    return roi_sample_units_impl(__func__, videos, nullptr, n_videos, unit_ids, n_ids, yxhw, dtype, roi, stream);
+}
+
+extern "C" int ivosw_roi_sample_units_lab(const ivosw_video_t* videos, const ivosw_labels_t* labels, int n_videos, const int32_t* unit_ids,
+                                          int n_ids, const float* yxhw, int dtype, void* roi, ivosw_stream_t stream) {
+    return roi_sample_units_impl(__func__, videos, labels, n_videos, unit_ids, n_ids, yxhw, dtype, roi, stream);
+}
+#undef REQUIRE_AS
 
 // ---------------------------------------------------------------- shader-clock probe (measurement aid, bench.py roofline.sclk_mhz)
 // One wave spins for `spin_us` of wall time and reports {shader cycles (s_memtime), 100 MHz wall ticks (s_memrealtime)} of the

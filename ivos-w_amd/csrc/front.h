@@ -33,14 +33,23 @@ struct VideoDesc {
     int n_frames, n_obj, H, W;
     int u8;                              // frame source: 0 fp32 planes, 1 RGBX8
     int vec_ok;                          // the scan may use 16-byte loads on this video's planes (what launch_mask_bbox derives)
+    // Label-map masks (include/ivosw.h: ivosw_labels_t).  lab != NULL: the video's masks are ONE uint8 [n_frames,H,W] map, object obj
+    // owns the value obj + 1, and the plane of unit (frame, obj) is (lab[frame * lab_stride + i] == obj + 1) ? 1.0f : 0.0f - `masks` and
+    // its strides are not looked at.  vec_ok then says: H * W % 16 == 0, map base and lab_stride 16-byte aligned (16 pixels per load).
+    const uint8_t* lab;
+    long lab_stride;                     // between frames, in elements (= bytes)
 };
 struct VideoTable {
     VideoDesc v[IVOSW_MAX_VIDEOS];
     int first[IVOSW_MAX_VIDEOS];         // first unit of video i; INT_MAX for i >= n
     int n, units;
+    int any_lab;                         // host only: some video is a label video - the launchers then run the Lab instantiations
 };
+// The table and the per-call pointer arrays next to it are kernel ARGUMENTS: together they must stay inside the 4 KB a launch carries.
+static_assert(sizeof(VideoTable) + IVOSW_MAX_VIDEOS * 16 + 64 <= 4096, "VideoTable + DeltaArgs no longer fit the kernel arguments");
 // Validates the caller's array (every refusal of include/ivosw.h, the message names the video) and fills the table.
-int video_table_build(const ivosw_video_t* videos, int n_videos, const char* who, VideoTable* out);
+// labels (may be NULL): the HOST array of the *_lab entries; labels[v].map != NULL makes video v a label video.
+int video_table_build(const ivosw_video_t* videos, int n_videos, const char* who, VideoTable* out, const ivosw_labels_t* labels = nullptr);
 // ids != NULL: rows [b0, b0 + B) of a unit list (a device array) instead of the units [b0, b0 + B): row b works on unit ids[b0 + b]
 void launch_mask_bbox_multi(const VideoTable& vt, int b0, int B, float* yxhw, int32_t* scratch, hipStream_t st, const int32_t* ids = nullptr);
 void launch_roi_sample_multi(const VideoTable& vt, const float* yxhw, int b0, int B, int dtype, const RoiNorm& nrm, void* roi, hipStream_t st,

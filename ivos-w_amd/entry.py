@@ -62,6 +62,9 @@ DEFAULTS = dict(
     rescore="all",                     # the assessment pass of an interaction scores "all" (frame, object) units, or only the "changed" ones:
                                        # the device compares every mask plane with the session's copy of the planes it was last scored on and
                                        # the tower sees the units that differ (same scores; utils_agent.score_cache holds the copies)
+    masks="float32",                   # how the assessment path holds a session's masks: "float32" probabilities [n,O+1,H,W] (the reference's
+                                       # all_P), or "labels": ONE uint8 [n,H,W] map of hard labels (models.assessment.LabelMasks; 1 byte per pixel
+                                       # and frame instead of 4 * (O + 1)) - the argmax of all_P, so its soft values are discarded
     report_save_dir="results",
     eval_max_nb_interactions=8,        # the eval scripts fix 8 interactions on the val subset (eval_agent_manet.py:64-65)
     data=dict(num_workers=0, root_dir_davis="data/DAVIS", root_dir_scribble_youtube_vos="data/Scribble_Youtube_VOS",
@@ -97,6 +100,25 @@ def frames_option(cfg):
     if not isinstance(mode, str) or mode not in FRAME_MODES:
         raise ValueError(f"frames must be 'float32' or 'uint8', got {mode!r}")
     return mode
+
+
+MASK_MODES = ("float32", "labels")
+
+
+def masks_option(cfg):
+    """cfg.masks (absent: "float32"), refused unless it is one of MASK_MODES."""
+    mode = cfg.get("masks", "float32")
+    if not isinstance(mode, str) or mode not in MASK_MODES:
+        raise ValueError(f"masks must be 'float32' or 'labels', got {mode!r}")
+    return mode
+
+
+def _harden(all_P, masks):
+    """What the recommender is handed in all_P's place: all_P itself, or under masks=labels its hard labels as a LabelMasks."""
+    if masks != "labels":
+        return all_P
+    from .models.assessment import LabelMasks
+    return LabelMasks.from_probs(all_P)
 
 
 def rescore_option(cfg):
@@ -144,6 +166,7 @@ def parse_cli(argv, **overrides):
         node[parts[-1]] = _coerce(val)
     try:
         frames_option(cfg)
+        masks_option(cfg)
         rescore_option(cfg)
     except ValueError as e:
         raise SystemExit(f"[ivos-w] {e}")
@@ -373,12 +396,17 @@ def _print_rescored(rescore, needs_assess):
     print(f"# rescore: changed  rescored {again} of {units} units ({100.0 * again / max(units, 1):.1f} %)")
 
 
+_MASKS_NOTE = ("[ivos-w] masks=labels: the soft probabilities of every interaction are hardened to their argmax (one uint8 label map per "
+               "session) before the assessment path sees them, so the numbers of this run differ from masks=float32")
+
+
 # ------------------------------------------------------------------------------------------ eval_agent_*  (synthetic back end)
 def run_eval(cfg, backbone="MANet"):
     """The loop of eval_agent_manet.py:246-480 on the synthetic back end.  Writes <report_save_dir>/summary.json =
     {"auc", "curve": {metric: [...]}} like the reference and returns it."""
     from .utils import misc, utils_agent, utils_manet
     frames = frames_option(cfg)                                        # (a bad value is refused here, before anything runs)
+    masks = masks_option(cfg)
     rescore = rescore_option(cfg)
     cfg.phase = "eval"
     cfg.data.subset = "val"
@@ -390,6 +418,8 @@ def run_eval(cfg, backbone="MANet"):
     if frames == "uint8":
         print("[ivos-w] frames=uint8: the synthetic frames are quantised with round(f * 255) and packed as RGBX8 on the device, so the "
               "numbers of this run differ from frames=float32 (on the real stack the decoded frames ARE bytes and the two modes agree)")
+    if masks == "labels":
+        print(_MASKS_NOTE)
     misc.set_random_seed(int(cfg.seed))
     davis = SyntheticDavis(cfg, device)
     needs_assess = cfg.setting == "wild" and cfg.method in ("ours", "worst")
@@ -423,7 +453,7 @@ def run_eval(cfg, backbone="MANet"):
             quality = misc.sequence_metric(metric, davis.load_annotations(sequence), labels, n_objects)
             tic = time.time()
             candidates = [int(i) for i in utils_agent.recommend_candidates(cfg, assess_net, agent, device, [dict(
-                n_frame=n_frame, n_objects=n_objects, all_F=all_F, all_P=all_P,
+                n_frame=n_frame, n_objects=n_objects, all_F=all_F, all_P=_harden(all_P, masks),
                 new_masks_quality=quality, prev_frames=prev_frames, annotated_frames_list=copy.deepcopy(annotated),
                 mask_quality=quality_pred, first_frame=first_frame, max_nb_interactions=max_nb)])[0]]
             next_frame = candidates[0]                                # the session annotates the first candidate
@@ -448,6 +478,7 @@ def run_eval(cfg, backbone="MANet"):
     _print_rescored(rescore, needs_assess)
     summary["backend"] = "synthetic"
     summary["frames"] = frames
+    summary["masks"] = masks
     summary["report_dir"] = report_dir
     return summary
 
@@ -468,7 +499,10 @@ def run_eval_real(cfg, backbone, device):
     from .utils import misc, utils_agent
     adapter_mod = importlib.import_module(adapter_module_name(backbone, cfg))
     frames = frames_option(cfg)
+    masks = masks_option(cfg)
     rescore = rescore_option(cfg)
+    if masks == "labels":
+        print(_MASKS_NOTE)
     misc.set_random_seed(int(cfg.seed))
     root = cfg.data.root_dir_davis
     needs_assess = cfg.setting == "wild" and cfg.method in ("ours", "worst")
@@ -525,7 +559,8 @@ def run_eval_real(cfg, backbone, device):
             quality = misc.sequence_metric(metric, gt_masks, new_masks, n_objects)
             tic = time.time()
             next_frame = int(utils_agent.recommend_frame(
-                cfg, assess_net, agent, device, n_frame=n_frame, n_objects=n_objects, all_F=all_F, all_P=all_P, new_masks_quality=quality,
+                cfg, assess_net, agent, device, n_frame=n_frame, n_objects=n_objects, all_F=all_F, all_P=_harden(all_P, masks),
+                new_masks_quality=quality,
                 prev_frames=prev_frames, annotated_frames_list=copy.deepcopy(annotated_list), mask_quality=quality_pred,
                 first_frame=first_frame, max_nb_interactions=max_nb))
             if prev_frames is not None:
@@ -550,6 +585,7 @@ def run_eval_real(cfg, backbone, device):
     _print_rescored(rescore, needs_assess)
     summary["backend"] = "real"
     summary["frames"] = frames
+    summary["masks"] = masks
     summary["report_dir"] = report_dir
     return summary
 

@@ -141,12 +141,77 @@ def pack_frames(u8, device, layout="hwc"):
     return PackedFrames(rgbx)
 
 
+MASK_KINDS = ("float32", "labels")
+
+
+class LabelMasks:
+    """The masks of a video as ONE hard label map on the device: ``map`` uint8 [n,H,W], value i + 1 = object i, 0 (and any value above
+    the number of objects) = no object - the format ivosw_seg_epilogue writes and ivosw_jf_counts reads.  Hand one to AssessNet /
+    utils_agent wherever an ``all_P`` is accepted: the plane of (frame, object i) is then (map == i + 1) as 1.0 / 0.0, and every result
+    is bit for bit what the float path gives on ``to_planes()`` - from 1 byte per pixel and frame instead of 4 * (objects + 1).
+    Only this type selects the label path: a plain uint8 tensor in all_P's place is cast to float as before.
+    The two last dimensions are made contiguous (a copy only if they are not); frames may be strided."""
+
+    def __init__(self, map):
+        if not isinstance(map, torch.Tensor) or map.dtype != torch.uint8:
+            raise TypeError("LabelMasks holds a torch.uint8 tensor")
+        if map.dim() != 3 or min(map.shape) < 1:
+            raise ValueError(f"LabelMasks holds a [n,H,W] tensor, got {tuple(map.shape)}")
+        n, H, W = (int(v) for v in map.shape)
+        if map.stride(2) != 1 or map.stride(1) != W or (n > 1 and map.stride(0) < H * W):
+            map = map.contiguous()
+        self.map = map
+        self.n, self.H, self.W = n, H, W
+
+    @property
+    def device(self):
+        return self.map.device
+
+    @property
+    def is_cuda(self):
+        return self.map.is_cuda
+
+    def __len__(self):
+        return self.n
+
+    def to(self, device):
+        """The same masks on ``device`` (self when they are there already)."""
+        device = torch.device(device)
+        return self if self.map.device == device else LabelMasks(self.map.to(device))
+
+    @classmethod
+    def from_probs(cls, all_P):
+        """all_P [n,C,H,W] (channel 0 = background, channel i + 1 = object i) -> its hard labels, ``all_P.argmax(1)`` with the FIRST
+        maximum on ties.  This DISCARDS the soft values: the float path scores the probabilities themselves (it thresholds them at
+        0.5 for the box and samples them for the tile), the label path scores the one-hot planes of the argmax."""
+        if not isinstance(all_P, torch.Tensor) or all_P.dim() != 4:
+            raise ValueError("from_probs takes all_P [n,C,H,W]")
+        if all_P.shape[1] > 256:
+            raise ValueError(f"a label map holds at most 255 objects, all_P has {all_P.shape[1] - 1}")
+        if all_P.is_cuda:
+            lab = all_P.argmax(1)
+        else:                                    # numpy's argmax names the first maximum by definition
+            lab = torch.from_numpy(np.argmax(all_P.detach().numpy(), axis=1))
+        return cls(lab.to(torch.uint8))
+
+    def to_planes(self, n_obj):
+        """The one-hot float32 [n, n_obj + 1, H, W] the label path is defined on: channel i + 1 = (map == i + 1), channel 0 = everything
+        else (label 0 and labels above n_obj).  For tests and fallbacks: 4 * (n_obj + 1) times the map's bytes."""
+        n_obj = int(n_obj)
+        if not 1 <= n_obj <= 255:
+            raise ValueError(f"n_obj must be 1 .. 255, got {n_obj}")
+        m = self.map[:, None].to(torch.int64)
+        obj = (m == torch.arange(1, n_obj + 1, device=self.map.device).view(1, n_obj, 1, 1)).to(torch.float32)
+        return torch.cat([1.0 - obj.sum(1, keepdim=True), obj], 1)
+
+
 class ScoreCache:
     """What one video's session keeps between interactions for the incremental forward (``AssessNet.forward_videos_incremental``): the
     planes it was last scored on (``planes``: dense [n_obj, n_frames, H*W] fp32 on the device, unit order), the score table
     (``scores`` [n_obj, n_frames]) and a key - the identity of the frames object (held by a STRONG reference, as utils_agent._FrameCache
     holds its host tensor, so the allocator cannot hand its address to another video while the entry lives), n_frames, n_obj, H, W, and
-    the net's precision and ``_weights_key()``.  Any mismatch makes the cache cold: every unit is scored again.  The key guards what the
+    the net's precision and ``_weights_key()``.  For a LabelMasks session ``planes`` is a uint8 [n_frames, H*W] copy of the map
+    instead, and the mask kind is part of the key.  Any mismatch makes the cache cold: every unit is scored again.  The key guards what the
     device comparison cannot see (other frames, other weights); the masks are compared bit for bit against whatever planes the cache
     holds, so a wrong guess about "same session" costs time, never results.  Frames rewritten in place behind an unchanged tensor
     object (through numpy, or .data) are not seen: drop the cache then (``utils_agent.clear_score_cache``).
@@ -157,20 +222,28 @@ class ScoreCache:
         self.units, self._rescored = 0, 0
 
     @staticmethod
-    def make_key(net, frames, n_frames, n_obj, H, W):
-        """(key, src): src is the object whose identity stands for the frames."""
+    def make_key(net, frames, n_frames, n_obj, H, W, masks="float32"):
+        """(key, src): src is the object whose identity stands for the frames.  masks: the kind of the session's masks (MASK_KINDS)."""
+        if masks not in MASK_KINDS:
+            raise ValueError(f"masks must be 'float32' or 'labels', got {masks!r}")
         src = frames
         t = frames.rgbx if isinstance(frames, PackedFrames) else frames
         ident = (t.data_ptr(), t._version) if isinstance(t, torch.Tensor) else ()
-        return (id(src), ident, int(n_frames), int(n_obj), int(H), int(W), net.precision, net._weights_key()), src
+        return (id(src), ident, int(n_frames), int(n_obj), int(H), int(W), net.precision, net._weights_key(), masks), src
 
     @staticmethod
-    def nbytes_for(n_frames, n_obj, H, W):
-        return 4 * int(n_frames) * int(n_obj) * (int(H) * int(W) + 1)
+    def nbytes_for(n_frames, n_obj, H, W, masks="float32"):
+        """Device bytes of a bound cache: the copy of the masks (fp32 planes per unit, or one uint8 map per frame) plus the score table."""
+        if masks not in MASK_KINDS:
+            raise ValueError(f"masks must be 'float32' or 'labels', got {masks!r}")
+        n_frames, n_obj, plane = int(n_frames), int(n_obj), int(H) * int(W)
+        if masks == "labels":
+            return n_frames * plane + 4 * n_frames * n_obj
+        return 4 * n_frames * n_obj * (plane + 1)
 
     @property
     def nbytes(self):
-        return 0 if self.key is None else self.nbytes_for(*self.key[2:6])
+        return 0 if self.key is None else self.nbytes_for(*self.key[2:6], masks=self.key[8])
 
     @property
     def rescored(self):
@@ -178,14 +251,16 @@ class ScoreCache:
             self._rescored = int(self._rescored.item())
         return self._rescored
 
-    def bind(self, net, frames, n_frames, n_obj, H, W, device):
-        """Make the cache one for this video; returns True when it is cold (its planes and scores are undefined)."""
-        key, src = self.make_key(net, frames, n_frames, n_obj, H, W)
+    def bind(self, net, frames, n_frames, n_obj, H, W, device, masks="float32"):
+        """Make the cache one for this video; returns True when it is cold (its planes and scores are undefined).  Switching the mask
+        kind changes the key: the cache turns cold and its copy is reallocated in the other format."""
+        key, src = self.make_key(net, frames, n_frames, n_obj, H, W, masks)
         device = torch.device(device)
         warm = (self.key == key and self.src is src and self.planes is not None and self.planes.device == device)
         if not warm:
-            if self.planes is None or self.planes.device != device or self.planes.numel() != n_obj * n_frames * H * W:
-                self.planes = torch.empty(n_obj * n_frames * H * W, dtype=torch.float32, device=device)
+            numel, dt = (n_frames * H * W, torch.uint8) if masks == "labels" else (n_obj * n_frames * H * W, torch.float32)
+            if self.planes is None or self.planes.device != device or self.planes.numel() != numel or self.planes.dtype != dt:
+                self.planes = torch.empty(numel, dtype=dt, device=device)
             self.scores = torch.empty(n_obj, n_frames, dtype=torch.float32, device=device)
             self.key, self.src = key, src
         self.units = n_obj * n_frames
@@ -311,6 +386,8 @@ class AssessNet(nn.Module):
         Returns [n_objects, n] fp32 on the device."""
         if self.training:
             raise RuntimeError("AssessNet on the MI355X path is inference-only; call .eval()")
+        if isinstance(all_P, LabelMasks):                   # label-map masks: the table path with one video (the only one that reads them)
+            return self.forward_videos([(all_F, all_P, n_objects)])[0]
         u8 = isinstance(all_F, PackedFrames)
         if u8:
             n, H, W = all_F.n, all_F.H, all_F.W
@@ -338,8 +415,8 @@ class AssessNet(nn.Module):
         return scores
 
     def _video_entry(self, k, video, keep):
-        """One (all_F | PackedFrames, all_P, n_objects) of forward_videos -> (L.Video, n), normalised by forward_objects' rules; tensors the
-        descriptor points into are appended to `keep`."""
+        """One (all_F | PackedFrames, all_P | LabelMasks, n_objects) of forward_videos -> (L.Video, L.Labels, n), normalised by
+        forward_objects' rules; tensors the descriptors point into are appended to `keep`.  The Labels entry of a float video is empty."""
         all_F, all_P, n_objects = video
         n_objects = int(n_objects)
         u8 = isinstance(all_F, PackedFrames)
@@ -351,6 +428,14 @@ class AssessNet(nn.Module):
             assert C3 == 3, f"video {k}: all_F must be [n,3,H,W]"
             if all_F.dtype != torch.float32 or not all_F.is_contiguous():
                 all_F = all_F.detach().to(torch.float32).contiguous()
+        kind = L.FRAMES_RGBX8 if u8 else L.FRAMES_F32
+        if isinstance(all_P, LabelMasks):
+            assert (all_P.n, all_P.H, all_P.W) == (n, H, W) and n_objects >= 1, f"video {k}: LabelMasks shape"
+            if not all_P.is_cuda or all_P.device != all_F.device:
+                raise RuntimeError(f"ivos_w_amd: video {k}: the label map must live on the frames' GPU (there is no CPU fallback)")
+            keep += [all_F, all_P.map]
+            return (L.Video(L.dptr(all_F).value, None, 0, 0, kind, n, n_objects, H, W),
+                    L.Labels(all_P.map.data_ptr(), all_P.map.stride(0) if n > 1 else H * W), n)
         assert all_P.shape[0] == n and tuple(all_P.shape[2:]) == (H, W) and all_P.shape[1] > n_objects >= 1, f"video {k}: all_P shape"
         if all_P.dtype != torch.float32 or all_P.stride(3) != 1 or all_P.stride(2) != W:
             all_P = all_P.detach().to(torch.float32).contiguous()
@@ -358,8 +443,7 @@ class AssessNet(nn.Module):
             raise RuntimeError(f"ivos_w_amd: video {k}: all_P must live on the frames' GPU (there is no CPU fallback)")
         masks = all_P[:, 1:]                                # a view: channel 0 is the background
         keep += [all_F, all_P]
-        return L.Video(L.dptr(all_F).value, masks.data_ptr(), all_P.stride(0), all_P.stride(1),
-                       L.FRAMES_RGBX8 if u8 else L.FRAMES_F32, n, n_objects, H, W), n
+        return L.Video(L.dptr(all_F).value, masks.data_ptr(), all_P.stride(0), all_P.stride(1), kind, n, n_objects, H, W), L.Labels(None, 0), n
 
     def forward_videos(self, videos):
         """Scores of every (object, frame) unit of SEVERAL videos in one pass (ivosw_assess_forward_videos): ``videos`` is a sequence of
@@ -372,10 +456,11 @@ class AssessNet(nn.Module):
         videos = list(videos)
         if not videos:
             return []
-        keep, descs, shapes = [], [], []
+        keep, descs, labs, shapes = [], [], [], []
         for k, video in enumerate(videos):
-            d, n = self._video_entry(k, video, keep)
+            d, lab, n = self._video_entry(k, video, keep)
             descs.append(d)
+            labs.append(lab)
             shapes.append((d.n_obj, n))
         dev = keep[0].device
         packed = self._ensure_packed()
@@ -383,16 +468,24 @@ class AssessNet(nn.Module):
         scores = torch.empty(sum(o * n for o, n in shapes), dtype=torch.float32, device=dev)
         off = 0
         for g in range(0, len(descs), L.MAX_VIDEOS):
-            group = descs[g:g + L.MAX_VIDEOS]
+            group, glab = descs[g:g + L.MAX_VIDEOS], labs[g:g + L.MAX_VIDEOS]
             arr = (L.Video * len(group))(*group)
-            units = int(lib.ivosw_assess_videos_units(arr, len(group)))
-            if units < 0:
-                L.check(units, "assess_videos_units")
+            larr = (L.Labels * len(group))(*glab) if any(lab.map for lab in glab) else None       # the _lab entry only with a label video
+            if larr is None:
+                units = int(lib.ivosw_assess_videos_units(arr, len(group)))
+                if units < 0:
+                    L.check(units, "assess_videos_units")
+            else:
+                units = sum(d.n_frames * d.n_obj for d in group)
             nbytes = lib.ivosw_assess_ws_bytes(dt, units, group[0].H, group[0].W, self.chunk)     # (H, W are not looked at)
             ws = self._ws.get(nbytes, dev)
             out = scores[off:off + units]
-            L.check(lib.ivosw_assess_forward_videos(L.dptr(packed), dt, arr, len(group), L.dptr(out), L.dptr(ws), nbytes, self.chunk,
-                                                    0, None, L.stream_ptr(dev)), "assess_forward_videos")
+            if larr is None:
+                L.check(lib.ivosw_assess_forward_videos(L.dptr(packed), dt, arr, len(group), L.dptr(out), L.dptr(ws), nbytes, self.chunk,
+                                                        0, None, L.stream_ptr(dev)), "assess_forward_videos")
+            else:
+                L.check(lib.ivosw_assess_forward_videos_lab(L.dptr(packed), dt, arr, larr, len(group), L.dptr(out), L.dptr(ws), nbytes,
+                                                            self.chunk, 0, None, L.stream_ptr(dev)), "assess_forward_videos_lab")
             off += units
         views, off = [], 0
         for o, n in shapes:
@@ -417,10 +510,11 @@ class AssessNet(nn.Module):
         sources = [v[0] for v in videos] if sources is None else list(sources)
         if not videos:
             return []
-        keep, descs, shapes = [], [], []
+        keep, descs, labs, shapes = [], [], [], []
         for k, video in enumerate(videos):
-            d, n = self._video_entry(k, video, keep)
+            d, lab, n = self._video_entry(k, video, keep)
             descs.append(d)
+            labs.append(lab)
             shapes.append((d.n_obj, n))
         dev = keep[0].device
         packed = self._ensure_packed()
@@ -428,29 +522,41 @@ class AssessNet(nn.Module):
         scores = torch.empty(sum(o * n for o, n in shapes), dtype=torch.float32, device=dev)
         off = 0
         for g in range(0, len(descs), L.MAX_VIDEOS):
-            group, gc = descs[g:g + L.MAX_VIDEOS], caches[g:g + L.MAX_VIDEOS]
+            group, gc, glab = descs[g:g + L.MAX_VIDEOS], caches[g:g + L.MAX_VIDEOS], labs[g:g + L.MAX_VIDEOS]
             arr = (L.Video * len(group))(*group)
-            units = int(lib.ivosw_assess_videos_units(arr, len(group)))
-            if units < 0:
-                L.check(units, "assess_videos_units")
+            larr = (L.Labels * len(group))(*glab) if any(lab.map for lab in glab) else None       # the _lab entries only with a label video
+            if larr is None:
+                units = int(lib.ivosw_assess_videos_units(arr, len(group)))
+                if units < 0:
+                    L.check(units, "assess_videos_units")
+            else:
+                units = sum(d.n_frames * d.n_obj for d in group)
             out = scores[off:off + units]
             cold, o = [], 0
-            for d, c, src in zip(group, gc, sources[g:g + L.MAX_VIDEOS]):
-                cold.append(c.bind(self, src, d.n_frames, d.n_obj, d.H, d.W, dev))
+            for d, lab, c, src in zip(group, glab, gc, sources[g:g + L.MAX_VIDEOS]):
+                cold.append(c.bind(self, src, d.n_frames, d.n_obj, d.H, d.W, dev, masks="labels" if lab.map else "float32"))
                 if not cold[-1]:
                     out[o:o + c.units].copy_(c.scores.view(-1))      # the table of the last call; the dirty entries are overwritten below
                 o += c.units
             ptrs = (ctypes.c_void_p * len(group))(*[c.planes.data_ptr() for c in gc])
             meta = torch.empty(2 * units + 1, dtype=torch.int32, device=dev)       # [flags (units) | unit ids (units) | n_dirty]
             flags, ids, n_dirty = meta[:units], meta[units:2 * units], meta[2 * units:]
-            L.check(lib.ivosw_mask_delta_videos(arr, len(group), ptrs, L.int_array(cold), L.dptr(flags), L.dptr(ids), L.dptr(n_dirty), st),
-                    "mask_delta_videos")
+            if larr is None:
+                L.check(lib.ivosw_mask_delta_videos(arr, len(group), ptrs, L.int_array(cold), L.dptr(flags), L.dptr(ids), L.dptr(n_dirty), st),
+                        "mask_delta_videos")
+            else:
+                L.check(lib.ivosw_mask_delta_videos_lab(arr, larr, len(group), ptrs, L.int_array(cold), L.dptr(flags), L.dptr(ids),
+                                                        L.dptr(n_dirty), st), "mask_delta_videos_lab")
             n_ids = int(n_dirty.item())                                 # the one synchronisation of the incremental path
             if n_ids:
                 nbytes = lib.ivosw_assess_units_ws_bytes(dt, n_ids, self.chunk)
                 ws = self._ws.get(nbytes, dev)
-                L.check(lib.ivosw_assess_forward_units(L.dptr(packed), dt, arr, len(group), L.dptr(ids), n_ids, L.dptr(out), L.dptr(ws),
-                                                       nbytes, self.chunk, st), "assess_forward_units")
+                if larr is None:
+                    L.check(lib.ivosw_assess_forward_units(L.dptr(packed), dt, arr, len(group), L.dptr(ids), n_ids, L.dptr(out), L.dptr(ws),
+                                                           nbytes, self.chunk, st), "assess_forward_units")
+                else:
+                    L.check(lib.ivosw_assess_forward_units_lab(L.dptr(packed), dt, arr, larr, len(group), L.dptr(ids), n_ids, L.dptr(out),
+                                                               L.dptr(ws), nbytes, self.chunk, st), "assess_forward_units_lab")
             o = 0
             for c, was_cold in zip(gc, cold):
                 c.scores.view(-1).copy_(out[o:o + c.units])

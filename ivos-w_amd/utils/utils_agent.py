@@ -157,6 +157,19 @@ def _is_packed(all_F):
     return isinstance(all_F, PackedFrames)
 
 
+def _is_labels(all_P):
+    from ..models.assessment import LabelMasks
+    return isinstance(all_P, LabelMasks)
+
+
+def _masks_on(all_P, device):
+    """all_P - a float tensor or a LabelMasks (masks=labels) - on ``device``: handed on when it is there, uploaded when it is not."""
+    device = torch.device(device)
+    if _is_labels(all_P):
+        return all_P.to(device)
+    return all_P if (all_P.is_cuda and all_P.device == device) else all_P.to(device)
+
+
 def pack_video(u8, device, layout="hwc"):
     """The decoded 8-bit frames of a video ([n,H,W,3], or [n,3,H,W] with layout="chw"; torch or numpy uint8, host or device) ->
     ``models.assessment.PackedFrames`` on ``device``: a quarter of the fp32 video's bytes over PCIe and in HBM.  Hand the result to
@@ -176,7 +189,7 @@ def clear_frame_cache():
 
 RESCORE_MODES = ("all", "changed")
 # score_cache keeps the sessions' plane copies and score tables up to this many bytes (least recently used first out).  One 100-frame,
-# 3-object 480p session costs 0.49 GB (300 planes of 480 x 854 fp32).
+# 3-object 480p session costs 0.49 GB (300 planes of 480 x 854 fp32), or 41 MB with label-map masks (100 uint8 maps).
 SCORE_CACHE_BYTES = 8 << 30
 
 
@@ -212,13 +225,14 @@ class _ScoreCacheLRU:
         """One ScoreCache per (all_F, all_P, n_objects) of a call, made on first sight; the ones handed out become the most recent."""
         from ..models.assessment import ScoreCache
         out, seen = [], {}
-        for all_F, _, n_objects in videos:
+        for all_F, all_P, n_objects in videos:             # (all_P is looked at for its kind only: a LabelMasks or not)
             n, H, W = _video_dims(all_F)
-            key, _ = ScoreCache.make_key(assess_net, all_F, n, int(n_objects), H, W)
+            kind = "labels" if _is_labels(all_P) else "float32"
+            key, _ = ScoreCache.make_key(assess_net, all_F, n, int(n_objects), H, W, kind)
             rank = seen[key] = seen.get(key, -1) + 1
             entry = self.entries.get((key, rank))
             if entry is None or (entry[0].src is not None and entry[0].src is not all_F):
-                entry = (ScoreCache(), ScoreCache.nbytes_for(n, int(n_objects), H, W))
+                entry = (ScoreCache(), ScoreCache.nbytes_for(n, int(n_objects), H, W, kind))
             self.entries[(key, rank)] = entry
             self.entries.move_to_end((key, rank))
             out.append(entry[0])
@@ -275,7 +289,7 @@ def clear_score_cache():
 
 def _forward_changed(assess_net, on_dev, sources):
     """forward_videos through the score caches: on_dev = the device-resident (frames, probs, n_objects), sources = the callers' all_F."""
-    caches = score_cache.get_many(assess_net, [(src, None, v[2]) for src, v in zip(sources, on_dev)])
+    caches = score_cache.get_many(assess_net, [(src, v[1] if _is_labels(v[1]) else None, v[2]) for src, v in zip(sources, on_dev)])
     out = assess_net.forward_videos_incremental(on_dev, caches, sources=sources)
     score_cache.account(caches)
     return out
@@ -287,7 +301,7 @@ def assess_all_objects_device(assess_net, all_F, all_P, n_objects, device, resco
     indirection inside ivosw_assess_forward_objects) - nothing is repeated, transposed or copied.
     rescore="changed": only the units whose masks changed since this video was last scored are scored again (score_cache); same values."""
     frames = frame_cache.get(all_F, device)
-    probs = all_P if (all_P.is_cuda and all_P.device == torch.device(device)) else all_P.to(device)
+    probs = _masks_on(all_P, device)                     # (a LabelMasks - masks=labels - travels in all_P's place)
     if rescore == "changed":
         return _forward_changed(assess_net, [(frames, probs, n_objects)], [all_F])[0]
     return assess_net.forward_objects(frames, probs, n_objects)
@@ -335,7 +349,7 @@ def _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, cou
 
 def assess_videos_device(assess_net, videos, device, rescore="all"):
     """Quality predictions of SEVERAL videos from one assessment pass (AssessNet.forward_videos): ``videos`` is a sequence of
-    (all_F | PackedFrames, all_P, n_objects); returns one [n_objects, n_frame] device tensor per video, each bit for bit what
+    (all_F | PackedFrames, all_P | LabelMasks, n_objects); returns one [n_objects, n_frame] device tensor per video, each bit for bit what
     ``assess_all_objects_device`` gives for that video alone.  Host-resident tensors are uploaded for this call only: the single-entry
     ``frame_cache`` is neither read nor written (several videos would evict each other on every call) - multi-session callers keep
     their videos on the device (``pack_video``, or ``all_F.to(device)`` once per sequence).
@@ -347,9 +361,7 @@ def assess_videos_device(assess_net, videos, device, rescore="all"):
         sources.append(all_F)
         if not _is_packed(all_F) and not (all_F.is_cuda and all_F.device == device):
             all_F = all_F.to(device=device, dtype=torch.float32)
-        if not (all_P.is_cuda and all_P.device == device):
-            all_P = all_P.to(device)
-        on_dev.append((all_F, all_P, n_objects))
+        on_dev.append((all_F, _masks_on(all_P, device), n_objects))
     if rescore == "changed":
         return _forward_changed(assess_net, on_dev, sources)
     return assess_net.forward_videos(on_dev)
