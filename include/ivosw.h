@@ -572,6 +572,42 @@ int ivosw_seg_epilogue(const float* logits, int n, int C, int hs, int ws, int H,
                        long probs_stride_n, long probs_stride_c, int64_t* label_i64, uint8_t* label_u8,
                        float* label_f32, ivosw_stream_t stream);
 
+/* ------------------------------------------------------------------ ATNet epilogue (8f-4, ATNet) */
+/* Replaces, for ONE frame t of run_VOS_singleiact (utils/utils_atnet.py), torch.sigmoid(output_logit)[:, 0], the blend
+ * (alpha * prob) + ((1 - alpha) * prob_map_of_frames[t]) and the store into prob_map_of_frames[t] (:100-101,123-124,146-150), and
+ * that frame's share of the end-of-interaction combine_masks_with_batch(...)[:, 0, hpad1:-hpad2, wpad1:-wpad2] and
+ * torch.cat([zeros, prob_map], 1)[..., hpad1:-hpad2, wpad1:-wpad2] (:152-159).  One launch, one streaming pass, no allocation and no
+ * copy (capture-safe).  ATNet propagates frame by frame - each frame's input is the previous frame's output - so a call is one frame.
+ *   logits      [n_obj,PH,PW] fp32 on the padded grid, or NULL.
+ *   prob_map_t  [n_obj,PH,PW] fp32: frame t of prob_map_of_frames, read and written IN PLACE.
+ *   crop        the window rows hpad1 .. hpad1+H-1, columns wpad1 .. wpad1+W-1 of the padded grid.
+ * Per padded pixel and object: s = sigmoid(logit) in fp32 (1 / (1 + expf(-x)), IEEE division: sigmoid(0) == 0.5f exactly, finite in
+ * [0, 1] for every finite logit); p = blend ? fadd_rn(fmul_rn(alpha32, s), fmul_rn(beta32, old)) : s - three separately rounded
+ * operations, never an FMA, as torch's three ops are; pass alpha32 = (float)alpha and beta32 = (float)(1 - alpha) with 1 - alpha formed in
+ * double, which is what torch makes of a Python scalar.  logits == NULL: p = old, nothing is blended, prob_map_t and prob_pad are NOT
+ * written - the mode that rebuilds a store slot and labels from an existing map (a resumed session, a frame the loop did not visit).
+ * Label of a pixel: o* = the FIRST index of max_o p[o]; the label is o* + 1 if p[o*] > th (strictly), else 0.  This rule is the
+ * definition: it restates combine_masks_with_batch(prob, n_obj, th) of the ATNet clone's libs/utils_torch.py, which is not part of the
+ * reference tree - parity with the clone is unpinned.  NaN logits: unspecified.
+ * Outputs, each optional:
+ *   prob_map_t  p over the whole padded grid (whenever logits != NULL).
+ *   prob_pad    [n_obj,PH,PW]: the UNBLENDED s - output_prob_anno / output_prob_prop, the next forward_TNet call's predmask_prev.
+ *   probs       window only: p of object o at (y, x) goes to probs[o * probs_stride_c + y * W + x]; pass the address of channel 1,
+ *               frame t of an object-major store and n_total * H * W as the stride (channel 0, the reference's bg_dummy zeros, is
+ *               zeroed once when the store is made).
+ *   label_u8 / label_f32  [H,W]: the label at [y * W + x].
+ * 16-byte loads and stores on the padded planes when PW % 4 == 0 and logits, prob_map_t and prob_pad are 16-byte aligned; the window
+ * outputs are shifted by wpad1 against the padded rows, so they go out as vectors only when wpad1 % 4 == 0, W % 4 == 0,
+ * probs_stride_c % 4 == 0 and probs / label_f32 (16 bytes) and label_u8 (4 bytes) are aligned, else element by element beside vector
+ * loads.  Everything else takes a scalar kernel (IVOSW_ATNET_SCALAR in the environment forces it); all paths agree bit for bit.
+ * Refused (IVOSW_ERR_ARG) before any launch, nothing written: a NULL prob_map_t, n_obj < 1, n_obj > 255 with label_u8, H or W < 1,
+ * hpad1 or wpad1 < 0, hpad1 + H > PH or wpad1 + W > PW, probs_stride_c < H * W with probs and n_obj > 1, PH * PW or n_obj * PH * PW >
+ * INT_MAX, a blend that is not 0 / 1, blend with NULL logits, and a call with nothing to write (NULL logits and no probs, label_u8 or
+ * label_f32).                                                                                                                       */
+int ivosw_atnet_epilogue(const float* logits, float* prob_map_t, int n_obj, int PH, int PW, int hpad1, int wpad1, int H, int W,
+                         int blend, float alpha32, float beta32, float th, float* prob_pad, float* probs, long probs_stride_c,
+                         uint8_t* label_u8, float* label_f32, ivosw_stream_t stream);
+
 /* ------------------------------------------------------------------ launch-sequence capture ---- */
 /* HIP-graph capture of any sequence of the calls above on one stream (not in the reference: it replaces the ~40 host
  * launches per Agent.update_agent step, models/agent.py:128-160, by ONE hipGraphLaunch).  begin puts `stream` (non-null)
