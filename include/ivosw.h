@@ -608,6 +608,46 @@ int ivosw_atnet_epilogue(const float* logits, float* prob_map_t, int n_obj, int 
                          int blend, float alpha32, float beta32, float th, float* prob_pad, float* probs, long probs_stride_c,
                          uint8_t* label_u8, float* label_f32, ivosw_stream_t stream);
 
+/* ------------------------------------------------------------------ IPN glue (8f-4, IPN) */
+/* The host code between the IPN clone's model.Run and the tensors the rest of the loop consumes (utils/utils_ipn.py), on the device.
+ * Both entries are one streaming pass each, allocate nothing and copy nothing (capture-safe); IVOSW_IPN_SCALAR in the environment
+ * forces their element-by-element kernels, which agree with the vector ones bit for bit.
+ *
+ * ivosw_ipn_dilate: the whole of Dilate_mask (:26-34) for n scribble maps [n,H,W] int8 (sparse, indexed, -1 = ignore) in ONE launch.
+ *   out[y,x] = the largest o in 0 .. num_objects found among the pixels (y+dy, x+dx) with |dy| + |dx| <= 2 that lie inside the image,
+ *   -1 if there is none; input values outside -1 .. num_objects count as -1.
+ * This is what the reference's loop yields: two iterations of the 3x3 cross are the radius-2 diamond, cv2's default border never
+ * contributes to a dilation, and the ascending object loop with overwrite is a maximum.  4-byte loads and stores (4 pixels of a row per
+ * lane) when W % 4 == 0 and mask and out are 4-byte aligned, else element by element.
+ * Refused (IVOSW_ERR_ARG) before any launch, nothing written: a NULL mask or out, n, H or W < 1, num_objects outside 0 .. 126,
+ * H * W > INT_MAX, out == mask.                                                                                                       */
+int ivosw_ipn_dilate(const int8_t* mask, int n, int H, int W, int num_objects, int8_t* out, ivosw_stream_t stream);
+
+/* ivosw_ipn_merge: one interaction's end for the whole session - the merge of the new estimate with the earlier rounds' by the
+ * Get_weight weights (:37-72), To_np_label (:75-81) and all_P (eval_agent_ipn.py:261).
+ *   all_E, prev_E  [K,T,H,W] fp32 on the device: IPN's 1,o,t,h,w without the batch axis, K = objects + background.
+ *   w_new32, w_old32  HOST arrays of length T, read during the call; they travel inside the kernel arguments, in launches of at most 256
+ *                  frames each.  Pass (float)w and (float)(1 - w) with 1 - w formed in double: what torch makes of Python scalars.
+ *   index          HOST int[K], a permutation of 0 .. K-1, NULL = identity: index[j] is the canonical channel held at position j, so
+ *                  canonical channel i is read from position inv[i].
+ * With prev_E: e = fadd_rn(fmul_rn(w_new32[f], all_E), fmul_rn(w_old32[f], prev_E)) - three separately rounded operations, never an FMA,
+ * on EVERY frame, those with weight 1 included - written back to all_E in place.  With prev_E == NULL nothing is blended, all_E is not
+ * written and the weights may be NULL.  This blend rule is the definition: IPN's model.Run lives in the external clone, not in the
+ * reference tree, so parity with the clone's own merge is unpinned.
+ * Outputs, each optional:
+ *   probs          canonical channel i of frame f goes to probs[i * probs_stride_c + f * H * W + p] (an object-major store).  Pass NULL
+ *                  when index is the identity: all_E itself is then the store.
+ *   label_u8 / label_f32  [T,H,W]: the FIRST maximum over i = 0 .. K-1 of the merged estimate, as numpy's argmax gives it: a NaN is the
+ *                  maximum, and the first NaN wins; -0.0 and 0.0 tie.
+ * 16-byte loads and stores when H * W % 4 == 0 and all_E, prev_E, probs, probs_stride_c and label_f32 are on the 16-byte grid (label_u8
+ * on the 4-byte grid), else element by element.
+ * Refused (IVOSW_ERR_ARG) before any launch, nothing written: a NULL all_E, K outside 1 .. 32 (and K > 256 with label_u8), T, H or W < 1,
+ * H * W > INT_MAX or K * T * H * W > 2^40 (offsets are long; nothing larger is addressed), an index that is not a permutation, prev_E
+ * without both weight arrays, probs overlapping all_E, probs_stride_c < T * H * W (or (K - 1) * probs_stride_c + T * H * W > 2^40) with
+ * K > 1, and a call with nothing to write (no prev_E, probs, label_u8 or label_f32).                                                    */
+int ivosw_ipn_merge(float* all_E, const float* prev_E, int K, int T, int H, int W, const float* w_new32, const float* w_old32,
+                    const int* index, float* probs, long probs_stride_c, uint8_t* label_u8, float* label_f32, ivosw_stream_t stream);
+
 /* ------------------------------------------------------------------ launch-sequence capture ---- */
 /* HIP-graph capture of any sequence of the calls above on one stream (not in the reference: it replaces the ~40 host
  * launches per Agent.update_agent step, models/agent.py:128-160, by ONE hipGraphLaunch).  begin puts `stream` (non-null)

@@ -125,6 +125,8 @@ SIGNATURES = {
     "ivosw_jf_counts": (_i, [_p, _p, _i, _i, _i, C.c_char_p, _i, _i, _p, _p, _sz, _p]),
     "ivosw_seg_epilogue": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, C.c_long, C.c_long, _p, _p, _p, _p]),
     "ivosw_atnet_epilogue": (_i, [_p, _p] + [_i] * 8 + [_f, _f, _f, _p, _p, C.c_long, _p, _p, _p]),
+    "ivosw_ipn_dilate": (_i, [_p, _i, _i, _i, _i, _p, _p]),
+    "ivosw_ipn_merge": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, C.c_long, _p, _p, _p]),
     "ivosw_graph_begin": (_i, [_p]),
     "ivosw_graph_end": (_i, [_p, C.POINTER(_p), C.POINTER(_i)]),
     "ivosw_graph_launch": (_i, [_p, _p]),
