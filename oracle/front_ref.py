@@ -12,6 +12,14 @@ float64 references of the small kernels around the conv tower, and the test inpu
   * ``quality_ref``    pred.mean(1) of the reference's float64 [n_frames, n_obj] array (numpy's own summation order)
   * ``head_ref``       float64 mean over the 8 x 8 positions, float64 dot product with fc1
 
+and, for the table-driven front end (tests/test_oracle_front_multi.py, tests/test_gpu_front_multi_edges.py):
+
+  * ``scan_seams_multi`` / ``scan_edges``   the chunk of a launch over a video table and the flat indices at which a lone pixel
+                       shows a wrong chunk seam, stride or last vector (float4 scan and 16-byte label scan)
+  * ``scan_walk``      the kernel's carried (y, x) walk, with switches for two deliberately wrong scans
+  * ``label_planes`` / ``label_delta_ref``   the one-hot planes of a label map in unit order, and the dirty units between two maps
+  * ``hard_byte_map``  label bytes next to the values a sloppy zero-byte test confuses them with
+
 Plain numpy; imports nothing from the product.
 """
 import numpy as np
@@ -116,14 +124,148 @@ def bbox_planes(H, W):
     return np.stack(ps).astype(np.float32), seams
 
 
-def stride_edges(H, W):
+def stride_edges(H, W, stride=1024, vec=4):
     """Flat indices on each side of every 1024-element stride of the float4 scan (a workgroup of 256 lanes x 4 elements advances
-    by 1024 and carries (y, x) across), plus the plane's first and last pixels and the ends of the first and last row."""
+    by 1024 and carries (y, x) across), plus the plane's first and last pixels, its last vector and the ends of the first and last
+    row.  ``stride=4096, vec=16``: the same for the 16-pixel byte vectors of the label scan."""
     plane = H * W
-    pos = {0, W - 1, plane - W, plane - 1, max(0, plane - 4)}
-    for s in range(1024, plane, 1024):
-        pos |= {s - 1, s, min(plane - 1, s + 3)}
+    pos = {0, W - 1, plane - W, plane - 1, max(0, plane - vec)}
+    for s in range(stride, plane, stride):
+        pos |= {s - 1, s, min(plane - 1, s + vec - 1)}
     return sorted(pos)
+
+
+# ---------------------------------------------------------------- mask -> box over a video table (units, label maps)
+def scan_seams_multi(planes, B):
+    """The rule of launch_mask_bbox_multi restated: a launch over B unit rows whose videos' planes hold ``planes`` elements asks for
+    S = max(1, min(64, 2048 // B)) workgroups per row, cuts the LARGEST plane into chunks of ceil(max(planes) / S) elements rounded up
+    to 1024 and recomputes S from that chunk; every video is cut at the same chunk, and a workgroup that starts behind a smaller
+    plane leaves.  -> (chunk, [the seams inside plane p for p in planes])."""
+    planes = [int(p) for p in planes]
+    big = max(planes)
+    S = max(1, min(64, 2048 // int(B)))
+    chunk = -(-big // S)
+    chunk = -(-chunk // 1024) * 1024
+    S = -(-big // chunk)
+    seams = [list(range(chunk, p, chunk)) for p in planes]
+    assert max(len(s) for s in seams) == S - 1
+    return chunk, seams
+
+
+def scan_edges(H, W, chunk, stride=1024, vec=4):
+    """Where a lone pixel shows a wrong chunked vector scan of an H x W plane (``stride`` = 1024 elements and ``vec`` = 4 for the float
+    scan, 4096 and 16 for the label scan): both sides of every seam between two chunks, both sides of every stride a workgroup takes
+    INSIDE its chunk (counted from the chunk's start: 7168 is no multiple of 4096) with the last element of the vector that starts
+    there, the plane's first and last element, the first element of its last vector and the ends of the first and last row."""
+    plane = H * W
+    pos = {0, W - 1, plane - W, plane - 1, max(0, plane - vec)}
+    for beg in range(0, plane, chunk):
+        if beg:
+            pos |= {beg - 1, beg}
+        for s in range(beg + stride, min(plane, beg + chunk), stride):
+            pos |= {s - 1, s, min(plane - 1, s + vec - 1)}
+    return sorted(pos)
+
+
+def lone_positions(H, W, B, label=False, strides=True):
+    """(chunk, scan_edges) of ONE H x W plane scanned in a launch of B rows; ``strides=False`` leaves the strides inside a chunk out
+    (480 x 854 at S = 64 has 58 x 6 of them: the carried step there is already used by the pixel before every seam)."""
+    chunk, _ = scan_seams_multi([H * W], B)
+    stride, vec = (4096, 16) if label else (1024, 4)
+    return chunk, scan_edges(H, W, chunk, stride if strides else chunk, vec)
+
+
+def scan_walk(p, H, W, chunk, stride=1024, vec=4, wrap=True, drop_last=False):
+    """The (y, x) at which the vector scan of bbox_scan_multi_kernel meets flat index p, by the kernel's own walk: the lane's first
+    vector of the chunk gets its coordinates from a division, every later visit from the carried step (sy, sx) = divmod(stride, W)
+    with one row wrap, and the elements inside a vector count on with a wrap each.  Equal to divmod(p, W) when the walk is right.
+    The two switches build the WRONG scans that the lone-pixel inputs have to tell from the right one: ``wrap=False`` forgets the row
+    wrap of the carried step, ``drop_last=True`` never visits the last vector of a chunk (-> None)."""
+    plane = H * W
+    beg = p // chunk * chunk
+    end = min(plane, beg + chunk)
+    o = p - beg
+    if drop_last and o >= (end - beg) - vec:
+        return None
+    first = beg + o % stride // vec * vec
+    y, x = divmod(first, W)
+    sy, sx = divmod(stride, W)
+    for _ in range(o // stride):
+        y, x = y + sy, x + sx
+        if wrap and x >= W:
+            y, x = y + 1, x - W
+    for _ in range(o % vec):
+        x += 1
+        if x == W:
+            y, x = y + 1, 0
+    return y, x
+
+
+def label_planes(lab, n_obj):
+    """lab [n_frames,H,W] uint8 -> the one-hot planes of include/ivosw.h in unit order, float32 [n_obj * n_frames, H, W]: the plane of
+    unit obj * n_frames + frame is (lab[frame] == obj + 1) ? 1 : 0.  The box reference of a label video is bbox_ref / bbox_minmax_ref
+    on these planes."""
+    lab = np.asarray(lab, np.uint8)
+    return np.concatenate([(lab == o + 1).astype(np.float32) for o in range(n_obj)], 0)
+
+
+def label_delta_ref(old, new, n_obj):
+    """old, new [n_frames,H,W] uint8 -> the dirty units of ivosw_mask_delta_videos_lab on a warm video, ascending, numbered inside the
+    video (obj * n_frames + frame): a byte going a -> b dirties (frame, a - 1) and (frame, b - 1) when those labels lie in 1 .. n_obj."""
+    old, new = np.asarray(old, np.uint8), np.asarray(new, np.uint8)
+    n_frames = old.shape[0]
+    f = np.nonzero(old != new)[0]
+    dirty = set()
+    for lab in (old[old != new], new[old != new]):
+        ok = (lab >= 1) & (lab <= n_obj)
+        dirty |= set(((lab[ok].astype(np.int64) - 1) * n_frames + f[ok]).tolist())
+    return sorted(dirty)
+
+
+MULTI_CARRY_SIZES = ((70, 1100), (80, 1024))                     # chunk 2048 at B <= 32: the second visit is carried (sy = 0 / sx = 0)
+ONE_CHUNK_SIZES = ((4, 1025), (4, 1024), (4, 1100), (2048, 2), (8, 8))
+LABEL_ONE_CHUNK_SIZES = ((16, 1100), (16, 1024))
+
+
+def hard_bytes(label):
+    """Twelve bytes around ``label`` for a zero-byte test on word ^ label: two words that hold the label next to label ^ 0x80,
+    label - 1, label + 1, 0 and 255, and one that holds only those neighbours (for label 255 the 255 is left out)."""
+    lo, hi, fl, top = (label - 1) & 255, (label + 1) & 255, label ^ 0x80, 255 if label != 255 else 0
+    return np.array([fl, label, lo, hi, label, 0, top, fl, fl, lo, hi, top], np.uint8)
+
+
+def hard_byte_map():
+    """uint8 [5,16,256] for n_obj = 255: label L's twelve hard_bytes sit in the 16-byte vector at flat index 16 * L (at a word offset
+    that alternates), on a background of 0.  Frame 0 holds the even labels below 128, frame 1 the odd ones, frames 2 and 3 the same
+    above 127 - so no frame holds a label together with label - 1, label + 1 or label ^ 0x80 as labels of their own, and the plane of
+    a frame's own label is exactly its two bytes (255 alone is everybody's neighbour: frame 4 holds only its block)."""
+    m = np.zeros((5, 16 * 256), np.uint8)
+    for lab in range(1, 256):
+        f = 4 if lab == 255 else 2 * (lab >> 7) + (lab & 1)
+        at = 16 * lab + 4 * ((lab >> 1) & 1)
+        m[f, at:at + 12] = hard_bytes(lab)
+    return m.reshape(5, 16, 256)
+
+
+def hard_byte_units(n_obj=255):
+    """(frame, label) of the hard_byte_map units whose plane is exactly the label's own two bytes."""
+    return [(4 if lab == 255 else 2 * (lab >> 7) + (lab & 1), lab) for lab in range(1, n_obj + 1)]
+
+
+def lone_planes(H, W, positions):
+    """float32 [len(positions), H, W]: plane k is zero but for a 1 at flat index positions[k]."""
+    out = np.zeros((len(positions), H * W), np.float32)
+    out[np.arange(len(positions)), np.asarray(positions, np.int64)] = 1.0
+    return out.reshape(-1, H, W)
+
+
+def lone_label_map(H, W, positions):
+    """uint8 [H, W] (up to 255 positions): label k + 1 at flat index positions[k] and nowhere else, 0 around - the one-hot plane of
+    object k is lone_planes' plane k."""
+    assert len(positions) <= 255 and len(set(positions)) == len(positions)
+    out = np.zeros(H * W, np.uint8)
+    out[np.asarray(positions, np.int64)] = np.arange(1, len(positions) + 1)
+    return out.reshape(H, W)
 
 
 # ---------------------------------------------------------------- ROI sampler
