@@ -560,6 +560,49 @@ const char* ivosw_assess_dominant_kernel(int dtype);
 size_t ivosw_jf_ws_bytes(int N, int H, int W, int n_obj);
 int ivosw_jf_counts(const uint8_t* gt, const uint8_t* pred, int N, int H, int W, const uint8_t* obj_ids,
                     int n_obj, int bound_pix, int64_t* counts, void* ws, size_t ws_bytes, ivosw_stream_t stream);
+/* ivosw_jf_counts for several videos in ONE pass: one memset, one boundary launch and one match launch whatever their number.
+ * `videos` is a HOST array of n_videos (1 .. IVOSW_MAX_JF_VIDEOS) descriptors with DEVICE label maps; it is read during the call only
+ * and travels to the kernels inside their arguments (no allocation, no copy: capture-safe).  Per video: gt, pred uint8
+ * [n_frames,H,W], the n_obj (1 .. 32) label values to score in obj_ids, and bound_pix (0 .. 32) - each video its own; the disk's half
+ * widths are derived from bound_pix inside the kernel.  The frame / (frame, object) grid dimension runs flat over the videos, the row,
+ * column and word dimensions are sized by the largest video; a workgroup beyond its own video's extent returns before it forms an address.
+ * counts is flat and video-major: video v's [n_frames][n_obj][6] block follows those of the videos before it.  Per video the six
+ * integers equal those of ivosw_jf_counts on that video alone, exactly.  Workspace: ivosw_jf_videos_ws_bytes(videos, n_videos) = the sum
+ * of ivosw_jf_ws_bytes over the videos (0 if the array would be refused), owned by the caller.
+ * Refused (IVOSW_ERR_ARG) before anything is launched, the message names the video's index: a NULL pointer, n_videos outside
+ * [1, IVOSW_MAX_JF_VIDEOS], n_frames, H or W < 1, n_obj outside 1 .. 32, bound_pix outside 0 .. 32, H * ceil(W / 32) > 2^30, more than
+ * 65535 frames in total (the boundary kernel's flat grid dimension) or more than 65535 (frame, object) pairs in total (the match
+ * kernel's): the message says which, and the caller splits the group.  A short workspace: IVOSW_ERR_WS.                              */
+#define IVOSW_MAX_JF_VIDEOS 32
+typedef struct ivosw_jf_video {
+    const uint8_t* gt;                           /* device */
+    const uint8_t* pred;                         /* device */
+    int n_frames, H, W, n_obj;
+    uint8_t obj_ids[32];
+    int bound_pix;
+} ivosw_jf_video_t;
+size_t ivosw_jf_videos_ws_bytes(const ivosw_jf_video_t* videos, int n_videos);
+int ivosw_jf_counts_videos(const ivosw_jf_video_t* videos, int n_videos, int64_t* counts, void* ws, size_t ws_bytes,
+                           ivosw_stream_t stream);
+/* The last step of J / F on the device: the float64 ratios and their per-frame mean over the objects for n_seqs (1 .. IVOSW_MAX_SEQS)
+ * videos in ONE launch, from the flat counts ivosw_jf_counts_videos (or ivosw_jf_counts per video, concatenated) wrote.  n_obj and
+ * lengths are HOST arrays (they travel inside the kernel's arguments); R = the sum of lengths.
+ * Per (frame, object), in float64 with every operation rounded by itself (no FMA contraction), the expressions of
+ * ivos_w_amd/metrics.py: J = 1 when the union is 0, else inter / union; precision / recall = 1 / 0, 0 / 1, 1 / 1 when the pred
+ * boundary, the gt boundary or both are empty, else matched / total; F = 0 when precision + recall == 0, else
+ * ((2 * precision) * recall) / (precision + recall).  Per frame the mean over the objects is numpy's ndarray.mean(axis=1) on a
+ * C-contiguous float64 [N,O] array: its pairwise summation order along the row (sequential below 8 objects) and one division by O.
+ * IVOSW_METRIC_J_AND_F is .5 * mean(J) + .5 * mean(F).
+ * quality [R] float64.  per_obj (nullable) [sum of n_obj * lengths] float64, flat in the order of counts: the un-averaged values (J,
+ * F, or .5 * J + .5 * F).  state (nullable together with annot_counts [R] fp32) [R,2] fp32 = (float32(quality), annot_counts): the
+ * Brain's input.  No atomics, no workspace; capture-safe.
+ * Refused (IVOSW_ERR_ARG) before the launch, naming the video's index: what ivosw_brain_ragged_rows refuses, an n_obj outside
+ * 1 .. 32, a metric outside the enum, a NULL counts / n_obj / lengths / quality, state without annot_counts or the reverse.          */
+#define IVOSW_METRIC_J 0
+#define IVOSW_METRIC_F 1
+#define IVOSW_METRIC_J_AND_F 2
+int ivosw_jf_reduce_ragged(const int64_t* counts, const int* n_obj, const int* lengths, int n_seqs, int metric,
+                           const float* annot_counts, double* per_obj, double* quality, float* state, ivosw_stream_t stream);
 
 /* ------------------------------------------------------------------ segmentation epilogue (8f-4) */
 /* Replaces, per frame batch, F.interpolate(logits, (H,W), 'bilinear', align_corners=True) -> argmax(dim=1)

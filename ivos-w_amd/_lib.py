@@ -24,6 +24,8 @@ MAX_VIDEOS = 32                                      # IVOSW_MAX_VIDEOS
 MAX_SEQS = 128                                       # IVOSW_MAX_SEQS
 MAX_CANDIDATES = 16                                  # IVOSW_MAX_CANDIDATES
 FRAMES_F32, FRAMES_RGBX8 = 0, 1                      # IVOSW_FRAMES_*
+MAX_JF_VIDEOS = 32                                   # IVOSW_MAX_JF_VIDEOS
+METRIC_J, METRIC_F, METRIC_J_AND_F = 0, 1, 2         # IVOSW_METRIC_*
 
 
 class Video(C.Structure):
@@ -35,6 +37,12 @@ class Video(C.Structure):
 class Labels(C.Structure):
     """ivosw_labels_t: the label map of one video of a *_lab call (device pointer, frame stride in elements); map = None: a float video."""
     _fields_ = [("map", C.c_void_p), ("stride_frame", C.c_long)]
+
+
+class JfVideo(C.Structure):
+    """ivosw_jf_video_t: one video of a multi-video J / F pass (device label maps, the label values to score, the F tolerance in pixels)."""
+    _fields_ = [("gt", C.c_void_p), ("pred", C.c_void_p), ("n_frames", C.c_int), ("H", C.c_int), ("W", C.c_int), ("n_obj", C.c_int),
+                ("obj_ids", C.c_uint8 * 32), ("bound_pix", C.c_int)]
 
 
 SIGNATURES = {
@@ -123,6 +131,9 @@ SIGNATURES = {
     "ivosw_assess_dominant_kernel": (C.c_char_p, [_i]),
     "ivosw_jf_ws_bytes": (_sz, [_i, _i, _i, _i]),
     "ivosw_jf_counts": (_i, [_p, _p, _i, _i, _i, C.c_char_p, _i, _i, _p, _p, _sz, _p]),
+    "ivosw_jf_videos_ws_bytes": (_sz, [_p, _i]),
+    "ivosw_jf_counts_videos": (_i, [_p, _i, _p, _p, _sz, _p]),
+    "ivosw_jf_reduce_ragged": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
     "ivosw_seg_epilogue": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, C.c_long, C.c_long, _p, _p, _p, _p]),
     "ivosw_atnet_epilogue": (_i, [_p, _p] + [_i] * 8 + [_f, _f, _f, _p, _p, C.c_long, _p, _p, _p]),
     "ivosw_ipn_dilate": (_i, [_p, _i, _i, _i, _i, _p, _p]),

@@ -18,6 +18,10 @@
 //                       boundary-pixel counts (DPP wave reduction, one atomic per counter and block)
 //   jf_match_kernel     one thread = one boundary word of map A: skipped when empty (boundaries are sparse), otherwise
 //                       ORs the (2r+1) row-smears of map B around it (disk = per-row half widths) and counts A & dil(B)
+// Several sessions (ivosw_jf_counts_videos, ivosw_jf_reduce_ragged; the oracle chain of utils_agent.oracle_recommend): the same two
+// bodies over a table of per-video descriptors in the kernel arguments (jf_*_videos_kernel), and
+//   jf_reduce_ragged_kernel  one thread = one frame: the host's float64 ratio expressions and numpy's row mean on the device, so the
+//                       counts no longer travel to the host between the J / F pass and the Brain
 #include "common.h"
 #include <stdlib.h>
 
@@ -39,6 +43,27 @@ struct JfArgs {
     uint32_t* bp;                 // pred boundary bitmaps
     unsigned long long* counts;   // [N][n_obj][6]: inter, union, n_fg (pred boundary), n_gt, fg_match, gt_match
 };
+
+// One video of ivosw_jf_counts_videos as the kernels see it, and the table that travels in their arguments (32 x 88 + 2 x 132 + 32
+// bytes = 3112 of the 4 KB budget).  The field names are JfArgs's, so one body serves both.
+struct JfVideo {
+    const uint8_t* gt;
+    const uint8_t* pred;
+    int N, H, W, WW, n_obj, r;
+    uint8_t ids[JF_MAX_OBJ];
+    unsigned long long bm_off;        // words from the workspace base to the video's gt bitmaps; its pred bitmaps follow plane_words later
+    unsigned long long plane_words;
+    unsigned long long cnt_off;       // elements from counts to the video's [N][n_obj][6] block
+};
+struct JfTable {
+    JfVideo v[IVOSW_MAX_JF_VIDEOS];
+    int frame_off[IVOSW_MAX_JF_VIDEOS + 1];     // video k owns the flat frames [frame_off[k], frame_off[k + 1])
+    int fo_off[IVOSW_MAX_JF_VIDEOS + 1];        // ... and the flat (frame, object) pairs [fo_off[k], fo_off[k + 1])
+    int n_videos;
+    uint32_t* bitmaps;
+    unsigned long long* counts;
+};
+static_assert(sizeof(JfTable) <= 3584, "the table must fit the kernel-argument budget (4 KB) with room to spare");
 
 }  // namespace
 
@@ -90,10 +115,13 @@ __device__ __forceinline__ void load16(const uint8_t* base, size_t off, size_t t
 // A wave walks JF_RPW consecutive rows: the south row of one step is the own row of the next, so JF_RPW + 1 row loads and
 // mask computations serve JF_RPW rows, and the counts are reduced once per object and wave (the kernel is VALU-bound).
 constexpr int JF_RPW = 4;
-__global__ __launch_bounds__(256) void jf_boundary_row_kernel(JfArgs a) {
+// The body serves both descriptor sources: `a` is the single video's JfArgs (ivosw_jf_counts) or one JfVideo of the table
+// (ivosw_jf_counts_videos) - the same field names; bgm / bpm / counts are that video's bitmaps and count block, n its frame.
+template <class A>
+__device__ __forceinline__ void jf_boundary_body(const A& a, uint32_t* __restrict__ bgm, uint32_t* __restrict__ bpm,
+                                                 unsigned long long* __restrict__ counts, int n, int seg, int yblk) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = blockIdx.z, seg = blockIdx.y;
-    const int y0 = (blockIdx.x * 4 + wave) * JF_RPW;
+    const int y0 = (yblk * 4 + wave) * JF_RPW;
     const int x0 = seg * 1024 + lane * 16;
     const bool col_live = x0 < a.W;
     const size_t total = (size_t)a.N * a.H * a.W;
@@ -151,8 +179,8 @@ __global__ __launch_bounds__(256) void jf_boundary_row_kernel(JfArgs a) {
             const uint32_t hg = lane_next(bgw), hp = lane_next(bpw);
             if (row_ok && col_live && !(lane & 1)) {
                 const size_t widx = (((size_t)o * a.N + n) * a.H + y) * a.WW + (x0 >> 5);
-                a.bg[widx] = bgw | (hg << 16);
-                a.bp[widx] = bpw | (hp << 16);
+                bgm[widx] = bgw | (hg << 16);
+                bpm[widx] = bpw | (hp << 16);
             }
             const uint32_t sg = mg[r] & 0xffffu, sp = mp[r] & 0xffffu;
             // each count is <= 16 per lane and row, <= 4096 per wave: two counters share one 32-bit word through the reduction
@@ -165,21 +193,49 @@ __global__ __launch_bounds__(256) void jf_boundary_row_kernel(JfArgs a) {
         __syncthreads();
         if (threadIdx.x < 4) {
             const unsigned long long v = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-            if (v) atomicAdd(a.counts + ((size_t)n * a.n_obj + o) * 6 + threadIdx.x, v);
+            if (v) atomicAdd(counts + ((size_t)n * a.n_obj + o) * 6 + threadIdx.x, v);
         }
         __syncthreads();
     }
 }
 
+__global__ __launch_bounds__(256) void jf_boundary_row_kernel(JfArgs a) {
+    jf_boundary_body(a, a.bg, a.bp, a.counts, blockIdx.z, blockIdx.y, blockIdx.x);
+}
+
+// Several videos in one launch (ivosw_jf_counts_videos): grid.z runs flat over the frames of all videos, grid.x / grid.y are sized by
+// the tallest / widest video.  A block finds its video in the prefix table and returns, before it forms any address, when it lies beyond
+// that video's own rows or columns (block-uniform: no barrier is skipped by part of a block).
+__device__ __forceinline__ int jf_find_video(const int* off, int n_videos, int i) {
+    int lo = 0, hi = n_videos - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (off[mid] <= i) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(256) void jf_boundary_row_videos_kernel(JfTable t) {
+    const int v = jf_find_video(t.frame_off, t.n_videos, blockIdx.z);
+    const JfVideo& a = t.v[v];
+    if ((int)blockIdx.x * (4 * JF_RPW) >= a.H || (int)blockIdx.y * 1024 >= a.W) return;
+    uint32_t* bgm = t.bitmaps + a.bm_off;
+    jf_boundary_body(a, bgm, bgm + a.plane_words, t.counts + a.cnt_off, (int)blockIdx.z - t.frame_off[v], blockIdx.y, blockIdx.x);
+}
+
 // grid (blocks over H*WW, N * n_obj, 2): z = 0 counts pred-boundary pixels inside dil(gt boundary) (fg_match),
 // z = 1 gt-boundary pixels inside dil(pred boundary) (gt_match)
-__global__ __launch_bounds__(256) void jf_match_kernel(JfArgs a) {
-    const int on = blockIdx.y;                    // o * N + n
+// `hw(d)`: the disk's half width at |dy| = d - the table in the single video's arguments, or the one a block of the multi-video
+// kernel derives from bound_pix.  on = o * N + n inside the video, z = 0 / 1 as above.
+template <class A, class HW>
+__device__ __forceinline__ void jf_match_body(const A& a, const uint32_t* __restrict__ bgm, const uint32_t* __restrict__ bpm,
+                                              unsigned long long* __restrict__ counts, HW hw, int on, int xblk, int z) {
     const int o = on / a.N, n = on - o * a.N;
-    const int item = blockIdx.x * 256 + threadIdx.x;
+    const int item = xblk * 256 + threadIdx.x;
     const int y = item / a.WW, j = item - y * a.WW;
-    const uint32_t* own = (blockIdx.z == 0 ? a.bp : a.bg) + (size_t)on * a.H * a.WW;
-    const uint32_t* oth = (blockIdx.z == 0 ? a.bg : a.bp) + (size_t)on * a.H * a.WW;
+    const uint32_t* own = (z == 0 ? bpm : bgm) + (size_t)on * a.H * a.WW;
+    const uint32_t* oth = (z == 0 ? bgm : bpm) + (size_t)on * a.H * a.WW;
     unsigned long long c = 0;
     if (y < a.H) {
         const uint32_t mine = own[(size_t)y * a.WW + j];
@@ -202,7 +258,7 @@ __global__ __launch_bounds__(256) void jf_match_kernel(JfArgs a) {
                 for (int k = 0; k < 8; ++k) {
                     if (!(cu[k] | pv[k] | nx[k])) continue;
                     const int dy = d0 + k;
-                    const int w = a.hw[dy < 0 ? -dy : dy];
+                    const int w = hw(dy < 0 ? -dy : dy);
                     // a set bit at x covers x-w .. x+w: smear towards higher x inside [prev | cur], towards lower x inside [cur | next]
                     uint64_t sl = (uint64_t)pv[k] | ((uint64_t)cu[k] << 32), sr = (uint64_t)cu[k] | ((uint64_t)nx[k] << 32);
                     for (int covered = 0; covered < w;) {
@@ -220,8 +276,31 @@ __global__ __launch_bounds__(256) void jf_match_kernel(JfArgs a) {
     // boundaries are sparse: most waves have nothing to add and skip the reduction; a word contributes <= 32
     if (__ballot(c != 0) != 0ull) {
         const uint32_t t = wave_total_in_lane63((uint32_t)c);
-        if ((threadIdx.x & 63) == 63 && t) atomicAdd(a.counts + ((size_t)n * a.n_obj + o) * 6 + 4 + blockIdx.z, (unsigned long long)t);
+        if ((threadIdx.x & 63) == 63 && t) atomicAdd(counts + ((size_t)n * a.n_obj + o) * 6 + 4 + z, (unsigned long long)t);
     }
+}
+
+__global__ __launch_bounds__(256) void jf_match_kernel(JfArgs a) {
+    jf_match_body(a, a.bg, a.bp, a.counts, [&](int d) { return (int)a.hw[d]; }, blockIdx.y, blockIdx.x, blockIdx.z);
+}
+
+// grid (blocks over the largest H * WW, all (frame, object) pairs of all videos, 2).  The disk's half widths are not carried per video
+// (33 bytes x 32 videos would not fit the argument budget): the first r + 1 threads of a block derive them from bound_pix.
+__global__ __launch_bounds__(256) void jf_match_videos_kernel(JfTable t) {
+    const int v = jf_find_video(t.fo_off, t.n_videos, blockIdx.y);
+    const JfVideo& a = t.v[v];
+    if ((long long)blockIdx.x * 256 >= (long long)a.H * a.WW) return;
+    __shared__ uint8_t hw_s[JF_MAX_R + 1];
+    if ((int)threadIdx.x <= a.r) {
+        const int d = threadIdx.x;
+        int w = 0;
+        while ((w + 1) * (w + 1) + d * d <= a.r * a.r) ++w;
+        hw_s[d] = (uint8_t)w;
+    }
+    __syncthreads();
+    const uint32_t* bgm = t.bitmaps + a.bm_off;
+    jf_match_body(a, bgm, bgm + a.plane_words, t.counts + a.cnt_off, [&](int d) { return (int)hw_s[d]; }, (int)blockIdx.y - t.fo_off[v],
+                  blockIdx.x, blockIdx.z);
 }
 
 }  // namespace ivosw
@@ -264,6 +343,228 @@ extern "C" int ivosw_jf_counts(const uint8_t* gt, const uint8_t* pred, int N, in
     const unsigned nblk = (unsigned)(((size_t)H * a.WW + 255) / 256);
     hipLaunchKernelGGL(jf_boundary_row_kernel, dim3((H + 4 * JF_RPW - 1) / (4 * JF_RPW), (W + 1023) / 1024, N), dim3(256), 0, st, a);
     hipLaunchKernelGGL(jf_match_kernel, dim3(nblk, N * n_obj, 2), dim3(256), 0, st, a);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ several videos in one pass
+namespace ivosw {
+namespace {
+
+// Host-side check of a descriptor array (the caller has checked the pointer and names itself): fills the table (nullable) and the
+// totals, or returns IVOSW_ERR_ARG with the message set.  Nothing is launched before it has passed.
+int jf_videos_table(const char* who, const ivosw_jf_video_t* videos, int n_videos, JfTable* t, size_t* ws_bytes, size_t* n_counts,
+                    int* max_h, int* max_w, long long* max_words) {
+    if (n_videos < 1 || n_videos > IVOSW_MAX_JF_VIDEOS) {
+        set_error("%s: n_videos %d outside [1, %d]", who, n_videos, IVOSW_MAX_JF_VIDEOS);
+        return IVOSW_ERR_ARG;
+    }
+    size_t bytes = 0, cnt = 0;
+    long long frames = 0, pairs = 0, words = 0;
+    int mh = 0, mw = 0;
+    for (int k = 0; k < n_videos; ++k) {
+        const ivosw_jf_video_t& d = videos[k];
+        const char* why = nullptr;
+        if (!d.gt || !d.pred) why = "a NULL label map";
+        else if (d.n_frames < 1 || d.H < 1 || d.W < 1) why = "n_frames, H and W must be positive";
+        else if (d.n_obj < 1 || d.n_obj > JF_MAX_OBJ) why = "1..32 object ids";
+        else if (d.bound_pix < 0 || d.bound_pix > JF_MAX_R) why = "boundary tolerance 0..32 pixels";
+        else if ((long long)d.H * ((d.W + 31) / 32) > (1LL << 30)) why = "H * W too large";
+        if (why) {
+            set_error("%s: video %d: %s", who, k, why);
+            return IVOSW_ERR_ARG;
+        }
+        const int ww = (d.W + 31) / 32;
+        const size_t plane = align_up((size_t)d.n_obj * d.n_frames * d.H * ww * sizeof(uint32_t), 256);
+        if (t) {
+            JfVideo& v = t->v[k];
+            v.gt = d.gt; v.pred = d.pred; v.N = d.n_frames; v.H = d.H; v.W = d.W; v.WW = ww; v.n_obj = d.n_obj; v.r = d.bound_pix;
+            memcpy(v.ids, d.obj_ids, JF_MAX_OBJ);
+            v.bm_off = bytes / sizeof(uint32_t);
+            v.plane_words = plane / sizeof(uint32_t);
+            v.cnt_off = cnt;
+            t->frame_off[k] = (int)frames;
+            t->fo_off[k] = (int)pairs;
+        }
+        bytes += 2 * plane;
+        cnt += (size_t)d.n_frames * d.n_obj * 6;
+        frames += d.n_frames;
+        pairs += (long long)d.n_frames * d.n_obj;
+        if (frames > 65535) {
+            set_error("%s: video %d: more than 65535 frames in total (the boundary kernel's flat grid dimension): split the group", who, k);
+            return IVOSW_ERR_ARG;
+        }
+        if (pairs > 65535) {
+            set_error("%s: video %d: more than 65535 (frame, object) pairs in total (the match kernel's flat grid dimension): split the group",
+                      who, k);
+            return IVOSW_ERR_ARG;
+        }
+        mh = d.H > mh ? d.H : mh;
+        mw = d.W > mw ? d.W : mw;
+        words = (long long)d.H * ww > words ? (long long)d.H * ww : words;
+    }
+    if (t) {
+        for (int k = n_videos; k <= IVOSW_MAX_JF_VIDEOS; ++k) {
+            t->frame_off[k] = (int)frames;
+            t->fo_off[k] = (int)pairs;
+        }
+        for (int k = n_videos; k < IVOSW_MAX_JF_VIDEOS; ++k) t->v[k] = JfVideo{};
+        t->n_videos = n_videos;
+    }
+    if (ws_bytes) *ws_bytes = bytes;
+    if (n_counts) *n_counts = cnt;
+    if (max_h) *max_h = mh;
+    if (max_w) *max_w = mw;
+    if (max_words) *max_words = words;
+    return IVOSW_OK;
+}
+
+// J and F of one (frame, object) from its six counts, with the expressions of ivos_w_amd/metrics.py (_jaccard_from, _f_from) in float64.
+// Contraction is off in everything below: every product, sum and quotient is rounded by itself, as on the host.
+#pragma clang fp contract(off)
+__device__ __forceinline__ double jf_jaccard(const long long* c) {
+    return c[1] == 0 ? 1.0 : (double)c[0] / (double)c[1];         // np.isclose(union, 0) on an integer count: union == 0
+}
+__device__ __forceinline__ double jf_fmeasure(const long long* c) {
+    const long long n_fg = c[2], n_gt = c[3];
+    double precision, recall;
+    if (n_fg == 0 && n_gt > 0) { precision = 1.0; recall = 0.0; }
+    else if (n_fg > 0 && n_gt == 0) { precision = 0.0; recall = 1.0; }
+    else if (n_fg == 0 && n_gt == 0) { precision = 1.0; recall = 1.0; }
+    else { precision = (double)c[4] / (double)n_fg; recall = (double)c[5] / (double)n_gt; }
+    const double s = precision + recall;
+    if (s == 0.0) return 0.0;
+    const double twice = 2.0 * precision;
+    const double prod = twice * recall;
+    return prod / s;
+}
+// ndarray.mean(axis=1) of a C-contiguous float64 row: numpy's pairwise add.reduce (sequential below 8 elements, else 8 interleaved
+// partial sums combined pairwise plus a sequential tail; rows are at most 32 long, below its 128-element block) and ONE division by n.
+__device__ __forceinline__ double jf_row_mean(const double* v, int n) {
+    double sum;
+    if (n < 8) {
+        sum = v[0];
+        for (int o = 1; o < n; ++o) sum = sum + v[o];
+    } else {
+        double r[8];
+        for (int j = 0; j < 8; ++j) r[j] = v[j];
+        int i = 8;
+        for (; i + 8 <= n; i += 8)
+            for (int j = 0; j < 8; ++j) r[j] = r[j] + v[i + j];
+        sum = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
+        for (; i < n; ++i) sum = sum + v[i];
+    }
+    return sum / (double)n;
+}
+
+struct JfReduceTable {
+    SeqTable seq;
+    uint8_t n_obj[IVOSW_MAX_SEQS];
+    long long pair_off[IVOSW_MAX_SEQS];       // (frame, object) pairs in front of video k
+};
+
+// One thread per flat row (frame): the row's video from the table, its n_obj count sextets -> J / F per object -> the row mean(s).
+__global__ __launch_bounds__(64) void jf_reduce_ragged_kernel(const long long* __restrict__ counts, JfReduceTable tab, int n_seqs, int rows,
+                                                              int metric, const float* __restrict__ annot, double* __restrict__ per_obj,
+                                                              double* __restrict__ quality, float* __restrict__ state) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    if (f >= rows) return;
+    int lo = 0, hi = n_seqs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tab.seq.row_off[mid] <= f) lo = mid;
+        else hi = mid - 1;
+    }
+    const int O = tab.n_obj[lo];
+    const long long pair0 = tab.pair_off[lo] + (long long)(f - tab.seq.row_off[lo]) * O;
+    double vj[JF_MAX_OBJ], vf[JF_MAX_OBJ];
+    for (int o = 0; o < O; ++o) {
+        const long long* c = counts + (pair0 + o) * 6;
+        const double j = metric != IVOSW_METRIC_F ? jf_jaccard(c) : 0.0;
+        const double fm = metric != IVOSW_METRIC_J ? jf_fmeasure(c) : 0.0;
+        vj[o] = j;
+        vf[o] = fm;
+        if (per_obj) {
+            const double hj = .5 * j, hf = .5 * fm;
+            per_obj[pair0 + o] = metric == IVOSW_METRIC_J ? j : metric == IVOSW_METRIC_F ? fm : hj + hf;
+        }
+    }
+    double q;
+    if (metric == IVOSW_METRIC_J) q = jf_row_mean(vj, O);
+    else if (metric == IVOSW_METRIC_F) q = jf_row_mean(vf, O);
+    else {
+        const double hj = .5 * jf_row_mean(vj, O), hf = .5 * jf_row_mean(vf, O);
+        q = hj + hf;
+    }
+    quality[f] = q;
+    if (state) {
+        state[2 * (size_t)f] = (float)q;
+        state[2 * (size_t)f + 1] = annot[f];
+    }
+}
+
+}  // namespace
+}  // namespace ivosw
+
+extern "C" size_t ivosw_jf_videos_ws_bytes(const ivosw_jf_video_t* videos, int n_videos) {
+    size_t bytes = 0;
+    if (!videos || ivosw::jf_videos_table(__func__, videos, n_videos, nullptr, &bytes, nullptr, nullptr, nullptr, nullptr) != IVOSW_OK) return 0;
+    return bytes;
+}
+
+extern "C" int ivosw_jf_counts_videos(const ivosw_jf_video_t* videos, int n_videos, int64_t* counts, void* ws, size_t ws_bytes,
+                                      ivosw_stream_t stream) {
+    using namespace ivosw;
+    IVOSW_REQUIRE(videos && counts && ws, "null pointer");
+    JfTable t;
+    size_t need = 0, n_counts = 0;
+    int max_h = 0, max_w = 0;
+    long long max_words = 0;
+    if (jf_videos_table(__func__, videos, n_videos, &t, &need, &n_counts, &max_h, &max_w, &max_words) != IVOSW_OK) return IVOSW_ERR_ARG;
+    IVOSW_ON_DEVICE_OF(counts);
+    if (ws_bytes < need) {
+        set_error("ivosw_jf_counts_videos: workspace %zu < %zu", ws_bytes, need);
+        return IVOSW_ERR_WS;
+    }
+    hipStream_t st = as_stream(stream);
+    t.bitmaps = static_cast<uint32_t*>(ws);
+    t.counts = reinterpret_cast<unsigned long long*>(counts);
+    const int frames = t.frame_off[n_videos], pairs = t.fo_off[n_videos];
+    (void)hipMemsetAsync(counts, 0, n_counts * sizeof(int64_t), st);
+    hipLaunchKernelGGL(jf_boundary_row_videos_kernel, dim3((max_h + 4 * JF_RPW - 1) / (4 * JF_RPW), (max_w + 1023) / 1024, frames), dim3(256),
+                       0, st, t);
+    hipLaunchKernelGGL(jf_match_videos_kernel, dim3((unsigned)((max_words + 255) / 256), pairs, 2), dim3(256), 0, st, t);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_jf_reduce_ragged(const int64_t* counts, const int* n_obj, const int* lengths, int n_seqs, int metric,
+                                      const float* annot_counts, double* per_obj, double* quality, float* state, ivosw_stream_t stream) {
+    using namespace ivosw;
+    IVOSW_REQUIRE(counts && n_obj && lengths && quality, "null pointer");
+    IVOSW_REQUIRE((state == nullptr) == (annot_counts == nullptr), "state and annot_counts go together: both or neither");
+    if (metric != IVOSW_METRIC_J && metric != IVOSW_METRIC_F && metric != IVOSW_METRIC_J_AND_F) {
+        set_error("%s: unknown metric %d (IVOSW_METRIC_J = 0, IVOSW_METRIC_F = 1, IVOSW_METRIC_J_AND_F = 2)", __func__, metric);
+        return IVOSW_ERR_ARG;
+    }
+    JfReduceTable tab;
+    const long rows = ragged_rows(__func__, lengths, n_seqs, &tab.seq);
+    if (rows < 0) return IVOSW_ERR_ARG;
+    long long pairs = 0;
+    for (int k = 0; k < IVOSW_MAX_SEQS; ++k) {
+        tab.n_obj[k] = 1;
+        tab.pair_off[k] = pairs;
+        if (k >= n_seqs) continue;
+        if (n_obj[k] < 1 || n_obj[k] > JF_MAX_OBJ) {
+            set_error("%s: video %d: n_obj %d outside [1, %d]", __func__, k, n_obj[k], JF_MAX_OBJ);
+            return IVOSW_ERR_ARG;
+        }
+        tab.n_obj[k] = (uint8_t)n_obj[k];
+        pairs += (long long)n_obj[k] * lengths[k];
+    }
+    IVOSW_ON_DEVICE_OF(quality);
+    hipLaunchKernelGGL(jf_reduce_ragged_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, as_stream(stream),
+                       reinterpret_cast<const long long*>(counts), tab, n_seqs, (int)rows, metric, annot_counts, per_obj, quality, state);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }

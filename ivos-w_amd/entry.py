@@ -65,6 +65,9 @@ DEFAULTS = dict(
     masks="float32",                   # how the assessment path holds a session's masks: "float32" probabilities [n,O+1,H,W] (the reference's
                                        # all_P), or "labels": ONE uint8 [n,H,W] map of hard labels (models.assessment.LabelMasks; 1 byte per pixel
                                        # and frame instead of 4 * (O + 1)) - the argmax of all_P, so its soft values are discarded
+    metric="host",                     # where the oracle setting forms J / F and recommends: "host" (sequence_metric: the counts come back and
+                                       # the ratios are formed in Python, then recommend_frame), or "device": ratios, per-frame means, the Brain's
+                                       # state and the ranking in one device chain with one copy back (utils_agent.oracle_recommend; same values)
     report_save_dir="results",
     eval_max_nb_interactions=8,        # the eval scripts fix 8 interactions on the val subset (eval_agent_manet.py:64-65)
     data=dict(num_workers=0, root_dir_davis="data/DAVIS", root_dir_scribble_youtube_vos="data/Scribble_Youtube_VOS",
@@ -127,6 +130,19 @@ def rescore_option(cfg):
     return utils_agent.rescore_option(cfg)
 
 
+def metric_option(cfg):
+    """cfg.metric (absent: "host"), refused unless it is "host" or "device" (utils_agent.METRIC_MODES)."""
+    from .utils import utils_agent
+    return utils_agent.metric_option(cfg)
+
+
+def _print_metric_mode(cfg):
+    mode = metric_option(cfg)
+    print(f"[ivos-w] metric={mode}: " + ("J / F ratios, the per-frame means and the oracle recommendation run as one device chain "
+                                         "(utils_agent.oracle_recommend), one copy back per interaction" if mode == "device" else
+                                         "J / F counts on the device, ratios on the host (sequence_metric)"))
+
+
 def _coerce(text):
     for cast in (int, float):
         try:
@@ -168,6 +184,7 @@ def parse_cli(argv, **overrides):
         frames_option(cfg)
         masks_option(cfg)
         rescore_option(cfg)
+        metric_option(cfg)
     except ValueError as e:
         raise SystemExit(f"[ivos-w] {e}")
     return _attr(cfg)
@@ -408,6 +425,7 @@ def run_eval(cfg, backbone="MANet"):
     frames = frames_option(cfg)                                        # (a bad value is refused here, before anything runs)
     masks = masks_option(cfg)
     rescore = rescore_option(cfg)
+    oracle_chain = metric_option(cfg) == "device" and cfg.setting == "oracle" and cfg.method in ("ours", "worst")
     cfg.phase = "eval"
     cfg.data.subset = "val"
     if not torch.cuda.is_available():
@@ -450,12 +468,19 @@ def run_eval(cfg, backbone="MANet"):
                 annotated.append(next_frame)
                 n_interaction += 1
             labels, all_P = _segment(vos, davis, sequence, n_objects, annotated, store)
-            quality = misc.sequence_metric(metric, davis.load_annotations(sequence), labels, n_objects)
-            tic = time.time()
-            candidates = [int(i) for i in utils_agent.recommend_candidates(cfg, assess_net, agent, device, [dict(
-                n_frame=n_frame, n_objects=n_objects, all_F=all_F, all_P=_harden(all_P, masks),
-                new_masks_quality=quality, prev_frames=prev_frames, annotated_frames_list=copy.deepcopy(annotated),
-                mask_quality=quality_pred, first_frame=first_frame, max_nb_interactions=max_nb)])[0]]
+            if oracle_chain:                                          # metric=device: J / F, state, Brain and ranking in one device chain
+                tic = time.time()
+                qualities, picks = utils_agent.oracle_recommend(cfg, agent, device, [dict(
+                    gt_masks=davis.load_annotations(sequence), pred_masks=labels, n_objects=n_objects,
+                    annotated_frames_list=copy.deepcopy(annotated), prev_frames=prev_frames)], as_list=True)
+                quality, candidates = qualities[0], [int(i) for i in picks[0]]
+            else:
+                quality = misc.sequence_metric(metric, davis.load_annotations(sequence), labels, n_objects)
+                tic = time.time()
+                candidates = [int(i) for i in utils_agent.recommend_candidates(cfg, assess_net, agent, device, [dict(
+                    n_frame=n_frame, n_objects=n_objects, all_F=all_F, all_P=_harden(all_P, masks),
+                    new_masks_quality=quality, prev_frames=prev_frames, annotated_frames_list=copy.deepcopy(annotated),
+                    mask_quality=quality_pred, first_frame=first_frame, max_nb_interactions=max_nb)])[0]]
             next_frame = candidates[0]                                # the session annotates the first candidate
             if prev_frames is not None:
                 prev_frames.append(next_frame)
@@ -501,6 +526,7 @@ def run_eval_real(cfg, backbone, device):
     frames = frames_option(cfg)
     masks = masks_option(cfg)
     rescore = rescore_option(cfg)
+    metric_mode = metric_option(cfg)
     if masks == "labels":
         print(_MASKS_NOTE)
     misc.set_random_seed(int(cfg.seed))
@@ -556,7 +582,10 @@ def run_eval_real(cfg, backbone, device):
             with torch.no_grad():
                 labels, all_P = vos.segment(sequence, scribbles, next_frame, first_scribble, n_interaction)
             new_masks = labels.cpu().numpy() if torch.is_tensor(labels) else np.asarray(labels)
-            quality = misc.sequence_metric(metric, gt_masks, new_masks, n_objects)
+            if metric_mode == "device":                               # the ratios and the means on the device, one copy back
+                quality = misc.sequence_metric_videos(metric, [(gt_masks, labels if torch.is_tensor(labels) else new_masks, n_objects)])[0]
+            else:
+                quality = misc.sequence_metric(metric, gt_masks, new_masks, n_objects)
             tic = time.time()
             next_frame = int(utils_agent.recommend_frame(
                 cfg, assess_net, agent, device, n_frame=n_frame, n_objects=n_objects, all_F=all_F, all_P=_harden(all_P, masks),
@@ -624,12 +653,18 @@ def _episode(cfg, davis, vos, sess, agent, device, df, train_loader_fn, policy, 
             n_interaction += 1
         lg = vos.logits(gt, n_objects, annotated)
         utils_manet.seg_epilogue(lg, h, w, store, 0)
-        new_metric = misc.sequence_metric(metric, gt, store.labels_u8, n_objects)
         rcfg = AttrDict(cfg, setting="oracle" if policy == "ours" else "wild", method=policy)
-        next_frame = int(utils_agent.recommend_frame(
-            rcfg, None, agent, device, n_frame=len_subseq, n_objects=n_objects, all_F=None, all_P=store.all_P,
-            new_masks_quality=new_metric, prev_frames=prev_frames, annotated_frames_list=copy.deepcopy(annotated), mask_quality=None,
-            first_frame=next_frame, max_nb_interactions=max_nb))
+        if policy == "ours" and metric_option(cfg) == "device":      # metric=device: J / F, state, Brain and argmax in one device chain
+            metrics_, picks = utils_agent.oracle_recommend(rcfg, agent, device, [dict(
+                gt_masks=gt, pred_masks=store.labels_u8, n_objects=n_objects, annotated_frames_list=copy.deepcopy(annotated),
+                prev_frames=prev_frames)])
+            new_metric, next_frame = metrics_[0], int(picks[0])
+        else:
+            new_metric = misc.sequence_metric(metric, gt, store.labels_u8, n_objects)
+            next_frame = int(utils_agent.recommend_frame(
+                rcfg, None, agent, device, n_frame=len_subseq, n_objects=n_objects, all_F=None, all_P=store.all_P,
+                new_masks_quality=new_metric, prev_frames=prev_frames, annotated_frames_list=copy.deepcopy(annotated), mask_quality=None,
+                first_frame=next_frame, max_nb_interactions=max_nb))
         prev_frames.append(next_frame)
         full = davis.load_annotations(sequence).clone()
         full[torch.as_tensor(subseq, device=device)] = store.labels_u8
@@ -792,9 +827,11 @@ def run_train(cfg):
 
 def main_eval(backbone, argv=None):
     cfg = parse_cli(sys.argv[1:] if argv is None else argv)
+    _print_metric_mode(cfg)
     return run_eval(cfg, backbone)
 
 
 def main_train(argv=None):
     cfg = parse_cli(sys.argv[1:] if argv is None else argv, phase="train")
+    _print_metric_mode(cfg)
     return run_train(cfg)

@@ -120,3 +120,20 @@ def sequence_metric(metric_to_optimize, gt_masks, pred_masks, nb_objects, averag
                                                    nb_objects=nb_objects)
         metric = .5 * jaccard + .5 * contour
     return metric
+
+
+def sequence_metric_videos(metric_to_optimize, videos, average_over_objects=True):
+    """``sequence_metric`` for several videos at once: ``videos`` = [(gt_masks, pred_masks, nb_objects), ...], each of its own length and
+    size.  One J / F pass on the device for all of them, the float64 ratios and the mean over the objects included
+    (``metrics.jf_videos``), and ONE device-to-host copy.  Returns one numpy float64 array per video - [N], or [N,O] without the average -
+    equal to ``sequence_metric`` on that video, bit for bit."""
+    from .. import metrics
+
+    res = metrics.jf_videos(videos, metric_to_optimize, per_object=not average_over_objects)
+    if average_over_objects:
+        host = res.quality.cpu().numpy()                                 # the one D2H copy of the call
+        offs = np.concatenate([[0], np.cumsum(res.lengths)])
+        return [host[int(a):int(b)].copy() for a, b in zip(offs[:-1], offs[1:])]
+    host = res.per_object_flat.cpu().numpy()
+    offs = np.concatenate([[0], np.cumsum([n * o for n, o in zip(res.lengths, res.n_obj)])])
+    return [host[int(a):int(b)].reshape(n, o).copy() for a, b, n, o in zip(offs[:-1], offs[1:], res.lengths, res.n_obj)]

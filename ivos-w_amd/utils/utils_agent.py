@@ -658,3 +658,103 @@ def _prioritized_update_loop(agent, loader, max_steps):
     for v in losses:
         agent.note_loss(v)
     return losses
+
+
+METRIC_MODES = ("host", "device")
+
+
+def metric_option(cfg):
+    """cfg.metric (absent: "host"), refused unless it is one of METRIC_MODES.  "device": the oracle setting scores J / F and recommends in
+    one device chain (``oracle_recommend``, ``misc.sequence_metric_videos``) instead of ``sequence_metric`` + ``recommend_frame``; same
+    results."""
+    mode = (cfg.get("metric", "host") if hasattr(cfg, "get") else getattr(cfg, "metric", "host")) if cfg is not None else "host"
+    if not isinstance(mode, str) or mode not in METRIC_MODES:
+        raise ValueError(f"metric must be 'host' or 'device', got {mode!r}")
+    return mode
+
+
+# oracle_recommend runs J / F -> state -> Brain -> ranking as ONE device chain from this many sessions on, and sequence_metric +
+# recommend_frame per session below it.  tools/jf_videos_probe.py times both (profiles/jf_videos_probe.txt): the one-pass chain is the
+# faster one from a single session on, at every condition measured, by more than the run's spread.
+ORACLE_MIN_SESSIONS = 1
+
+
+def _oracle_metric_name(cfg_yl):
+    di = cfg_yl.get("davis_interactive") if hasattr(cfg_yl, "get") else getattr(cfg_yl, "davis_interactive", None)
+    name = (di.get("metric") if hasattr(di, "get") else getattr(di, "metric", None)) if di is not None else None
+    if name is None:
+        raise ValueError("oracle_recommend: cfg.davis_interactive.metric is not set (J, F or J_AND_F)")
+    return name
+
+
+def oracle_recommend(cfg_yl, agent, device, sessions, as_list=False):
+    """The oracle setting's interaction tail for several sessions at once: ``misc.sequence_metric`` + ``recommend_frame`` (setting
+    "oracle") per session, as ONE device chain.  ``sessions`` is a sequence of dicts with gt_masks, pred_masks ([N,H,W] label maps, numpy
+    or device tensors; each session its own length and size), n_objects, annotated_frames_list and prev_frames; the metric is
+    cfg.davis_interactive.metric.  Returns (metrics, picks): one numpy float64 [N] array per session - what ``sequence_metric`` returns -
+    and the recommended index per session (with ``as_list`` the candidates of ``recommend_candidates``).
+
+    method "ours": one upload of the concatenated annotation counts -> ``metrics.jf_videos`` (one memset and two launches for all
+    sessions' counts, one launch for the float64 ratios, the per-frame means and the Brain's fp32 state) -> ``agent.action`` (one
+    session) or ``agent.actions`` (several: one ragged Brain forward and one ragged argmax / top-k / spread ranking) -> ONE device-to-host
+    copy of [quality (R) float64 | K k indices int64].  agent.candidates, agent.skip_annotated and agent.candidate_gap work as in the
+    wild chain of ``recommend_frames``; ``steps_done`` and both host RNG streams move exactly as under sequential ``recommend_frame``
+    calls.  method "worst": the quality of the same pass and its one copy, then ``select_next_frame`` / ``worst_candidates`` on the host.
+    Metrics and indices equal those of the per-session path bit for bit.  Below ORACLE_MIN_SESSIONS sessions: the per-session path."""
+    from . import misc
+    from .. import metrics as M
+    from ..models.agent import merge_candidates, spread_candidates
+    sessions = list(sessions)
+    setting, method = cfg_yl.setting, cfg_yl.method
+    if setting != "oracle" or method not in ("ours", "worst"):
+        raise NotImplementedError(f"oracle_recommend serves setting 'oracle' with method 'ours' or 'worst', got {setting!r} / {method!r}")
+    if not sessions:
+        return [], []
+    name = _oracle_metric_name(cfg_yl)
+    k, _, gap = _topk_options(cfg_yl, agent)
+    K = len(sessions)
+    if K < ORACLE_MIN_SESSIONS:
+        out_m, out_p = [], []
+        for s in sessions:
+            m = misc.sequence_metric(name, s["gt_masks"], s["pred_masks"], s["n_objects"])
+            out_m.append(m)
+            out_p.append(_recommend_one(cfg_yl, None, agent, device, len(m), s["n_objects"], None, None, m, s["prev_frames"],
+                                        s["annotated_frames_list"], None, None, None, k=k, as_list=as_list, gap=gap))
+        return out_m, out_p
+    ns = [int(s["gt_masks"].shape[0]) for s in sessions]
+    R = sum(ns)
+    offs = np.concatenate([[0], np.cumsum(ns)])[:-1]
+    with torch.no_grad():
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        cnt = None
+        if method == "ours":                                              # one upload for all sessions
+            cnt = torch.as_tensor(np.concatenate([_annotation_counts(n, s["annotated_frames_list"])
+                                                  for n, s in zip(ns, sessions)]).astype(np.float32)).to(dev, non_blocking=True)
+        out = torch.zeros(R + K * k, dtype=torch.float64, device=dev)       # [quality of every session (R) | the K k indices (int64 bits)]
+        res = M.jf_videos([(s["gt_masks"], s["pred_masks"], s["n_objects"]) for s in sessions], name, annot_counts=cnt, out=out)
+        picked = [None] * K
+        if method == "ours":
+            idx_dev = out[R:].view(torch.int64)
+            if K == 1:
+                picked = [agent.action(res.state, device_out=idx_dev)]
+            else:
+                picked = agent.actions([res.state[int(o):int(o) + n] for o, n in zip(offs, ns)], device_out=idx_dev)
+        host = out.cpu()                                                    # the one D2H copy of the call
+    quality, index = host.numpy(), host.view(torch.int64).numpy()
+    out_m, out_p = [], []
+    for j, (s, n, o, pk) in enumerate(zip(sessions, ns, offs, picked)):
+        m = quality[int(o):int(o) + n].copy()
+        out_m.append(m)
+        i = R + j * k
+        if method == "worst":
+            out_p.append(worst_candidates(m, k, s["prev_frames"], gap) if as_list else
+                         select_next_frame(m, metric="worst", prev_frames=s["prev_frames"]))
+        elif k > 1:                                                         # (a spread ranking is final: the pick is its slot 0 already)
+            cand = spread_candidates(index[i:i + k]) if gap > 1 else merge_candidates(pk, index[i:i + k], k)
+            out_p.append(cand if as_list else cand[0])
+        else:
+            pick = pk if pk is not None else np.int64(index[i])
+            out_p.append(_candidate_list(pick, 1) if as_list else pick)
+    return out_m, out_p
