@@ -691,6 +691,63 @@ int ivosw_ipn_dilate(const int8_t* mask, int n, int H, int W, int num_objects, i
 int ivosw_ipn_merge(float* all_E, const float* prev_E, int K, int T, int H, int W, const float* w_new32, const float* w_old32,
                     const int* index, float* probs, long probs_stride_c, uint8_t* label_u8, float* label_f32, ivosw_stream_t stream);
 
+/* ------------------------------------------------------------------ session overlays (8f-4, IPN) */
+/* The pictures an annotator is shown - a frame with the current mask drawn on it - for the frames of ONE video, on the device.
+ * Reference (utils/utils_ipn.py, each on one uint8 image and one binary mask, on the CPU in float64 and through
+ * scipy.ndimage.binary_dilation): overlay_davis (:113-128), checkerboard / BIG_BOARD (:131-143), overlay_checker (:146-157),
+ * overlay_color (:160-171), overlay_fade (:174-190).  Each style below is what the reference function yields on the binary mask, bit
+ * for bit on uint8 images.
+ *   frames     device: IVOSW_FRAMES_RGBX8 uint8 [n_frames,H,W,4] (4-byte aligned) or IVOSW_FRAMES_F32 float32 [n_frames,3,H,W].  The image
+ *              byte of a float is rintf(f * 255.0f) clamped to 0 .. 255, a NaN giving 0: on u8 / 255 floats that is u8 again, so the
+ *              two kinds give identical pictures.
+ *   labels     device uint8 [n_frames,H,W]: value i + 1 is object i; 0 and values above n_objects are no object.
+ *   frame_ids  HOST int[n_ids]: the frames to render, in any order, repeats allowed; NULL = all frames in order (n_ids is then not
+ *              read).  The ids travel inside the kernel arguments, in launches of at most 256 pictures each.  m = the list's length.
+ *   out        device: IVOSW_OUT_RGB8 uint8 [m,H,W,3] (the numpy / encoder image) or IVOSW_OUT_RGBX8 uint8 [m,H,W,4] (4-byte aligned, byte
+ *              3 written 0).  It must not overlap frames or labels.
+ *   opt        HOST, read during the call.  select picks the binary mask: o in 1 .. n_objects is (label == o), 0 is
+ *              (1 <= label <= n_objects).  A pixel is on the CONTOUR of a mask when it is not in it and one of its four edge neighbours
+ *              inside the image is (binary_dilation(mask) ^ mask, scipy's default cross, border_value = 0).
+ *     IVOSW_OVERLAY_DAVIS    select = o: overlay_davis(image, label == o, rgb = palette[o - 1], alpha = alpha): inside, each channel is
+ *                            (uint8) trunc(double(v) * alpha + k), k = (1.0 * (1 - alpha)) * double(c) formed on the host, the product and
+ *                            the sum rounded separately; contour pixels are 0.  select = 0: that function applied once per object, in
+ *                            ascending object order, to the running image - so a pixel of object 2 next to object 1 ends as
+ *                            trunc(0 * alpha + k2) and a pixel of object 1 next to object 2 ends as 0.
+ *     IVOSW_OVERLAY_FADE     outside the mask each channel is (uint8) trunc(0.4 * double(v)); contour pixels are (0, 255, 255).
+ *     IVOSW_OVERLAY_CHECKER  outside the mask the board: 223 where (y / 20 + x / 20) is even, 32 where it is odd (BIG_BOARD).  The
+ *                            reference raises above 1000 pixels a side; here the pattern simply continues.
+ *     IVOSW_OVERLAY_COLOR    outside the mask opt->color (the reference's default is (255, 0, 255)).
+ *                            (FADE, CHECKER and COLOR keep the image inside the mask; alpha and palette are read by DAVIS only.)
+ * One streaming pass, asynchronous on `stream`, on the device that owns the buffers; allocates nothing, copies nothing (capture-safe).
+ * Four pixels of a row per lane (one 16-byte RGBX8 load or three float4 plane loads, label words of the rows above, at and below, 12
+ * or 16 bytes stored) when W % 4 == 0, labels and an RGB8 out are on the 4-byte grid, frames and an RGBX8 out on the 16-byte grid;
+ * two pixels per lane (8-byte loads, 2-byte label words, 6 or 8 bytes stored) when that holds with 2, 2 and 8 in place of 4, 4 and
+ * 16 - the case of W = 854, the width of DAVIS 480p; otherwise pixel by pixel (IVOSW_OVERLAY_SCALAR in the environment forces that).
+ * All paths agree bit for bit.  ivosw_overlay_lane_pixels: host only; the pixels per lane (4, 2 or 1) of the kernel that a call with
+ * these buffers runs.
+ * Refused (IVOSW_ERR_ARG) before any launch, nothing written, the message says which check failed: a NULL frames, labels, opt or out,
+ * an unknown frames_kind, out_kind or style, n_frames, H or W < 1, H * W > INT_MAX, n_objects outside 1 .. 32, select outside
+ * 0 .. n_objects, alpha not in [0, 1] (a NaN included), a list of length < 1, a frame id outside [0, n_frames) (the message names its
+ * position), frames or an RGBX8 out off the 4-byte grid, more than 2^40 pixels of pictures or of frames, out overlapping frames or
+ * labels.                                                                                                                           */
+#define IVOSW_OUT_RGB8 0
+#define IVOSW_OUT_RGBX8 1
+#define IVOSW_OVERLAY_DAVIS 0
+#define IVOSW_OVERLAY_FADE 1
+#define IVOSW_OVERLAY_CHECKER 2
+#define IVOSW_OVERLAY_COLOR 3
+typedef struct ivosw_overlay {
+    int style;                                   /* IVOSW_OVERLAY_* */
+    int n_objects;                               /* 1 .. 32 */
+    int select;                                  /* 0 = every object, o = object o alone */
+    double alpha;                                /* DAVIS: the image's share inside an object, in [0, 1] */
+    uint8_t palette[32][3];                      /* DAVIS: the colour of object i + 1 */
+    uint8_t color[3];                            /* COLOR: the colour outside the mask */
+} ivosw_overlay_t;
+int ivosw_overlay_lane_pixels(const void* frames, const uint8_t* labels, int W, const void* out, int out_kind);
+int ivosw_overlay_frames(const void* frames, int frames_kind, const uint8_t* labels, int n_frames, int H, int W,
+                         const int* frame_ids, int n_ids, const ivosw_overlay_t* opt, void* out, int out_kind, ivosw_stream_t stream);
+
 /* ------------------------------------------------------------------ launch-sequence capture ---- */
 /* HIP-graph capture of any sequence of the calls above on one stream (not in the reference: it replaces the ~40 host
  * launches per Agent.update_agent step, models/agent.py:128-160, by ONE hipGraphLaunch).  begin puts `stream` (non-null)

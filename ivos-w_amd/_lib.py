@@ -26,6 +26,8 @@ MAX_CANDIDATES = 16                                  # IVOSW_MAX_CANDIDATES
 FRAMES_F32, FRAMES_RGBX8 = 0, 1                      # IVOSW_FRAMES_*
 MAX_JF_VIDEOS = 32                                   # IVOSW_MAX_JF_VIDEOS
 METRIC_J, METRIC_F, METRIC_J_AND_F = 0, 1, 2         # IVOSW_METRIC_*
+OUT_RGB8, OUT_RGBX8 = 0, 1                           # IVOSW_OUT_*
+OVERLAY_DAVIS, OVERLAY_FADE, OVERLAY_CHECKER, OVERLAY_COLOR = 0, 1, 2, 3      # IVOSW_OVERLAY_*
 
 
 class Video(C.Structure):
@@ -43,6 +45,12 @@ class JfVideo(C.Structure):
     """ivosw_jf_video_t: one video of a multi-video J / F pass (device label maps, the label values to score, the F tolerance in pixels)."""
     _fields_ = [("gt", C.c_void_p), ("pred", C.c_void_p), ("n_frames", C.c_int), ("H", C.c_int), ("W", C.c_int), ("n_obj", C.c_int),
                 ("obj_ids", C.c_uint8 * 32), ("bound_pix", C.c_int)]
+
+
+class Overlay(C.Structure):
+    """ivosw_overlay_t: how ivosw_overlay_frames draws (host struct, read during the call)."""
+    _fields_ = [("style", C.c_int), ("n_objects", C.c_int), ("select", C.c_int), ("alpha", C.c_double), ("palette", C.c_uint8 * 3 * 32),
+                ("color", C.c_uint8 * 3)]
 
 
 SIGNATURES = {
@@ -138,6 +146,8 @@ SIGNATURES = {
     "ivosw_atnet_epilogue": (_i, [_p, _p] + [_i] * 8 + [_f, _f, _f, _p, _p, C.c_long, _p, _p, _p]),
     "ivosw_ipn_dilate": (_i, [_p, _i, _i, _i, _i, _p, _p]),
     "ivosw_ipn_merge": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, C.c_long, _p, _p, _p]),
+    "ivosw_overlay_lane_pixels": (_i, [_p, _p, _i, _p, _i]),
+    "ivosw_overlay_frames": (_i, [_p, _i, _p, _i, _i, _i, _p, _i, _p, _p, _i, _p]),
     "ivosw_graph_begin": (_i, [_p]),
     "ivosw_graph_end": (_i, [_p, C.POINTER(_p), C.POINTER(_i)]),
     "ivosw_graph_launch": (_i, [_p, _p]),

@@ -68,6 +68,10 @@ DEFAULTS = dict(
     metric="host",                     # where the oracle setting forms J / F and recommends: "host" (sequence_metric: the counts come back and
                                        # the ratios are formed in Python, then recommend_frame), or "device": ratios, per-frame means, the Brain's
                                        # state and the ranking in one device chain with one copy back (utils_agent.oracle_recommend; same values)
+    overlay="none",                    # the pictures an annotator is shown, written after every interaction of the eval scripts: "none", or the
+                                       # current masks drawn on the session's frames as "davis", "fade", "checker" or "color" (utils_ipn.overlay_session:
+                                       # one device call and one copy back per interaction), under <report_dir>/overlays/
+    overlay_frames="candidates",       # which frames are drawn then: the recommended "candidates", or "all" frames of the video
     report_save_dir="results",
     eval_max_nb_interactions=8,        # the eval scripts fix 8 interactions on the val subset (eval_agent_manet.py:64-65)
     data=dict(num_workers=0, root_dir_davis="data/DAVIS", root_dir_scribble_youtube_vos="data/Scribble_Youtube_VOS",
@@ -114,6 +118,60 @@ def masks_option(cfg):
     if not isinstance(mode, str) or mode not in MASK_MODES:
         raise ValueError(f"masks must be 'float32' or 'labels', got {mode!r}")
     return mode
+
+
+OVERLAY_STYLES = ("none", "davis", "fade", "checker", "color")
+OVERLAY_FRAMES = ("candidates", "all")
+
+
+def overlay_option(cfg):
+    """(cfg.overlay, cfg.overlay_frames) (absent: "none", "candidates"), refused unless they are one of OVERLAY_STYLES / OVERLAY_FRAMES."""
+    style, which = cfg.get("overlay", "none"), cfg.get("overlay_frames", "candidates")
+    if style is None:                                   # `overlay=none` on the command line reads as None (_coerce)
+        style = "none"
+    if not isinstance(style, str) or style not in OVERLAY_STYLES:
+        raise ValueError(f"overlay must be 'none', 'davis', 'fade', 'checker' or 'color', got {style!r}")
+    if not isinstance(which, str) or which not in OVERLAY_FRAMES:
+        raise ValueError(f"overlay_frames must be 'candidates' or 'all', got {which!r}")
+    return style, which
+
+
+def write_image(path_stem, rgb):
+    """A uint8 [H,W,3] picture to ``path_stem`` + ".png" through PIL when it is importable, else + ".ppm" (binary P6) from plain Python.
+    Returns the path written."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    try:
+        from PIL import Image
+    except ImportError:
+        path = path_stem + ".ppm"
+        with open(path, "wb") as fp:
+            fp.write(b"P6\n%d %d\n255\n" % (rgb.shape[1], rgb.shape[0]) + rgb.tobytes())
+        return path
+    path = path_stem + ".png"
+    Image.fromarray(rgb).save(path)
+    return path
+
+
+def write_overlays(overlay, report_dir, sequence, visit, interaction, all_F, labels, n_objects, candidates, device):
+    """overlay = overlay_option(cfg).  Under a style other than "none": the candidate frames (or all frames) of the current session with
+    the current masks drawn on them - ONE utils_ipn.overlay_session call and ONE device-to-host copy (labels handed in on the host, as
+    the real stack's are, cost one upload first; the candidates are drawn once each, in ascending order) - written to
+    <report_dir>/overlays/<sequence>_<visit>/<interaction>/<frame:05d>.png (.ppm without PIL).  Returns the paths written."""
+    style, which = overlay
+    if style == "none":
+        return []
+    from .utils import utils_agent, utils_ipn
+    frames = utils_agent.frame_cache.get(all_F, device)               # the session's frames on the device (a PackedFrames is handed on)
+    if not torch.is_tensor(labels):
+        labels = torch.from_numpy(np.ascontiguousarray(np.asarray(labels), dtype=np.uint8))
+    labels = labels.to(device=device, dtype=torch.uint8)
+    ids = list(range(int(labels.shape[0]))) if which == "all" else sorted(set(int(f) for f in candidates))
+    pics = utils_ipn.overlay_session(frames, labels, n_objects, style=style, frame_ids=ids).cpu().numpy()
+    out_dir = os.path.join(report_dir, "overlays", f"{sequence}_{visit}", str(interaction))
+    os.makedirs(out_dir, exist_ok=True)
+    paths = [write_image(os.path.join(out_dir, f"{f:05d}"), pics[j]) for j, f in enumerate(ids)]
+    print(f"[ivos-w] overlay={style}: {len(paths)} pictures of {sequence}_{visit}, interaction {interaction}, in {out_dir}")
+    return paths
 
 
 def _harden(all_P, masks):
@@ -185,6 +243,7 @@ def parse_cli(argv, **overrides):
         masks_option(cfg)
         rescore_option(cfg)
         metric_option(cfg)
+        cfg["overlay"] = overlay_option(cfg)[0]
     except ValueError as e:
         raise SystemExit(f"[ivos-w] {e}")
     return _attr(cfg)
@@ -425,6 +484,7 @@ def run_eval(cfg, backbone="MANet"):
     frames = frames_option(cfg)                                        # (a bad value is refused here, before anything runs)
     masks = masks_option(cfg)
     rescore = rescore_option(cfg)
+    overlay = overlay_option(cfg)
     oracle_chain = metric_option(cfg) == "device" and cfg.setting == "oracle" and cfg.method in ("ours", "worst")
     cfg.phase = "eval"
     cfg.data.subset = "val"
@@ -485,6 +545,8 @@ def run_eval(cfg, backbone="MANet"):
             if prev_frames is not None:
                 prev_frames.append(next_frame)
             rec_time.update(time.time() - tic)
+            if overlay[0] != "none":                                  # what the annotator is shown: the candidates with the current masks on them
+                write_overlays(overlay, report_dir, sequence, seen_seq[sequence], n_interaction, all_F, labels, n_objects, candidates, device)
             sess.submit_masks(labels, next_scribble_frame_candidates=candidates)
             corr = float(np.corrcoef([quality, quality_pred])[0, 1]) if quality_pred is not None else float("nan")
             corr_all.update(0.0 if np.isnan(corr) else corr)
@@ -527,6 +589,7 @@ def run_eval_real(cfg, backbone, device):
     masks = masks_option(cfg)
     rescore = rescore_option(cfg)
     metric_mode = metric_option(cfg)
+    overlay = overlay_option(cfg)
     if masks == "labels":
         print(_MASKS_NOTE)
     misc.set_random_seed(int(cfg.seed))
@@ -595,6 +658,8 @@ def run_eval_real(cfg, backbone, device):
             if prev_frames is not None:
                 prev_frames.append(next_frame)
             rec_time.update(time.time() - tic)
+            if overlay[0] != "none":
+                write_overlays(overlay, report_dir, sequence, seen_seq[sequence], n_interaction, all_F, labels, n_objects, [next_frame], device)
             sess.submit_masks(new_masks, next_scribble_frame_candidates=[next_frame])
             corr = float(np.corrcoef([quality, quality_pred])[0, 1]) if quality_pred is not None else float("nan")
             corr_all.update(0.0 if np.isnan(corr) else corr)

@@ -16,6 +16,14 @@ The IPN network itself (``model.Run``) is an external clone and stays whatever t
 
 The blend rule (``w * new + (1 - w) * old``, three separately rounded fp32 operations on every frame) is this project's definition:
 IPN's ``model.Run`` lives in the external clone, not in the reference tree, so parity with the clone's own merge is unpinned.
+* the overlays (``overlay_davis`` :113-128, ``checkerboard`` / ``BIG_BOARD`` :131-143, ``overlay_checker`` :146-157, ``overlay_color``
+  :160-171, ``overlay_fade`` :174-190): the reference blends one whole image per object in float64 on the CPU and finds the contour
+  with ``scipy.ndimage.binary_dilation``; ``overlay_session`` renders any list of a session's frames from the frames and the label map
+  that already sit on the device with ONE ``ivosw_overlay_frames`` call (``csrc/overlay.hip``), bit for bit what the reference
+  functions give on uint8 images (tests/golden/overlay_fixtures.npz).  The four functions of the reference's names are drop-ins
+  around the same kernel with one frame.  The reference's board stops at 1000 pixels a side (a larger image raises there); here the
+  checker pattern simply continues.  Float images are not restated: a non-uint8 image is a TypeError.
+
 There is no CPU fallback for the device entries.
 """
 import ctypes
@@ -28,6 +36,8 @@ from .utils_manet import ProbStore, torch_ptr
 
 MAX_OBJECTS = 126             # ivosw_ipn_dilate: labels are int8 and -1 is taken
 MAX_CHANNELS = 32             # ivosw_ipn_merge
+MAX_OVERLAY_OBJECTS = 32      # ivosw_overlay_frames
+OVERLAY_STYLES = {"davis": L.OVERLAY_DAVIS, "fade": L.OVERLAY_FADE, "checker": L.OVERLAY_CHECKER, "color": L.OVERLAY_COLOR}
 
 
 # ----------------------------------------------------------------------------------------------- small host functions
@@ -229,3 +239,123 @@ def To_np_label(all_E, K, index):
     label = torch.empty(E.shape[1:], dtype=torch.uint8, device=E.device)
     merge_call(E, None, None, index, None, 0, label, None)
     return label.cpu().numpy()
+
+
+# ----------------------------------------------------------------------------------------------- overlays
+def davis_palette(n=MAX_OVERLAY_OBJECTS):
+    """The DAVIS / PASCAL-VOC colour map for objects 1 .. n, uint8 [n,3]: bit j of the object id goes to bit 7 - j // 3 of channel
+    j % 3 (object 1 = (128, 0, 0), 2 = (0, 128, 0), 3 = (128, 128, 0), ...)."""
+    pal = np.zeros((int(n), 3), dtype=np.uint8)
+    for o in range(1, int(n) + 1):
+        for j in range(24):
+            pal[o - 1, j % 3] |= ((o >> j) & 1) << (7 - j // 3)
+    return pal
+
+
+def overlay_options(style, n_objects, select=0, alpha=0.5, palette=None, color=(255, 0, 255)):
+    """The checked ``ivosw_overlay_t`` of a call (``_lib.Overlay``); ``palette`` None = ``davis_palette()``, else up to 32 rows of uint8
+    RGB (object i + 1 takes row i; missing rows are black)."""
+    if not isinstance(style, str) or style not in OVERLAY_STYLES:
+        raise ValueError(f"overlay: style must be one of {sorted(OVERLAY_STYLES)}, got {style!r}")
+    n_objects, select, alpha = int(n_objects), int(select), float(alpha)
+    if not 1 <= n_objects <= MAX_OVERLAY_OBJECTS:
+        raise ValueError(f"overlay: n_objects {n_objects} outside [1, {MAX_OVERLAY_OBJECTS}]")
+    if not 0 <= select <= n_objects:
+        raise ValueError(f"overlay: select {select} outside [0, {n_objects}]")
+    if not 0.0 <= alpha <= 1.0:
+        raise ValueError(f"overlay: alpha {alpha} not in [0, 1]")
+    pal = np.zeros((MAX_OVERLAY_OBJECTS, 3), dtype=np.uint8)
+    rows = davis_palette() if palette is None else np.array(palette, dtype=np.uint8)
+    if rows.ndim != 2 or rows.shape[1] != 3 or rows.shape[0] > MAX_OVERLAY_OBJECTS:
+        raise ValueError(f"overlay: palette must be uint8 [k,3] with k <= {MAX_OVERLAY_OBJECTS}, got {rows.shape}")
+    pal[:rows.shape[0]] = rows
+    col = np.array(color, dtype=np.uint8).reshape(-1)
+    if col.size != 3:
+        raise ValueError("overlay: color must be three uint8 values")
+    opt = L.Overlay(style=OVERLAY_STYLES[style], n_objects=n_objects, select=select, alpha=alpha)
+    ctypes.memmove(opt.palette, pal.ctypes.data, pal.nbytes)
+    ctypes.memmove(opt.color, col.ctypes.data, 3)
+    return opt
+
+
+def overlay_session(frames, labels, n_objects, style="davis", frame_ids=None, select=0, alpha=0.5, palette=None, color=(255, 0, 255),
+                    out="rgb"):
+    """The pictures of a session on the device, ONE ``ivosw_overlay_frames`` call, no synchronisation: ``frames`` (a float32 [n,3,H,W]
+    video on the device or a ``PackedFrames``) with ``labels`` (a device uint8 [n,H,W] label map or a ``LabelMasks``; value i + 1 is
+    object i) drawn on them in ``style`` ("davis", "fade", "checker", "color").  ``frame_ids``: the frames to render, any order, repeats
+    allowed (None: all, in order).  ``select``: 0 draws every object 1 .. n_objects, o draws object o alone.  Returns a device uint8
+    tensor [m,H,W,3] (``out="rgb"``: what numpy and an image encoder take) or [m,H,W,4] (``out="rgbx"``, byte 3 = 0)."""
+    from ..models.assessment import LabelMasks, PackedFrames
+    if out not in ("rgb", "rgbx"):
+        raise ValueError(f"overlay_session: out must be 'rgb' or 'rgbx', got {out!r}")
+    opt = overlay_options(style, n_objects, select, alpha, palette, color)
+    if isinstance(frames, PackedFrames):
+        fr, kind, (n, H, W) = frames.rgbx, L.FRAMES_RGBX8, (frames.n, frames.H, frames.W)
+    else:
+        if not isinstance(frames, torch.Tensor) or frames.dtype != torch.float32 or frames.dim() != 4 or frames.shape[1] != 3:
+            raise TypeError("overlay_session: frames must be a float32 [n,3,H,W] tensor or a PackedFrames")
+        fr, kind, (n, H, W) = frames.contiguous(), L.FRAMES_F32, (int(frames.shape[0]), int(frames.shape[2]), int(frames.shape[3]))
+    lab = labels.map if isinstance(labels, LabelMasks) else labels
+    if not isinstance(lab, torch.Tensor) or lab.dtype != torch.uint8 or tuple(lab.shape) != (n, H, W):
+        raise TypeError(f"overlay_session: labels must be a uint8 [{n},{H},{W}] tensor or a LabelMasks of that shape")
+    if not fr.is_cuda or not lab.is_cuda:
+        raise RuntimeError("overlay_session: frames and labels must be CUDA tensors (no CPU fallback)")
+    if fr.device != lab.device:
+        raise ValueError("overlay_session: frames and labels are on different devices")
+    lab = lab.contiguous()
+    ids = None
+    if frame_ids is not None:
+        ids = [int(f) for f in frame_ids]
+        if not ids or min(ids) < 0 or max(ids) >= n:
+            raise ValueError(f"overlay_session: frame_ids must be a non-empty list of frames in [0, {n}), got {ids}")
+    m = n if ids is None else len(ids)
+    pics = torch.empty((m, H, W, 4 if out == "rgbx" else 3), dtype=torch.uint8, device=fr.device)
+    L.check(L.lib().ivosw_overlay_frames(L.dptr(fr), kind, L.dptr(lab), n, H, W, None if ids is None else L.int_array(ids), m,
+                                         ctypes.byref(opt), L.dptr(pics), L.OUT_RGBX8 if out == "rgbx" else L.OUT_RGB8,
+                                         L.stream_ptr(fr.device)), "overlay_frames")
+    return pics
+
+
+def _overlay_image(who, image, mask, style, device=None, **kw):
+    """One numpy uint8 [H,W,3] image and the binary mask ``mask == 1`` through the kernel, one frame; numpy of the image's dtype back."""
+    from ..models.assessment import PackedFrames
+    image = np.asarray(image)
+    if image.dtype != np.uint8:
+        raise TypeError(f"{who}: a uint8 image is expected, got {image.dtype} (the reference's float-image behaviour is not restated)")
+    if image.ndim != 3 or image.shape[2] != 3 or image.size < 1:
+        raise ValueError(f"{who}: an [H,W,3] image is expected, got {image.shape}")
+    binary = np.asarray(mask) == 1
+    if binary.shape != image.shape[:2]:
+        raise ValueError(f"{who}: the mask {binary.shape} does not fit the image {image.shape[:2]}")
+    overlay_options(style, 1, 1, **kw)                                       # (bad options are refused before the GPU is touched)
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"{who}: runs on the MI355X only (no CPU fallback)")
+    dev = torch.device("cuda" if device is None else device)
+    rgbx = np.zeros(image.shape[:2] + (4,), dtype=np.uint8)
+    rgbx[..., :3] = image
+    pics = overlay_session(PackedFrames(torch.from_numpy(rgbx[None]).to(dev)), torch.from_numpy(binary.astype(np.uint8)[None]).to(dev), 1,
+                           style=style, select=1, **kw)
+    return pics[0].cpu().numpy().astype(image.dtype)
+
+
+def overlay_davis(image, mask, rgb=[255, 0, 0], cscale=2, alpha=0.5, device=None):
+    """Drop-in for utils/utils_ipn.py:113-128 on uint8 images: inside ``mask == 1`` each channel is trunc(v * alpha + (1 - alpha) * c),
+    the mask's contour is black.  ``cscale`` is accepted and ignored, as in the reference."""
+    return _overlay_image("overlay_davis", image, mask, "davis", device, alpha=alpha, palette=[rgb])
+
+
+def overlay_fade(image, mask, device=None):
+    """Drop-in for utils/utils_ipn.py:174-190 on uint8 images: outside ``mask == 1`` each channel is trunc(0.4 * v), the contour is
+    (0, 255, 255)."""
+    return _overlay_image("overlay_fade", image, mask, "fade", device)
+
+
+def overlay_checker(image, mask, device=None):
+    """Drop-in for utils/utils_ipn.py:146-157 on uint8 images: outside ``mask == 1`` the 20-pixel checkerboard of 223 and 32 (BIG_BOARD;
+    the reference raises above 1000 pixels a side, here the pattern continues)."""
+    return _overlay_image("overlay_checker", image, mask, "checker", device)
+
+
+def overlay_color(image, mask, rgb=[255, 0, 255], device=None):
+    """Drop-in for utils/utils_ipn.py:160-171 on uint8 images: outside ``mask == 1`` the colour ``rgb``."""
+    return _overlay_image("overlay_color", image, mask, "color", device, color=rgb)
