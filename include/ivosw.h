@@ -604,6 +604,57 @@ int ivosw_jf_counts_videos(const ivosw_jf_video_t* videos, int n_videos, int64_t
 int ivosw_jf_reduce_ragged(const int64_t* counts, const int* n_obj, const int* lengths, int n_seqs, int metric,
                            const float* annot_counts, double* per_obj, double* quality, float* state, ivosw_stream_t stream);
 
+/* ------------------------------------------------------------------ assessment samples: 8-bit prob maps, per-unit J&F targets - */
+/* Replaces the two host steps by which the reference builds AssessNet's training samples and their targets: save_seg_preds
+ * (utils/misc.py:165-181: all_P to the host as float32, cv2.imwrite(path, probs[i, n] * 255) per object plane) and the target /
+ * loss / diff loop of quality_assessment.py:178-196, 235-263.
+ *
+ * ivosw_qa_quantize: all_P (fp32, device) -> planes uint8 [n_obj][n_frames][H][W], object-major, objects 1 .. n_obj only: element
+ * (f, c, y, x) is read at probs[f * probs_stride_n + c * probs_stride_c + y * W + x] for c = 1 .. n_obj (strides in elements, as
+ * ivosw_seg_epilogue's: (n_obj + 1) * H * W, H * W for the reference's [n, O+1, H, W]; H * W, n_total * H * W for an object-major
+ * store); channel 0 is never read.  The rule is the definition: q = clamp(rint(fl32(p * 255.0f)), 0, 255) - one fp32 product, round
+ * half to even, NaN -> 0, -inf -> 0, +inf -> 255.  It restates numpy's float32 `probs * 255` followed by OpenCV's saturating 8-bit
+ * conversion (cvRound, then the clamp); OpenCV is not part of this project's environment, so parity with cv2 is restated, not recorded.
+ * One streaming pass: no LDS, no atomics, no scratch, no allocation; capture-safe.  Four pixels per lane (16-byte load, 4-byte store)
+ * when H * W % 4 == 0, both strides % 4 == 0, probs is 16-byte and planes 4-byte aligned; one pixel per lane otherwise and with
+ * IVOSW_QA_SCALAR in the environment; both agree bit for bit.
+ * Refused (IVOSW_ERR_ARG) before the launch: a NULL pointer, n_frames or n_obj outside 1 .. 65535, H or W < 1, H * W >= 2^31, a stride
+ * below H * W.                                                                                                                       */
+int ivosw_qa_quantize(const float* probs, int n_frames, int n_obj, int H, int W, long probs_stride_n, long probs_stride_c,
+                      uint8_t* planes, ivosw_stream_t stream);
+/* The six integer counts of ivosw_jf_counts_videos with the prediction read from byte planes instead of a label map: one memset and two
+ * launches for up to IVOSW_MAX_JF_VIDEOS videos.  Per video: gt uint8 [n_frames,H,W] (label map), planes uint8 [n_obj][n_frames][H][W]
+ * (what ivosw_qa_quantize writes), obj_ids, thr, bound_pix.  For unit (object o, frame f): gt mask = (gt[f] == obj_ids[o]), pred mask =
+ * (planes[o][f] >= thr) - the planes of different objects may overlap, which no label map can express.  thr = 205 is the reference's
+ * rule: byte / 255 > 0.8 first holds at 205, in float64 and in float32.  counts: video-major, [n_frames][n_obj][6] per video, as
+ * ivosw_jf_counts_videos writes them; for planes that do not overlap they equal its counts on the equivalent label map.  Workspace:
+ * ivosw_qa_counts_ws_bytes (0 if the array would be refused).  The same kernel bodies as the label-map pass; capture-safe.
+ * Refused before anything is launched, the message names the video: what ivosw_jf_counts_videos refuses, and a NULL planes.          */
+typedef struct ivosw_qa_video {
+    const uint8_t* gt;                           /* device */
+    const uint8_t* planes;                       /* device */
+    int n_frames, H, W, n_obj;
+    uint8_t obj_ids[32];
+    int bound_pix;
+    uint8_t thr;
+} ivosw_qa_video_t;
+size_t ivosw_qa_counts_ws_bytes(const ivosw_qa_video_t* videos, int n_videos);
+int ivosw_qa_counts_videos(const ivosw_qa_video_t* videos, int n_videos, int64_t* counts, void* ws, size_t ws_bytes,
+                           ivosw_stream_t stream);
+/* Per-unit targets from those counts, in ONE launch for n_seqs (1 .. IVOSW_MAX_SEQS) videos, in the ASSESSMENT's unit order - the order
+ * of ivosw_assess_forward_videos' scores: u = first_unit[v] + obj * lengths[v] + frame, first_unit[v] = the sum of n_obj * lengths over
+ * the videos before v - while counts are frame-major inside a video.  n_obj and lengths are HOST arrays (kernel arguments).
+ *   target [units] float64: J, F or .5 * J + .5 * F of the unit, by ivosw_jf_reduce_ragged's expressions, not averaged over objects.
+ *   valid  [units] uint8:   union > 0 (the reference skips a sample whose label and mask are both empty).
+ * With scores (fp32 [units], nullable together with loss, diff, n_valid), per video: loss, diff fp32 [n_seqs] and n_valid int32
+ * [n_seqs] = the reference loop exactly: t = float32(target); the terms (s - t) * (s - t) and |s - t| in fp32, each operation rounded
+ * by itself; added sequentially in ascending unit order over the valid units, in fp32, from 0; one fp32 division by n_valid.  A video
+ * without a valid unit: loss = diff = 0, n_valid = 0.  No atomics, no workspace; capture-safe.
+ * Refused (IVOSW_ERR_ARG) before the launch, naming the video: what ivosw_jf_reduce_ragged refuses; a NULL target or valid; scores
+ * without loss / diff / n_valid or the reverse.                                                                                      */
+int ivosw_qa_targets(const int64_t* counts, const int* n_obj, const int* lengths, int n_seqs, int metric, const float* scores,
+                     double* target, uint8_t* valid, float* loss, float* diff, int* n_valid, ivosw_stream_t stream);
+
 /* ------------------------------------------------------------------ segmentation epilogue (8f-4) */
 /* Replaces, per frame batch, F.interpolate(logits, (H,W), 'bilinear', align_corners=True) -> argmax(dim=1)
  * [-> .float()] and the final torch.softmax(cat(probs), 1) of utils/utils_manet.py:78-84,110-116,146-151,

@@ -47,6 +47,12 @@ class JfVideo(C.Structure):
                 ("obj_ids", C.c_uint8 * 32), ("bound_pix", C.c_int)]
 
 
+class QaVideo(C.Structure):
+    """ivosw_qa_video_t: one video of ivosw_qa_counts_videos (device label map and byte planes [O,N,H,W], the plane threshold)."""
+    _fields_ = [("gt", C.c_void_p), ("planes", C.c_void_p), ("n_frames", C.c_int), ("H", C.c_int), ("W", C.c_int), ("n_obj", C.c_int),
+                ("obj_ids", C.c_uint8 * 32), ("bound_pix", C.c_int), ("thr", C.c_uint8)]
+
+
 class Overlay(C.Structure):
     """ivosw_overlay_t: how ivosw_overlay_frames draws (host struct, read during the call)."""
     _fields_ = [("style", C.c_int), ("n_objects", C.c_int), ("select", C.c_int), ("alpha", C.c_double), ("palette", C.c_uint8 * 3 * 32),
@@ -142,6 +148,10 @@ SIGNATURES = {
     "ivosw_jf_videos_ws_bytes": (_sz, [_p, _i]),
     "ivosw_jf_counts_videos": (_i, [_p, _i, _p, _p, _sz, _p]),
     "ivosw_jf_reduce_ragged": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _p]),
+    "ivosw_qa_quantize": (_i, [_p, _i, _i, _i, _i, C.c_long, C.c_long, _p, _p]),
+    "ivosw_qa_counts_ws_bytes": (_sz, [_p, _i]),
+    "ivosw_qa_counts_videos": (_i, [_p, _i, _p, _p, _sz, _p]),
+    "ivosw_qa_targets": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "ivosw_seg_epilogue": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, C.c_long, C.c_long, _p, _p, _p, _p]),
     "ivosw_atnet_epilogue": (_i, [_p, _p] + [_i] * 8 + [_f, _f, _f, _p, _p, C.c_long, _p, _p, _p]),
     "ivosw_ipn_dilate": (_i, [_p, _i, _i, _i, _i, _p, _p]),

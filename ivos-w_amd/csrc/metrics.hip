@@ -101,6 +101,21 @@ __device__ __forceinline__ uint32_t mask16(const uint32_t (&w)[4], uint32_t id4)
     return m;
 }
 
+// The byte-plane source's mask: bit k = (byte k of w >= the byte repeated in thr4), by a SWAR unsigned compare.  Per byte, with x7 / t7
+// the low seven bits: d = (x7 + 128) - t7 stays inside the byte (1 .. 255, no borrow crosses), and its bit 7 says x7 >= t7; where the
+// top bits of x and t differ the top bit of x decides, where they agree bit 7 of d does.
+__device__ __forceinline__ uint32_t ge16(const uint32_t (&w)[4], uint32_t thr4) {
+    uint32_t m = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t x = w[k];
+        const uint32_t d = (x | 0x80808080u) - (thr4 & 0x7F7F7F7Fu);
+        const uint32_t t = ((x & ~thr4) | (~(x ^ thr4) & d)) & 0x80808080u;            // 0x80 in every byte of x that is >= its threshold
+        m |= ((((t >> 7) * 0x00204081u) >> 21) & 0xFu) << (4 * k);
+    }
+    return m;
+}
+
 __device__ __forceinline__ void load16(const uint8_t* base, size_t off, size_t total, bool on, uint32_t (&w)[4]) {
     w[0] = w[1] = w[2] = w[3] = 0u;
     if (!on) return;
@@ -117,9 +132,15 @@ __device__ __forceinline__ void load16(const uint8_t* base, size_t off, size_t t
 constexpr int JF_RPW = 4;
 // The body serves both descriptor sources: `a` is the single video's JfArgs (ivosw_jf_counts) or one JfVideo of the table
 // (ivosw_jf_counts_videos) - the same field names; bgm / bpm / counts are that video's bitmaps and count block, n its frame.
-template <class A>
+//
+// The prediction source is a compile-time parameter.  JF_PRED_LABELS: a.pred is a label map [N][H][W] like a.gt, loaded once in front of
+// the object loop, the mask of object o is pred == ids[o].  JF_PRED_PLANES (ivosw_qa_counts_videos): a.pred is a stack of byte planes
+// [n_obj][N][H][W], the mask of object o is planes[o] >= thr - the planes of two objects may overlap, which no label map can express -
+// so the 16 bytes are loaded INSIDE the object loop and compared by ge16 in the place of mask16.  Everything behind the masks is shared.
+constexpr int JF_PRED_LABELS = 0, JF_PRED_PLANES = 1;
+template <int SRC, class A>
 __device__ __forceinline__ void jf_boundary_body(const A& a, uint32_t* __restrict__ bgm, uint32_t* __restrict__ bpm,
-                                                 unsigned long long* __restrict__ counts, int n, int seg, int yblk) {
+                                                 unsigned long long* __restrict__ counts, int n, int seg, int yblk, uint32_t thr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int y0 = (yblk * 4 + wave) * JF_RPW;
     const int x0 = seg * 1024 + lane * 16;
@@ -134,9 +155,9 @@ __device__ __forceinline__ void jf_boundary_body(const A& a, uint32_t* __restric
         const bool on = col_live && y < a.H;
         const size_t off = ((size_t)n * a.H + (y < a.H ? y : 0)) * a.W + x0;
         load16(a.gt, off, total, on, g[r]);
-        load16(a.pred, off, total, on, p[r]);
+        if constexpr (SRC == JF_PRED_LABELS) load16(a.pred, off, total, on, p[r]);
         tg[r] = (tail && on) ? a.gt[off + 16] : 0;
-        tp[r] = (tail && on) ? a.pred[off + 16] : 0;
+        if constexpr (SRC == JF_PRED_LABELS) tp[r] = (tail && on) ? a.pred[off + 16] : 0;
     }
     const int nvalid = col_live ? min(16, a.W - x0) : 0;
     const uint32_t vm = (1u << nvalid) - 1u;
@@ -146,18 +167,30 @@ __device__ __forceinline__ void jf_boundary_body(const A& a, uint32_t* __restric
     for (int o = 0; o < a.n_obj; ++o) {
         const uint8_t id = a.ids[o];
         const uint32_t id4 = id * 0x01010101u;
+        if constexpr (SRC == JF_PRED_PLANES) {
+            const size_t plane0 = ((size_t)o * a.N + n) * a.H;               // this object's plane of frame n, in rows from a.pred
+#pragma unroll
+            for (int r = 0; r <= JF_RPW; ++r) {
+                const int y = y0 + r;
+                const bool on = col_live && y < a.H;
+                const size_t off = (plane0 + (y < a.H ? y : 0)) * a.W + x0;
+                load16(a.pred, off, total * a.n_obj, on, p[r]);
+                tp[r] = (tail && on) ? a.pred[off + 16] : 0;
+            }
+        }
         // bits 0..15 = this lane's pixels, bit 16 = the east neighbour of pixel 15 (rows >= H load zeros: no match for id > 0,
         // and the valid mask clears id == 0 matches of rows that do not exist through `rows` below)
         uint32_t mg[JF_RPW + 1], mp[JF_RPW + 1];
 #pragma unroll
         for (int r = 0; r <= JF_RPW; ++r) {
             const bool row_ok = y0 + r < a.H;
-            const uint32_t m0 = row_ok ? (mask16(g[r], id4) & vm) : 0u, m1 = row_ok ? (mask16(p[r], id4) & vm) : 0u;
+            const uint32_t m0 = row_ok ? (mask16(g[r], id4) & vm) : 0u;
+            const uint32_t m1 = row_ok ? ((SRC == JF_PRED_PLANES ? ge16(p[r], thr * 0x01010101u) : mask16(p[r], id4)) & vm) : 0u;
             // the shuffle runs in EVERY lane, outside the lane-63 select: inside its `lane != 63` arm lane 63 is switched off, and a DPP
             // read of a switched-off lane returns 0 - lane 62 then lost the east neighbour of its last pixel (column 1007 | 1008 of a segment)
             const uint32_t n0 = lane_next(m0) & 1u, n1 = lane_next(m1) & 1u;
             const uint32_t e0 = lane == 63 ? ((tail && row_ok && tg[r] == id) ? 1u : 0u) : n0;
-            const uint32_t e1 = lane == 63 ? ((tail && row_ok && tp[r] == id) ? 1u : 0u) : n1;
+            const uint32_t e1 = lane == 63 ? ((tail && row_ok && (SRC == JF_PRED_PLANES ? tp[r] >= thr : tp[r] == id)) ? 1u : 0u) : n1;
             mg[r] = m0 | (e0 << 16);
             mp[r] = m1 | (e1 << 16);
         }
@@ -200,7 +233,7 @@ __device__ __forceinline__ void jf_boundary_body(const A& a, uint32_t* __restric
 }
 
 __global__ __launch_bounds__(256) void jf_boundary_row_kernel(JfArgs a) {
-    jf_boundary_body(a, a.bg, a.bp, a.counts, blockIdx.z, blockIdx.y, blockIdx.x);
+    jf_boundary_body<JF_PRED_LABELS>(a, a.bg, a.bp, a.counts, blockIdx.z, blockIdx.y, blockIdx.x, 0u);
 }
 
 // Several videos in one launch (ivosw_jf_counts_videos): grid.z runs flat over the frames of all videos, grid.x / grid.y are sized by
@@ -221,7 +254,22 @@ __global__ __launch_bounds__(256) void jf_boundary_row_videos_kernel(JfTable t) 
     const JfVideo& a = t.v[v];
     if ((int)blockIdx.x * (4 * JF_RPW) >= a.H || (int)blockIdx.y * 1024 >= a.W) return;
     uint32_t* bgm = t.bitmaps + a.bm_off;
-    jf_boundary_body(a, bgm, bgm + a.plane_words, t.counts + a.cnt_off, (int)blockIdx.z - t.frame_off[v], blockIdx.y, blockIdx.x);
+    jf_boundary_body<JF_PRED_LABELS>(a, bgm, bgm + a.plane_words, t.counts + a.cnt_off, (int)blockIdx.z - t.frame_off[v], blockIdx.y,
+                                     blockIdx.x, 0u);
+}
+
+// The same launch shape with the prediction read from byte planes (ivosw_qa_counts_videos): JfVideo::pred is the video's
+// [n_obj][N][H][W] plane stack; the per-video thresholds travel beside the table (JfTable itself keeps its size for the label kernels).
+struct JfThresholds {
+    uint8_t thr[IVOSW_MAX_JF_VIDEOS];
+};
+__global__ __launch_bounds__(256) void jf_boundary_row_planes_videos_kernel(JfTable t, JfThresholds th) {
+    const int v = jf_find_video(t.frame_off, t.n_videos, blockIdx.z);
+    const JfVideo& a = t.v[v];
+    if ((int)blockIdx.x * (4 * JF_RPW) >= a.H || (int)blockIdx.y * 1024 >= a.W) return;
+    uint32_t* bgm = t.bitmaps + a.bm_off;
+    jf_boundary_body<JF_PRED_PLANES>(a, bgm, bgm + a.plane_words, t.counts + a.cnt_off, (int)blockIdx.z - t.frame_off[v], blockIdx.y,
+                                     blockIdx.x, (uint32_t)th.thr[v]);
 }
 
 // grid (blocks over H*WW, N * n_obj, 2): z = 0 counts pred-boundary pixels inside dil(gt boundary) (fg_match),
@@ -503,6 +551,61 @@ __global__ __launch_bounds__(64) void jf_reduce_ragged_kernel(const long long* _
     }
 }
 
+// Assessment targets (ivosw_qa_targets).  The first `unit_blocks` blocks: one thread per unit u, in the ASSESSMENT's unit order - video
+// v's units start at pair_off[v] and run object-major, u = pair_off[v] + obj * N + frame - while its count sextets lie frame-major at
+// pair_off[v] + frame * O + obj.  The blocks behind them (only with scores): one thread per video walks that video's units in ascending
+// order and forms the reference loop's fp32 sums (quality_assessment.py:251-263); it recomputes each target from the counts with the
+// same device function, so it does not wait for the unit threads.
+__device__ __forceinline__ double qa_unit_target(const long long* c, int metric) {
+    if (metric == IVOSW_METRIC_J) return jf_jaccard(c);
+    if (metric == IVOSW_METRIC_F) return jf_fmeasure(c);
+    const double hj = .5 * jf_jaccard(c), hf = .5 * jf_fmeasure(c);
+    return hj + hf;
+}
+
+__global__ __launch_bounds__(64) void qa_targets_kernel(const long long* __restrict__ counts, JfReduceTable tab, int n_seqs, long long units,
+                                                        int unit_blocks, int metric, const float* __restrict__ scores,
+                                                        double* __restrict__ target, uint8_t* __restrict__ valid, float* __restrict__ loss,
+                                                        float* __restrict__ diff, int* __restrict__ n_valid) {
+    if ((int)blockIdx.x < unit_blocks) {
+        const long long u = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+        if (u >= units) return;
+        int lo = 0, hi = n_seqs - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (tab.pair_off[mid] <= u) lo = mid;
+            else hi = mid - 1;
+        }
+        const int O = tab.n_obj[lo], N = tab.seq.row_off[lo + 1] - tab.seq.row_off[lo];
+        const long long local = u - tab.pair_off[lo];
+        const int obj = (int)(local / N), frame = (int)(local - (long long)obj * N);
+        const long long* c = counts + (tab.pair_off[lo] + (long long)frame * O + obj) * 6;
+        target[u] = qa_unit_target(c, metric);
+        valid[u] = c[1] > 0 ? 1 : 0;
+        return;
+    }
+    const int v = ((int)blockIdx.x - unit_blocks) * blockDim.x + threadIdx.x;
+    if (v >= n_seqs) return;
+    const int O = tab.n_obj[v], N = tab.seq.row_off[v + 1] - tab.seq.row_off[v];
+    const long long u0 = tab.pair_off[v];
+    float l = 0.f, d = 0.f;
+    int cnt = 0;
+    for (int obj = 0; obj < O; ++obj)
+        for (int frame = 0; frame < N; ++frame) {
+            const long long* c = counts + (u0 + (long long)frame * O + obj) * 6;
+            if (c[1] <= 0) continue;
+            const float t = (float)qa_unit_target(c, metric);
+            const float e = scores[u0 + (long long)obj * N + frame] - t;
+            const float sq = e * e;
+            l = l + sq;
+            d = d + fabsf(e);
+            ++cnt;
+        }
+    loss[v] = cnt ? l / (float)cnt : 0.f;
+    diff[v] = cnt ? d / (float)cnt : 0.f;
+    n_valid[v] = cnt;
+}
+
 }  // namespace
 }  // namespace ivosw
 
@@ -565,6 +668,105 @@ extern "C" int ivosw_jf_reduce_ragged(const int64_t* counts, const int* n_obj, c
     IVOSW_ON_DEVICE_OF(quality);
     hipLaunchKernelGGL(jf_reduce_ragged_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, as_stream(stream),
                        reinterpret_cast<const long long*>(counts), tab, n_seqs, (int)rows, metric, annot_counts, per_obj, quality, state);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ assessment samples (8-bit planes)
+namespace ivosw {
+namespace {
+// ivosw_qa_video_t -> the label-map descriptors jf_videos_table checks and lays out (pred = the plane stack); thresholds beside them.
+int qa_videos_as_jf(const char* who, const ivosw_qa_video_t* videos, int n_videos, ivosw_jf_video_t* out, JfThresholds* th) {
+    if (n_videos < 1 || n_videos > IVOSW_MAX_JF_VIDEOS) {
+        set_error("%s: n_videos %d outside [1, %d]", who, n_videos, IVOSW_MAX_JF_VIDEOS);
+        return IVOSW_ERR_ARG;
+    }
+    for (int k = 0; k < n_videos; ++k) {
+        const ivosw_qa_video_t& d = videos[k];
+        if (!d.planes) {
+            set_error("%s: video %d: NULL planes", who, k);
+            return IVOSW_ERR_ARG;
+        }
+        ivosw_jf_video_t& j = out[k];
+        j.gt = d.gt; j.pred = d.planes; j.n_frames = d.n_frames; j.H = d.H; j.W = d.W; j.n_obj = d.n_obj; j.bound_pix = d.bound_pix;
+        memcpy(j.obj_ids, d.obj_ids, sizeof j.obj_ids);
+        if (th) th->thr[k] = d.thr;
+    }
+    if (th)
+        for (int k = n_videos; k < IVOSW_MAX_JF_VIDEOS; ++k) th->thr[k] = 0;
+    return IVOSW_OK;
+}
+}  // namespace
+}  // namespace ivosw
+
+extern "C" size_t ivosw_qa_counts_ws_bytes(const ivosw_qa_video_t* videos, int n_videos) {
+    using namespace ivosw;
+    ivosw_jf_video_t jv[IVOSW_MAX_JF_VIDEOS];
+    size_t bytes = 0;
+    if (!videos || qa_videos_as_jf(__func__, videos, n_videos, jv, nullptr) != IVOSW_OK) return 0;
+    if (jf_videos_table(__func__, jv, n_videos, nullptr, &bytes, nullptr, nullptr, nullptr, nullptr) != IVOSW_OK) return 0;
+    return bytes;
+}
+
+extern "C" int ivosw_qa_counts_videos(const ivosw_qa_video_t* videos, int n_videos, int64_t* counts, void* ws, size_t ws_bytes,
+                                      ivosw_stream_t stream) {
+    using namespace ivosw;
+    IVOSW_REQUIRE(videos && counts && ws, "null pointer");
+    ivosw_jf_video_t jv[IVOSW_MAX_JF_VIDEOS];
+    JfThresholds th;
+    if (qa_videos_as_jf(__func__, videos, n_videos, jv, &th) != IVOSW_OK) return IVOSW_ERR_ARG;
+    JfTable t;
+    size_t need = 0, n_counts = 0;
+    int max_h = 0, max_w = 0;
+    long long max_words = 0;
+    if (jf_videos_table(__func__, jv, n_videos, &t, &need, &n_counts, &max_h, &max_w, &max_words) != IVOSW_OK) return IVOSW_ERR_ARG;
+    IVOSW_ON_DEVICE_OF(counts);
+    if (ws_bytes < need) {
+        set_error("ivosw_qa_counts_videos: workspace %zu < %zu", ws_bytes, need);
+        return IVOSW_ERR_WS;
+    }
+    hipStream_t st = as_stream(stream);
+    t.bitmaps = static_cast<uint32_t*>(ws);
+    t.counts = reinterpret_cast<unsigned long long*>(counts);
+    const int frames = t.frame_off[n_videos], pairs = t.fo_off[n_videos];
+    (void)hipMemsetAsync(counts, 0, n_counts * sizeof(int64_t), st);
+    hipLaunchKernelGGL(jf_boundary_row_planes_videos_kernel, dim3((max_h + 4 * JF_RPW - 1) / (4 * JF_RPW), (max_w + 1023) / 1024, frames),
+                       dim3(256), 0, st, t, th);
+    hipLaunchKernelGGL(jf_match_videos_kernel, dim3((unsigned)((max_words + 255) / 256), pairs, 2), dim3(256), 0, st, t);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_qa_targets(const int64_t* counts, const int* n_obj, const int* lengths, int n_seqs, int metric, const float* scores,
+                                double* target, uint8_t* valid, float* loss, float* diff, int* n_valid, ivosw_stream_t stream) {
+    using namespace ivosw;
+    IVOSW_REQUIRE(counts && n_obj && lengths && target && valid, "null pointer");
+    IVOSW_REQUIRE(scores ? (loss && diff && n_valid) : (!loss && !diff && !n_valid),
+                  "scores, loss, diff and n_valid go together: all or none");
+    if (metric != IVOSW_METRIC_J && metric != IVOSW_METRIC_F && metric != IVOSW_METRIC_J_AND_F) {
+        set_error("%s: unknown metric %d (IVOSW_METRIC_J = 0, IVOSW_METRIC_F = 1, IVOSW_METRIC_J_AND_F = 2)", __func__, metric);
+        return IVOSW_ERR_ARG;
+    }
+    JfReduceTable tab;
+    const long rows = ragged_rows(__func__, lengths, n_seqs, &tab.seq);
+    if (rows < 0) return IVOSW_ERR_ARG;
+    long long units = 0;
+    for (int k = 0; k < IVOSW_MAX_SEQS; ++k) {
+        tab.n_obj[k] = 1;
+        tab.pair_off[k] = units;
+        if (k >= n_seqs) continue;
+        if (n_obj[k] < 1 || n_obj[k] > JF_MAX_OBJ) {
+            set_error("%s: video %d: n_obj %d outside [1, %d]", __func__, k, n_obj[k], JF_MAX_OBJ);
+            return IVOSW_ERR_ARG;
+        }
+        tab.n_obj[k] = (uint8_t)n_obj[k];
+        units += (long long)n_obj[k] * lengths[k];
+    }
+    IVOSW_ON_DEVICE_OF(target);
+    const int unit_blocks = (int)((units + 63) / 64), video_blocks = scores ? (n_seqs + 63) / 64 : 0;      // units <= 32 * 2^20
+    hipLaunchKernelGGL(qa_targets_kernel, dim3((unsigned)(unit_blocks + video_blocks)), dim3(64), 0, as_stream(stream),
+                       reinterpret_cast<const long long*>(counts), tab, n_seqs, units, unit_blocks, metric, scores, target, valid, loss, diff,
+                       n_valid);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }

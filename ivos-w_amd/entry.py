@@ -22,6 +22,7 @@ Everything ON the hot path is the product: AssessNet / Agent (HIP), ``recommend_
 ``sequence_metric`` (HIP J&F), ``ReplayMemory`` / ``load_agent_dataset``, ``save_agent_checkpoint``.
 The CLI keeps sacred's ``with key=value`` form: ``python eval_agent_manet.py with setting=wild method=ours dataset=davis``.
 """
+import contextlib
 import copy
 import importlib.util
 import json
@@ -72,6 +73,12 @@ DEFAULTS = dict(
                                        # current masks drawn on the session's frames as "davis", "fade", "checker" or "color" (utils_ipn.overlay_session:
                                        # one device call and one copy back per interaction), under <report_dir>/overlays/
     overlay_frames="candidates",       # which frames are drawn then: the recommended "candidates", or "all" frames of the video
+    save_probs=False,                  # true: after every interaction of the eval scripts the session's probability maps are written as 8-bit
+                                       # planes under agent.save_result_dir, as the reference's generate_data.py writes AssessNet's training
+                                       # samples (utils.misc.save_seg_preds: one quantise launch, one uint8 copy; refused under masks=labels)
+    qa_report=False,                   # true (wild setting, method ours | worst): per interaction the reference's training-loop measures of the
+                                       # AssessNet scores against the true per-unit targets - qa_loss (mean squared), qa_diff (mean absolute)
+                                       # and valid/units - beside corr, and their session means under "qa" in summary.json
     report_save_dir="results",
     eval_max_nb_interactions=8,        # the eval scripts fix 8 interactions on the val subset (eval_agent_manet.py:64-65)
     data=dict(num_workers=0, root_dir_davis="data/DAVIS", root_dir_scribble_youtube_vos="data/Scribble_Youtube_VOS",
@@ -134,6 +141,91 @@ def overlay_option(cfg):
     if not isinstance(which, str) or which not in OVERLAY_FRAMES:
         raise ValueError(f"overlay_frames must be 'candidates' or 'all', got {which!r}")
     return style, which
+
+
+def qa_option(cfg):
+    """(cfg.save_probs, cfg.qa_report) (absent: False, False).  Refused: a value that is not a bool; either key under phase=train (the
+    training script has no such step); qa_report outside the wild setting
+    with method ours | worst (no AssessNet scores exist elsewhere); save_probs under masks=labels (the soft values are gone)."""
+    save_probs, qa_report = cfg.get("save_probs", False), cfg.get("qa_report", False)
+    if not isinstance(save_probs, bool):
+        raise ValueError(f"save_probs must be true or false, got {save_probs!r}")
+    if not isinstance(qa_report, bool):
+        raise ValueError(f"qa_report must be true or false, got {qa_report!r}")
+    if (save_probs or qa_report) and cfg.get("phase", "eval") == "train":
+        raise ValueError("save_probs / qa_report belong to the eval scripts (eval_agent_*.py, generate_data.py): train_agent.py would ignore them")
+    if qa_report and not (cfg.get("setting") == "wild" and cfg.get("method") in ("ours", "worst")):
+        raise ValueError(f"qa_report=true needs AssessNet's scores: setting=wild with method=ours or method=worst, got setting="
+                         f"{cfg.get('setting')!r} method={cfg.get('method')!r}")
+    if save_probs and cfg.get("masks", "float32") == "labels":
+        raise ValueError("save_probs=true is refused under masks=labels: the soft probabilities are hardened to labels there, so there is "
+                         "nothing to quantise (use masks=float32)")
+    return save_probs, qa_report
+
+
+_QA_LABELS_NOTE = ("[ivos-w] qa_report under masks=labels: the soft values are gone, the report scores the one-hot planes of the label map "
+                   "(255 where the label is the object, else 0)")
+
+
+class QaSession:
+    """What run_eval / run_eval_real do under save_probs / qa_report, one call per interaction (nothing is made when both are off).
+    qa_report: the assessment passes' per-unit scores are tapped (utils_agent.score_tap), and ``after`` chains quantise -> counts from
+    the planes -> targets on the device (utils_agent.assess_report) with one copy of [loss, diff, n_valid]."""
+
+    def __init__(self, cfg, options, metric, masks):
+        from .utils import misc, utils_agent
+        self.save_probs, self.qa_report = options
+        self.metric, self.masks, self.out_dir = metric, masks, cfg.agent.save_result_dir
+        self.loss, self.diff, self.valid, self.units = misc.AverageMeter(), misc.AverageMeter(), 0, 0
+        if self.qa_report:
+            utils_agent.score_tap = []
+            if masks == "labels":
+                print(_QA_LABELS_NOTE)
+        if self.save_probs:
+            print(f"[ivos-w] save_probs=true: 8-bit probability planes of every interaction under {self.out_dir} (quantised on the device)")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        """Releases the score tap whether the loop ended or raised: later assessment passes of the process keep nothing."""
+        from .utils import utils_agent
+        if self.qa_report:
+            utils_agent.score_tap = None
+        return False
+
+    def after(self, sequence, visit, n_interaction, gt_masks, labels, all_P, n_objects, device):
+        """-> the text that goes beside `corr` ("" without qa_report)."""
+        from . import metrics
+        from .utils import misc, utils_agent
+        planes = None
+        if self.masks != "labels":
+            planes = metrics.quantize_probs(all_P, n_objects)              # one launch serves the files and the report
+        if self.save_probs:
+            misc.save_seg_preds(planes, dict(sequence=sequence, scribble_iter=visit, n_interaction=n_interaction), self.out_dir)
+        if not self.qa_report:
+            return ""
+        scores, utils_agent.score_tap = utils_agent.score_tap, []
+        if planes is None:                                                 # masks=labels: one-hot planes of the label map
+            lab = labels if torch.is_tensor(labels) else torch.from_numpy(np.ascontiguousarray(np.asarray(labels), dtype=np.uint8))
+            lab = lab.to(device=device, dtype=torch.uint8)
+            ids = torch.arange(1, n_objects + 1, device=device, dtype=torch.uint8).view(-1, 1, 1, 1)
+            planes = (lab.unsqueeze(0) == ids).to(torch.uint8) * 255
+        rep, _ = utils_agent.assess_report([(gt_masks, planes, n_objects)], scores[-1:], self.metric)
+        loss, diff, n_valid = float(rep[0, 0]), float(rep[0, 1]), int(rep[0, 2])
+        units = int(planes.shape[0]) * int(planes.shape[1])
+        if n_valid:
+            self.loss.update(loss)
+            self.diff.update(diff)
+        self.valid += n_valid
+        self.units += units
+        return f"qa_loss: {loss:.4f} qa_diff: {diff:.4f} valid: {n_valid}/{units} "
+
+    def summary(self):
+        """The "qa" block of summary.json (None without qa_report)."""
+        if not self.qa_report:
+            return None
+        return {"loss": float(self.loss.avg), "diff": float(self.diff.avg), "valid": int(self.valid), "units": int(self.units)}
 
 
 def write_image(path_stem, rgb):
@@ -244,6 +336,7 @@ def parse_cli(argv, **overrides):
         rescore_option(cfg)
         metric_option(cfg)
         cfg["overlay"] = overlay_option(cfg)[0]
+        qa_option(cfg)
     except ValueError as e:
         raise SystemExit(f"[ivos-w] {e}")
     return _attr(cfg)
@@ -485,6 +578,7 @@ def run_eval(cfg, backbone="MANet"):
     masks = masks_option(cfg)
     rescore = rescore_option(cfg)
     overlay = overlay_option(cfg)
+    qa = qa_option(cfg)
     oracle_chain = metric_option(cfg) == "device" and cfg.setting == "oracle" and cfg.method in ("ours", "worst")
     cfg.phase = "eval"
     cfg.data.subset = "val"
@@ -509,7 +603,9 @@ def run_eval(cfg, backbone="MANet"):
     report_dir = os.path.join(cfg.report_save_dir, backbone, cfg.setting, cfg.dataset, cfg.method)
     os.makedirs(report_dir, exist_ok=True)
     corr_all, rec_time, seen_seq = misc.AverageMeter(), misc.AverageMeter(), {}
-    with SyntheticSession(davis, cfg.data.subset, metric, max_nb, report_dir, seed=int(cfg.seed)) as sess:
+    qa_sess = QaSession(cfg, qa, metric, masks) if any(qa) else None
+    with SyntheticSession(davis, cfg.data.subset, metric, max_nb, report_dir, seed=int(cfg.seed)) as sess, \
+            (qa_sess or contextlib.nullcontext()):
         while sess.next():
             sequence, scribbles, first_scribble = sess.get_scribbles(only_last=True)
             if first_scribble:
@@ -548,16 +644,20 @@ def run_eval(cfg, backbone="MANet"):
             if overlay[0] != "none":                                  # what the annotator is shown: the candidates with the current masks on them
                 write_overlays(overlay, report_dir, sequence, seen_seq[sequence], n_interaction, all_F, labels, n_objects, candidates, device)
             sess.submit_masks(labels, next_scribble_frame_candidates=candidates)
+            qa_text = "" if qa_sess is None else qa_sess.after(sequence, seen_seq[sequence], n_interaction, davis.load_annotations(sequence),
+                                                               labels, all_P, n_objects, device)
             corr = float(np.corrcoef([quality, quality_pred])[0, 1]) if quality_pred is not None else float("nan")
             corr_all.update(0.0 if np.isnan(corr) else corr)
             print(f"avg_{metric}: {quality.mean() * 100:.2f} rec_time:{rec_time.val * 1e3:.1f} ms next_frame: {next_frame:2d} "
                   + (f"candidates: {candidates} " if len(candidates) > 1 else "") +
-                  f"[{int((quality < quality[next_frame]).sum()) + 1:2d}/{n_frame:2d}] corr: {corr:.2f} "
+                  f"[{int((quality < quality[next_frame]).sum()) + 1:2d}/{n_frame:2d}] corr: {corr:.2f} {qa_text}"
                   f"seq: {sequence}_{seen_seq[sequence]} [{n_interaction:2d}/{max_nb:2d}]")
         gs = sess.get_global_summary()
     curve = gs["curve"][metric][:-1]
     auc = float(np.trapz(curve) / (len(curve) - 1)) if len(curve) > 1 else float(curve[0])
     summary = {"auc": auc, "curve": {metric: curve}}
+    if qa_sess is not None and qa_sess.qa_report:
+        summary["qa"] = qa_sess.summary()
     with open(os.path.join(report_dir, "summary.json"), "w") as fp:
         json.dump(summary, fp)
     print(f"# global_summary: auc:{auc * 100:.4f}  recommend_frame avg {rec_time.avg * 1e3:.2f} ms  frame-cache uploads "
@@ -590,6 +690,7 @@ def run_eval_real(cfg, backbone, device):
     rescore = rescore_option(cfg)
     metric_mode = metric_option(cfg)
     overlay = overlay_option(cfg)
+    qa = qa_option(cfg)
     if masks == "labels":
         print(_MASKS_NOTE)
     misc.set_random_seed(int(cfg.seed))
@@ -605,9 +706,10 @@ def run_eval_real(cfg, backbone, device):
     davis = Davis(root)
     seen_seq, frames_of = {}, {}
     rec_time, corr_all, final_q = misc.AverageMeter(), misc.AverageMeter(), misc.AverageMeter()
+    qa_sess = QaSession(cfg, qa, metric, masks) if any(qa) else None
     with DavisInteractiveSession(host="localhost", davis_root=root, subset=cfg.data.subset, metric_to_optimize=metric,
                                  max_nb_interactions=max_nb, max_time=int(cfg.davis_interactive.max_time_per_interaction) or None,
-                                 report_save_dir=report_dir) as sess:
+                                 report_save_dir=report_dir) as sess, (qa_sess or contextlib.nullcontext()):
         while sess.next():
             sequence, scribbles, first_scribble = sess.get_scribbles(only_last=True)
             annotated = interactive_utils.scribbles.annotated_frames(scribbles)
@@ -661,10 +763,12 @@ def run_eval_real(cfg, backbone, device):
             if overlay[0] != "none":
                 write_overlays(overlay, report_dir, sequence, seen_seq[sequence], n_interaction, all_F, labels, n_objects, [next_frame], device)
             sess.submit_masks(new_masks, next_scribble_frame_candidates=[next_frame])
+            qa_text = "" if qa_sess is None else qa_sess.after(sequence, seen_seq[sequence], n_interaction, gt_masks, labels, all_P, n_objects,
+                                                               device)
             corr = float(np.corrcoef([quality, quality_pred])[0, 1]) if quality_pred is not None else float("nan")
             corr_all.update(0.0 if np.isnan(corr) else corr)
             print(f"avg_{metric}: {quality.mean() * 100:.2f} rec_time:{rec_time.val:.2f} next_frame: {next_frame:2d} "
-                  f"[{int((quality < quality[next_frame]).sum()) + 1:2d}/{n_frame:2d}] corr: {corr:.2f} ({corr_all.avg:.2f}) "
+                  f"[{int((quality < quality[next_frame]).sum()) + 1:2d}/{n_frame:2d}] corr: {corr:.2f} ({corr_all.avg:.2f}) {qa_text}"
                   f"seq: {sequence}_{seen_seq[sequence]} [{n_interaction:2d}/{max_nb:2d}]")
             if n_interaction == max_nb:
                 final_q.update(float(quality.mean()) * 100)
@@ -672,6 +776,8 @@ def run_eval_real(cfg, backbone, device):
     curve = list(gs["curve"][metric][:-1])
     auc = float(np.trapz(curve) / (len(curve) - 1)) if len(curve) > 1 else float(curve[0])
     summary = {"auc": auc, "curve": {metric: curve}}
+    if qa_sess is not None and qa_sess.qa_report:
+        summary["qa"] = qa_sess.summary()
     with open(os.path.join(report_dir, "summary.json"), "w") as fp:
         json.dump(summary, fp)
     print(f"# final avg {metric}: {final_q.avg:.4f}  final avg corr: {corr_all.avg:.4f}\n# global_summary: auc:{auc * 100:.4f}  frames: {frames}\n"
@@ -894,6 +1000,16 @@ def main_eval(backbone, argv=None):
     cfg = parse_cli(sys.argv[1:] if argv is None else argv)
     _print_metric_mode(cfg)
     return run_eval(cfg, backbone)
+
+
+def main_generate(argv=None):
+    """generate_data.py: the eval loop on the synthetic back end with save_probs=true - AssessNet's training samples as 8-bit planes."""
+    cfg = parse_cli(["synthetic=1", "save_probs=true"] + list(sys.argv[1:] if argv is None else argv))
+    if not cfg.save_probs or cfg.synthetic != 1:
+        raise SystemExit("[ivos-w] generate_data.py writes the probability planes of the synthetic back end: save_probs=true synthetic=1 are fixed")
+    print(f"[ivos-w] generate_data: the synthetic back end (stand-in VOS model, synthetic sequences), save_probs=true -> {cfg.agent.save_result_dir}")
+    _print_metric_mode(cfg)
+    return run_eval(cfg, "MANet")
 
 
 def main_train(argv=None):

@@ -137,3 +137,46 @@ def sequence_metric_videos(metric_to_optimize, videos, average_over_objects=True
     host = res.per_object_flat.cpu().numpy()
     offs = np.concatenate([[0], np.cumsum([n * o for n, o in zip(res.lengths, res.n_obj)])])
     return [host[int(a):int(b)].reshape(n, o).copy() for a, b, n, o in zip(offs[:-1], offs[1:], res.lengths, res.n_obj)]
+
+
+def write_gray(path_stem, plane):
+    """A uint8 [H,W] plane to ``path_stem`` + ".png" (8-bit greyscale) through PIL when it is importable, else + ".pgm" (binary P5) from
+    plain Python.  Returns the path written."""
+    plane = np.ascontiguousarray(plane, dtype=np.uint8)
+    try:
+        from PIL import Image
+    except ImportError:
+        path = path_stem + ".pgm"
+        with open(path, "wb") as fp:
+            fp.write(b"P5\n%d %d\n255\n" % (plane.shape[1], plane.shape[0]) + plane.tobytes())
+        return path
+    path = path_stem + ".png"
+    Image.fromarray(plane, mode="L").save(path)
+    return path
+
+
+def save_seg_preds(probs, new_masks_meta, save_result_dir):
+    """utils/misc.py:165-181 with the bytes formed on the device: the reference copies the whole float32 all_P to the host and writes
+    ``probs[i, n] * 255`` per object plane through cv2.imwrite; here ONE ``metrics.quantize_probs`` launch forms the same bytes where
+    all_P lives and ONE uint8 copy - a quarter of the bytes - reaches the host.  Same signature and directory layout:
+    <save_result_dir>/interaction-{n}/scribble-{s}/{sequence}/probs/{obj}/{i:05d}.png for the objects 1 .. O (channel 0 is not written),
+    8-bit greyscale through PIL (binary .pgm without it).  ``probs``: all_P as ``quantize_probs`` takes it ([n, O+1, H, W] float32 on the
+    device, a store, or a host array), or the already quantised uint8 [O, n, H, W] device tensor.  Returns the paths written, object-major."""
+    from .. import metrics
+
+    if isinstance(probs, torch.Tensor) and probs.dtype == torch.uint8:
+        if probs.ndim != 4:
+            raise ValueError(f"save_seg_preds: quantised planes must be uint8 [O, n, H, W], got {tuple(probs.shape)}")
+        planes = probs
+    else:
+        p = probs.all_P if hasattr(probs, "all_P") else probs
+        planes = metrics.quantize_probs(p, int(p.shape[1]) - 1)
+    host = planes.cpu().numpy()                                          # the one D2H copy of the call
+    meta = new_masks_meta
+    root = os.path.join(save_result_dir, f"interaction-{meta['n_interaction']}", f"scribble-{meta['scribble_iter']}", meta["sequence"], "probs")
+    paths = []
+    for o in range(host.shape[0]):                                       # object o + 1; channel 0 has no directory
+        obj_dir = os.path.join(root, str(o + 1))
+        os.makedirs(obj_dir, exist_ok=True)
+        paths += [write_gray(os.path.join(obj_dir, f"{i:05d}"), host[o, i]) for i in range(host.shape[1])]
+    return paths

@@ -312,6 +312,32 @@ def assess_all_objects(assess_net, all_F, all_P, n_objects, device, rescore="all
     return assess_all_objects_device(assess_net, all_F, all_P, n_objects, device, rescore).transpose(0, 1).cpu().numpy()
 
 
+# The per-unit scores of the assessment passes, for a caller that reports on them (entry's qa_report): None (the default: nothing is
+# kept, nothing is launched), or a list that _wild_assess / _recommend_many append one [n_objects, n_frame] device copy per video to.
+score_tap = None
+
+
+def _tap(scores):
+    if score_tap is not None:
+        score_tap.append(scores.detach().clone())
+
+
+def assess_report(videos, scores, metric, thr=None, bound_th=0.008):
+    """How far AssessNet's scores are from the truth, as the reference's training loop measures it (quality_assessment.py:235-263), in one
+    device chain: ``videos`` = [(gt_labels [N,H,W], all_P | store | quantised uint8 planes [O,N,H,W], n_objects), ...], ``scores`` the
+    session's per-unit scores (one [O, N] device tensor per video, as ``assess_videos_device`` returns them, or one flat tensor).
+    metrics.quantize_probs (one launch per float video) -> the count pass from the byte planes (one memset, two launches) ->
+    ivosw_qa_targets (one launch) -> ONE copy of [loss, diff, n_valid] per video.  Returns (report float32 numpy [V, 3], QaTargets)."""
+    from .. import metrics
+    thr = metrics.QA_THRESHOLD if thr is None else thr
+    table = []
+    for gt, probs, n_objects in videos:
+        planes = probs if (isinstance(probs, torch.Tensor) and probs.dtype == torch.uint8) else metrics.quantize_probs(probs, n_objects)
+        table.append((gt, planes, n_objects))
+    res = metrics.qa_targets(table, metric, scores=scores, thr=thr, bound_th=bound_th)
+    return res.report.cpu().numpy(), res                                  # the one D2H copy of the call
+
+
 def _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, counts, mask_quality, prev_frames, k=1, as_list=False,
                  rescore="all", gap=1):
     """wild/worst and wild/ours (utils/utils_agent.py:111-122) with the chain quality -> state -> Brain -> argmax on the
@@ -323,6 +349,7 @@ def _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, cou
     from .. import _lib as L
     from ..models.agent import merge_candidates, spread_candidates
     scores = assess_all_objects_device(assess_net, all_F, all_P, n_objects, device, rescore)
+    _tap(scores)
     n = scores.shape[1]
     dev = scores.device
     out = torch.empty(n + k, dtype=torch.float64, device=dev)          # [quality (n) | k recommended indices (int64 bits)]
@@ -427,6 +454,8 @@ def _recommend_many(cfg_yl, assess_net, agent, device, requests, as_list):
     K = len(requests)
     with torch.no_grad():
         scores = assess_videos_device(assess_net, [(r["all_F"], r["all_P"], r["n_objects"]) for r in requests], device, rescore_option(cfg_yl))
+        for s in scores:
+            _tap(s)
         dev = scores[0].device
         ns = [int(s.shape[1]) for s in scores]
         counts = [_annotation_counts(len(r["new_masks_quality"]), r["annotated_frames_list"]) for r in requests]
