@@ -799,6 +799,59 @@ int ivosw_overlay_lane_pixels(const void* frames, const uint8_t* labels, int W, 
 int ivosw_overlay_frames(const void* frames, int frames_kind, const uint8_t* labels, int n_frames, int H, int W,
                          const int* frame_ids, int n_ids, const ivosw_overlay_t* opt, void* out, int out_kind, ivosw_stream_t stream);
 
+/* ------------------------------------------------------------------ scribbles (8f-4, the input side) */
+/* The scribbles an annotator (or the robot) has just drawn, as label maps on the device: what eval_agent_manet.py:368-374 builds with
+ * davisinteractive's scribbles2mask, ToTensor and rough_ROI, and eval_agent_ipn.py with scribbles2mask and Dilate_mask.
+ * scribbles2mask is not in the reference tree: the rules below are this project's DEFINITION (tests/scribble_ref.py), parity with the
+ * library's own rasteriser is unpinned.  rough_ROI (utils/utils_manet.py:22-39) is in the tree and is kept bit for bit.
+ *
+ * Packing (the caller's, on the host; utils/scribbles.py): for a map of (H, W) a path point (x, y) in [0, 1]^2 becomes the pixel
+ *   px = min((int)(x * W), W - 1), py = min((int)(y * H), H - 1), the products in double and truncated.  The kernels see integers only.
+ * Line rule: consecutive points of a path are joined, the path is not closed.  For (x0,y0) -> (x1,y1): dx = |x1 - x0|, dy = |y1 - y0|,
+ *   the signs are +1 if the difference is > 0, else -1.  x drives if dx > dy, otherwise (dx == dy included) y drives.  With the driving
+ *   length a and the minor length b:   D = 2b - a; m = 0;  for s in 0 .. a: plot(driving = s, minor = m); if D >= 0: m += 1, D -= 2a;
+ *   D += 2b.   The kernel uses the closed form m(s) = (2 b s + a) / (2 a) for a > 0 (the same pixels; tests/test_scribble_option.py
+ *   compares them for all b <= a <= 64).  A one-point path plots that pixel, a zero-length segment one pixel; with bresenham == 0 only
+ *   the points themselves are plotted.
+ * Order: within a map the paths are drawn in table order, a later path overwrites an earlier one; untouched pixels hold default_value.
+ * rough_ROI with distance d, per map / image: the box (hmin, hmax, wmin, wmax) is that of the pixels != -1 (a NaN counts as != -1); rows
+ *   [max(hmin - d, 0), min(hmax + d, h - 1)) x columns [max(wmin - d, 0), min(wmax + d, w - 1)) keep their value, every other pixel
+ *   becomes 0.  Both ends are exclusive: a scribble on the last row or column loses that row or column, as in the reference.  One
+ *   difference: a map without such a pixel raises in the reference (torch.min of an empty tensor); here it comes out all 0, with no
+ *   synchronisation.
+ *
+ * ivosw_scribble_raster:
+ *   points      device int32 [n_points,2] = (px, py).
+ *   paths       device int32 [n_paths,4] = {first point, number of points, object id, map index}.
+ *   paths_host  a HOST copy of the same table, read during the call (as `lengths` is by the ragged entries): the table is validated
+ *               from it before anything is launched.  The point ranges ascend and do not overlap (first[k] >= first[k-1] + n[k-1]):
+ *               the draw kernel finds the path of a point by a binary search.  Points no path owns are ignored.
+ *   out_i8      device int8 [n_maps,H,W], out_f32 device float32 [n_maps,H,W] with the same values (what MANet takes); either may be
+ *               NULL, not both.
+ *   roi_dist    < 0: off; >= 0: the rough_ROI rule with that distance applied to every map in the finalise pass.
+ *   ws          caller-owned, ivosw_scribble_raster_ws_bytes(n_maps, H, W) bytes on the 16-byte grid (0 = the shape would be refused).
+ * One memset (a uint32 key plane and four box integers per map), one draw launch (a wave per point, its lanes over the steps of the
+ * segment that starts there: atomicMax of path index + 1 into the key plane - the highest path index on a pixel is the last
+ * assignment, so the result does not depend on the schedule - and four atomicMax into the map's box), one finalise launch
+ * (key ? object[key - 1] : default_value, the ROI, 16-byte stores when out_i8 and out_f32 are on the 16-byte grid, else and for the
+ * last partial group element by element; IVOSW_SCRIBBLE_SCALAR in the environment forces that).  A segment with an end point outside
+ * the map is not drawn.  Asynchronous on `stream`; allocates nothing, synchronises nothing (capture-safe).
+ * Refused (IVOSW_ERR_ARG) before anything is launched, nothing written, the message names the argument: a NULL ws, a NULL points, paths
+ * or paths_host with n_paths > 0, both outputs NULL, n_maps, H or W < 1, n_maps * H * W > INT_MAX, n_paths < 0 (0 is legal: every map
+ * comes out at its default), n_points < 0, default_value outside int8, a ws off the 16-byte grid, and a path (the message names its
+ * index) whose point range is empty, leaves [0, n_points) or does not lie behind the previous path's, whose object id is outside
+ * [0, 126] or whose map index is outside [0, n_maps).  A short workspace: IVOSW_ERR_WS.
+ *
+ * ivosw_rough_roi: the stand-alone drop-in body on float32 [b,1,h,w] (out may be in): a memset of ws (ivosw_rough_roi_ws_bytes(b)), a
+ * box scan (wave reductions, four atomics per wave into ws) and a fill (float4 when in and out are on the 16-byte grid), two launches.
+ * Refused (IVOSW_ERR_ARG): a NULL in, out or ws, b, h or w < 1, b > 65535, b * h * w > INT_MAX, dist < 0.  A short ws: IVOSW_ERR_WS. */
+size_t ivosw_scribble_raster_ws_bytes(int n_maps, int H, int W);
+int ivosw_scribble_raster(const int32_t* points, int n_points, const int32_t* paths, const int32_t* paths_host, int n_paths,
+                          int n_maps, int H, int W, int default_value, int bresenham, int roi_dist, int8_t* out_i8, float* out_f32,
+                          void* ws, size_t ws_bytes, ivosw_stream_t stream);
+size_t ivosw_rough_roi_ws_bytes(int b);
+int ivosw_rough_roi(const float* in, float* out, int b, int h, int w, int dist, void* ws, size_t ws_bytes, ivosw_stream_t stream);
+
 /* ------------------------------------------------------------------ launch-sequence capture ---- */
 /* HIP-graph capture of any sequence of the calls above on one stream (not in the reference: it replaces the ~40 host
  * launches per Agent.update_agent step, models/agent.py:128-160, by ONE hipGraphLaunch).  begin puts `stream` (non-null)

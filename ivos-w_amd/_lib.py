@@ -158,6 +158,10 @@ SIGNATURES = {
     "ivosw_ipn_merge": (_i, [_p, _p, _i, _i, _i, _i, _p, _p, _p, _p, C.c_long, _p, _p, _p]),
     "ivosw_overlay_lane_pixels": (_i, [_p, _p, _i, _p, _i]),
     "ivosw_overlay_frames": (_i, [_p, _i, _p, _i, _i, _i, _p, _i, _p, _p, _i, _p]),
+    "ivosw_scribble_raster_ws_bytes": (_sz, [_i, _i, _i]),
+    "ivosw_scribble_raster": (_i, [_p, _i, _p, _p] + [_i] * 7 + [_p, _p, _p, _sz, _p]),
+    "ivosw_rough_roi_ws_bytes": (_sz, [_i]),
+    "ivosw_rough_roi": (_i, [_p, _p, _i, _i, _i, _i, _p, _sz, _p]),
     "ivosw_graph_begin": (_i, [_p]),
     "ivosw_graph_end": (_i, [_p, C.POINTER(_p), C.POINTER(_i)]),
     "ivosw_graph_launch": (_i, [_p, _p]),
@@ -255,6 +259,12 @@ def dptr(t, dtype=None):
     if not t.is_contiguous():
         raise ValueError("tensor must be contiguous")
     return C.c_void_p(t.data_ptr())
+
+
+def torch_ptr(t, elem_offset):
+    """Raw device pointer of element ``elem_offset`` of a contiguous CUDA tensor (``dptr``'s checks)."""
+    dptr(t)
+    return C.c_void_p(t.data_ptr() + int(elem_offset) * t.element_size())
 
 
 def int_array(values):

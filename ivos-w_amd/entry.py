@@ -79,6 +79,9 @@ DEFAULTS = dict(
     qa_report=False,                   # true (wild setting, method ours | worst): per interaction the reference's training-loop measures of the
                                        # AssessNet scores against the true per-unit targets - qa_loss (mean squared), qa_diff (mean absolute)
                                        # and valid/units - beside corr, and their session means under "qa" in summary.json
+    scribbles="frame",                 # what the synthetic session's robot hands out: "frame" (a scribble only names the annotated frame), or
+                                       # "paths": one real polyline per object in davisinteractive's schema, drawn on the device at the stand-in's
+                                       # logit resolution (utils.scribbles.scribble_maps) and fed to the stand-in VOS model
     report_save_dir="results",
     eval_max_nb_interactions=8,        # the eval scripts fix 8 interactions on the val subset (eval_agent_manet.py:64-65)
     data=dict(num_workers=0, root_dir_davis="data/DAVIS", root_dir_scribble_youtube_vos="data/Scribble_Youtube_VOS",
@@ -141,6 +144,17 @@ def overlay_option(cfg):
     if not isinstance(which, str) or which not in OVERLAY_FRAMES:
         raise ValueError(f"overlay_frames must be 'candidates' or 'all', got {which!r}")
     return style, which
+
+
+SCRIBBLE_MODES = ("frame", "paths")
+
+
+def scribbles_option(cfg):
+    """cfg.scribbles (absent: "frame"), refused unless it is one of SCRIBBLE_MODES."""
+    mode = cfg.get("scribbles", "frame")
+    if not isinstance(mode, str) or mode not in SCRIBBLE_MODES:
+        raise ValueError(f"scribbles must be 'frame' or 'paths', got {mode!r}")
+    return mode
 
 
 def qa_option(cfg):
@@ -337,6 +351,7 @@ def parse_cli(argv, **overrides):
         metric_option(cfg)
         cfg["overlay"] = overlay_option(cfg)[0]
         qa_option(cfg)
+        scribbles_option(cfg)
     except ValueError as e:
         raise SystemExit(f"[ivos-w] {e}")
     return _attr(cfg)
@@ -446,10 +461,12 @@ class SyntheticDavis:
 
 class SyntheticSession:
     """The protocol of DavisInteractiveSession as the entry scripts use it (next / get_scribbles / submit_masks /
-    get_global_summary, ``samples``), with the J&F curve bookkeeping; a "scribble" names the annotated frame only."""
+    get_global_summary, ``samples``), with the J&F curve bookkeeping; a "scribble" names the annotated frame only, unless
+    ``scribbles="paths"``: then the annotated frame's entry holds real paths (``robot_paths``)."""
 
-    def __init__(self, davis, subset, metric_to_optimize, max_nb_interactions, report_save_dir, seed=0, rounds=1):
+    def __init__(self, davis, subset, metric_to_optimize, max_nb_interactions, report_save_dir, seed=0, rounds=1, scribbles="frame"):
         self.davis, self.metric, self.max_nb = davis, metric_to_optimize, int(max_nb_interactions)
+        self.scribble_mode = scribbles
         self.report_save_dir = report_save_dir
         rs = np.random.RandomState(77 + seed)
         self.samples = [(seq, int(rs.randint(davis.dataset[seq]["num_frames"]))) for _ in range(rounds) for seq in davis.sets[subset]]
@@ -476,8 +493,10 @@ class SyntheticSession:
     def get_scribbles(self, only_last=False):
         seq = self.samples[self._i][0]
         n = self.davis.dataset[seq]["num_frames"]
-        scribbles = dict(sequence=seq, annotated_frame=self._frame,
-                         scribbles=[[dict(frame=self._frame)] if f == self._frame else [] for f in range(n)])
+        mine = [dict(frame=self._frame)]
+        if self.scribble_mode == "paths":
+            mine = robot_paths(self.davis.load_annotations(seq)[self._frame].cpu().numpy(), self.davis.dataset[seq]["num_objects"])
+        scribbles = dict(sequence=seq, annotated_frame=self._frame, scribbles=[mine if f == self._frame else [] for f in range(n)])
         self._tic = time.time()
         return seq, scribbles, self._k == 0
 
@@ -504,15 +523,42 @@ class SyntheticSession:
                     metric_at_threshold={self.metric: curve[-1], "threshold": 60})
 
 
+def robot_paths(gt, n_objects, max_points=5):
+    """The synthetic robot's scribbles on one ground-truth label map ``gt`` [H,W] (numpy), in davisinteractive's schema: one polyline
+    ``dict(path=[[x, y], ...], object_id=o, start_time=0, end_time=0)`` per object o = 1 .. n_objects that has pixels on the frame, in
+    ascending object order.  Construction, deterministic: the first of the object's rows that holds the most of its pixels; on that row
+    the first of its longest runs of consecutive pixels, without a quarter of its length at either end (a robot draws inside the object,
+    not along its edge); up to ``max_points`` pixels spread evenly from the first to the last pixel of what is left (``np.linspace``,
+    rounded, duplicates dropped).  The polyline joins them in order, so every pixel it crosses is a pixel of the object.  A
+    pixel (px, py) becomes the point ((px + 0.5) / W, (py + 0.5) / H), which maps back to it."""
+    H, W = gt.shape
+    paths = []
+    for o in range(1, int(n_objects) + 1):
+        mine = gt == o
+        counts = mine.sum(1)
+        if counts.max() == 0:
+            continue
+        y = int(counts.argmax())
+        edges = np.flatnonzero(np.diff(np.concatenate(([0], mine[y].astype(np.int8), [0]))))      # run starts and ends, alternating
+        starts, ends = edges[0::2], edges[1::2]
+        k = int((ends - starts).argmax())
+        inset = int(ends[k] - starts[k]) // 4
+        x0, x1 = int(starts[k]) + inset, int(ends[k]) - 1 - inset
+        xs = np.unique(np.linspace(x0, x1, min(int(max_points), x1 - x0 + 1)).round().astype(int))
+        paths.append(dict(path=[[(float(x) + 0.5) / W, (y + 0.5) / H] for x in xs], object_id=o, start_time=0, end_time=0))
+    return paths
+
+
 class StandInVOS:
     """Deterministic stand-in for the VOS backbone: stride-4 logits whose error grows with the distance to the nearest annotated
     frame (the ground truth shifted by 1.5 px per frame of distance, plus seeded noise).  Annotated frames come out (almost) exact,
-    so annotating the worst frame helps most — the structure the agent learns from."""
+    so annotating the worst frame helps most — the structure the agent learns from.  ``scribble_low`` = (frame, int8 [h // 4, w // 4]
+    scribble map on the device): the scribbled object's logit gains 8 at the scribbled low-resolution pixels of that frame."""
 
     def __init__(self, device, seed=0):
         self.device, self.seed = device, seed
 
-    def logits(self, gt_u8, n_objects, annotated_frames):
+    def logits(self, gt_u8, n_objects, annotated_frames, scribble_low=None):
         n, h, w = gt_u8.shape
         C = n_objects + 1
         onehot = torch.nn.functional.one_hot(gt_u8.long().clamp_(0, C - 1), C).permute(0, 3, 1, 2).float()
@@ -526,7 +572,13 @@ class StandInVOS:
             d = int(dist[f])
             sh = int(round(1.5 * d / 4 * 4)) // 4 if d else 0
             out[f] = torch.roll(low[f], shifts=(sh, -sh), dims=(1, 2))
-        return 8.0 * (out - 0.5) + noise * (0.3 + 0.25 * dist.float())[:, None, None, None]
+        res = 8.0 * (out - 0.5) + noise * (0.3 + 0.25 * dist.float())[:, None, None, None]
+        if scribble_low is not None:                                  # device tensor work, no synchronisation
+            frame, low_map = scribble_low
+            lab = low_map.long()
+            hit = ((lab >= 0) & (lab < C)).float()
+            res[int(frame)] += 8.0 * hit[None] * torch.nn.functional.one_hot(lab.clamp(0, C - 1), C).permute(2, 0, 1).float()
+        return res
 
 
 # ------------------------------------------------------------------------------------------ building the hot-path objects
@@ -548,10 +600,10 @@ def build_hot_path(cfg, device, need_assess):
     return agent, assess_net
 
 
-def _segment(vos, davis, seq, n_objects, annotated, store):
+def _segment(vos, davis, seq, n_objects, annotated, store, scribble_low=None):
     from .utils import utils_manet
     gt = davis.load_annotations(seq)
-    lg = vos.logits(gt, n_objects, annotated)
+    lg = vos.logits(gt, n_objects, annotated, scribble_low=scribble_low)
     utils_manet.seg_epilogue(lg, gt.shape[1], gt.shape[2], store, 0)
     return store.labels_u8, store.all_P
 
@@ -579,6 +631,7 @@ def run_eval(cfg, backbone="MANet"):
     rescore = rescore_option(cfg)
     overlay = overlay_option(cfg)
     qa = qa_option(cfg)
+    scribble_mode = scribbles_option(cfg)
     oracle_chain = metric_option(cfg) == "device" and cfg.setting == "oracle" and cfg.method in ("ours", "worst")
     cfg.phase = "eval"
     cfg.data.subset = "val"
@@ -604,7 +657,7 @@ def run_eval(cfg, backbone="MANet"):
     os.makedirs(report_dir, exist_ok=True)
     corr_all, rec_time, seen_seq = misc.AverageMeter(), misc.AverageMeter(), {}
     qa_sess = QaSession(cfg, qa, metric, masks) if any(qa) else None
-    with SyntheticSession(davis, cfg.data.subset, metric, max_nb, report_dir, seed=int(cfg.seed)) as sess, \
+    with SyntheticSession(davis, cfg.data.subset, metric, max_nb, report_dir, seed=int(cfg.seed), scribbles=scribble_mode) as sess, \
             (qa_sess or contextlib.nullcontext()):
         while sess.next():
             sequence, scribbles, first_scribble = sess.get_scribbles(only_last=True)
@@ -623,7 +676,16 @@ def run_eval(cfg, backbone="MANet"):
             else:
                 annotated.append(next_frame)
                 n_interaction += 1
-            labels, all_P = _segment(vos, davis, sequence, n_objects, annotated, store)
+            scribble_low, scribble_text = None, ""
+            if scribble_mode == "paths":                              # the paths drawn at the stand-in's stride-4 logit resolution, as MANet
+                from .utils import scribbles as S                     # draws them at its embedding resolution
+                drawn = int(scribbles["annotated_frame"])
+                scribble_low = (drawn, S.scribble_maps(scribbles, (h // 4, w // 4), frames=[drawn], device=device)[0])
+                scribble_text = f"scribble: {len(scribbles['scribbles'][drawn])} paths "
+            if scribble_low is None:                                  # (tests/test_qa_option.py replaces _segment by a six-argument double)
+                labels, all_P = _segment(vos, davis, sequence, n_objects, annotated, store)
+            else:
+                labels, all_P = _segment(vos, davis, sequence, n_objects, annotated, store, scribble_low)
             if oracle_chain:                                          # metric=device: J / F, state, Brain and ranking in one device chain
                 tic = time.time()
                 qualities, picks = utils_agent.oracle_recommend(cfg, agent, device, [dict(
@@ -650,7 +712,7 @@ def run_eval(cfg, backbone="MANet"):
             corr_all.update(0.0 if np.isnan(corr) else corr)
             print(f"avg_{metric}: {quality.mean() * 100:.2f} rec_time:{rec_time.val * 1e3:.1f} ms next_frame: {next_frame:2d} "
                   + (f"candidates: {candidates} " if len(candidates) > 1 else "") +
-                  f"[{int((quality < quality[next_frame]).sum()) + 1:2d}/{n_frame:2d}] corr: {corr:.2f} {qa_text}"
+                  f"[{int((quality < quality[next_frame]).sum()) + 1:2d}/{n_frame:2d}] corr: {corr:.2f} {qa_text}{scribble_text}"
                   f"seq: {sequence}_{seen_seq[sequence]} [{n_interaction:2d}/{max_nb:2d}]")
         gs = sess.get_global_summary()
     curve = gs["curve"][metric][:-1]

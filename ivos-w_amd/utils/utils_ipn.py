@@ -24,6 +24,9 @@ IPN's ``model.Run`` lives in the external clone, not in the reference tree, so p
   around the same kernel with one frame.  The reference's board stops at 1000 pixels a side (a larger image raises there); here the
   checker pattern simply continues.  Float images are not restated: a non-uint8 image is a TypeError.
 
+* the scribble input (eval_agent_ipn.py: ``scribbles2mask`` at full resolution, then ``Dilate_mask``): ``scribble_input`` draws the
+  annotated frame's paths on the device (``csrc/scribble.hip``, ``utils/scribbles.py``) and dilates the map where it lies.
+
 There is no CPU fallback for the device entries.
 """
 import ctypes
@@ -118,6 +121,17 @@ def Dilate_mask(mask, num_objects, device=None):
     m8 = np.where((mask >= 0) & (mask <= int(num_objects)), mask, -1).astype(np.int8)      # no (mask == o) of the reference sees the rest
     dev = torch.device("cuda" if device is None else device)
     return dilate_scribbles(torch.from_numpy(m8).to(dev), num_objects).cpu().numpy().astype(np.int64)
+
+
+def scribble_input(scribbles, frame, size, num_objects, device=None):
+    """``Dilate_mask(scribbles2mask(scribbles, size)[frame], num_objects)`` on the device: the int8 map [H,W] of ``frame`` drawn by
+    ``ivosw_scribble_raster`` (that frame's paths only) and dilated by ``ivosw_ipn_dilate`` - three launches, no host array, no
+    synchronisation.  The line rule is this project's (utils/scribbles.py)."""
+    from . import scribbles as S
+    if not 0 <= int(num_objects) <= MAX_OBJECTS:
+        raise ValueError(f"scribble_input: num_objects {num_objects} outside [0, {MAX_OBJECTS}]")
+    m = S.scribble_maps(scribbles, size, frames=[int(frame)], device=device)
+    return dilate_scribbles(m, num_objects)[0]
 
 
 # ----------------------------------------------------------------------------------------------- merge, labels, all_P

@@ -7,10 +7,18 @@ the loop consumes: bilinear upsampling, argmax (the label that drives the next p
 and the softmax that becomes ``all_P`` — fused into one HIP kernel per frame (``csrc/seg_epilogue.hip``), writing
 ``all_P`` once, object-major, so ``assess_all_objects`` slices per-object soft masks without a transpose copy.
 There is no CPU fallback.
+
+The input side of an interaction is here too (``csrc/scribble.hip``): ``rough_ROI`` (reference ``utils/utils_manet.py:22-39``) and
+``scribble_label``, lines 368-374 of the reference's loop (``scribbles2mask`` at the embedding resolution, ``ToTensor``, ``rough_ROI`` on
+the first interaction, ``.cuda()``) as one device chain.
 """
 import torch
 
 from .. import _lib as L
+from . import scribbles as S
+
+ROI_DIST = 20                 # rough_ROI's `dist` (utils/utils_manet.py:24)
+_roi_ws = {}                  # device -> Workspace
 
 
 class ProbStore:
@@ -58,10 +66,38 @@ def seg_epilogue(pred_label, h, w, store=None, frame=None):
     return label, slot.permute(1, 0, 2, 3)
 
 
-def torch_ptr(t, elem_offset):
-    import ctypes
-    L.dptr(t)          # CUDA + contiguity check
-    return ctypes.c_void_p(t.data_ptr() + elem_offset * t.element_size())
+torch_ptr = L.torch_ptr      # (utils_atnet and utils_ipn import it from here)
+
+
+def rough_ROI(ref_scribble_labels):
+    """Drop-in for utils/utils_manet.py:22-39 on a device float32 tensor [b,1,h,w]: per image the box of the pixels != -1, grown by 20
+    and cut with EXCLUSIVE ends at h - 1 and w - 1 as the reference's slices are, keeps its values; everything else becomes 0.  A new
+    tensor, two launches, no synchronisation.  One difference: an image without such a pixel raises in the reference (``torch.min`` of an
+    empty tensor); here it comes out all 0."""
+    t = ref_scribble_labels
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise TypeError("rough_ROI: the scribble labels must be a torch.float32 tensor")
+    if t.dim() != 4 or t.shape[1] != 1 or min(t.shape) < 1:
+        raise ValueError(f"rough_ROI: the scribble labels must be [b,1,h,w], got {tuple(t.shape)}")
+    if not t.is_cuda:
+        raise RuntimeError("rough_ROI: the scribble labels must be a CUDA tensor (no CPU fallback)")
+    t = t.contiguous()
+    out = torch.empty_like(t)
+    b, _, h, w = (int(v) for v in t.shape)
+    lib = L.lib()
+    ws = _roi_ws.setdefault(t.device, L.Workspace()).get(max(lib.ivosw_rough_roi_ws_bytes(b), 16), t.device)
+    L.check(lib.ivosw_rough_roi(L.dptr(t), L.dptr(out), b, h, w, ROI_DIST, L.dptr(ws), ws.numel(), L.stream_ptr(t.device)), "rough_roi")
+    return out
+
+
+def scribble_label(scribbles, frame, size, first_scribble, device=None):
+    """eval_agent_manet.py:368-374 as one device chain: the scribble map of ``frame`` at ``size`` = (emb_h, emb_w) as float32 [1,1,h,w]
+    on ``device``, with ``rough_ROI`` fused into the rasteriser's finalise pass when ``first_scribble``.  Only that frame's paths go up
+    and only its map is drawn (one small upload, one memset, two launches).  A first scribble without any path gives all 0 where the
+    reference's rough_ROI raises."""
+    h, w = (int(v) for v in size)
+    m = S.scribble_maps(scribbles, (h, w), frames=[int(frame)], device=device, roi_dist=ROI_DIST if first_scribble else None, as_float=True)
+    return m.view(1, 1, h, w)
 
 
 def get_results(model, ref_frame_embedding, scribble_label, prev_label, eval_global_map_tmp_dic, local_map_dics,
