@@ -852,6 +852,46 @@ int ivosw_scribble_raster(const int32_t* points, int n_points, const int32_t* pa
 size_t ivosw_rough_roi_ws_bytes(int b);
 int ivosw_rough_roi(const float* in, float* out, int b, int h, int w, int dist, void* ws, size_t ws_bytes, ivosw_stream_t stream);
 
+/* ------------------------------------------------------------------ scribble robot (8f-4, the annotator's side) */
+/* The skeleton of the region where a prediction misses an object: what davisinteractive's scribble robot builds on the CPU at every
+ * interaction (a skeletonisation of the error mask, then paths along it; produce_reward.py:133 sets its min_nb_nodes).  The robot is not
+ * in the reference tree and neither davisinteractive nor skimage is a dependency: the rule below is this project's DEFINITION
+ * (tests/robot_ref.py restates it per pixel), parity with the library's own skeletoniser is restated, not recorded.
+ *
+ * A unit is one (frame, object) pair.  Error plane: pixel (y, x) is set iff gt[frame][y][x] == object && pred[frame][y][x] != object; a
+ *   NULL pred is all background (the first interaction: the error region is the object itself).
+ * Thinning: Zhang and Suen, "A fast parallel algorithm for thinning digital patterns" (1984), as published.  The neighbours of P1 are named
+ *   clockwise from north: P2 = N, P3 = NE, P4 = E, P5 = SE, P6 = S, P7 = SW, P8 = W, P9 = NW; everything outside the image is 0.
+ *   B = the number of set neighbours, A = the number of 0 -> 1 steps around the cycle P2, P3, .., P9, P2.  A pixel is deleted iff it is
+ *   set, 2 <= B <= 6, A == 1 and, in sub-iteration 1, P2 * P4 * P6 == 0 and P4 * P6 * P8 == 0; in sub-iteration 2, P2 * P4 * P8 == 0 and
+ *   P2 * P6 * P8 == 0.  Every decision of a sub-iteration reads the plane as it was before that sub-iteration.  An iteration is
+ *   sub-iteration 1, then 2; iterations run until one deletes nothing, at most max(H, W) of them.  iters = the number of iterations
+ *   that deleted a pixel (an empty plane: 0), or -1 when the max(H, W)-th iteration still deleted one.  The algorithm's known artefacts
+ *   stay: an isolated 2 x 2 block is deleted whole, a single pixel is kept.
+ *
+ * ivosw_robot_skeleton:
+ *   gt, pred    device uint8 [n,H,W] label maps; pred may be NULL.
+ *   units_host  a HOST int32 [m,2] = (frame, object), read during the call (as `lengths` is by the ragged entries): the table travels
+ *               inside the kernel arguments, 64 units per launch, a longer list in groups of 64.
+ *   points      device int32 [m,cap]: the skeleton pixels of unit k as (y << 16) | x in ascending raster order; nothing is written at or
+ *               beyond cap.
+ *   counts      device int32 [m]: the TRUE number of skeleton pixels, also when it exceeds cap.
+ *   iters       device int32 [m].
+ *   skel        NULL, or device uint32 [m,H,ceil(W/32)]: the skeleton's bit plane, bit (x & 31) of word (x >> 5) of row y; bits at
+ *               x >= W are 0.
+ * One workgroup of 1024 threads per unit thins the plane entirely in LDS (two bit planes, ping and pong; 32 pixels per lane and step
+ * with word logic; no global pass, no atomics on global memory).  Asynchronous on `stream`; allocates nothing, copies nothing,
+ * synchronises nothing (capture-safe).
+ * Size limit: 2 * H * ceil(W/32) * 4 bytes + 256 must fit in the 160 KB of LDS of one gfx950 workgroup; ivosw_robot_skeleton_fits(H, W)
+ * (host only) returns 1 if a size fits, else 0.  480 x 854 (DAVIS 480p: 103 936 bytes) fits, 720 x 1280 (230 656 bytes) does not: the
+ * robot serves 480p.
+ * Refused (IVOSW_ERR_ARG) before anything is launched, nothing written, the message names the argument: a NULL gt, units_host, points,
+ * counts or iters, n < 1, m < 1, cap < 1, H or W outside [1, 65535], a size that does not fit (the message names H, W and the limit), a
+ * unit (the message names its index) whose frame is outside [0, n) or whose object is outside [1, 255].                             */
+int ivosw_robot_skeleton_fits(int H, int W);
+int ivosw_robot_skeleton(const uint8_t* gt, const uint8_t* pred, int n, int H, int W, const int32_t* units_host, int m, int cap,
+                         int32_t* points, int32_t* counts, int32_t* iters, uint32_t* skel, ivosw_stream_t stream);
+
 /* ------------------------------------------------------------------ launch-sequence capture ---- */
 /* HIP-graph capture of any sequence of the calls above on one stream (not in the reference: it replaces the ~40 host
  * launches per Agent.update_agent step, models/agent.py:128-160, by ONE hipGraphLaunch).  begin puts `stream` (non-null)

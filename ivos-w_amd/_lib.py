@@ -162,6 +162,8 @@ SIGNATURES = {
     "ivosw_scribble_raster": (_i, [_p, _i, _p, _p] + [_i] * 7 + [_p, _p, _p, _sz, _p]),
     "ivosw_rough_roi_ws_bytes": (_sz, [_i]),
     "ivosw_rough_roi": (_i, [_p, _p, _i, _i, _i, _i, _p, _sz, _p]),
+    "ivosw_robot_skeleton_fits": (_i, [_i, _i]),
+    "ivosw_robot_skeleton": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p]),
     "ivosw_graph_begin": (_i, [_p]),
     "ivosw_graph_end": (_i, [_p, C.POINTER(_p), C.POINTER(_i)]),
     "ivosw_graph_launch": (_i, [_p, _p]),

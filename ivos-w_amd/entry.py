@@ -82,6 +82,10 @@ DEFAULTS = dict(
     scribbles="frame",                 # what the synthetic session's robot hands out: "frame" (a scribble only names the annotated frame), or
                                        # "paths": one real polyline per object in davisinteractive's schema, drawn on the device at the stand-in's
                                        # logit resolution (utils.scribbles.scribble_maps) and fed to the stand-in VOS model
+    robot="gt",                        # where the synthetic session's robot draws under scribbles=paths: "gt" (one straight run inside each object of
+                                       # the ground truth, whatever was predicted), or "errors": along the skeleton of each object's error region
+                                       # gt == o and pred != o of the masks last submitted, thinned on the device (utils.robot.interact)
+    robot_min_nodes=4,                 # robot=errors: an error skeleton of fewer connected pixels draws no path (davisinteractive's min_nb_nodes)
     report_save_dir="results",
     eval_max_nb_interactions=8,        # the eval scripts fix 8 interactions on the val subset (eval_agent_manet.py:64-65)
     data=dict(num_workers=0, root_dir_davis="data/DAVIS", root_dir_scribble_youtube_vos="data/Scribble_Youtube_VOS",
@@ -155,6 +159,22 @@ def scribbles_option(cfg):
     if not isinstance(mode, str) or mode not in SCRIBBLE_MODES:
         raise ValueError(f"scribbles must be 'frame' or 'paths', got {mode!r}")
     return mode
+
+
+ROBOT_MODES = ("gt", "errors")
+
+
+def robot_option(cfg):
+    """(cfg.robot, cfg.robot_min_nodes) (absent: "gt", 4).  Refused: a robot that is not one of ROBOT_MODES; robot=errors unless
+    scribbles=paths (a scribble that only names its frame has nothing to draw); a robot_min_nodes that is not an integer >= 1."""
+    mode, min_nodes = cfg.get("robot", "gt"), cfg.get("robot_min_nodes", 4)
+    if not isinstance(mode, str) or mode not in ROBOT_MODES:
+        raise ValueError(f"robot must be 'gt' or 'errors', got {mode!r}")
+    if isinstance(min_nodes, bool) or not isinstance(min_nodes, int) or min_nodes < 1:
+        raise ValueError(f"robot_min_nodes must be an integer >= 1, got {min_nodes!r}")
+    if mode == "errors" and cfg.get("scribbles", "frame") != "paths":
+        raise ValueError("robot=errors draws paths: it needs scribbles=paths")
+    return mode, min_nodes
 
 
 def qa_option(cfg):
@@ -352,6 +372,7 @@ def parse_cli(argv, **overrides):
         cfg["overlay"] = overlay_option(cfg)[0]
         qa_option(cfg)
         scribbles_option(cfg)
+        robot_option(cfg)
     except ValueError as e:
         raise SystemExit(f"[ivos-w] {e}")
     return _attr(cfg)
@@ -462,11 +483,17 @@ class SyntheticDavis:
 class SyntheticSession:
     """The protocol of DavisInteractiveSession as the entry scripts use it (next / get_scribbles / submit_masks /
     get_global_summary, ``samples``), with the J&F curve bookkeeping; a "scribble" names the annotated frame only, unless
-    ``scribbles="paths"``: then the annotated frame's entry holds real paths (``robot_paths``)."""
+    ``scribbles="paths"``: then the annotated frame's entry holds real paths - ``robot_paths`` on the ground truth, or with
+    ``robot="errors"`` the paths of ``utils.robot.interact`` along the error skeletons of the masks last submitted for this sample
+    (none yet: the objects themselves); ``robot_paths`` stands in only when no object at all yields a path.  ``drew`` names the robot
+    that drew the last scribbles: "gt", "errors" or "gt (no error path)"."""
 
-    def __init__(self, davis, subset, metric_to_optimize, max_nb_interactions, report_save_dir, seed=0, rounds=1, scribbles="frame"):
+    def __init__(self, davis, subset, metric_to_optimize, max_nb_interactions, report_save_dir, seed=0, rounds=1, scribbles="frame",
+                 robot="gt", robot_min_nodes=4):
         self.davis, self.metric, self.max_nb = davis, metric_to_optimize, int(max_nb_interactions)
         self.scribble_mode = scribbles
+        self.robot, self.robot_min_nodes = robot, int(robot_min_nodes)
+        self.drew, self._submitted = None, None
         self.report_save_dir = report_save_dir
         rs = np.random.RandomState(77 + seed)
         self.samples = [(seq, int(rs.randint(davis.dataset[seq]["num_frames"]))) for _ in range(rounds) for seq in davis.sets[subset]]
@@ -488,6 +515,7 @@ class SyntheticSession:
         if self._i >= len(self.samples):
             return False
         self._frame = self.samples[self._i][1]
+        self._submitted = None
         return True
 
     def get_scribbles(self, only_last=False):
@@ -495,7 +523,16 @@ class SyntheticSession:
         n = self.davis.dataset[seq]["num_frames"]
         mine = [dict(frame=self._frame)]
         if self.scribble_mode == "paths":
-            mine = robot_paths(self.davis.load_annotations(seq)[self._frame].cpu().numpy(), self.davis.dataset[seq]["num_objects"])
+            gt, n_objects = self.davis.load_annotations(seq), self.davis.dataset[seq]["num_objects"]
+            mine, self.drew = None, "gt"
+            if self.robot == "errors":                                # every node of the skeleton path: the polyline stays on the error region
+                from .utils import robot as R
+                mine, self.drew = R.interact(gt, self._submitted, n_objects, self._frame, min_nb_nodes=self.robot_min_nodes,
+                                             nb_points=None), "errors"
+                if not mine:
+                    mine, self.drew = None, "gt (no error path)"
+            if mine is None:
+                mine = robot_paths(gt[self._frame].cpu().numpy(), n_objects)
         scribbles = dict(sequence=seq, annotated_frame=self._frame, scribbles=[mine if f == self._frame else [] for f in range(n)])
         self._tic = time.time()
         return seq, scribbles, self._k == 0
@@ -507,6 +544,8 @@ class SyntheticSession:
         gt = self.davis.load_annotations(seq)
         m = misc.sequence_metric(self.metric, gt, masks, self.davis.dataset[seq]["num_objects"])
         self._k += 1
+        if self.robot == "errors":                                    # what the next scribble answers (a copy: the caller's store is rewritten)
+            self._submitted = torch.as_tensor(masks, device=gt.device).to(torch.uint8).clone()
         self.records.append((seq, self._i, self._k, float(np.mean(m)), time.time() - (self._tic or time.time())))
         if next_scribble_frame_candidates:
             self._frame = int(next_scribble_frame_candidates[0])
@@ -632,6 +671,7 @@ def run_eval(cfg, backbone="MANet"):
     overlay = overlay_option(cfg)
     qa = qa_option(cfg)
     scribble_mode = scribbles_option(cfg)
+    robot, robot_min_nodes = robot_option(cfg)
     oracle_chain = metric_option(cfg) == "device" and cfg.setting == "oracle" and cfg.method in ("ours", "worst")
     cfg.phase = "eval"
     cfg.data.subset = "val"
@@ -657,7 +697,8 @@ def run_eval(cfg, backbone="MANet"):
     os.makedirs(report_dir, exist_ok=True)
     corr_all, rec_time, seen_seq = misc.AverageMeter(), misc.AverageMeter(), {}
     qa_sess = QaSession(cfg, qa, metric, masks) if any(qa) else None
-    with SyntheticSession(davis, cfg.data.subset, metric, max_nb, report_dir, seed=int(cfg.seed), scribbles=scribble_mode) as sess, \
+    with SyntheticSession(davis, cfg.data.subset, metric, max_nb, report_dir, seed=int(cfg.seed), scribbles=scribble_mode, robot=robot,
+                          robot_min_nodes=robot_min_nodes) as sess, \
             (qa_sess or contextlib.nullcontext()):
         while sess.next():
             sequence, scribbles, first_scribble = sess.get_scribbles(only_last=True)
@@ -682,6 +723,8 @@ def run_eval(cfg, backbone="MANet"):
                 drawn = int(scribbles["annotated_frame"])
                 scribble_low = (drawn, S.scribble_maps(scribbles, (h // 4, w // 4), frames=[drawn], device=device)[0])
                 scribble_text = f"scribble: {len(scribbles['scribbles'][drawn])} paths "
+                if robot == "errors":
+                    scribble_text += f"robot: {sess.drew} "
             if scribble_low is None:                                  # (tests/test_qa_option.py replaces _segment by a six-argument double)
                 labels, all_P = _segment(vos, davis, sequence, n_objects, annotated, store)
             else:

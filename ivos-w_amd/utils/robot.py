@@ -1,0 +1,170 @@
+"""The error-driven scribble robot (``csrc/robot.hip``): scribbles where the segmentation is wrong.  For every object of the annotated frame
+the device thins the error region ``gt == o and pred != o`` to a skeleton - one workgroup per (frame, object) unit, entirely in LDS, one
+launch - and the few hundred skeleton pixels that come back become paths in davisinteractive's schema on the host.
+
+davisinteractive's ``InteractiveScribblesRobot`` does the same on the CPU with skimage's skeletoniser at every interaction of every
+episode.  Neither package is a dependency of this one and the robot is not in the reference tree: the rules - Zhang-Suen thinning as
+published, the component / double-BFS / resampling step below - are stated in ``include/ivosw.h`` and, as numpy, in ``tests/robot_ref.py``.
+They are this project's DEFINITION; parity with the library's own robot is restated, not recorded.
+
+Not built: scribbles on the background (object 0), which the library's robot draws on false positives; sizes beyond the LDS limit
+(``fits``: 480 x 854 fits, 720p does not - the robot serves DAVIS 480p).
+
+There is no CPU fallback for ``skeleton_points``; ``paths_from_points`` is host work.
+"""
+import numpy as np
+import torch
+
+from .. import _lib as L
+
+# P2 .. P9 of the thinning rule, and the order in which the BFS visits a node's neighbours: N, NE, E, SE, S, SW, W, NW as (dy, dx)
+NEIGHBOURS = ((-1, 0), (-1, 1), (0, 1), (1, 1), (1, 0), (1, -1), (0, -1), (-1, -1))
+
+
+def fits(size):
+    """Whether maps of ``size`` = (H, W) fit the kernel's two LDS bit planes (``ivosw_robot_skeleton_fits``)."""
+    H, W = (int(v) for v in size)
+    return bool(L.lib().ivosw_robot_skeleton_fits(H, W))
+
+
+def _label_map(t, who):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError(f"robot: {who} must be a device tensor: the skeleton is built on the MI355X only (no CPU fallback)")
+    if t.dtype != torch.uint8 or t.dim() != 3:
+        raise TypeError(f"robot: {who} must be a uint8 label map [n,H,W], got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def _launch(gt, pred, units, cap, want_bits):
+    """(buffer int32 [m * (2 + cap)] = [counts | iters | points], m, bit planes or None)."""
+    gt = _label_map(gt, "gt")
+    if pred is not None:
+        pred = _label_map(pred, "pred")
+        if pred.shape != gt.shape or pred.device != gt.device:
+            raise ValueError(f"robot: pred {tuple(pred.shape)} on {pred.device} does not match gt {tuple(gt.shape)} on {gt.device}")
+    table = np.ascontiguousarray(np.asarray(units, dtype=np.int32).reshape(-1, 2))
+    m, cap = len(table), int(cap)
+    n, H, W = gt.shape
+    buf = torch.empty(m * (2 + max(cap, 0)), dtype=torch.int32, device=gt.device)
+    bits = torch.empty((m, H, (W + 31) // 32), dtype=torch.int32, device=gt.device) if want_bits else None
+    L.check(L.lib().ivosw_robot_skeleton(L.dptr(gt), None if pred is None else L.dptr(pred), n, H, W, table.ctypes.data, m, cap,
+                                         L.torch_ptr(buf, 2 * m), L.dptr(buf), L.torch_ptr(buf, m), None if bits is None else L.dptr(bits),
+                                         L.stream_ptr(gt.device)), "robot_skeleton")
+    return buf, m, bits
+
+
+def skeleton_points(gt, pred, units, cap=4096, want_bits=False):
+    """``ivosw_robot_skeleton`` on device label maps ``gt`` and ``pred`` (uint8 [n,H,W]; ``pred`` None: all background) for ``units`` =
+    [(frame, object), ...]: device tensors ``(points, counts, iters)`` - int32 [m,cap] skeleton pixels as (y << 16) | x in raster order,
+    int32 [m] true pixel counts (also beyond ``cap``) and int32 [m] iteration counts (-1: not converged) - and, ``want_bits``, the
+    skeleton's bit planes [m,H,ceil(W/32)] as a fourth (bit x & 31 of word x >> 5; an int32 tensor holding the uint32 words).  The three
+    are views of ONE buffer, so a single copy brings them to the host.  One launch per 64 units, no synchronisation."""
+    buf, m, bits = _launch(gt, pred, units, cap, want_bits)
+    points, counts, iters = buf[2 * m:].view(m, int(cap)), buf[:m], buf[m:2 * m]
+    return (points, counts, iters, bits) if want_bits else (points, counts, iters)
+
+
+def _components(pixels):
+    """8-connected components of a raster-ordered list of (y, x): raster-ordered lists, in the order of their first pixels."""
+    index = {p: i for i, p in enumerate(pixels)}
+    seen = np.zeros(len(pixels), bool)
+    comps = []
+    for i, p in enumerate(pixels):
+        if seen[i]:
+            continue
+        seen[i] = True
+        stack, members = [p], []
+        while stack:
+            y, x = stack.pop()
+            members.append((y, x))
+            for dy, dx in NEIGHBOURS:
+                j = index.get((y + dy, x + dx))
+                if j is not None and not seen[j]:
+                    seen[j] = True
+                    stack.append((y + dy, x + dx))
+        members.sort()
+        comps.append(members)
+    return comps
+
+
+def _bfs(inside, start):
+    dist, parent, queue = {start: 0}, {start: None}, [start]
+    for y, x in queue:                                            # (the list grows while it is walked)
+        d = dist[(y, x)] + 1
+        for dy, dx in NEIGHBOURS:
+            q = (y + dy, x + dx)
+            if q in inside and q not in dist:
+                dist[q], parent[q] = d, (y, x)
+                queue.append(q)
+    return dist, parent
+
+
+def _farthest(dist):
+    best = max(dist.values())
+    return min(p for p, d in dist.items() if d == best)           # ties: the lower raster index
+
+
+def longest_paths(pixels, min_nb_nodes=4, max_paths=2):
+    """The paths before resampling, as lists of (y, x) nodes.  ``pixels``: skeleton pixels (y, x) in raster order.  Components of fewer
+    than ``min_nb_nodes`` pixels are dropped; per component a longest shortest path by double BFS (from the component's first pixel to
+    the farthest node a, from a to the farthest node b; neighbours in the order N, NE, E, SE, S, SW, W, NW, a tie between farthest
+    nodes goes to the lower raster index; the path runs from a to b); the ``max_paths`` longest are kept, longest first, ties to the
+    component with the lower first pixel."""
+    paths = []
+    for members in _components(pixels):
+        if len(members) < int(min_nb_nodes):
+            continue
+        inside = set(members)
+        a = _farthest(_bfs(inside, members[0])[0])
+        dist, parent = _bfs(inside, a)
+        node, path = _farthest(dist), []
+        while node is not None:
+            path.append(node)
+            node = parent[node]
+        paths.append(path[::-1])
+    order = sorted(range(len(paths)), key=lambda k: (-len(paths[k]), k))
+    return [paths[k] for k in order[:int(max_paths)]]
+
+
+def paths_from_points(points, count, size, object_id, min_nb_nodes=4, max_paths=2, nb_points=8):
+    """The paths of one unit from its skeleton pixels ``points`` (host int32 [cap], (y << 16) | x in raster order, ``count`` of them
+    valid) on maps of ``size`` = (H, W): ``longest_paths``, each thinned to at most ``nb_points`` nodes (``np.linspace`` over the node
+    indices, rounded, duplicates dropped - ``entry.robot_paths``' rule; None keeps every node, so that the polyline stays on the
+    skeleton) and emitted as ``dict(path=[[(x + 0.5) / W, (y + 0.5) / H], ...], object_id=o, start_time=0, end_time=0)``.
+    ``count`` above ``len(points)`` (the skeleton did not fit the cap) is a ValueError."""
+    H, W = (int(v) for v in size)
+    points, count = np.asarray(points).reshape(-1), int(count)
+    if count > len(points):
+        raise ValueError(f"robot: object {object_id}: the skeleton has {count} pixels, more than the cap of {len(points)} points")
+    v = points[:count].astype(np.int64) & 0xffffffff
+    pixels = list(zip((v >> 16).tolist(), (v & 0xffff).tolist()))
+    out = []
+    for path in longest_paths(pixels, min_nb_nodes, max_paths):
+        if nb_points is not None:
+            idx = np.unique(np.linspace(0, len(path) - 1, min(int(nb_points), len(path))).round().astype(int))
+            path = [path[i] for i in idx]
+        out.append(dict(path=[[(x + 0.5) / W, (y + 0.5) / H] for y, x in path], object_id=int(object_id), start_time=0, end_time=0))
+    return out
+
+
+def interact(gt, pred, n_objects, frame, cap=4096, **kw):
+    """The scribbles of one frame in davisinteractive's schema: a list of paths for the objects 1 .. ``n_objects`` in ascending order, drawn
+    along the skeleton of each object's error region on ``frame``.  ``gt`` and ``pred``: device uint8 [n,H,W] (``pred`` None: nothing
+    predicted yet, the error region is the object).  An object without an error skeleton of at least ``min_nb_nodes`` connected pixels
+    gets no path; the background (object 0) gets none either.  ``kw``: ``min_nb_nodes``, ``max_paths``, ``nb_points`` of
+    ``paths_from_points``.  One launch, one device-to-host copy of [counts | iters | points], then the numpy step."""
+    frame, n_objects = int(frame), int(n_objects)
+    if n_objects < 1:
+        return []
+    units = [(frame, o) for o in range(1, n_objects + 1)]
+    buf, m, _ = _launch(gt, pred, units, cap, False)
+    flat = buf.cpu().numpy()                                      # the one copy (and the one synchronisation)
+    counts_h, points_h = flat[:m], flat[2 * m:].reshape(m, -1)
+    H, W = gt.shape[1:]
+    out = []
+    for k, (f, o) in enumerate(units):
+        if counts_h[k] > points_h.shape[1]:
+            raise ValueError(f"robot: unit {k} (frame {f}, object {o}): the skeleton has {int(counts_h[k])} pixels, more than cap = "
+                             f"{points_h.shape[1]}")
+        out += paths_from_points(points_h[k], counts_h[k], (H, W), o, **kw)
+    return out
