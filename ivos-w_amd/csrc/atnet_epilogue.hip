@@ -20,9 +20,8 @@
 // tree, so parity with the clone is unpinned (as the J/F kernels' parity with davisinteractive is).  NaN logits: unspecified.
 //
 // HBM-bound: 4 B x n_obj x (2 reads + 2 writes on the padded grid + 1 write in the crop) + 5 B of labels per pixel.
-#include "common.h"
+#include "lane_group.h"
 #include <limits.h>
-#include <stdlib.h>
 
 namespace ivosw {
 
@@ -75,20 +74,12 @@ __global__ __launch_bounds__(256) void atnet_epilogue_kernel(AtnetArgs a) {
         float pv[V];
         if (a.logits) {
             float s[V];
-            if (V == 4) {
-                const float4 l = *reinterpret_cast<const float4*>(a.logits + off);
-                s[0] = sigmoidf(l.x); s[1] = sigmoidf(l.y); s[2] = sigmoidf(l.z); s[V - 1] = sigmoidf(l.w);
-            } else {
-                s[0] = sigmoidf(a.logits[off]);
-            }
+            load_group(a.logits + off, s);
+#pragma unroll
+            for (int p = 0; p < V; ++p) s[p] = sigmoidf(s[p]);
             if (a.blend) {
                 float old[V];
-                if (V == 4) {
-                    const float4 q = *reinterpret_cast<const float4*>(a.map + off);
-                    old[0] = q.x; old[1] = q.y; old[2] = q.z; old[V - 1] = q.w;
-                } else {
-                    old[0] = a.map[off];
-                }
+                load_group(a.map + off, old);
 #pragma unroll
                 for (int p = 0; p < V; ++p) {
                     const float m1 = a.alpha * s[p];
@@ -99,20 +90,10 @@ __global__ __launch_bounds__(256) void atnet_epilogue_kernel(AtnetArgs a) {
 #pragma unroll
                 for (int p = 0; p < V; ++p) pv[p] = s[p];
             }
-            if (V == 4) {
-                *reinterpret_cast<float4*>(a.map + off) = make_float4(pv[0], pv[1], pv[2], pv[V - 1]);
-                if (a.prob_pad) *reinterpret_cast<float4*>(a.prob_pad + off) = make_float4(s[0], s[1], s[2], s[V - 1]);
-            } else {
-                a.map[off] = pv[0];
-                if (a.prob_pad) a.prob_pad[off] = s[0];
-            }
+            store_group(a.map + off, pv);
+            if (a.prob_pad) store_group(a.prob_pad + off, s);
         } else {
-            if (V == 4) {
-                const float4 q = *reinterpret_cast<const float4*>(a.map + off);
-                pv[0] = q.x; pv[1] = q.y; pv[2] = q.z; pv[V - 1] = q.w;
-            } else {
-                pv[0] = a.map[off];
-            }
+            load_group(a.map + off, pv);
         }
         if (!some || !any_out) continue;
 #pragma unroll
@@ -121,7 +102,7 @@ __global__ __launch_bounds__(256) void atnet_epilogue_kernel(AtnetArgs a) {
         if (a.probs) {
             float* out = a.probs + (size_t)o * a.sc + cidx0;
             if (CROPV) {
-                *reinterpret_cast<float4*>(out) = make_float4(pv[0], pv[1], pv[2], pv[V - 1]);
+                store_group(out, pv);
             } else {
 #pragma unroll
                 for (int p = 0; p < V; ++p)
@@ -134,9 +115,8 @@ __global__ __launch_bounds__(256) void atnet_epilogue_kernel(AtnetArgs a) {
 #pragma unroll
     for (int p = 0; p < V; ++p) lab[p] = best[p] > a.th ? am[p] + 1 : 0;
     if (CROPV) {
-        if (a.label_u8)
-            *reinterpret_cast<uint32_t*>(a.label_u8 + cidx0) = (uint32_t)lab[0] | ((uint32_t)lab[1] << 8) | ((uint32_t)lab[2] << 16) | ((uint32_t)lab[V - 1] << 24);
-        if (a.label_f32) *reinterpret_cast<float4*>(a.label_f32 + cidx0) = make_float4((float)lab[0], (float)lab[1], (float)lab[2], (float)lab[V - 1]);
+        if (a.label_u8) store_bytes(a.label_u8 + cidx0, lab);
+        if (a.label_f32) store_group_as(a.label_f32 + cidx0, lab);
     } else {
 #pragma unroll
         for (int p = 0; p < V; ++p)
@@ -172,15 +152,12 @@ extern "C" int ivosw_atnet_epilogue(const float* logits, float* prob_map_t, int 
     a.n_obj = n_obj; a.PH = PH; a.PW = PW; a.hpad1 = hpad1; a.wpad1 = wpad1; a.H = H; a.W = W; a.blend = blend;
     a.alpha = alpha32; a.beta = beta32; a.th = th;
     hipStream_t st = as_stream(stream);
-    const bool vec = getenv("IVOSW_ATNET_SCALAR") == nullptr && PW % 4 == 0 &&
-                     (((uintptr_t)logits | (uintptr_t)prob_map_t | (uintptr_t)a.prob_pad) & 15) == 0;
-    const bool cropv = vec && wpad1 % 4 == 0 && W % 4 == 0 && ((uintptr_t)label_u8 & 3) == 0 && ((uintptr_t)label_f32 & 15) == 0 &&
-                       (!probs || (((uintptr_t)probs & 15) == 0 && (n_obj == 1 || probs_stride_c % 4 == 0)));
-    const long items = vec ? (long)PH * PW / 4 : (long)PH * PW;
-    const dim3 grid((unsigned)((items + 255) / 256));
+    const int V = !scalar_forced("IVOSW_ATNET_SCALAR") && PW % 4 == 0 && on_grid(16, logits, prob_map_t, a.prob_pad) ? 4 : 1;
+    const bool cropv = V == 4 && multiples_of(4, wpad1, W) && on_grid(4, label_u8) && on_grid(16, label_f32, probs) &&
+                       (!probs || n_obj == 1 || probs_stride_c % 4 == 0);
+    const dim3 grid(lane_blocks((long)PH * PW, V));
     if (cropv) hipLaunchKernelGGL((atnet_epilogue_kernel<4, true>), grid, dim3(256), 0, st, a);
-    else if (vec) hipLaunchKernelGGL((atnet_epilogue_kernel<4, false>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((atnet_epilogue_kernel<1, false>), grid, dim3(256), 0, st, a);
+    else dispatch_lanes<4, 1>(V, [&](auto v) { hipLaunchKernelGGL((atnet_epilogue_kernel<decltype(v)::value, false>), grid, dim3(256), 0, st, a); });
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }

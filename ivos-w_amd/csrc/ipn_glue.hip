@@ -22,9 +22,8 @@
 // The per-frame weights travel inside the kernel arguments, IPN_MAX_FRAMES frames per launch, as the sequence table of the ragged
 // entries does: no allocation, no copy, capture-safe.  Both kernels are plain streaming kernels: no LDS, no atomics, no scratch.
 // HBM-bound: the merge moves 4 B x K x (2 reads + 1 write [+ 1 write with probs]) + 5 B of labels per pixel and frame.
-#include "common.h"
+#include "lane_group.h"
 #include <limits.h>
-#include <stdlib.h>
 
 namespace ivosw {
 
@@ -108,12 +107,7 @@ __global__ __launch_bounds__(256) void ipn_dilate_kernel(DilateArgs a) {
         dilate_row<V, 2>(row, x0, a.W, a.num_objects, best);
         if (y + 1 < a.H) dilate_row<V, 1>(row + a.W, x0, a.W, a.num_objects, best);
         if (y + 2 < a.H) dilate_row<V, 0>(row + 2 * (long)a.W, x0, a.W, a.num_objects, best);
-        int8_t* o = a.out + m * plane + (long)y * a.W + x0;
-        if constexpr (V == 4)
-            *reinterpret_cast<uint32_t*>(o) = (uint32_t)(uint8_t)best[0] | ((uint32_t)(uint8_t)best[1] << 8) | ((uint32_t)(uint8_t)best[2] << 16) |
-                                              ((uint32_t)(uint8_t)best[V - 1] << 24);
-        else
-            o[0] = (int8_t)best[0];
+        store_bytes(a.out + m * plane + (long)y * a.W + x0, best);
     }
 }
 
@@ -132,34 +126,19 @@ __global__ __launch_bounds__(256) void ipn_merge_kernel(MergeArgs a) {
     for (int i = 0; i < a.K; ++i) {
         const long off = (long)a.inv[i] * a.chan + fo;
         float v[V];
-        if constexpr (V == 4) {
-            const float4 e = *reinterpret_cast<const float4*>(a.E + off);
-            v[0] = e.x; v[1] = e.y; v[2] = e.z; v[V - 1] = e.w;
-        } else {
-            v[0] = a.E[off];
-        }
+        load_group(a.E + off, v);
         if (a.prev) {
             float q[V];
-            if constexpr (V == 4) {
-                const float4 e = *reinterpret_cast<const float4*>(a.prev + off);
-                q[0] = e.x; q[1] = e.y; q[2] = e.z; q[V - 1] = e.w;
-            } else {
-                q[0] = a.prev[off];
-            }
+            load_group(a.prev + off, q);
 #pragma unroll
             for (int p = 0; p < V; ++p) {
                 const float m1 = wn * v[p];
                 const float m2 = wo * q[p];
                 v[p] = m1 + m2;
             }
-            if constexpr (V == 4) *reinterpret_cast<float4*>(a.E + off) = make_float4(v[0], v[1], v[2], v[V - 1]);
-            else a.E[off] = v[0];
+            store_group(a.E + off, v);
         }
-        if (a.probs) {
-            float* out = a.probs + (long)i * a.sc + fo;
-            if constexpr (V == 4) *reinterpret_cast<float4*>(out) = make_float4(v[0], v[1], v[2], v[V - 1]);
-            else out[0] = v[0];
-        }
+        if (a.probs) store_group(a.probs + (long)i * a.sc + fo, v);
         if (want_label) {
 #pragma unroll
             for (int p = 0; p < V; ++p)                                    // running FIRST maximum; a NaN is the maximum and is never replaced
@@ -167,14 +146,8 @@ __global__ __launch_bounds__(256) void ipn_merge_kernel(MergeArgs a) {
         }
     }
     if (!want_label) return;
-    if constexpr (V == 4) {
-        if (a.label_u8)
-            *reinterpret_cast<uint32_t*>(a.label_u8 + fo) = (uint32_t)am[0] | ((uint32_t)am[1] << 8) | ((uint32_t)am[2] << 16) | ((uint32_t)am[V - 1] << 24);
-        if (a.label_f32) *reinterpret_cast<float4*>(a.label_f32 + fo) = make_float4((float)am[0], (float)am[1], (float)am[2], (float)am[V - 1]);
-    } else {
-        if (a.label_u8) a.label_u8[fo] = (uint8_t)am[0];
-        if (a.label_f32) a.label_f32[fo] = (float)am[0];
-    }
+    if (a.label_u8) store_bytes(a.label_u8 + fo, am);
+    if (a.label_f32) store_group_as(a.label_f32 + fo, am);
 }
 
 }  // namespace ivosw
@@ -189,12 +162,10 @@ extern "C" int ivosw_ipn_dilate(const int8_t* mask, int n, int H, int W, int num
     IVOSW_REQUIRE(out != mask, "out must not be mask (a pixel reads its neighbours)");
     IVOSW_ON_DEVICE_OF(mask);
     DilateArgs a{mask, out, n, H, W, num_objects};
-    const bool vec = getenv("IVOSW_IPN_SCALAR") == nullptr && W % 4 == 0 && (((uintptr_t)mask | (uintptr_t)out) & 3) == 0;
-    const long items = vec ? (long)H * W / 4 : (long)H * W;
-    const dim3 grid((unsigned)((items + 255) / 256), (unsigned)(n < 65535 ? n : 65535));
+    const int V = !scalar_forced("IVOSW_IPN_SCALAR") && W % 4 == 0 && on_grid(4, mask, out) ? 4 : 1;
+    const dim3 grid(lane_blocks((long)H * W, V), (unsigned)(n < 65535 ? n : 65535));
     hipStream_t st = as_stream(stream);
-    if (vec) hipLaunchKernelGGL((ipn_dilate_kernel<4>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((ipn_dilate_kernel<1>), grid, dim3(256), 0, st, a);
+    dispatch_lanes<4, 1>(V, [&](auto v) { hipLaunchKernelGGL((ipn_dilate_kernel<decltype(v)::value>), grid, dim3(256), 0, st, a); });
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }
@@ -234,10 +205,9 @@ extern "C" int ivosw_ipn_merge(float* all_E, const float* prev_E, int K, int T, 
     IVOSW_ON_DEVICE_OF(all_E);
     a.E = all_E; a.prev = prev_E; a.probs = probs; a.sc = K == 1 ? 0 : probs_stride_c; a.label_u8 = label_u8; a.label_f32 = label_f32;
     a.chan = chan; a.K = K; a.HW = (int)HW;
-    const bool vec = getenv("IVOSW_IPN_SCALAR") == nullptr && HW % 4 == 0 && (a.sc % 4 == 0 || !probs) &&
-                     (((uintptr_t)all_E | (uintptr_t)prev_E | (uintptr_t)probs | (uintptr_t)label_f32) & 15) == 0 && ((uintptr_t)label_u8 & 3) == 0;
-    const long items = vec ? HW / 4 : HW;
-    const unsigned gx = (unsigned)((items + 255) / 256);
+    const int V = !scalar_forced("IVOSW_IPN_SCALAR") && HW % 4 == 0 && (a.sc % 4 == 0 || !probs) && on_grid(16, all_E, prev_E, probs, label_f32) &&
+                          on_grid(4, label_u8) ? 4 : 1;
+    const unsigned gx = lane_blocks(HW, V);
     hipStream_t st = as_stream(stream);
     for (int f0 = 0; f0 < T; f0 += IPN_MAX_FRAMES) {
         const int nf = T - f0 < IPN_MAX_FRAMES ? T - f0 : IPN_MAX_FRAMES;
@@ -246,8 +216,7 @@ extern "C" int ivosw_ipn_merge(float* all_E, const float* prev_E, int K, int T, 
             memcpy(a.w_new, w_new32 + f0, nf * sizeof(float));
             memcpy(a.w_old, w_old32 + f0, nf * sizeof(float));
         }
-        if (vec) hipLaunchKernelGGL((ipn_merge_kernel<4>), dim3(gx, nf), dim3(256), 0, st, a);
-        else hipLaunchKernelGGL((ipn_merge_kernel<1>), dim3(gx, nf), dim3(256), 0, st, a);
+        dispatch_lanes<4, 1>(V, [&](auto v) { hipLaunchKernelGGL((ipn_merge_kernel<decltype(v)::value>), dim3(gx, nf), dim3(256), 0, st, a); });
         IVOSW_CHECK_LAUNCH();
     }
     return IVOSW_OK;

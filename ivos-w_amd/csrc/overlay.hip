@@ -24,9 +24,8 @@
 // capture-safe.  A plain streaming kernel: no LDS, no atomics, no scratch.  Per pixel it moves 4 B (RGBX8) or 12 B (fp32) of frame,
 // 1 B of label (the rows above and below come from the caches) and 3 or 4 B of picture; how far each path is from the memory roof is
 // measured by tools/overlay_probe.py (profiles/overlay_probe.txt).
-#include "common.h"
+#include "lane_group.h"
 #include <limits.h>
-#include <stdlib.h>
 #include <string.h>
 
 namespace ivosw {
@@ -109,28 +108,14 @@ __global__ __launch_bounds__(256) void overlay_kernel(OverlayArgs a) {
         const float* fr = static_cast<const float*>(a.frames) + f * 3 * HW + pix;
 #pragma unroll
         for (int ch = 0; ch < 3; ++ch) {
-            if constexpr (V == 4) {
-                const float4 q = *reinterpret_cast<const float4*>(fr + ch * HW);
-                c[0][ch] = byte_of(q.x); c[1][ch] = byte_of(q.y); c[2][ch] = byte_of(q.z); c[V - 1][ch] = byte_of(q.w);
-            } else if constexpr (V == 2) {
-                const float2 q = *reinterpret_cast<const float2*>(fr + ch * HW);
-                c[0][ch] = byte_of(q.x); c[V - 1][ch] = byte_of(q.y);
-            } else {
-                c[0][ch] = byte_of(fr[ch * HW]);
-            }
+            float q[V];
+            load_group(fr + ch * HW, q);
+#pragma unroll
+            for (int p = 0; p < V; ++p) c[p][ch] = byte_of(q[p]);
         }
     } else {
-        const uint32_t* fr = static_cast<const uint32_t*>(a.frames) + f * HW + pix;
         uint32_t w[V];
-        if constexpr (V == 4) {
-            const uint4 q = *reinterpret_cast<const uint4*>(fr);
-            w[0] = q.x; w[1] = q.y; w[2] = q.z; w[V - 1] = q.w;
-        } else if constexpr (V == 2) {
-            const uint2 q = *reinterpret_cast<const uint2*>(fr);
-            w[0] = q.x; w[V - 1] = q.y;
-        } else {
-            w[0] = fr[0];
-        }
+        load_group(static_cast<const uint32_t*>(a.frames) + f * HW + pix, w);
 #pragma unroll
         for (int p = 0; p < V; ++p) { c[p][0] = w[p] & 255u; c[p][1] = (w[p] >> 8) & 255u; c[p][2] = (w[p] >> 16) & 255u; }
     }
@@ -169,10 +154,7 @@ __global__ __launch_bounds__(256) void overlay_kernel(OverlayArgs a) {
     // ---- the picture
     const long opix = (long)(a.m0 + (int)blockIdx.y) * HW + pix;
     if constexpr (X) {
-        uint32_t* o = reinterpret_cast<uint32_t*>(a.out) + opix;
-        if constexpr (V == 4) *reinterpret_cast<uint4*>(o) = make_uint4(px[0], px[1], px[2], px[V - 1]);
-        else if constexpr (V == 2) *reinterpret_cast<uint2*>(o) = make_uint2(px[0], px[V - 1]);
-        else o[0] = px[0];
+        store_group(reinterpret_cast<uint32_t*>(a.out) + opix, px);
     } else {
         uint8_t* o = a.out + 3 * opix;
         if constexpr (V == 4) {                                                // 12 bytes: R0 G0 B0 R1 | G1 B1 R2 G2 | B2 R3 G3 B3
@@ -195,11 +177,9 @@ __global__ __launch_bounds__(256) void overlay_kernel(OverlayArgs a) {
 
 // pixels per lane of the kernel a call with these buffers runs: 4, 2 or 1 - the widest whose words all lie on their grids
 extern "C" int ivosw_overlay_lane_pixels(const void* frames, const uint8_t* labels, int W, const void* out, int out_kind) {
-    if (getenv("IVOSW_OVERLAY_SCALAR") != nullptr || W < 1) return 1;
-    for (int v = 4; v > 1; v >>= 1) {                    // per lane: v label bytes, 4 v bytes of frame (of each plane), 3 v or 4 v bytes of picture
-        const uintptr_t lab = v - 1, fr = 4 * v - 1, pic = out_kind == IVOSW_OUT_RGBX8 ? 4 * v - 1 : v - 1;
-        if (W % v == 0 && ((uintptr_t)labels & lab) == 0 && ((uintptr_t)frames & fr) == 0 && ((uintptr_t)out & pic) == 0) return v;
-    }
+    if (ivosw::scalar_forced("IVOSW_OVERLAY_SCALAR") || W < 1) return 1;
+    for (int v = 4; v > 1; v >>= 1)                      // per lane: v label bytes, 4 v bytes of frame (of each plane), 3 v or 4 v bytes of picture
+        if (W % v == 0 && ivosw::on_grid(v, labels) && ivosw::on_grid(4 * v, frames) && ivosw::on_grid(out_kind == IVOSW_OUT_RGBX8 ? 4 * v : v, out)) return v;
     return 1;
 }
 
@@ -248,25 +228,20 @@ extern "C" int ivosw_overlay_frames(const void* frames, int frames_kind, const u
         for (int ch = 0; ch < 3; ++ch) a.k[o][ch] = rest * (double)opt->palette[o][ch];
     const bool f32 = frames_kind == IVOSW_FRAMES_F32, x = out_kind == IVOSW_OUT_RGBX8;
     const int V = ivosw_overlay_lane_pixels(frames, labels, W, out, out_kind);
-    const long items = HW / V;
-    const unsigned gx = (unsigned)((items + 255) / 256);
+    const unsigned gx = lane_blocks(HW, V);
     hipStream_t st = as_stream(stream);
     for (long m0 = 0; m0 < m; m0 += OVL_MAX_FRAMES) {
         const int nf = (int)(m - m0 < OVL_MAX_FRAMES ? m - m0 : OVL_MAX_FRAMES);
         a.m0 = (int)m0;
         for (int j = 0; j < nf; ++j) a.frame[j] = frame_ids ? frame_ids[m0 + j] : (int)(m0 + j);
         const dim3 grid(gx, nf), block(256);
-#define IVOSW_OVL_LAUNCH(V)                                                                              \
-        do {                                                                                             \
-            if (f32 && x) hipLaunchKernelGGL((overlay_kernel<V, true, true>), grid, block, 0, st, a);       \
-            else if (f32) hipLaunchKernelGGL((overlay_kernel<V, true, false>), grid, block, 0, st, a);     \
-            else if (x) hipLaunchKernelGGL((overlay_kernel<V, false, true>), grid, block, 0, st, a);       \
-            else hipLaunchKernelGGL((overlay_kernel<V, false, false>), grid, block, 0, st, a);            \
-        } while (0)
-        if (V == 4) IVOSW_OVL_LAUNCH(4);
-        else if (V == 2) IVOSW_OVL_LAUNCH(2);
-        else IVOSW_OVL_LAUNCH(1);
-#undef IVOSW_OVL_LAUNCH
+        dispatch_lanes<4, 2, 1>(V, [&](auto v) {
+            constexpr int LV = decltype(v)::value;
+            if (f32 && x) hipLaunchKernelGGL((overlay_kernel<LV, true, true>), grid, block, 0, st, a);
+            else if (f32) hipLaunchKernelGGL((overlay_kernel<LV, true, false>), grid, block, 0, st, a);
+            else if (x) hipLaunchKernelGGL((overlay_kernel<LV, false, true>), grid, block, 0, st, a);
+            else hipLaunchKernelGGL((overlay_kernel<LV, false, false>), grid, block, 0, st, a);
+        });
         IVOSW_CHECK_LAUNCH();
     }
     return IVOSW_OK;

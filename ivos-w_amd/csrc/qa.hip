@@ -11,8 +11,7 @@
 // not available where this was written, so parity with cv2 is restated, not recorded (tests/qa_ref.py restates it in numpy).
 //
 // 5 bytes per pixel (4 in, 1 out), no reuse: HBM-bound.  No LDS, no atomics, no scratch, no allocation; capture-safe.
-#include "common.h"
-#include <stdlib.h>
+#include "lane_group.h"
 
 namespace ivosw {
 
@@ -40,12 +39,12 @@ __global__ __launch_bounds__(256) void qa_quantize_kernel(QaQuantArgs a) {
     const int f = blockIdx.y, o = blockIdx.z;
     const float* src = a.probs + (size_t)f * a.sn + (size_t)(o + 1) * a.sc + i0;
     uint8_t* dst = a.planes + ((size_t)o * a.n + f) * a.hw + i0;
-    if (V == 4) {
-        const float4 v = *reinterpret_cast<const float4*>(src);
-        *reinterpret_cast<uint32_t*>(dst) = qa_byte(v.x) | (qa_byte(v.y) << 8) | (qa_byte(v.z) << 16) | (qa_byte(v.w) << 24);
-    } else {
-        *dst = (uint8_t)qa_byte(*src);
-    }
+    float v[V];
+    int q[V];
+    load_group(src, v);
+#pragma unroll
+    for (int p = 0; p < V; ++p) q[p] = (int)qa_byte(v[p]);
+    store_bytes(dst, q);
 }
 
 }  // namespace ivosw
@@ -60,13 +59,10 @@ extern "C" int ivosw_qa_quantize(const float* probs, int n_frames, int n_obj, in
     IVOSW_ON_DEVICE_OF(planes);
     QaQuantArgs a{};
     a.probs = probs; a.sn = probs_stride_n; a.sc = probs_stride_c; a.planes = planes; a.n = n_frames; a.hw = H * W;
-    const bool vec = getenv("IVOSW_QA_SCALAR") == nullptr && a.hw % 4 == 0 && probs_stride_n % 4 == 0 && probs_stride_c % 4 == 0 &&
-                     ((uintptr_t)probs & 15) == 0 && ((uintptr_t)planes & 3) == 0;
-    const long items = vec ? a.hw / 4 : a.hw;
-    const dim3 grid((unsigned)((items + 255) / 256), n_frames, n_obj);
+    const int V = !scalar_forced("IVOSW_QA_SCALAR") && multiples_of(4, a.hw, probs_stride_n, probs_stride_c) && on_grid(16, probs) && on_grid(4, planes) ? 4 : 1;
+    const dim3 grid(lane_blocks(a.hw, V), n_frames, n_obj);
     hipStream_t st = as_stream(stream);
-    if (vec) hipLaunchKernelGGL(qa_quantize_kernel<4>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(qa_quantize_kernel<1>, grid, dim3(256), 0, st, a);
+    dispatch_lanes<4, 1>(V, [&](auto v) { hipLaunchKernelGGL(qa_quantize_kernel<decltype(v)::value>, grid, dim3(256), 0, st, a); });
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }

@@ -22,9 +22,8 @@
 // ivosw_rough_roi, the stand-alone body: a memset of four integers per image, a box scan (per-lane running maxima, a wave reduction, four
 // atomics per wave) and a fill (float4 when in and out are on the 16-byte grid), two launches.
 // Vector memory operations only; no LDS, no scratch.
-#include "common.h"
+#include "lane_group.h"
 #include <limits.h>
-#include <stdlib.h>
 
 namespace ivosw {
 
@@ -134,11 +133,7 @@ __global__ __launch_bounds__(256) void scribble_final_kernel(FinalArgs a) {
     Roi r = roi_of_map(a, m);
     if constexpr (V > 1) if (g0 <= a.N - V) {
         uint32_t key[V];
-#pragma unroll
-        for (int q = 0; q < V / 4; ++q) {
-            const uint4 k4 = *reinterpret_cast<const uint4*>(a.keys + g0 + 4 * q);
-            key[4 * q] = k4.x; key[4 * q + 1] = k4.y; key[4 * q + 2] = k4.z; key[4 * q + 3] = k4.w;
-        }
+        load_group(a.keys + g0, key);
         int v[V];
 #pragma unroll
         for (int j = 0; j < V; ++j) {
@@ -151,20 +146,8 @@ __global__ __launch_bounds__(256) void scribble_final_kernel(FinalArgs a) {
                 }
             }
         }
-        if (a.out_i8) {
-            uint32_t w[V / 4];
-#pragma unroll
-            for (int q = 0; q < V / 4; ++q)
-                w[q] = (uint32_t)(uint8_t)v[4 * q] | ((uint32_t)(uint8_t)v[4 * q + 1] << 8) | ((uint32_t)(uint8_t)v[4 * q + 2] << 16) |
-                       ((uint32_t)(uint8_t)v[4 * q + 3] << 24);
-            *reinterpret_cast<uint4*>(a.out_i8 + g0) = make_uint4(w[0], w[1], w[2], w[3]);
-        }
-        if (a.out_f32) {
-#pragma unroll
-            for (int q = 0; q < V / 4; ++q)
-                *reinterpret_cast<float4*>(a.out_f32 + g0 + 4 * q) =
-                    make_float4((float)v[4 * q], (float)v[4 * q + 1], (float)v[4 * q + 2], (float)v[4 * q + 3]);
-        }
+        if (a.out_i8) store_bytes(a.out_i8 + g0, v);
+        if (a.out_f32) store_group_as(a.out_f32 + g0, v);
         return;
     }
     const int cnt = min(V, a.N - g0);
@@ -211,10 +194,7 @@ __global__ __launch_bounds__(256) void rough_roi_fill_kernel(RoiArgs a) {
     Roi r = roi_of_box(a.box + 4 * (long)m, a.H, a.W, a.dist);
     float v[V];
     const bool full = g0 + V <= N;
-    if constexpr (V == 4) if (full) {
-        const float4 f = *reinterpret_cast<const float4*>(a.in + g0);
-        v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-    }
+    if constexpr (V == 4) if (full) load_group(a.in + g0, v);
     const int cnt = full ? V : (int)(N - g0);
 #pragma unroll
     for (int j = 0; j < V; ++j) {
@@ -231,7 +211,7 @@ __global__ __launch_bounds__(256) void rough_roi_fill_kernel(RoiArgs a) {
             }
         }
     }
-    if constexpr (V == 4) if (full) *reinterpret_cast<float4*>(a.out + g0) = make_float4(v[0], v[1], v[2], v[3]);
+    if constexpr (V == 4) if (full) store_group(a.out + g0, v);
 }
 
 }  // namespace ivosw
@@ -294,11 +274,8 @@ extern "C" int ivosw_scribble_raster(const int32_t* points, int n_points, const 
     const int max_side = H > W ? H : W;
     FinalArgs f{keys, box, paths, out_i8, out_f32, (int)N, (int)HW, H, W, n_maps, default_value,
                 roi_dist < 0 ? -1 : (roi_dist < max_side ? roi_dist : max_side)};
-    const bool vec = getenv("IVOSW_SCRIBBLE_SCALAR") == nullptr && (((uintptr_t)out_i8 | (uintptr_t)out_f32) & 15) == 0;
-    const long items = vec ? (N + 15) / 16 : N;
-    const dim3 grid((unsigned)((items + 255) / 256));
-    if (vec) hipLaunchKernelGGL((scribble_final_kernel<16>), grid, dim3(256), 0, st, f);
-    else hipLaunchKernelGGL((scribble_final_kernel<1>), grid, dim3(256), 0, st, f);
+    const int V = !scalar_forced("IVOSW_SCRIBBLE_SCALAR") && on_grid(16, out_i8, out_f32) ? 16 : 1;
+    dispatch_lanes<16, 1>(V, [&](auto v) { hipLaunchKernelGGL((scribble_final_kernel<decltype(v)::value>), dim3(lane_blocks(N, V)), dim3(256), 0, st, f); });
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }
@@ -332,11 +309,8 @@ extern "C" int ivosw_rough_roi(const float* in, float* out, int b, int h, int w,
     hipLaunchKernelGGL(rough_roi_scan_kernel, dim3(gx < 256u ? gx : 256u, (unsigned)b), dim3(256), 0, st, a);
     IVOSW_CHECK_LAUNCH();
     const long N = (long)b * HW;
-    const bool vec = getenv("IVOSW_SCRIBBLE_SCALAR") == nullptr && (((uintptr_t)in | (uintptr_t)out) & 15) == 0;
-    const long items = vec ? (N + 3) / 4 : N;
-    const dim3 grid((unsigned)((items + 255) / 256));
-    if (vec) hipLaunchKernelGGL((rough_roi_fill_kernel<4>), grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((rough_roi_fill_kernel<1>), grid, dim3(256), 0, st, a);
+    const int V = !scalar_forced("IVOSW_SCRIBBLE_SCALAR") && on_grid(16, in, out) ? 4 : 1;
+    dispatch_lanes<4, 1>(V, [&](auto v) { hipLaunchKernelGGL((rough_roi_fill_kernel<decltype(v)::value>), dim3(lane_blocks(N, V)), dim3(256), 0, st, a); });
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }

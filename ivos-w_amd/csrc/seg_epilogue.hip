@@ -14,8 +14,7 @@
 // Arithmetic follows ATen: upsample_bilinear2d with align_corners (scale = (in-1)/(out-1), src = scale * dst, lambda =
 // src - floor, clamped +1 neighbour), evaluated without FMA contraction (#pragma clang fp contract(off)); argmax = first maximum; softmax =
 // exp(x - max) / sum(exp(x - max)).  HBM-bound on the probability stream ((O+1) x 4 B per pixel).
-#include "common.h"
-#include <stdlib.h>
+#include "lane_group.h"
 
 namespace ivosw {
 
@@ -115,24 +114,12 @@ __global__ __launch_bounds__(256) void seg_epilogue_kernel(SegArgs a) {
         float* out = a.probs + (size_t)f * a.sn + idx0;
 #pragma unroll
         for (int c = 0; c < CMAX; ++c)
-            if (c < C) {
-                if (V == 4) *reinterpret_cast<float4*>(out + (size_t)c * a.sc) = make_float4(pv[c][0], pv[c][1], pv[c][2], pv[c][V - 1]);
-                else out[(size_t)c * a.sc] = pv[c][0];
-            }
+            if (c < C) store_group(out + (size_t)c * a.sc, pv[c]);
     }
     const size_t li = (size_t)f * a.H * a.W + idx0;
-    if (V == 4) {
-        if (a.label_i64) {
-            *reinterpret_cast<longlong2*>(a.label_i64 + li) = make_longlong2(am[0], am[1]);
-            *reinterpret_cast<longlong2*>(a.label_i64 + li + 2) = make_longlong2(am[2], am[V - 1]);
-        }
-        if (a.label_u8) *reinterpret_cast<uint32_t*>(a.label_u8 + li) = (uint32_t)am[0] | ((uint32_t)am[1] << 8) | ((uint32_t)am[2] << 16) | ((uint32_t)am[V - 1] << 24);
-        if (a.label_f32) *reinterpret_cast<float4*>(a.label_f32 + li) = make_float4((float)am[0], (float)am[1], (float)am[2], (float)am[V - 1]);
-    } else {
-        if (a.label_i64) a.label_i64[li] = am[0];
-        if (a.label_u8) a.label_u8[li] = (uint8_t)am[0];
-        if (a.label_f32) a.label_f32[li] = (float)am[0];
-    }
+    if (a.label_i64) store_group_as(a.label_i64 + li, am);
+    if (a.label_u8) store_bytes(a.label_u8 + li, am);
+    if (a.label_f32) store_group_as(a.label_f32 + li, am);
 }
 
 }  // namespace ivosw
@@ -155,21 +142,16 @@ extern "C" int ivosw_seg_epilogue(const float* logits, int n, int C, int hs, int
     a.probs = probs; a.sn = probs_stride_n; a.sc = probs_stride_c;
     a.label_i64 = label_i64; a.label_u8 = label_u8; a.label_f32 = label_f32;
     hipStream_t st = as_stream(stream);
-    const bool vec = getenv("IVOSW_SEG_SCALAR") == nullptr && ((long)H * W) % 4 == 0 && (!probs || (probs_stride_n % 4 == 0 && probs_stride_c % 4 == 0 && ((uintptr_t)probs & 15) == 0)) &&
-                     (((uintptr_t)label_i64 | (uintptr_t)label_f32) & 15) == 0 && ((uintptr_t)label_u8 & 3) == 0;
-    const long items = vec ? (long)H * W / 4 : (long)H * W;
-    const dim3 grid((unsigned)((items + 255) / 256), n);
-#define IVOSW_SEG_LAUNCH(CM)                                                                                   \
-    do {                                                                                                       \
-        if (vec && C == CM) hipLaunchKernelGGL((seg_epilogue_kernel<CM, 4, true>), grid, dim3(256), 0, st, a); \
-        else if (vec) hipLaunchKernelGGL((seg_epilogue_kernel<CM, 4>), grid, dim3(256), 0, st, a);             \
-        else hipLaunchKernelGGL((seg_epilogue_kernel<CM, 1>), grid, dim3(256), 0, st, a);                      \
-    } while (0)
-    if (C <= 4) IVOSW_SEG_LAUNCH(4);
-    else if (C <= 8) IVOSW_SEG_LAUNCH(8);
-    else if (C <= 16) IVOSW_SEG_LAUNCH(16);
-    else hipLaunchKernelGGL((seg_epilogue_kernel<0, 1>), dim3((unsigned)(((long)H * W + 255) / 256), n), dim3(256), 0, st, a);
-#undef IVOSW_SEG_LAUNCH
+    const long HW = (long)H * W;
+    const int V = C <= 16 && !scalar_forced("IVOSW_SEG_SCALAR") && HW % 4 == 0 && (!probs || multiples_of(4, probs_stride_n, probs_stride_c)) &&
+                          on_grid(16, probs, label_i64, label_f32) && on_grid(4, label_u8) ? 4 : 1;
+    const dim3 grid(lane_blocks(HW, V), n);
+    if (C > 16) hipLaunchKernelGGL((seg_epilogue_kernel<0, 1>), grid, dim3(256), 0, st, a);
+    else dispatch_lanes<4, 8, 16>(C <= 4 ? 4 : C <= 8 ? 8 : 16, [&](auto cm) {
+        constexpr int CM = decltype(cm)::value;
+        if (V == 4 && C == CM) hipLaunchKernelGGL((seg_epilogue_kernel<CM, 4, true>), grid, dim3(256), 0, st, a);
+        else dispatch_lanes<4, 1>(V, [&](auto v) { hipLaunchKernelGGL((seg_epilogue_kernel<CM, decltype(v)::value>), grid, dim3(256), 0, st, a); });
+    });
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }

@@ -90,6 +90,30 @@ def test_quantize_vector_scalar_and_restatement_agree(lib, dev, scalar_results, 
     np.testing.assert_array_equal(scalar_results[f"c{k}"], want)
 
 
+@pytest.mark.parametrize("pad_c,pad_n,plane_off", [(1, 0, 0), (0, 2, 0), (0, 0, 1)], ids=["stride_c", "stride_n", "planes_off"])
+def test_quantize_stride_or_planes_off_the_grid_take_the_scalar_kernel(lib, dev, pad_c, pad_n, plane_off):
+    """4 x 8 (H * W % 4 == 0) on a 16-byte aligned base: a channel or frame stride that is no multiple of 4 floats, or planes one byte
+    off the 4-byte grid, run one pixel per lane - the bytes of the aligned dense call, nothing behind the planes."""
+    H, W, O, n = 4, 8, 2, 3
+    hw = H * W
+    a, _ = _quant_input(H, W, O, n, "reference", 99)
+    sc = hw + pad_c
+    sn = (O + 1) * sc + pad_n
+    mem = np.full(n * sn, np.nan, np.float32)
+    for f in range(n):
+        for c in range(O + 1):
+            mem[f * sn + c * sc:f * sn + c * sc + hw] = a[f, c].reshape(-1)
+    src = torch.from_numpy(mem).to(dev)
+    out = torch.full((4 + O * n * hw + GUARD,), 0xA5, dtype=torch.uint8, device=dev)
+    assert src.data_ptr() % 16 == 0 and out.data_ptr() % 16 == 0
+    L.check(lib.ivosw_qa_quantize(L.dptr(src), n, O, H, W, sn, sc, ctypes.c_void_p(out.data_ptr() + plane_off), L.stream_ptr(dev)), "qa_quantize")
+    got = out.cpu().numpy()
+    assert (got[:plane_off] == 0xA5).all() and (got[plane_off + O * n * hw:] == 0xA5).all(), "written outside the planes"
+    dense, want = _quantize_abi(lib, dev, H, W, O, n, "reference", 0, 99)
+    np.testing.assert_array_equal(got[plane_off:plane_off + O * n * hw].reshape(O, n, H, W), want)
+    np.testing.assert_array_equal(dense, want)
+
+
 def test_quantize_covers_every_byte_and_the_specials(lib, dev):
     g = R.value_grid()
     pad = (-g.size) % 4

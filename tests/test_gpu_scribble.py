@@ -292,6 +292,29 @@ def test_fused_roi_raster_then_rough_roi_and_the_recorded_reference_agree(dev, f
             _same_f32(b_out.back("out").reshape(inp.shape), want, f"{name} rough_roi off={off} in_place={in_place}")
 
 
+def test_scalar_switch_gives_the_vector_kernels_bits(dev, monkeypatch):
+    """IVOSW_SCRIBBLE_SCALAR on 16-byte aligned buffers: the finalise pass and the rough_roi fill run element by element and give the
+    bytes of the 16- and 4-pixel kernels.  Two maps of 5 x 8 (80 pixels: five whole 16-pixel groups, the third spans both maps)."""
+    H, W = 5, 8
+    points, table = _table([([(1, 1), (6, 3)], 3), ([(7, 4)], 126), ([(0, 0), (7, 0)], 0)], [0, 1, 1])
+    want = sr.rough_roi(sr.raster(points, table, 2, H, W)[:, None].astype(np.float32), dist=1)[:, 0]
+    drawn = sr.raster(points, table, 2, H, W)[:, None].astype(np.float32)
+    got = {}
+    for scalar in (False, True):
+        if scalar:
+            monkeypatch.setenv("IVOSW_SCRIBBLE_SCALAR", "1")                          # read by the launcher at every call
+        call = Call(dev, points, table, 2, H, W)
+        _check(call, want.astype(np.int8), call.run(roi=1))
+        rc, (b_in, b_out, b_ws) = _roi(dev, drawn, dist=1)
+        assert rc == 0, L.lib().ivosw_last_error()
+        b_in.back("in", unchanged=True)
+        b_ws.back("ws")
+        got[scalar] = call.outputs() + (b_out.back("out"),)
+    for v, s in zip(got[False], got[True]):
+        np.testing.assert_array_equal(v.view(np.uint8), s.view(np.uint8))
+    _same_f32(got[True][2].reshape(drawn.shape), sr.rough_roi(drawn, dist=1), "rough_roi under the scalar switch")
+
+
 def test_rough_roi_nan_counts_other_distances_and_default(dev):
     m = np.full((2, 1, 33, 65), -1.0, np.float32)
     m[0, 0, 3, 4] = np.nan

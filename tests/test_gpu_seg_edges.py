@@ -54,7 +54,8 @@ def _run(dev, x, H, W, want=ALL, off=None, strides=None):
     off = off or {}
     k, C, hs, ws = x.shape
     d_x = torch.from_numpy(x).to(dev)
-    size = {"probs": k * C * H * W, "i64": k * H * W, "u8": k * H * W, "f32": k * H * W}
+    sn, sc = strides or (C * H * W, H * W)
+    size = {"probs": max(k * C * H * W, (k - 1) * sn + (C - 1) * sc + H * W), "i64": k * H * W, "u8": k * H * W, "f32": k * H * W}      # the extent the strides span
     bufs, ptrs, lo = {}, {}, {}
     for name in ALL:
         ptrs[name] = None
@@ -64,7 +65,6 @@ def _run(dev, x, H, W, want=ALL, off=None, strides=None):
             lo[name] = PAD + off.get(name, 0)
             ptrs[name] = ctypes.c_void_p(buf.data_ptr() + lo[name] * buf.element_size())
             bufs[name] = buf
-    sn, sc = strides or (C * H * W, H * W)
     rc = L.lib().ivosw_seg_epilogue(L.dptr(d_x), k, C, hs, ws, H, W, ptrs["probs"], sn, sc, ptrs["i64"], ptrs["u8"], ptrs["f32"],
                                     L.stream_ptr(dev))
     torch.cuda.synchronize(dev)
@@ -75,7 +75,14 @@ def _run(dev, x, H, W, want=ALL, off=None, strides=None):
         assert (h[:a] == FILL[name]).all() and (h[b:] == FILL[name]).all(), f"{name}: written outside its extent"
         if rc != 0:
             assert (h == FILL[name]).all(), f"{name}: written by a refused call"
-        out[name] = h[a:b].reshape((k, C, H, W) if name == "probs" else (k, H, W))
+        if name == "probs" and strides and rc == 0:              # the planes where the strides put them; the gaps between them keep their fill
+            idx = (np.arange(k)[:, None, None] * sn + np.arange(C)[None, :, None] * sc + np.arange(H * W)[None, None, :]).reshape(-1)
+            gaps = np.ones(b - a, bool)
+            gaps[idx] = False
+            assert (h[a:b][gaps] == FILL[name]).all(), "probs: written between the planes"
+            out[name] = h[a:b][idx].reshape(k, C, H, W)
+            continue
+        out[name] = h[a:a + (k * C * H * W if name == "probs" else size[name])].reshape((k, C, H, W) if name == "probs" else (k, H, W))
     return rc, out
 
 
@@ -223,6 +230,22 @@ def test_prob_store_slot_on_the_vector_path(dev):
     rc, dense = _run(dev, x, h, w, want=("probs",))
     assert rc == 0
     np.testing.assert_array_equal(got.view(np.uint8), dense["probs"].view(np.uint8))
+
+
+@pytest.mark.parametrize("C", [3, 4])
+def test_probability_strides_off_the_grid_take_the_scalar_kernel(dev, C):
+    """4 x 8 (H * W % 4 == 0), every pointer 16-byte aligned: a channel or a frame stride that is no multiple of 4 floats puts planes on
+    4-byte-aligned bases, so the call runs one pixel per lane - the bits of the dense call (4 pixels per lane), the gaps between the
+    planes and the guard bands untouched.  A padded stride that IS a multiple of 4 stays on the vector kernel: the same bits again."""
+    k, H, W = 2, 4, 8
+    hw = H * W
+    x = sr.logits(k, C, 3, 5, seed=40 + C)
+    rc, dense = _run(dev, x, H, W)
+    assert rc == 0
+    for strides in ((C * (hw + 1), hw + 1), (C * hw + 2, hw), (C * hw + 3, hw), (C * (hw + 4), hw + 4)):
+        rc, got = _run(dev, x, H, W, strides=strides)
+        assert rc == 0, L.lib().ivosw_last_error()
+        _assert_same_bits(dense, got, f"strides {strides}")
 
 
 def test_overlapping_strides_are_refused(dev):
