@@ -405,6 +405,13 @@ size_t ivosw_assess_ws_bytes(int dtype, int B, int H, int W, int chunk);
 /* 1 when ivosw_assess_forward(dtype, B, chunk) runs the batch as two independent halves on two streams (bf16, default chunk,
  * B >= 64, tunables STREAMS2 / STREAMS2_MIN; the workspace query above already covers both halves), else 0.  Scores do not depend on it. */
 int ivosw_assess_split(int dtype, int B, int chunk);
+/* What ivosw_assess_forward(dtype, B, chunk, tap_stage) would enqueue between the ROI sampler and the pooling head, as text and
+ * without a device (no HIP call): one line "slot kernel frames direction" per launch, in enqueue order - slot = 0 the caller's stream,
+ * 1 the side stream of a split call (taken whenever ivosw_assess_split says so); kernel = the function name a kernel trace prints,
+ * cut at '<' ("bneck_wide" stands for whichever single-block kernel of bottleneck_wide.hip runs); frames in the launch; direction =
+ * 1 for descending tile order.  The same selection code as the forward pass, under the tunables in force.  buf [cap] receives the
+ * NUL-terminated text; IVOSW_ERR_WS (the message names the size) if it does not fit.                                          */
+int ivosw_assess_describe(int dtype, int B, int chunk, int tap_stage, char* buf, size_t cap);
 int ivosw_assess_forward(const void* packed, int dtype, const float* tf, const float* tp,
                          int B, int H, int W, float* scores, void* ws, size_t ws_bytes, int chunk,
                          int tap_stage, void* tap_out, ivosw_stream_t stream);

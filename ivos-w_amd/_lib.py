@@ -119,6 +119,7 @@ SIGNATURES = {
     "ivosw_assess_pack": (_i, [_p, _i, C.POINTER(_p), _i, _p]),
     "ivosw_assess_ws_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "ivosw_assess_split": (_i, [_i, _i, _i]),
+    "ivosw_assess_describe": (_i, [_i, _i, _i, _i, C.c_char_p, _sz]),
     "ivosw_assess_forward": (_i, [_p, _i, _p, _p, _i, _i, _i, _p, _p, _sz, _i, _i, _p, _p]),
     "ivosw_assess_forward_objects": (_i, [_p, _i, _p, _i, _p, C.c_long, C.c_long, _i, _i, _i, _p, _p, _sz, _i, _p]),
     "ivosw_assess_forward_u8": (_i, [_p, _i, _p, _p, _i, _i, _i, _p, _p, _sz, _i, _i, _p, _p]),
@@ -249,6 +250,13 @@ def tune_set(key, value):
     if isinstance(key, str):
         key = key.encode()
     check(lib().ivosw_tune_set(key, int(value)), f"tune_set({key!r})")
+
+
+def assess_describe(dtype, B, chunk=0, tap_stage=0):
+    """ivosw_assess_describe: the tower launches of one forward pass as (slot, kernel, frames, direction) tuples, asked without a device."""
+    buf = C.create_string_buffer(1 << 20)
+    check(lib().ivosw_assess_describe(dtype, B, chunk, tap_stage, buf, len(buf)), "assess_describe")
+    return [(int(s), k, int(n), int(d)) for s, k, n, d in (ln.split() for ln in buf.value.decode().splitlines())]
 
 
 def dptr(t, dtype=None):

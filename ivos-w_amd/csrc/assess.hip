@@ -11,9 +11,9 @@
 #endif
 #include <limits.h>
 #include <algorithm>
-#include <vector>
-
 #include <mutex>
+#include <string>
+#include <vector>
 
 #include "conv.h"
 #include "front.h"
@@ -445,9 +445,10 @@ static int assess_forward_units_impl(const char* who, const void* packed, int dt
 }
 
 // units [u0, u0 + B) of the batch on stream st with their own workspace; `slot` = which of the (up to two) concurrent profiler spans
+// script != NULL: nothing is enqueued, the tower launches the range would make are appended as text (ivosw_assess_describe)
 static void assess_forward_range(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int u0, int B,
                                  int H, int W, float* scores, void* ws, int chunk, int tap_stage, void* tap_out, int slot, hipStream_t st,
-                                 const VideoTable* vt, const int32_t* ids);
+                                 const VideoTable* vt, const int32_t* ids, std::string* script = nullptr);
 
 // One helper stream + two events per device for the two-stream split (created on first use, all-or-nothing; the call holds
 // the device's mutex while it enqueues so two host threads cannot interleave their fork / join pairs).
@@ -532,259 +533,321 @@ static int assess_forward_impl(const void* packed, int dtype, const FrameSrc& fs
     return IVOSW_OK;
 }
 
+// ---------------------------------------------------------------- the tower's schedule
+// Every switch a range of the tower reads, resolved ONCE from the precision, the range's units, the tap, the plan and the tunables.
+// (The predicates of other files - bneck_wide_fusable, conv1x1_wide_ok, ... - read the tunables of their own kernels themselves.)
+struct TowerKnobs {
+    bool fwd2, ys2, stage2, chain, snake;
+    bool fuse, fuse_wide, fuse_ds, first3, inplace4, g8, wide1x1, fuse_stem, fuse_stem_x3, fuse_tail_x3, fuse_tail3_x3, ys2abl;
+    int df3, df3_min;
+};
+static TowerKnobs tower_knobs(int dtype, int B, int tap_stage, const Plan& P) {
+    TowerKnobs k{};
+    k.fuse = tune_get("FUSE", 1); k.fuse_wide = tune_get("FUSE_WIDE", 1); k.fuse_ds = tune_get("FUSE_DS", 1); k.first3 = tune_get("FIRST3", 1);
+    k.inplace4 = tune_get("INPLACE4", 1); k.g8 = tune_get("G8", 0); k.wide1x1 = tune_get("WIDE1X1", 1);
+    k.fuse_stem = tune_get("FUSE_STEM", 1); k.fuse_stem_x3 = tune_get("FUSE_STEM_X3", 1);
+    k.fuse_tail_x3 = tune_get("FUSE_TAIL_X3", 1); k.fuse_tail3_x3 = tune_get("FUSE_TAIL3_X3", 1);
+    k.ys2abl = IVOSW_ABLATION && tune_get("YS2ABL", 0);      // ablation: a stage's last block writes even pixels only
+    k.df3 = tune_get("DF3", 2); k.df3_min = tune_get("DF3_MIN", 128);
+    // conv1 forwarding through res2 (tunable FWD2): block b of res2 also applies block b+1's first 1x1 to its output tile while
+    // it is on chip; the last block applies res3's first 1x1, so that layer (a 0.8 GB pass over HBM) is never launched
+    k.fwd2 = dtype == IVOSW_BF16 && tune_get("FWD2", 1) && k.fuse_wide && tune_get("FUSE_WIDE2", 1) && tune_get("HALO64S", 1) &&
+             tune_get("HALO64S_DS", 1) && P.blocks[3].fwd1_off;
+    // ... and res2's last block then writes its output at the even pixels only (compact [nb,32,32,256]): with conv1 forwarded, the
+    // only reader left is res3's stride-2 downsample.  Off when an intermediate is tapped (the res2 tap wants the whole tensor).
+    k.ys2 = k.fwd2 && tap_stage == 0 && k.fuse_ds && tune_get("YS2", 1);
+    // ... or the whole of res2 in ONE launch (res2_stage.hip, tunable RES2_STAGE, default on): a workgroup carries its 8 x 16 tile
+    // through the three blocks, y0 / y1 never reach HBM.  Same summation orders as the per-block kernels: bit-identical stage output, so
+    // the choice moves no score.  In time the two are level (frames/s at B = 32 / 64 / 100 / 160 / 256: +0.8 / -1.2 / +1.9 / -0.6 /
+    // -0.8 %, alternating runs on one box; 946 against 983 us on one stream); the stage kernel moves 2.55 GB less HBM traffic per
+    // 256-frame pass (9.23 against 11.77 GB) in four launches fewer, which is why it is the default.
+    k.stage2 = k.fwd2 && tune_get("RES2_STAGE", 1);
+    // round 6: the register-chained form of the stage kernel (res2_chain.hip); RES2_CHAIN=0 is the round-3 stage kernel
+    k.chain = k.stage2 && P.chain_off && tune_get("RES2_CHAIN", 1);
+    // Snake order (tunable SNAKE, default on): consecutive launches of the tower walk their pixel tiles in OPPOSITE directions, so a
+    // launch starts with the tiles its producer wrote last - still in the memory-side cache (256 MB for ~128 MB tensors per stream) -
+    // instead of the ones written first and long evicted.  Tiles are independent: the order cannot change a result.
+    // From SNAKE_MIN (96) frames per stream: below that the tensors fit the cache either way (B = 32 / 100 / 160: +-0 / -0.6 / +0.4 %).
+    k.snake = dtype == IVOSW_BF16 && tune_get("SNAKE", 1) != 0 && B >= tune_get("SNAKE_MIN", 96);
+    return k;
+}
+
+// What the launches of one range share.  With `script` set (ivosw_assess_describe) the walk is the same and every launch becomes a
+// line "slot kernel frames direction" instead: packed and ws are then never-read stand-ins and no HIP call is made.
+struct Tower {
+    const Plan& P; TowerKnobs k; int dtype; size_t es; const char* base; Bufs bf; hipStream_t st; int slot; std::string* script;
+    int dir = 1;                 // the stem walks backward (its producer, the ROI crop, walks forward), the launch behind it forward ...
+    int next_dir() { const int d = k.snake ? dir : 0; dir ^= 1; return d; }
+    const float* f32(size_t off) const { return reinterpret_cast<const float*>(base + off); }
+    const float* bias(const ConvPlan& c) const { return f32(c.b_off); }
+    char* other(const char* x) const { return x == bf.pa ? bf.pb : bf.pa; }     // the ping-pong buffer x is not in
+    template <class F> void run(const char* kernel, int frames, int rev, F&& launch) {
+        if (!script) return launch();
+        char line[96];
+        snprintf(line, sizeof(line), "%d %s %d %d\n", slot, kernel, frames, rev);
+        *script += line;
+    }
+};
+constexpr int NBLK[4] = {3, 4, 6, 3}, FIRST_BLK[4] = {0, 3, 7, 13}, HW_IN[4] = {64, 64, 32, 16};
+static int block_hw(int s, int b) { return (s > 0 && b > 0) ? HW_IN[s] / 2 : HW_IN[s]; }      // res3..res5 halve H and W in their first block
+
+// a generic layer: the 8-phase / wide 1x1 kernels where they apply, else conv.hip's selector
+static void launch_layer(Tower& T, const ConvArgs& q, size_t fw_off) {
+    if (T.dtype == IVOSW_BF16 && T.k.g8 && T.k.wide1x1 && conv1x1_g8_ok(q)) T.run("gemm_8phase_kernel", q.B, q.rev, [&] { launch_conv1x1_g8(q, T.st); });
+    else if (T.dtype == IVOSW_BF16 && fw_off && conv1x1_wide_ok(q) && T.k.wide1x1) T.run("conv1x1_wide_kernel", q.B, q.rev, [&] { launch_conv1x1_wide(q, T.base + fw_off, T.st); });
+    else T.run(conv_kernel_name(conv_select(q, T.dtype, false)), q.B, q.rev, [&] { launch_conv(q, T.dtype, false, T.st); });
+}
+static ConvArgs conv_args(Tower& T, const ConvPlan& c, const void* in, int hin, int hout, const void* res, void* o, int relu, int nb) {
+    ConvArgs q{};
+    q.zeros = T.base + T.P.zero_off; q.x = in; q.w = T.base + c.w_off; q.bias = T.bias(c); q.res = res; q.y = o;
+    q.B = nb; q.H = hin; q.W = hin; q.Cin = c.Cin; q.Ho = hout; q.Wo = hout; q.Cout = c.Cout;
+    q.KH = c.K; q.KW = c.K; q.stride = c.stride; q.pad = c.pad; q.relu = relu;
+    q.rev = T.next_dir();
+    return q;
+}
+
+// the fragment / bias pointers of a wide block's three convs
+static void wide_weights(const Tower& T, const BlockPlan& bp, BneckWideArgs& q) {
+    q.fa = T.base + bp.f1_off; q.ba = T.bias(T.P.convs[bp.c1]);
+    q.fb = T.base + bp.f2_off; q.bb = T.bias(T.P.convs[bp.c2]);
+    q.fc = T.base + bp.f3_off; q.bc = T.bias(T.P.convs[bp.c3]);
+}
+static bool wide_offered(const Tower& T, const BlockPlan& bp) { return T.dtype == IVOSW_BF16 && bp.f1_off && T.k.fuse_wide; }
+// block b of stage s as a wide block: everything but x, y and the direction
+static BneckWideArgs wide_args(const Tower& T, int s, int b, int nb, int foff) {
+    const Plan& P = T.P;
+    const BlockPlan& bp = P.blocks[FIRST_BLK[s] + b];
+    BneckWideArgs q{};
+    q.zeros = T.base + P.zero_off;
+    wide_weights(T, bp, q);
+    if (bp.ds >= 0) { q.ds = 1; q.fc = T.base + bp.cat_fw_off; q.bc = T.f32(bp.cat_b_off); }
+    q.B = nb; q.H = q.W = block_hw(s, b); q.Cin = P.convs[bp.c1].Cin; q.Cmid = P.convs[bp.c1].Cout;
+    if (s == 0 && T.k.fwd2) {
+        // t1 ping-pong: b0 -> m2 -> b1 -> ds -> b2 -> m1 (res3's t1 for the frames of the enclosing res3 chunk)
+        const BlockPlan& nx = P.blocks[b + 1];           // the next block (res3's first after b == 2)
+        q.t1in = b == 0 ? nullptr : (b == 1 ? T.bf.m2 : T.bf.ds);
+        q.t1out = b == 0 ? T.bf.m2 : (b == 1 ? T.bf.ds : T.bf.m1 + (size_t)foff * 64 * 64 * 128 * T.es);
+        q.fd = T.base + (b == 2 ? nx.fwd1_off : nx.f1_off); q.bd = T.bias(P.convs[nx.c1]);
+        q.nd = P.convs[nx.c1].Cout;
+        q.y_s2 = (b == 2 && T.k.ys2) ? 1 : 0;
+    }
+    return q;
+}
+static BneckArgs bneck_args(const Tower& T, const BlockPlan& bp, int hw, int nb, const void* x, void* y) {
+    const Plan& P = T.P;
+    const ConvPlan &c1 = P.convs[bp.c1], &c2 = P.convs[bp.c2], &c3 = P.convs[bp.c3];
+    BneckArgs q{};
+    q.x = x; q.y = y; q.zeros = T.base + P.zero_off;
+    q.wa = T.base + c1.w_off; q.ba = T.bias(c1); q.wb = T.base + c2.w_off; q.bb = T.bias(c2); q.wc = T.base + c3.w_off; q.bc = T.bias(c3);
+    if (bp.ds >= 0) { q.wd = T.base + P.convs[bp.ds].w_off; q.bd = T.bias(P.convs[bp.ds]); }
+    q.B = nb; q.H = hw; q.W = hw; q.Cin = c1.Cin; q.Cmid = c1.Cout;
+    return q;
+}
+// res3's first block (input x at hw = 64, or 32 where res2 stored even pixels only) behind its forwarded conv1 in m1
+static StageFirstArgs stage_first_args(const Tower& T, const BlockPlan& bp, int nb, const void* x, void* y) {
+    const ConvPlan& c2 = T.P.convs[bp.c2];
+    StageFirstArgs q{};
+    q.t1 = T.bf.m1; q.x2 = x; q.y = y; q.zeros = T.base + T.P.zero_off;
+    q.fw2 = T.base + bp.f2_off; q.b2 = T.bias(c2);
+    q.fwc = T.base + bp.cat_fw_off; q.bc = T.f32(bp.cat_b_off);
+    q.B = nb; q.Ho = q.Wo = HW_IN[1] / c2.stride; q.Cm = c2.Cout; q.C2 = T.P.convs[bp.ds].Cin;
+    q.H2 = q.W2 = T.k.ys2 ? HW_IN[1] / 2 : HW_IN[1]; q.stride2 = T.k.ys2 ? 1 : 2;
+    return q;
+}
+
+// The form that runs block b of stage s in a launch of nb frames, and how many blocks it consumes (1, or the rest of the stage - for
+// b == 0 the whole of it).  The order of the tests is the priority.  A predicate that is asked on an argument struct gets the struct
+// the launch gets, weights included (an offset the plan does not hold turns the form down); only the activations, which no
+// predicate distinguishes beyond non-null, are workspace stand-ins.
+enum Form { F_RES2_CHAIN, F_RES2_STAGE, F_WIDE_DF3, F_WIDE_CHAIN, F_WIDE, F_BNECK64, F_STAGE_FIRST, F_TAIL2_X3, F_TAIL3_X3, F_TAIL2_X3_DS, F_LAYERS_CAT, F_LAYERS };
+struct Choice { Form form; int blocks; };
+static Choice choose_form(const Tower& T, int s, int b, int nb) {
+    const Plan& P = T.P;
+    const TowerKnobs& k = T.k;
+    const BlockPlan& bp = P.blocks[FIRST_BLK[s] + b];
+    const ConvPlan &c2 = P.convs[bp.c2], &c3 = P.convs[bp.c3];
+    const int hw = block_hw(s, b), rest = NBLK[s] - b;
+    const bool bf16 = T.dtype == IVOSW_BF16, x3 = T.dtype == IVOSW_F32X3;
+    if (s == 0 && b == 0 && k.chain) return {F_RES2_CHAIN, rest};
+    if (s == 0 && b == 0 && k.stage2) {
+        Res2StageArgs q = res2_stage_args(P, T.base);
+        q.x = T.bf.pa; q.y = q.t1out = T.bf.m1; q.B = nb;
+        if (res2_stage_ok(q)) return {F_RES2_STAGE, rest};
+    }
+    if (wide_offered(T, bp)) {
+        const BneckWideArgs q = wide_args(T, s, b, nb, 0);
+        // res3's three identity blocks depth first (run_wide_df3): only under the snake order, from DF3_MIN frames per launch
+        if (s == 1 && b == 1 && bp.ds < 0 && k.snake && bneck_wide_fusable(q) && k.df3 > 1 && nb >= k.df3_min) return {F_WIDE_DF3, rest};
+        // the rest of the stage is identity blocks of this shape: chain them inside one launch
+        if (bp.ds < 0 && bneck_wide_fusable(q) && bneck_stage_fusable(q) && rest > 1) return {F_WIDE_CHAIN, rest};
+        if (bneck_wide_fusable(q)) return {F_WIDE, 1};
+    }
+    if (bf16 && (bp.ds < 0 || c2.stride == 1) && k.fuse && bneck_fusable(bneck_args(T, bp, hw, nb, T.bf.pa, T.bf.pb))) return {F_BNECK64, 1};
+    // res3's first block behind its forwarded conv1 as ONE launch: t2 never leaves LDS (stage_first.hip; bit-identical to the two
+    // layer launches it replaces)
+    if (bf16 && s == 1 && b == 0 && k.fwd2 && bp.ds >= 0 && bp.f2_off && bp.cat_fw_off && k.first3 &&
+        stage_first_ok(stage_first_args(T, bp, nb, T.bf.in[0], T.bf.pa)))
+        return {F_STAGE_FIRST, 1};
+    // the three-pass mode behind a block's conv1: 3x3 -> conv3 + residual as one launch (conv.hip: t2 stays on the CU), for the
+    // identity blocks of res2 (64 channels at 64 x 64) and res3 (128 at 32 x 32) ...
+    auto tail = [&](int h, int c) { return x3 && hw == h && c2.K == 3 && c2.stride == 1 && c2.Cin == c && c2.Cout == c && c3.Cin == c && c3.Cout == 4 * c; };
+    if (s == 0 && bp.ds < 0 && tail(64, 64) && k.fuse_tail_x3) return {F_TAIL2_X3, 1};
+    if (s == 1 && bp.ds < 0 && tail(32, 128) && k.fuse_tail3_x3) return {F_TAIL3_X3, 1};
+    // ... and res2's first block: 3x3 -> [conv3 | downsample] (K = 64 + 64, the block input as the second half)
+    if (s == 0 && bp.ds >= 0 && tail(64, 64) && P.convs[bp.ds].Cin == 64 && P.convs[bp.ds].stride == 1 && k.fuse_ds && k.fuse_tail_x3) return {F_TAIL2_X3_DS, 1};
+    // first block of a stage, layer by layer: relu(conv3(t2) + downsample(x)) as ONE GEMM over K = C + Cin (the block input, sampled at
+    // the downsample stride, is the second A source): the 4C-channel downsample output never goes to HBM and back
+    if (bp.ds >= 0 && k.fuse_ds) return {F_LAYERS_CAT, 1};
+    return {F_LAYERS, 1};
+}
+
+// res3's three identity blocks DEPTH FIRST over DF3 (2) groups of the launch's frames: b1 b2 b3 for the first half, then for the
+// second.  Every block's input was written by the launch right before it and its x + y (64 + 64 MB per stream instead of 128 + 128)
+// fit the memory-side cache together with the other stream's.  Costs the tail balancing of a 512-workgroup launch (256 workgroups are
+// a single round): + 0.8 % frames/s on average over five boxes at 128 frames per stream (- 0.2 .. + 2.5 %), - 0.5 % with four groups;
+// a frame's result does not depend on the launch it travels in.
+static void run_wide_df3(Tower& T, int nb, const char* x, char* out) {
+    const BneckWideArgs q = wide_args(T, 1, 1, nb, 0);
+    const size_t fe = (size_t)q.H * q.W * q.Cin * T.es;
+    char* const y1 = T.other(x);
+    char* const bufs[4] = {const_cast<char*>(x), y1, T.other(y1), out};
+    for (int g = 0; g < T.k.df3; ++g) {
+        const int lo = (int)((long)nb * g / T.k.df3), hi = (int)((long)nb * (g + 1) / T.k.df3);
+        for (int bb = 1; bb <= 3; ++bb) {
+            BneckWideArgs r = q;
+            wide_weights(T, T.P.blocks[FIRST_BLK[1] + bb], r);
+            r.x = bufs[bb - 1] + (size_t)lo * fe; r.y = bufs[bb] + (size_t)lo * fe;
+            r.B = hi - lo;
+            r.rev = T.next_dir();
+            if (bb == 3 && T.k.ys2abl) r.debug |= 16;
+            T.run("bneck_wide", r.B, r.rev, [&] { launch_bneck_wide(r, T.st); });
+        }
+    }
+}
+// blocks b .. of a stage (res4's identity blocks) chained inside one launch
+static void run_wide_chain(Tower& T, int s, int b, int nb, const char* x, char* out) {
+    BneckWideArgs q = wide_args(T, s, b, nb, 0);
+    q.rev = T.next_dir();
+    BneckStageArgs sa{};
+    for (int bb = b; bb < NBLK[s]; ++bb) {
+        // in place (tunable INPLACE4): a frame belongs to ONE workgroup, phase A has consumed x before phase C writes, and an
+        // element of y goes where the residual it was formed from came from - half the footprint of the chain in the caches
+        char* y = (bb == NBLK[s] - 1) ? out : ((T.k.inplace4 && bb > b) ? const_cast<char*>(x) : T.other(x));
+        BneckWideArgs& r = sa.blk[sa.n++];
+        r = q;
+        r.x = x; r.y = y;
+        wide_weights(T, T.P.blocks[FIRST_BLK[s] + bb], r);
+        if (s == 2 && bb == NBLK[s] - 1 && T.k.ys2abl) r.debug |= 16;
+        x = y;
+    }
+    T.run("bneck_wide_stage_kernel", nb, q.rev, [&] { launch_bneck_wide_stage(sa, T.st); });
+}
+
+// one bottleneck stage (K5) on nb frames: x -> out (the stage's last block writes straight into `out`); foff: the launch's first
+// frame inside the enclosing res3 chunk (where res2 leaves res3's forwarded conv1)
+static void run_stage(Tower& T, int s, const char* x, int nb, char* out, int foff) {
+    const Plan& P = T.P;
+    const char* base = T.base;
+    hipStream_t st = T.st;
+    for (int b = 0; b < NBLK[s];) {
+        const Choice ch = choose_form(T, s, b, nb);
+        const BlockPlan& bp = P.blocks[FIRST_BLK[s] + b];
+        const ConvPlan &c1 = P.convs[bp.c1], &c2 = P.convs[bp.c2], &c3 = P.convs[bp.c3];
+        const int hw = block_hw(s, b), ho = hw / c2.stride;
+        char* y = (b + ch.blocks == NBLK[s]) ? out : T.other(x);
+        char* t1f = T.bf.m1 + (size_t)foff * 64 * 64 * 128 * T.es;
+        // a block that was offered to the wide kernels and turned down (res5's identity blocks, by default) has taken a direction
+        // all the same, ever since the snake order exists: the launches behind it keep the directions they were measured with
+        if (ch.form > F_WIDE && wide_offered(T, bp)) T.next_dir();
+        auto conv1 = [&] { if (!(s == 1 && b == 0 && T.k.fwd2)) launch_layer(T, conv_args(T, c1, x, hw, hw, nullptr, T.bf.m1, 1, nb), c1.fw_off); };  // forwarded: res2's last block wrote it
+        switch (ch.form) {
+        case F_RES2_CHAIN: {
+            Res2ChainArgs q{};
+            q.x = x; q.y = out; q.t1out = t1f; q.wstream = base + P.chain_off; q.zeros = base + P.zero_off;
+            q.B = nb; q.y_s2 = T.k.ys2 ? 1 : 0; q.rev = T.next_dir();
+            T.run("res2_chain_kernel", nb, q.rev, [&] { launch_res2_chain(q, st); });
+            break;
+        }
+        case F_RES2_STAGE: {
+            Res2StageArgs q = res2_stage_args(P, base);
+            q.x = x; q.y = out; q.t1out = t1f; q.B = nb; q.y_s2 = T.k.ys2 ? 1 : 0; q.rev = T.next_dir();
+            T.run("res2_stage_kernel", nb, q.rev, [&] { launch_res2_stage(q, st); });
+            break;
+        }
+        case F_WIDE_DF3: run_wide_df3(T, nb, x, out); break;
+        case F_WIDE_CHAIN: run_wide_chain(T, s, b, nb, x, out); break;
+        case F_WIDE: {
+            BneckWideArgs q = wide_args(T, s, b, nb, foff);
+            q.x = x; q.y = y; q.rev = T.next_dir();
+            T.run("bneck_wide", nb, q.rev, [&] { launch_bneck_wide(q, st); });
+            break;
+        }
+        case F_BNECK64: T.run("bneck64_kernel", nb, 0, [&] { launch_bneck(bneck_args(T, bp, hw, nb, x, y), st); }); break;
+        case F_STAGE_FIRST: {
+            StageFirstArgs q = stage_first_args(T, bp, nb, x, y);
+            q.rev = T.next_dir();
+            T.run("stage_first_kernel", nb, q.rev, [&] { launch_stage_first(q, st); });
+            break;
+        }
+        case F_TAIL2_X3: case F_TAIL3_X3: case F_TAIL2_X3_DS: {
+            conv1();
+            const bool ds = ch.form == F_TAIL2_X3_DS, r3 = ch.form == F_TAIL3_X3;
+            const void *w2 = base + c2.w_off, *w3 = base + (ds ? bp.cat_w_off : c3.w_off), *zeros = base + P.zero_off;
+            const float* b3 = ds ? T.f32(bp.cat_b_off) : T.bias(c3);
+            const int d = T.next_dir();
+            T.run(r3 ? "res3_tail_x3_kernel" : "res2_tail_x3_kernel", nb, d, [&] {
+                if (r3) launch_res3_tail_x3(T.bf.m1, x, w2, T.bias(c2), w3, b3, zeros, y, nb, hw, hw, d, st);
+                else launch_res2_tail_x3(T.bf.m1, ds ? nullptr : x, w2, T.bias(c2), w3, b3, zeros, y, nb, hw, hw, d, st, ds ? x : nullptr);
+            });
+            break;
+        }
+        case F_LAYERS_CAT: case F_LAYERS: {
+            conv1();
+            launch_layer(T, conv_args(T, c2, T.bf.m1, hw, ho, nullptr, T.bf.m2, 1, nb), c2.fw_off);
+            const ConvPlan* cd = bp.ds >= 0 ? &P.convs[bp.ds] : nullptr;
+            if (ch.form == F_LAYERS_CAT) {
+                ConvArgs q = conv_args(T, c3, T.bf.m2, ho, ho, nullptr, y, 1, nb);
+                q.w = base + bp.cat_w_off; q.bias = T.f32(bp.cat_b_off);
+                q.x2 = x; q.Cin2 = cd->Cin; q.H2 = hw; q.W2 = hw; q.stride2 = cd->stride;
+                if (s == 1 && T.k.ys2) { q.H2 = hw / 2; q.W2 = hw / 2; q.stride2 = 1; }      // res2's output arrives already subsampled
+                launch_layer(T, q, bp.cat_fw_off);
+                break;
+            }
+            if (cd) launch_layer(T, conv_args(T, *cd, x, hw, ho, nullptr, T.bf.ds, 0, nb), cd->fw_off);
+            launch_layer(T, conv_args(T, c3, T.bf.m2, ho, ho, cd ? T.bf.ds : x, y, 1, nb), c3.fw_off);  // relu(bn3(conv3) + identity)
+            break;
+        }
+        }
+        x = y;
+        b += ch.blocks;
+    }
+}
+
 static void assess_forward_range(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int u0, int B,
                                  int H, int W, float* scores, void* ws, int chunk, int tap_stage, void* tap_out, int slot, hipStream_t st,
-                                 const VideoTable* vt, const int32_t* ids) {
+                                 const VideoTable* vt, const int32_t* ids, std::string* script) {
     const Plan& P = plan_for(dtype);
     const size_t es = (dtype == IVOSW_BF16) ? 2 : 4;
     const char* base = static_cast<const char*>(packed);
+    Tower T{P, tower_knobs(dtype, B, tap_stage, P), dtype, es, base, Bufs{}, st, slot, script};
     Arena ar(ws);
-    Bufs bf{};
-    carve(ar, dtype, B, chunk, &bf);
+    carve(ar, dtype, B, chunk, &T.bf);
+    const Bufs& bf = T.bf;
+    const bool live = !script;               // describing: no front end, no taps, no spans, no head
     auto tap = [&](int stage, const void* src, size_t bytes) {
-        if (tap_stage != stage) return;
+        if (!live || tap_stage != stage) return;
         (void)hipMemcpyAsync(tap_out, src, bytes, hipMemcpyDeviceToDevice, st);
         // IVOSW_F32X3 keeps its activations (stem output .. res5) in the split hi | lo layout: the tap hands out plain fp32
         if (dtype == IVOSW_F32X3 && stage >= 2 && stage <= 7) launch_unsplit_x3(tap_out, bytes / sizeof(float), st);
     };
 
     // K1/K2: mask -> (y,x,h,w) for the whole batch, on device
-    if (vt) launch_mask_bbox_multi(*vt, u0, B, bf.yxhw, bf.box, st, ids);
-    else launch_mask_bbox(tp, u0, B, H, W, sm, bf.yxhw, bf.box, st);
+    if (live && vt) launch_mask_bbox_multi(*vt, u0, B, bf.yxhw, bf.box, st, ids);
+    else if (live) launch_mask_bbox(tp, u0, B, H, W, sm, bf.yxhw, bf.box, st);
     // Encoder.mean/std come from the checkpoint: the sampler reads them from the packed arena
     RoiNorm nrm{{0.f, 0.f, 0.f}, {1.f, 1.f, 1.f}, reinterpret_cast<const float*>(base + P.norm_off)};
-
-    const int nblk[4] = {3, 4, 6, 3}, first_blk[4] = {0, 3, 7, 13}, hw_in[4] = {64, 64, 32, 16};
     const int cs[4] = {chunk, chunk * 2, chunk * 4, chunk * 8};
-
-    // one bottleneck stage (K5) on nb frames: x -> out (the last block writes straight into `out`)
-    // conv1 forwarding through res2 (tunable FWD2): block b of res2 also applies block b+1's first 1x1 to its output tile while
-    // it is on chip; the last block applies res3's first 1x1, so that layer (a 0.8 GB pass over HBM) is never launched
-    const bool fwd2 = dtype == IVOSW_BF16 && tune_get("FWD2", 1) && tune_get("FUSE_WIDE", 1) && tune_get("FUSE_WIDE2", 1) &&
-                      tune_get("HALO64S", 1) && tune_get("HALO64S_DS", 1) && P.blocks[3].fwd1_off;
-    // ... and res2's last block then writes its output at the even pixels only (compact [nb,32,32,256]): with conv1 forwarded, the
-    // only reader left is res3's stride-2 downsample.  Off when an intermediate is tapped (the res2 tap wants the whole tensor).
-    const bool ys2 = fwd2 && tap_stage == 0 && tune_get("FUSE_DS", 1) && tune_get("YS2", 1);
-    // ... or the whole of res2 in ONE launch (res2_stage.hip, tunable RES2_STAGE, default on): a workgroup carries its 8 x 16 tile
-    // through the three blocks, y0 / y1 never reach HBM.  Same summation orders as the per-block kernels: bit-identical stage output, so
-    // the choice moves no score.  In time the two are level (frames/s at B = 32 / 64 / 100 / 160 / 256: +0.8 / -1.2 / +1.9 / -0.6 /
-    // -0.8 %, alternating runs on one box; 946 against 983 us on one stream); the stage kernel moves 2.55 GB less HBM traffic per
-    // 256-frame pass (9.23 against 11.77 GB) in four launches fewer, which is why it is the default.
-    const bool stage2 = fwd2 && tune_get("RES2_STAGE", 1);
-    // Snake order (tunable SNAKE, default on): consecutive launches of the tower walk their pixel tiles in OPPOSITE directions, so a
-    // launch starts with the tiles its producer wrote last - still in the memory-side cache (256 MB for ~128 MB tensors per stream) -
-    // instead of the ones written first and long evicted.  Tiles are independent: the order cannot change a result.
-    // From SNAKE_MIN (96) frames per stream: below that the tensors fit the cache either way (B = 32 / 100 / 160: +-0 / -0.6 / +0.4 %).
-    const bool snake = dtype == IVOSW_BF16 && tune_get("SNAKE", 1) != 0 && B >= tune_get("SNAKE_MIN", 96);
-    int dir = 1;                                     // the stem walks backward (its producer, the ROI crop, walks forward), the launch behind it forward ...
-    auto next_dir = [&]() { const int d = snake ? dir : 0; dir ^= 1; return d; };
-    auto run_stage = [&](int s, const char* x_in, int nb, char* out, int foff) {
-        const char* x = x_in;
-        int hw = hw_in[s];
-        if (s == 0 && stage2 && P.chain_off && tune_get("RES2_CHAIN", 1)) {
-            // round 6: the register-chained form of the stage kernel (res2_chain.hip); RES2_CHAIN=0 is the round-3 stage kernel
-            Res2ChainArgs q{};
-            q.x = x; q.y = out; q.t1out = bf.m1 + (size_t)foff * 64 * 64 * 128 * es;
-            q.wstream = base + P.chain_off; q.zeros = base + P.zero_off;
-            q.B = nb; q.y_s2 = ys2 ? 1 : 0;
-            q.rev = next_dir();
-            launch_res2_chain(q, st);
-            return;
-        }
-        if (s == 0 && stage2) {
-            Res2StageArgs q = res2_stage_args(P, base);
-            q.x = x; q.y = out; q.t1out = bf.m1 + (size_t)foff * 64 * 64 * 128 * es;
-            q.B = nb; q.y_s2 = ys2 ? 1 : 0;
-            q.rev = next_dir();
-            if (res2_stage_ok(q)) {
-                launch_res2_stage(q, st);
-                return;
-            }
-        }
-        for (int b = 0; b < nblk[s]; ++b) {
-            const BlockPlan& bp = P.blocks[first_blk[s] + b];
-            const ConvPlan &c1 = P.convs[bp.c1], &c2 = P.convs[bp.c2], &c3 = P.convs[bp.c3];
-            const int ho = hw / c2.stride;
-            char* y = (b == nblk[s] - 1) ? out : ((x == bf.pa) ? bf.pb : bf.pa);
-            auto mk = [&](const ConvPlan& c, const void* in, int hin, int hout, const void* res, void* o, int relu) {
-                ConvArgs q{};
-                q.zeros = base + P.zero_off; q.x = in; q.w = base + c.w_off; q.bias = reinterpret_cast<const float*>(base + c.b_off); q.res = res; q.y = o;
-                q.B = nb; q.H = hin; q.W = hin; q.Cin = c.Cin; q.Ho = hout; q.Wo = hout; q.Cout = c.Cout;
-                q.KH = c.K; q.KW = c.K; q.stride = c.stride; q.pad = c.pad; q.relu = relu;
-                q.rev = next_dir();
-                if (dtype == IVOSW_BF16 && tune_get("G8", 0) && tune_get("WIDE1X1", 1) && conv1x1_g8_ok(q)) launch_conv1x1_g8(q, st);
-                else if (dtype == IVOSW_BF16 && c.fw_off && conv1x1_wide_ok(q) && tune_get("WIDE1X1", 1)) launch_conv1x1_wide(q, base + c.fw_off, st);
-                else launch_conv(q, dtype, false, st);
-            };
-            if (dtype == IVOSW_BF16 && bp.f1_off && tune_get("FUSE_WIDE", 1)) {
-                BneckWideArgs q{};
-                q.x = x; q.y = y; q.zeros = base + P.zero_off;
-                q.fa = base + bp.f1_off; q.ba = reinterpret_cast<const float*>(base + c1.b_off);
-                q.fb = base + bp.f2_off; q.bb = reinterpret_cast<const float*>(base + c2.b_off);
-                q.fc = base + bp.f3_off; q.bc = reinterpret_cast<const float*>(base + c3.b_off);
-                if (bp.ds >= 0) {
-                    q.ds = 1; q.fc = base + bp.cat_fw_off; q.bc = reinterpret_cast<const float*>(base + bp.cat_b_off);
-                }
-                q.B = nb; q.H = hw; q.W = hw; q.Cin = c1.Cin; q.Cmid = c1.Cout;
-                if (s == 0 && fwd2) {
-                    // t1 ping-pong: b0 -> m2 -> b1 -> ds -> b2 -> m1 (res3's t1 for the frames of the enclosing res3 chunk)
-                    const BlockPlan& nx = P.blocks[first_blk[0] + b + 1];          // the next block (res3's first after b == 2)
-                    const ConvPlan& n1c = P.convs[nx.c1];
-                    q.t1in = b == 0 ? nullptr : (b == 1 ? bf.m2 : bf.ds);
-                    q.t1out = b == 0 ? bf.m2 : (b == 1 ? bf.ds : bf.m1 + (size_t)foff * 64 * 64 * 128 * es);
-                    q.fd = base + (b == 2 ? nx.fwd1_off : nx.f1_off);
-                    q.bd = reinterpret_cast<const float*>(base + n1c.b_off);
-                    q.nd = n1c.Cout;
-                    q.y_s2 = (b == 2 && ys2) ? 1 : 0;
-                }
-                if (s == 1 && b == 1 && bp.ds < 0 && snake && bneck_wide_fusable(q) && tune_get("DF3", 2) > 1 && nb >= tune_get("DF3_MIN", 128)) {
-                    // res3's three identity blocks DEPTH FIRST over DF3 (2) groups of the launch's frames: b1 b2 b3 for the first half, then
-                    // for the second.  Every block's input was written by the launch right before it and its x + y (64 + 64 MB per stream
-                    // instead of 128 + 128) fit the memory-side cache together with the other stream's.  Costs the tail balancing of a
-                    // 512-workgroup launch (256 workgroups are a single round): + 0.8 % frames/s on average over five boxes at 128 frames per
-                    // stream (- 0.2 .. + 2.5 %), - 0.5 % with four groups; a frame's result does not depend on the launch it travels in.
-                    const size_t fe = (size_t)hw * hw * c1.Cin * es;
-                    const int G = tune_get("DF3", 2);
-                    char* y1 = (x == bf.pa) ? bf.pb : bf.pa;
-                    char* y2 = (y1 == bf.pa) ? bf.pb : bf.pa;
-                    char* bufs[4] = {const_cast<char*>(x), y1, y2, out};
-                    for (int g = 0; g < G; ++g) {
-                        const int lo = (int)((long)nb * g / G), hi = (int)((long)nb * (g + 1) / G);
-                        for (int bb = 1; bb <= 3; ++bb) {
-                            const BlockPlan& bq = P.blocks[first_blk[1] + bb];
-                            const ConvPlan &d1 = P.convs[bq.c1], &d2 = P.convs[bq.c2], &d3 = P.convs[bq.c3];
-                            BneckWideArgs r = q;
-                            r.fa = base + bq.f1_off; r.ba = reinterpret_cast<const float*>(base + d1.b_off);
-                            r.fb = base + bq.f2_off; r.bb = reinterpret_cast<const float*>(base + d2.b_off);
-                            r.fc = base + bq.f3_off; r.bc = reinterpret_cast<const float*>(base + d3.b_off);
-                            r.x = bufs[bb - 1] + (size_t)lo * fe; r.y = bufs[bb] + (size_t)lo * fe;
-                            r.B = hi - lo;
-                            r.rev = next_dir();
-                            if (IVOSW_ABLATION && bb == 3 && tune_get("YS2ABL", 0)) r.debug |= 16;      // ablation: the stage's last block writes even pixels only
-                            launch_bneck_wide(r, st);
-                        }
-                    }
-                    x = out;
-                    break;
-                }
-                q.rev = next_dir();                  // (after the depth-first branch, which takes a direction per launch of its own)
-                if (bp.ds < 0 && bneck_wide_fusable(q) && bneck_stage_fusable(q) && b + 1 < nblk[s]) {
-                    // the rest of the stage is identity blocks of this shape: chain them inside one launch
-                    BneckStageArgs sa{};
-                    const char* xi = x;
-                    for (int bb = b; bb < nblk[s]; ++bb) {
-                        const BlockPlan& bq = P.blocks[first_blk[s] + bb];
-                        const ConvPlan &d1 = P.convs[bq.c1], &d2 = P.convs[bq.c2], &d3 = P.convs[bq.c3];
-                        // in place (tunable INPLACE4): a frame belongs to ONE workgroup, phase A has consumed x before phase C writes, and an
-                        // element of y goes where the residual it was formed from came from - half the footprint of the chain in the caches
-                        char* yi = (bb == nblk[s] - 1) ? out : ((tune_get("INPLACE4", 1) && bb > b) ? const_cast<char*>(xi) : ((xi == bf.pa) ? bf.pb : bf.pa));
-                        BneckWideArgs& r = sa.blk[sa.n++];
-                        r = q;
-                        r.x = xi; r.y = yi;
-                        r.fa = base + bq.f1_off; r.ba = reinterpret_cast<const float*>(base + d1.b_off);
-                        r.fb = base + bq.f2_off; r.bb = reinterpret_cast<const float*>(base + d2.b_off);
-                        r.fc = base + bq.f3_off; r.bc = reinterpret_cast<const float*>(base + d3.b_off);
-                        if (IVOSW_ABLATION && s == 2 && bb == nblk[s] - 1 && tune_get("YS2ABL", 0)) r.debug |= 16;
-                        xi = yi;
-                    }
-                    launch_bneck_wide_stage(sa, st);
-                    x = xi;
-                    break;
-                }
-                if (bneck_wide_fusable(q)) {
-                    launch_bneck_wide(q, st);
-                    x = y;
-                    continue;
-                }
-            }
-            if (dtype == IVOSW_BF16 && (bp.ds < 0 || c2.stride == 1) && tune_get("FUSE", 1)) {
-                BneckArgs q{};
-                q.x = x; q.y = y; q.zeros = base + P.zero_off;
-                q.wa = base + c1.w_off; q.ba = reinterpret_cast<const float*>(base + c1.b_off);
-                q.wb = base + c2.w_off; q.bb = reinterpret_cast<const float*>(base + c2.b_off);
-                q.wc = base + c3.w_off; q.bc = reinterpret_cast<const float*>(base + c3.b_off);
-                if (bp.ds >= 0) {
-                    q.wd = base + P.convs[bp.ds].w_off;
-                    q.bd = reinterpret_cast<const float*>(base + P.convs[bp.ds].b_off);
-                }
-                q.B = nb; q.H = hw; q.W = hw; q.Cin = c1.Cin; q.Cmid = c1.Cout;
-                if (bneck_fusable(q)) {
-                    launch_bneck(q, st);
-                    x = y;
-                    continue;
-                }
-            }
-            if (dtype == IVOSW_BF16 && s == 1 && b == 0 && fwd2 && bp.ds >= 0 && bp.f2_off && bp.cat_fw_off && tune_get("FIRST3", 1)) {
-                // res3's first block behind its forwarded conv1 as ONE launch: t2 never leaves LDS (stage_first.hip; bit-identical to the
-                // two layer launches below)
-                StageFirstArgs q{};
-                q.t1 = bf.m1; q.x2 = x; q.y = y; q.zeros = base + P.zero_off;
-                q.fw2 = base + bp.f2_off; q.b2 = reinterpret_cast<const float*>(base + c2.b_off);
-                q.fwc = base + bp.cat_fw_off; q.bc = reinterpret_cast<const float*>(base + bp.cat_b_off);
-                q.B = nb; q.Ho = ho; q.Wo = ho; q.Cm = c2.Cout; q.C2 = P.convs[bp.ds].Cin;
-                q.H2 = ys2 ? hw / 2 : hw; q.W2 = q.H2; q.stride2 = ys2 ? 1 : 2;
-                if (stage_first_ok(q)) {
-                    q.rev = next_dir();
-                    launch_stage_first(q, st);
-                    x = y;
-                    hw = ho;
-                    continue;
-                }
-            }
-            if (!(s == 1 && b == 0 && fwd2)) mk(c1, x, hw, hw, nullptr, bf.m1, 1);     // forwarded: res2's last block wrote it
-            if (dtype == IVOSW_F32X3 && s == 0 && bp.ds < 0 && hw == 64 && c2.K == 3 && c2.stride == 1 && c2.Cin == 64 && c2.Cout == 64 && c3.Cin == 64 &&
-                c3.Cout == 256 && tune_get("FUSE_TAIL_X3", 1)) {
-                // the three-pass mode's identity blocks of res2 behind their conv1: 3x3 -> conv3 + residual as one launch (conv.hip: t2 stays on the CU)
-                launch_res2_tail_x3(bf.m1, x, base + c2.w_off, reinterpret_cast<const float*>(base + c2.b_off), base + c3.w_off,
-                                    reinterpret_cast<const float*>(base + c3.b_off), base + P.zero_off, y, nb, hw, hw, next_dir(), st);
-                x = y;
-                continue;
-            }
-            if (dtype == IVOSW_F32X3 && s == 1 && bp.ds < 0 && hw == 32 && c2.K == 3 && c2.stride == 1 && c2.Cin == 128 && c2.Cout == 128 && c3.Cin == 128 &&
-                c3.Cout == 512 && tune_get("FUSE_TAIL3_X3", 1)) {
-                launch_res3_tail_x3(bf.m1, x, base + c2.w_off, reinterpret_cast<const float*>(base + c2.b_off), base + c3.w_off,
-                                    reinterpret_cast<const float*>(base + c3.b_off), base + P.zero_off, y, nb, hw, hw, next_dir(), st);
-                x = y;
-                continue;
-            }
-            if (dtype == IVOSW_F32X3 && s == 0 && bp.ds >= 0 && hw == 64 && c2.K == 3 && c2.stride == 1 && c2.Cin == 64 && c2.Cout == 64 && c3.Cin == 64 &&
-                c3.Cout == 256 && P.convs[bp.ds].Cin == 64 && P.convs[bp.ds].stride == 1 && tune_get("FUSE_DS", 1) && tune_get("FUSE_TAIL_X3", 1)) {
-                // res2's first block: 3x3 -> [conv3 | downsample] (K = 64 + 64, the block input as the second half) as one launch
-                launch_res2_tail_x3(bf.m1, nullptr, base + c2.w_off, reinterpret_cast<const float*>(base + c2.b_off), base + bp.cat_w_off,
-                                    reinterpret_cast<const float*>(base + bp.cat_b_off), base + P.zero_off, y, nb, hw, hw, next_dir(), st, x);
-                x = y;
-                continue;
-            }
-            mk(c2, bf.m1, hw, ho, nullptr, bf.m2, 1);
-            const void* idt = x;
-            if (bp.ds >= 0 && tune_get("FUSE_DS", 1)) {
-                // first block of a stage: relu(conv3(t2) + downsample(x)) as ONE GEMM over K = C + Cin (the block input,
-                // sampled at the downsample stride, is the second A source): the 4C-channel downsample output never
-                // goes to HBM and back
-                const ConvPlan& cd = P.convs[bp.ds];
-                ConvArgs q{};
-                q.zeros = base + P.zero_off; q.x = bf.m2; q.w = base + bp.cat_w_off; q.bias = reinterpret_cast<const float*>(base + bp.cat_b_off);
-                q.res = nullptr; q.y = y; q.B = nb; q.H = ho; q.W = ho; q.Cin = c3.Cin; q.Ho = ho; q.Wo = ho; q.Cout = c3.Cout;
-                q.KH = 1; q.KW = 1; q.stride = 1; q.pad = 0; q.relu = 1;
-                q.x2 = x; q.Cin2 = cd.Cin; q.H2 = hw; q.W2 = hw; q.stride2 = cd.stride;
-                q.rev = next_dir();
-                if (s == 1 && ys2) { q.H2 = hw / 2; q.W2 = hw / 2; q.stride2 = 1; }      // res2's output arrives already subsampled
-                if (dtype == IVOSW_BF16 && tune_get("G8", 0) && tune_get("WIDE1X1", 1) && conv1x1_g8_ok(q)) launch_conv1x1_g8(q, st);
-                else if (dtype == IVOSW_BF16 && bp.cat_fw_off && conv1x1_wide_ok(q) && tune_get("WIDE1X1", 1)) launch_conv1x1_wide(q, base + bp.cat_fw_off, st);
-                else launch_conv(q, dtype, false, st);
-                x = y;
-                hw = ho;
-                continue;
-            }
-            if (bp.ds >= 0) {
-                mk(P.convs[bp.ds], x, hw, ho, nullptr, bf.ds, 0);
-                idt = bf.ds;
-            }
-            mk(c3, bf.m2, ho, ho, idt, y, 1);  // relu(bn3(conv3) + identity)
-            x = y;
-            hw = ho;
-        }
-    };
+    const float* stem_b = reinterpret_cast<const float*>(base + P.stem_b_off);
 
     for (int f3 = 0; f3 < B; f3 += cs[3]) {
         const int n3 = std::min(cs[3], B - f3);
@@ -794,49 +857,83 @@ static void assess_forward_range(const void* packed, int dtype, const FrameSrc& 
                 const int n1 = std::min(cs[1], f2 + n2 - f1);
                 for (int f0 = f1; f0 < f1 + n1; f0 += cs[0]) {
                     const int nb = std::min(cs[0], f1 + n1 - f0);
-                    // K3: ROI crop-resize + normalise -> NHWC4
-                    span_close(st, slot);
-                    if (vt) launch_roi_sample_multi(*vt, bf.yxhw + (size_t)f0 * 4, u0 + f0, nb, dtype, nrm, bf.roi, st, ids);
-                    else launch_roi_sample(fs, tp, bf.yxhw + (size_t)f0 * 4, u0 + f0, nb, H, W, dtype, sm, nrm, bf.roi, st);
-                    tap(1, bf.roi, nb * E_ROI * es);
+                    if (live) {
+                        // K3: ROI crop-resize + normalise -> NHWC4
+                        span_close(st, slot);
+                        if (vt) launch_roi_sample_multi(*vt, bf.yxhw + (size_t)f0 * 4, u0 + f0, nb, dtype, nrm, bf.roi, st, ids);
+                        else launch_roi_sample(fs, tp, bf.yxhw + (size_t)f0 * 4, u0 + f0, nb, H, W, dtype, sm, nrm, bf.roi, st);
+                        tap(1, bf.roi, nb * E_ROI * es);
+                        span_open(st, slot);
+                    }
                     // K4: stem 7x7/2 (RGB|P) + BN + ReLU, then 3x3/2 max pool (bf16: one fused kernel unless the stem tap is wanted)
-                    span_open(st, slot);
-                    if (dtype == IVOSW_BF16 && tap_stage != 2 && tune_get("FUSE_STEM", 1)) {
-                        dir = 1;                 // every res2 chunk starts the alternation anew at its stem
-                        launch_stem_pool(bf.roi, base + P.stem_w_off, reinterpret_cast<const float*>(base + P.stem_b_off), nb, bf.pa, st, next_dir());
-                    } else if (dtype == IVOSW_F32X3 && tap_stage != 2 && tune_get("FUSE_STEM_X3", 1)) {
+                    if (dtype == IVOSW_BF16 && tap_stage != 2 && T.k.fuse_stem) {
+                        T.dir = 1;               // every res2 chunk starts the alternation anew at its stem
+                        const int d = T.next_dir();
+                        T.run("stem_pool_kernel", nb, d, [&] { launch_stem_pool(bf.roi, base + P.stem_w_off, stem_b, nb, bf.pa, st, d); });
+                    } else if (dtype == IVOSW_F32X3 && tap_stage != 2 && T.k.fuse_stem_x3) {
                         // the three-pass mode's stem + pool as one launch (stem.hip): fp32 ROI tile in, split pooled map out
-                        launch_stem_pool_x3(bf.roi, base + P.stem_w_off, reinterpret_cast<const float*>(base + P.stem_b_off), nb, bf.pa, st, 0);
+                        T.run("stem_pool_x3_kernel", nb, 0, [&] { launch_stem_pool_x3(bf.roi, base + P.stem_w_off, stem_b, nb, bf.pa, st, 0); });
                     } else {
                         ConvArgs a{};
-                        a.zeros = base + P.zero_off; a.x = bf.roi; a.w = base + P.stem_w_off; a.bias = reinterpret_cast<const float*>(base + P.stem_b_off);
+                        a.zeros = base + P.zero_off; a.x = bf.roi; a.w = base + P.stem_w_off; a.bias = stem_b;
                         a.res = nullptr; a.y = bf.stem; a.B = nb; a.H = 256; a.W = 256; a.Cin = 4; a.Ho = 128; a.Wo = 128;
                         a.Cout = 64; a.KH = 7; a.KW = 7; a.stride = 2; a.pad = 3; a.relu = 1;
-                        launch_conv(a, dtype, true, st);
+                        T.run(conv_kernel_name(conv_select(a, dtype, true)), nb, 0, [&] { launch_conv(a, dtype, true, st); });
                         tap(2, bf.stem, (size_t)nb * 128 * 128 * 64 * es);
-                        launch_maxpool(bf.stem, nb, 128, 128, 64, dtype, bf.pa, st);
+                        T.run(dtype == IVOSW_F32X3 ? "maxpool_x3_kernel" : "maxpool_kernel", nb, 0, [&] { launch_maxpool(bf.stem, nb, 128, 128, 64, dtype, bf.pa, st); });
                     }
                     tap(3, bf.pa, (size_t)nb * 64 * 64 * 64 * es);
-                    char* o2 = bf.in[0] + (size_t)(f0 - f1) * (ys2 ? E_OUT[0] / 4 : E_OUT[0]) * es;
-                    run_stage(0, bf.pa, nb, o2, f0 - f1);
+                    char* o2 = bf.in[0] + (size_t)(f0 - f1) * (T.k.ys2 ? E_OUT[0] / 4 : E_OUT[0]) * es;
+                    run_stage(T, 0, bf.pa, nb, o2, f0 - f1);
                     tap(4, o2, nb * E_OUT[0] * es);
                 }
                 char* o3 = bf.in[1] + (size_t)(f1 - f2) * E_OUT[1] * es;
-                run_stage(1, bf.in[0], n1, o3, 0);
+                run_stage(T, 1, bf.in[0], n1, o3, 0);
                 tap(5, o3, n1 * E_OUT[1] * es);
             }
             char* o4 = bf.in[2] + (size_t)(f2 - f3) * E_OUT[2] * es;
-            run_stage(2, bf.in[1], n2, o4, 0);
+            run_stage(T, 2, bf.in[1], n2, o4, 0);
             tap(6, o4, n2 * E_OUT[2] * es);
         }
-        run_stage(3, bf.in[2], n3, bf.pa, 0);  // c0*8 frames x 131k elements == c0 * E_BIG: fits a ping-pong buffer
+        run_stage(T, 3, bf.in[2], n3, bf.pa, 0);  // c0*8 frames x 131k elements == c0 * E_BIG: fits a ping-pong buffer
         tap(7, bf.pa, n3 * E_OUT[3] * es);
+        if (!live) continue;
         // K6: 8x8 average pool + fc1
         span_close(st, slot);
         launch_pool_fc(bf.pa, n3, dtype, reinterpret_cast<const float*>(base + P.fcw_off),
                        reinterpret_cast<const float*>(base + P.fcb_off), scores + f3, tap_stage == 8 ? bf.pooled : nullptr, st);
         tap(8, bf.pooled, (size_t)n3 * 2048 * sizeof(float));
     }
+}
+
+// The launches of ivosw_assess_forward(dtype, B, chunk, tap_stage) behind the ROI sampler and before the pooling head, as text (include/ivosw.h): the
+// same split decision and the same walk, asked without a device.  Stand-in arena and workspace addresses: nothing reads through them.
+extern "C" int ivosw_assess_describe(int dtype, int B, int chunk, int tap_stage, char* buf, size_t cap) {
+    IVOSW_REQUIRE(dtype == IVOSW_F32 || dtype == IVOSW_BF16 || dtype == IVOSW_F32X3, "dtype must be IVOSW_F32, IVOSW_BF16 or IVOSW_F32X3");
+    IVOSW_REQUIRE(B > 0 && tap_stage >= 0 && tap_stage <= 8 && buf && cap > 0, "B must be positive, tap_stage in 0 .. 8, buf non-null");
+    const bool split = split_wanted(dtype, B, chunk, tap_stage);
+    if (chunk <= 0) chunk = default_chunk(dtype);
+    if (chunk > B) chunk = B;
+    IVOSW_REQUIRE(tap_stage == 0 || B <= chunk, "taps need B <= chunk");
+    char* const packed = reinterpret_cast<char*>(uintptr_t(1) << 40);
+    char* const ws = reinterpret_cast<char*>(uintptr_t(1) << 41);
+    std::string s;
+    auto range = [&](int u0, int n, int c, int slot) {
+        assess_forward_range(packed, dtype, FrameSrc{nullptr, 0}, nullptr, SampleMap{1, 0, 0}, u0, n, 2, 2, nullptr, ws, c, tap_stage, nullptr, slot, nullptr, nullptr, nullptr, &s);
+    };
+    if (split) {
+        const int B0 = split_first_half(B);
+        range(0, B0, std::min(default_chunk(dtype), B0), 0);
+        range(B0, B - B0, std::min(default_chunk(dtype), B - B0), 1);
+    } else {
+        range(0, B, chunk, 0);
+    }
+    if (s.size() + 1 > cap) {
+        set_error("ivosw_assess_describe: buffer %zu < %zu", cap, s.size() + 1);
+        return IVOSW_ERR_WS;
+    }
+    memcpy(buf, s.c_str(), s.size() + 1);
+    return IVOSW_OK;
 }
 
 #ifdef IVOSW_PROBES

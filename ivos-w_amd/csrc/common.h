@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <mutex>
+
 #include "../../include/ivosw.h"
 
 namespace ivosw {
@@ -76,6 +78,21 @@ struct Arena {
         return p;
     }
 };
+
+// Compute units of the current device, for the persistent kernels that size their grid by it: a per-device table, each entry
+// filled once under a mutex (256, the MI355X's, where the query fails).
+inline int cu_count_current_device() {
+    static std::mutex mu;
+    static int ncu[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    std::lock_guard<std::mutex> lk(mu);
+    if (!ncu[dev]) {
+        hipDeviceProp_t pr;
+        ncu[dev] = hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256;
+    }
+    return ncu[dev];
+}
 
 // The sequence table of the ragged entries (ivosw_brain_forward_ragged and its kin): it travels inside the kernel arguments.
 struct SeqTable {

@@ -26,6 +26,17 @@ struct ConvArgs {
 };
 
 void launch_conv(const ConvArgs& a, int dtype, bool stem, hipStream_t st);
+// the instantiations launch_conv runs (conv.hip); conv_select picks one on the host from the layer shape, the precision and the tunables
+enum ConvKernel {
+    CK_STEM,                                                          // conv_igemm_kernel: the 7x7 stem
+    CK_PATCH_2F, CK_PATCH_4F_KXY, CK_PATCH_4F, CK_PATCH_KXY, CK_PATCH, // conv3x3_patch_kernel (bf16): 8x8 frames two / four per tile, 16-row patches; _KXY: PATCH_KEYXY
+    CK_DMA_SMALL, CK_WS_LW8, CK_WS_LW4, CK_DMA, CK_DMA_SHORTK,         // Cout % 128 == 0: 128 x 128 tiles of a small launch | wave-specialised, 8 / 4 load waves | every wave loads and multiplies | K <= 128
+    CK_PATCH_X3,                                                      // conv3x3_patch_x3_kernel (IVOSW_F32X3, res2's 3x3)
+    CK_WS64, CK_DMA64, CK_DMA64_SHORTK,                               // Cout == 64: 256 x 64 tiles
+    CK_COUNT
+};
+ConvKernel conv_select(const ConvArgs& a, int dtype, bool stem);
+const char* conv_kernel_name(ConvKernel id);
 // in place: every 32-float K-tile of w [rows][K] (128 bytes) becomes [32 x bf16 hi | 32 x bf16 lo], hi = RNE(w), lo = RNE(w - hi)
 void launch_split_weights_x3(void* w, long rows, int K, hipStream_t st);
 // split activation layout -> plain fp32, in place (test taps of the IVOSW_F32X3 mode); nfloats % 32 == 0
@@ -122,7 +133,7 @@ struct Res2ChainArgs {
     const void* x;                     // NHWC [B,64,64,64]: the pooled stem output
     void* y;                           // y2: NHWC [B,64,64,256], or (y_s2) its even pixels, compactly [B,32,32,256]
     void* t1out;                       // NHWC [B,64,64,128]: res3's first 1x1 (+ BN + ReLU) applied to y2
-    const void* wstream;               // the tile's 528 weight fragments in consumption order (launch_res2_chain_pack)
+    const void* wstream;               // the tile's 520 weight fragments in consumption order (launch_res2_chain_pack)
     const void* zeros;                 // >= 256 B of device zeros
     int B, y_s2, rev;
     unsigned long long* ts;            // optional [grid][8] s_memtime stamps: start, first group landed, A0, block 0, block 1, block 2, end

@@ -1837,8 +1837,8 @@ void launch_res3_tail_x3(const void* t1, const void* x, const void* w2, const fl
     prof_end(tok, st);
 }
 
-static bool patch3x3_x3_ok(const ConvArgs& a) {              // res2's 3x3 in the split activation format; the shape only, never the batch
-    return a.x3 == 2 && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && !a.res && !a.x2 && a.Cin == 64 && a.Cout == 64 &&
+static bool patch3x3_x3_ok(const ConvArgs& a) {              // res2's 3x3 in the split activation format (asked for IVOSW_F32X3 alone); the shape only, never the batch
+    return a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && !a.res && !a.x2 && a.Cin == 64 && a.Cout == 64 &&
            a.H == a.W && a.H % 16 == 0 && a.Ho == a.H && a.Wo == a.W && a.zeros;
 }
 
@@ -1851,73 +1851,75 @@ static bool patch3x3_ok(const ConvArgs& a) {
     return a.H == 32 || a.H == 16 || a.H == 8;
 }
 
-template <typename T, bool STEM, bool X3 = false>
-static void launch_conv_t(const ConvArgs& a, hipStream_t st) {
+// Which instantiation runs a generic layer: a host function of the layer shape, the precision and the tunables (no device is asked).
+// Tile / ring selection.  8 waves (2 per SIMD) so one wave's LDS-DMA issue overlaps the other's MFMAs; 256-row tiles halve the DMA
+// instructions per MFMA.  Short K loops (1x1 convs on 64/128 channels) use a 2-deep ring.
+ConvKernel conv_select(const ConvArgs& a, int dtype, bool stem) {
+    if (stem) return CK_STEM;
     const int M = a.B * a.Ho * a.Wo;
-    if constexpr (STEM) {
-        const int grid = ((M + 127) / 128) * (a.Cout / 64);
-        hipLaunchKernelGGL((conv_igemm_kernel<T, 2, 2, 2, 1, true, X3>), dim3(grid), dim3(256), 0, st, a);
-    } else {
-        // Tile / ring selection.  8 waves (2 per SIMD) so one wave's LDS-DMA issue overlaps the other's MFMAs;
-        // 256-row tiles halve the DMA instructions per MFMA.  Short K loops (1x1 convs on 64/128 channels) use a
-        // 2-deep ring.
-        const int nk = (a.KH * a.KW * a.Cin + (a.x2 ? a.Cin2 : 0)) / (128 / (int)sizeof(T));
-        if (a.Cout % 128 == 0) {
-            const int grid = ((M + 255) / 256) * (a.Cout / 128);
-            static const int tune_nk = getenv("IVOSW_TUNE_NK") ? atoi(getenv("IVOSW_TUNE_NK")) : 8;
-            static const int use_ws = getenv("IVOSW_TUNE_WS") ? atoi(getenv("IVOSW_TUNE_WS")) : 1;
-            if constexpr (sizeof(T) == 2) {
-                if (patch3x3_ok(a) && tune_get("PATCH3", 1)) {
-                    const int g3 = ((M + 255) / 256) * (a.Cout / 128);      // H == 8: four frames per tile, the last one may be partial
-                    // PATCH_KEYXY = 1: swizzle key from the patch coordinates - PMC: bank-conflict share of this kernel 0.49 -> 0.013, LDS cycles
-                    // per launch halved - and yet 74.7 against 72.4 us per res5 launch on alternating runs of one box (profiles/r05_lds_conflicts.txt):
-                    // the kernel is bound by its MFMA issue at a power-limited clock, not by LDS time, so the row-index key stays the default
-                    const bool kxy = tune_get("PATCH_KEYXY", 0) != 0;
-                    // evaluation-size launches (round 5): fewer 4-frame tiles than PATCH_SMALL workgroups (res5 at < 128 frames per launch:
-                    // 13 x 4 = 52 workgroups for 50 frames) -> 2-frame tiles, twice the workgroups; same (slice, tap) K order per output
-                    // element, so a frame's result does not depend on which of the two ran (kernel trace at 100 units: this layer took
-                    // 4.4 x its per-frame time at batch 256)
-                    if (a.H == 8 && !kxy && g3 < tune_get("PATCH_SMALL", 128)) {
-                        const int g2 = ((M + 127) / 128) * (a.Cout / 128);
-                        hipLaunchKernelGGL((conv3x3_patch_kernel<2, 8, false>), dim3(g2), dim3(1024), 0, st, a);
-                        return;
-                    }
-                    if (a.H == 8 && kxy) hipLaunchKernelGGL((conv3x3_patch_kernel<4, 8>), dim3(g3), dim3(1024), 0, st, a);
-                    else if (a.H == 8) hipLaunchKernelGGL((conv3x3_patch_kernel<4, 8, false>), dim3(g3), dim3(1024), 0, st, a);
-                    else if (kxy) hipLaunchKernelGGL((conv3x3_patch_kernel<1, 16>), dim3(g3), dim3(1024), 0, st, a);
-                    else hipLaunchKernelGGL((conv3x3_patch_kernel<1, 16, false>), dim3(g3), dim3(1024), 0, st, a);
-                    return;
-                }
-            }
-            const int lw = tune_get("LW", 8);
-            // small launches (an evaluation-size batch: fewer 256 x 128 tiles than SMALL_GRID workgroups): 128 x 128 tiles, two
-            // workgroups per CU - twice the workgroups; same K order per output element, so a frame's result does not depend on it
-            if (nk > tune_nk && grid < tune_get("SMALL_GRID", 128)) {
-                const int g2 = ((M + 127) / 128) * (a.Cout / 128);
-                hipLaunchKernelGGL((conv_igemm_dma_kernel<T, 4, 2, 1, 2, 3, X3>), dim3(g2), dim3(512), 0, st, a);
-                return;
-            }
-
-            if (nk > tune_nk && use_ws && lw == 8) hipLaunchKernelGGL((conv_igemm_ws_kernel<T, 4, 2, 2, 2, 3, 8, X3>), dim3(grid), dim3(1024), 0, st, a);
-            else if (nk > tune_nk && use_ws) hipLaunchKernelGGL((conv_igemm_ws_kernel<T, 4, 2, 2, 2, 3, 4, X3>), dim3(grid), dim3(768), 0, st, a);
-            else if (nk > tune_nk) hipLaunchKernelGGL((conv_igemm_dma_kernel<T, 4, 2, 2, 2, 3, X3>), dim3(grid), dim3(512), 0, st, a);
-            else {  // K <= 128: bound by the output/residual stream -> 128x128 tiles, 64 KB LDS, 2 workgroups per CU
-                const int g2 = ((M + 127) / 128) * (a.Cout / 128);
-                hipLaunchKernelGGL((conv_igemm_dma_kernel<T, 4, 2, 1, 2, 2, X3>), dim3(g2), dim3(512), 0, st, a);
-            }
-        } else {  // Cout == 64 layers: 256 x 64 tile
-            if constexpr (X3) {
-                if (patch3x3_x3_ok(a) && tune_get("PATCH3_X3", 1)) {
-                    hipLaunchKernelGGL(conv3x3_patch_x3_kernel, dim3(a.B * (a.H / 16) * (a.W / 16)), dim3(512), 0, st, a);
-                    return;
-                }
-            }
-            const int grid = ((M + 255) / 256) * (a.Cout / 64);
-            static const int use_ws64 = getenv("IVOSW_TUNE_WS") ? atoi(getenv("IVOSW_TUNE_WS")) : 1;
-            if (nk >= 4 && use_ws64) hipLaunchKernelGGL((conv_igemm_ws_kernel<T, 4, 2, 2, 1, 3, 4, X3>), dim3(grid), dim3(768), 0, st, a);
-            else if (nk >= 2) hipLaunchKernelGGL((conv_igemm_dma_kernel<T, 4, 2, 2, 1, 3, X3>), dim3(grid), dim3(512), 0, st, a);
-            else hipLaunchKernelGGL((conv_igemm_dma_kernel<T, 4, 2, 2, 1, 2, X3>), dim3(grid), dim3(512), 0, st, a);
+    const int nk = (a.KH * a.KW * a.Cin + (a.x2 ? a.Cin2 : 0)) / (128 / (dtype == IVOSW_BF16 ? 2 : 4));
+    const bool ws = tune_get("WS", 1) != 0;          // the wave-specialised kernels (off: every wave loads and multiplies)
+    if (a.Cout % 128 == 0) {
+        const int grid = ((M + 255) / 256) * (a.Cout / 128);         // (the patch kernel at H == 8: four frames per tile, the last one may be partial)
+        if (dtype == IVOSW_BF16 && patch3x3_ok(a) && tune_get("PATCH3", 1)) {
+            // PATCH_KEYXY = 1: swizzle key from the patch coordinates - PMC: bank-conflict share of this kernel 0.49 -> 0.013, LDS cycles
+            // per launch halved - and yet 74.7 against 72.4 us per res5 launch on alternating runs of one box (profiles/r05_lds_conflicts.txt):
+            // the kernel is bound by its MFMA issue at a power-limited clock, not by LDS time, so the row-index key stays the default
+            const bool kxy = tune_get("PATCH_KEYXY", 0) != 0;
+            // evaluation-size launches (round 5): fewer 4-frame tiles than PATCH_SMALL workgroups (res5 at < 128 frames per launch:
+            // 13 x 4 = 52 workgroups for 50 frames) -> 2-frame tiles, twice the workgroups; same (slice, tap) K order per output
+            // element, so a frame's result does not depend on which of the two ran (kernel trace at 100 units: this layer took
+            // 4.4 x its per-frame time at batch 256)
+            if (a.H == 8 && !kxy && grid < tune_get("PATCH_SMALL", 128)) return CK_PATCH_2F;
+            if (a.H == 8) return kxy ? CK_PATCH_4F_KXY : CK_PATCH_4F;
+            return kxy ? CK_PATCH_KXY : CK_PATCH;
         }
+        const bool deep = nk > tune_get("NK", 8);
+        // small launches (an evaluation-size batch: fewer 256 x 128 tiles than SMALL_GRID workgroups): 128 x 128 tiles, two
+        // workgroups per CU - twice the workgroups; same K order per output element, so a frame's result does not depend on it
+        if (deep && grid < tune_get("SMALL_GRID", 128)) return CK_DMA_SMALL;
+        if (deep && ws) return tune_get("LW", 8) == 8 ? CK_WS_LW8 : CK_WS_LW4;
+        return deep ? CK_DMA : CK_DMA_SHORTK;        // K <= 128: bound by the output/residual stream -> 128x128 tiles, 64 KB LDS, 2 workgroups per CU
+    }
+    // Cout == 64 layers: 256 x 64 tile
+    if (dtype == IVOSW_F32X3 && patch3x3_x3_ok(a) && tune_get("PATCH3_X3", 1)) return CK_PATCH_X3;
+    if (nk >= 4 && ws) return CK_WS64;
+    return nk >= 2 ? CK_DMA64 : CK_DMA64_SHORTK;
+}
+
+// one name per id: the kernel's function name as a kernel trace prints it, cut at the first '<' or '('
+const char* conv_kernel_name(ConvKernel id) {
+    static const char* const names[CK_COUNT] = {
+        "conv_igemm_kernel", "conv3x3_patch_kernel", "conv3x3_patch_kernel", "conv3x3_patch_kernel", "conv3x3_patch_kernel", "conv3x3_patch_kernel",
+        "conv_igemm_dma_kernel", "conv_igemm_ws_kernel", "conv_igemm_ws_kernel", "conv_igemm_dma_kernel", "conv_igemm_dma_kernel",
+        "conv3x3_patch_x3_kernel", "conv_igemm_ws_kernel", "conv_igemm_dma_kernel", "conv_igemm_dma_kernel"};
+    return names[id];
+}
+
+// the launch of an id: its grid (M rows x Cout columns of tiles) and block.  (The bf16-only and split-only kernels are instantiated
+// for their precision alone: conv_select never hands their ids to another one.)
+template <typename T, bool X3>
+static void launch_conv_id(ConvKernel id, const ConvArgs& a, hipStream_t st) {
+    const int M = a.B * a.Ho * a.Wo;
+    auto tiles = [&](int rows, int cols) { return dim3(((M + rows - 1) / rows) * (a.Cout / cols)); };
+    constexpr bool B16 = sizeof(T) == 2;
+    switch (id) {
+    case CK_STEM: hipLaunchKernelGGL((conv_igemm_kernel<T, 2, 2, 2, 1, true, X3>), tiles(128, 64), dim3(256), 0, st, a); break;
+    case CK_PATCH_2F: if constexpr (B16) hipLaunchKernelGGL((conv3x3_patch_kernel<2, 8, false>), tiles(128, 128), dim3(1024), 0, st, a); break;
+    case CK_PATCH_4F_KXY: if constexpr (B16) hipLaunchKernelGGL((conv3x3_patch_kernel<4, 8>), tiles(256, 128), dim3(1024), 0, st, a); break;
+    case CK_PATCH_4F: if constexpr (B16) hipLaunchKernelGGL((conv3x3_patch_kernel<4, 8, false>), tiles(256, 128), dim3(1024), 0, st, a); break;
+    case CK_PATCH_KXY: if constexpr (B16) hipLaunchKernelGGL((conv3x3_patch_kernel<1, 16>), tiles(256, 128), dim3(1024), 0, st, a); break;
+    case CK_PATCH: if constexpr (B16) hipLaunchKernelGGL((conv3x3_patch_kernel<1, 16, false>), tiles(256, 128), dim3(1024), 0, st, a); break;
+    case CK_DMA_SMALL: hipLaunchKernelGGL((conv_igemm_dma_kernel<T, 4, 2, 1, 2, 3, X3>), tiles(128, 128), dim3(512), 0, st, a); break;
+    case CK_WS_LW8: hipLaunchKernelGGL((conv_igemm_ws_kernel<T, 4, 2, 2, 2, 3, 8, X3>), tiles(256, 128), dim3(1024), 0, st, a); break;
+    case CK_WS_LW4: hipLaunchKernelGGL((conv_igemm_ws_kernel<T, 4, 2, 2, 2, 3, 4, X3>), tiles(256, 128), dim3(768), 0, st, a); break;
+    case CK_DMA: hipLaunchKernelGGL((conv_igemm_dma_kernel<T, 4, 2, 2, 2, 3, X3>), tiles(256, 128), dim3(512), 0, st, a); break;
+    case CK_DMA_SHORTK: hipLaunchKernelGGL((conv_igemm_dma_kernel<T, 4, 2, 1, 2, 2, X3>), tiles(128, 128), dim3(512), 0, st, a); break;
+    case CK_PATCH_X3: if constexpr (X3) hipLaunchKernelGGL(conv3x3_patch_x3_kernel, dim3(a.B * (a.H / 16) * (a.W / 16)), dim3(512), 0, st, a); break;
+    case CK_WS64: hipLaunchKernelGGL((conv_igemm_ws_kernel<T, 4, 2, 2, 1, 3, 4, X3>), tiles(256, 64), dim3(768), 0, st, a); break;
+    case CK_DMA64: hipLaunchKernelGGL((conv_igemm_dma_kernel<T, 4, 2, 2, 1, 3, X3>), tiles(256, 64), dim3(512), 0, st, a); break;
+    case CK_DMA64_SHORTK: hipLaunchKernelGGL((conv_igemm_dma_kernel<T, 4, 2, 2, 1, 2, X3>), tiles(256, 64), dim3(512), 0, st, a); break;
+    case CK_COUNT: break;
     }
 }
 
@@ -2003,13 +2005,10 @@ void launch_conv(const ConvArgs& a_in, int dtype, bool stem, hipStream_t st) {
     }
     a.x3 = dtype == IVOSW_F32X3 ? 2 : 0;         // 2: activations in the split layout (every output; every input except the stem's ROI tile)
     void* tok = prof_begin(a, (dtype == IVOSW_BF16) ? 2 : 4, st);
-    if (dtype == IVOSW_BF16) {
-        if (stem) launch_conv_t<bf16_t, true>(a, st); else launch_conv_t<bf16_t, false>(a, st);
-    } else if (a.x3) {
-        if (stem) launch_conv_t<float, true, true>(a, st); else launch_conv_t<float, false, true>(a, st);
-    } else {
-        if (stem) launch_conv_t<float, true>(a, st); else launch_conv_t<float, false>(a, st);
-    }
+    const ConvKernel id = conv_select(a, dtype, stem);
+    if (dtype == IVOSW_BF16) launch_conv_id<bf16_t, false>(id, a, st);
+    else if (a.x3) launch_conv_id<float, true>(id, a, st);
+    else launch_conv_id<float, false>(id, a, st);
     prof_end(tok, st);
 }
 

@@ -677,8 +677,7 @@ bool res2_chain_ok(const Res2ChainArgs& a) { return a.x && a.y && a.t1out && a.w
 void launch_res2_chain(const Res2ChainArgs& a, hipStream_t st) {
     // persistent form (tunable R2C_PERSIST, default on): one workgroup per CU walks over its tiles (8 x 16 pixels each) with the weight ring
     // running across the tile boundaries and the next tile's p halo prefetched during block 2; R2C_GRID workgroups (0 = one per CU)
-    static int ncu = 0;
-    if (!ncu) { int dev = 0; hipDeviceProp_t pr; (void)hipGetDevice(&dev); ncu = hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256; }
+    const int ncu = cu_count_current_device();
     const int ntiles = a.B * 32;
     const bool persist = tune_get("R2C_PERSIST", 1) != 0;
     int gmax = tune_get("R2C_GRID", 0);

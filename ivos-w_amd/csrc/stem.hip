@@ -389,8 +389,7 @@ void launch_stem_pool_x3(const void* roi, const void* wsplit, const float* bias,
     d.B = B; d.H = 256; d.W = 256; d.Cin = 4; d.Ho = 128; d.Wo = 128; d.Cout = 64; d.KH = 7; d.KW = 7; d.stride = 2;
     void* tok = prof_begin(d, 4, st);
     const int ntiles = B * 64;
-    static int ncu = 0;
-    if (!ncu) { int dev = 0; hipDeviceProp_t pr; (void)hipGetDevice(&dev); ncu = hipGetDeviceProperties(&pr, dev) == hipSuccess && pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 256; }
+    const int ncu = cu_count_current_device();
     const int grid = ntiles < ncu ? ntiles : ncu;               // one workgroup per CU, persistent over the tiles
     hipLaunchKernelGGL(stem_pool_x3_kernel, dim3(grid), dim3(256), 0, st, static_cast<const float*>(roi), static_cast<const unsigned char*>(wsplit),
                        bias, static_cast<uint4*>(out), ntiles, rev);

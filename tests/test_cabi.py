@@ -77,6 +77,7 @@ csrc = os.path.join(os.path.dirname(L.LIB_PATH), "csrc")
 keys = sorted({k for f in os.listdir(csrc) if f.endswith((".hip", ".h", ".cpp"))
                for k in re.findall(r'tune_get\("([A-Z0-9_]+)"', open(os.path.join(csrc, f)).read())})
 assert len(keys) >= 40, len(keys)
+assert "NK" in keys and "WS" in keys, keys      # the generic conv selector's two switches are table keys like every other
 for i, k in enumerate(keys + ["CABI_TEST_%d" % j for j in range(40)]):
     assert lib.ivosw_tune_set(k.encode(), 7) == 0, (i, k)
 try:

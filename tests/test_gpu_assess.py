@@ -712,8 +712,8 @@ def test_res2_stage_kernel_is_bit_identical_to_the_per_block_kernels(dev, net16)
 def test_res2_chain_kernel_vs_the_stage_kernel_and_the_fp32_path(dev, net16, net32):
     """bf16 mode, round 6: res2 + res3's forwarded conv1 with the pointwise chains kept in registers (res2_chain.hip, tunable
     RES2_CHAIN=1, default): accumulator tiles re-used as MFMA B operands, residual / bias as MFMAs, every weight through one LDS
-    ring.  Summation orders differ from the stage kernel (RES2_CHAIN=0) and block 0's downsample term takes one more bf16
-    rounding, so the two are compared at the bf16 tolerance - and, which is what matters, the chain kernel must sit as close to
+    ring.  Summation orders differ from the stage kernel (RES2_CHAIN=0); nothing is rounded more often (block 0's downsample
+    term joins conv3 in one fp32 sum over K = 128, as there), so the two are compared at the bf16 tolerance - and, which is what matters, the chain kernel must sit as close to
     the fp32 path as the stage kernel does: full res2 tensor (the tap turns the even-pixel output off), res3 and the scores;
     edge masks (boxes on the frame border: the zero padding of every halo ring), an odd batch, a chunked batch."""
     from ivos_w_amd import _lib as L
@@ -1022,3 +1022,36 @@ def test_small_launch_wide_1x1_tiles_are_bit_identical(dev, net16):
             L.tune_set(b"WIDE_SMALL", 0)
         for a, b in zip(got[160], got[0]):
             assert torch.equal(a, b), B
+
+
+def test_ws_tunable_set_at_run_time_is_the_environment_switch(dev, net16):
+    """The generic conv selector's WS switch (conv.hip: the wave-specialised kernels or the ones whose every wave loads and multiplies) is a key of the tunables table like
+    every other: ivosw_tune_set("WS", 0) in this process gives, bit for bit, the scores of IVOSW_TUNE_WS=0 set in the environment of a
+    fresh one, and while it is set the schedule holds no wave-specialised launch (so the switch was really taken)."""
+    import subprocess
+    import sys
+    from ivos_w_amd import _lib as L
+    _, _, ttf, ttp = inputs(dev, 8, True)
+    want = net16(ttf, ttp).float().cpu().numpy().reshape(-1)
+    try:
+        L.tune_set(b"WS", 0)
+        got = net16(ttf, ttp).float().cpu().numpy().reshape(-1)
+        off = {k for _, k, _, _ in L.assess_describe(L.BF16, 256)}     # (at B = 8 every deep layer is a small launch on 128 x 128 tiles before WS is asked)
+    finally:
+        L.tune_set(b"WS", 1)
+    assert "conv_igemm_ws_kernel" not in off and "conv_igemm_ws_kernel" in {k for _, k, _, _ in L.assess_describe(L.BF16, 256)}
+    code = r"""
+import sys
+sys.path.insert(0, sys.argv[1])
+import numpy as np, torch
+from tests.test_gpu_assess import inputs, make_net
+dev = torch.device("cuda:0")
+_, _, ttf, ttp = inputs(dev, 8, True)
+print("SCORES", make_net(dev, "bf16")(ttf, ttp).float().cpu().numpy().reshape(-1).tobytes().hex())
+"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, "-c", code, root], capture_output=True, text=True, timeout=300, env=dict(os.environ, IVOSW_TUNE_WS="0"))
+    assert r.returncode == 0 and "SCORES" in r.stdout, r.stdout[-1000:] + r.stderr[-2000:]
+    child = np.frombuffer(bytes.fromhex(r.stdout.split("SCORES")[1].split()[0]), np.float32)
+    assert np.array_equal(got, child), np.abs(got - child).max()
+    np.testing.assert_allclose(got, want, rtol=BF16_SCORE_RTOL)
