@@ -2162,7 +2162,8 @@ bool bneck_wide_fusable(const BneckWideArgs& a) {
     // first block of res2 (stride 1): fc = [conv3 | downsample] along K, bc = bias sum, no residual
     if (a.ds) return a.fa && a.fb && a.fc && a.zeros && a.Cmid == 64 && a.Cin == 64 && a.H == 64 && a.W == 64 && tune_get("HALO64S_DS", 1) != 0;
     if (!a.fa || !a.fb || !a.fc || a.Cin != 4 * a.Cmid || a.H != a.W) return false;
-    // res5 (Cmid 512, 8x8 frames, two per workgroup) is instantiated and correct but NOT used: 8.7 MB of weights per
+    // res5 (Cmid 512, 8x8 frames, two per workgroup) is instantiated and correct (tests/test_gpu_bneck_kernels.py holds both forms to
+    // fp64, element by element) but NOT used: 8.7 MB of weights per
     // 128-pixel workgroup and only B/2 workgroups make it slower (240 us) than the three layer kernels (201 us)
     if (a.Cmid == 512 && a.H == 8) { const int f5 = tune_get("FUSE_WIDE5", 0); return f5 == 2 || (f5 == 1 && a.B % 2 == 0); }
     if (a.Cmid == 128 && a.H == 32) return a.zeros != nullptr && tune_get("FUSE_WIDE3", 1) != 0;
@@ -2238,14 +2239,15 @@ extern "C" int ivosw_bneck_wide_probe(const void* x, void* y, const void* wa, co
     hipStream_t st = as_stream(stream);
     char* f = static_cast<char*>(frag);
     const size_t n1 = (size_t)Cmid * Cin * 2, n2 = (size_t)Cmid * 9 * Cmid * 2;
-    launch_fragpack(wa, Cmid, Cin, f, st);
-    launch_fragpack(wb, Cmid, 9 * Cmid, f + n1, st);
-    launch_fragpack(wc, Cin, Cmid, f + n1 + n2, st);
     BneckWideArgs a{};
     a.x = x; a.y = y; a.fa = f; a.ba = ba; a.fb = f + n1; a.bb = bb; a.fc = f + n1 + n2; a.bc = bc;
     a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cmid = Cmid; a.ts = ts;
     a.zeros = f + 2 * n1 + n2;                      // the caller provides 256 zeroed bytes behind the three weight copies
-    IVOSW_REQUIRE(bneck_wide_fusable(a), "shape is not covered by the wide fused bottleneck kernel");
+    // refuse BEFORE the weight reordering: a refused call launches nothing and leaves `frag` as it was
+    IVOSW_REQUIRE(B > 0 && bneck_wide_fusable(a), "shape is not covered by the wide fused bottleneck kernel");
+    launch_fragpack(wa, Cmid, Cin, f, st);
+    launch_fragpack(wb, Cmid, 9 * Cmid, f + n1, st);
+    launch_fragpack(wc, Cin, Cmid, f + n1 + n2, st);
     launch_bneck_wide(a, st);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;

@@ -51,9 +51,7 @@ names = ["A k-loop", "t1 store", "B taps", "t2 store", "C up to the last store p
 for i, n in enumerate(names):
     print(f"{n:24s} {d[:, i].mean():9.0f} {np.percentile(d[:, i], 10):8.0f} {np.percentile(d[:, i], 90):8.0f}")
 print(f"{'total':24s} {(t[:, 6] - t[:, 0]).mean():9.0f}   (shader clocks per workgroup)")
-xf = x[:2].float().permute(0, 3, 1, 2)
-t1 = torch.relu(torch.nn.functional.conv2d(xf, wa.float()[:, :, None, None], ba)).to(torch.bfloat16).float()
-wb4 = wb.float().view(Cm, 3, 3, Cm).permute(0, 3, 1, 2)
-t2 = torch.relu(torch.nn.functional.conv2d(t1, wb4, bb, padding=1)).to(torch.bfloat16).float()
-ref = torch.relu(torch.nn.functional.conv2d(t2, wc.float()[:, :, None, None], bc) + xf).permute(0, 2, 3, 1)
-print(f"max rel err vs torch reference: {(y[:2].float() - ref).abs().max().item() / ref.abs().max().item():.2e}")
+# check two frames against the fp64 restatement of the block, with the bounds the GPU tests hold the kernels to
+from tests import bneck_ref  # noqa: E402
+cpu = lambda t: t.float().cpu()
+print(bneck_ref.report(cpu(y[:2]), (cpu(x[:2]),) + tuple(cpu(t) for t in (wa, ba, wb, bb, wc, bc))))
