@@ -425,14 +425,55 @@ __global__ __launch_bounds__(512) void bneck_wide_stage_kernel(BneckStageArgs s)
     }
 }
 
-// ---------------------------------------------------------------- halo variant: res3 (C = 128, 32x32 frames) and res2 (C = 64, 64x64)
+// ---------------------------------------------------------------- halo variants: a workgroup owns a TILE of the frame
 // Same dataflow (wave-private fragment-ordered weights, t1 / t2 in LDS, transposed MFMAs), but the frame does not fit
-// one workgroup: a workgroup owns a 16x16-pixel tile and phase A computes t1 on its 18x18 halo (352 rows = 11 pixel
-// tiles, zeros stored for halo pixels outside the frame, so phase B needs no padding logic).  With NCT = C/32 channel
-// tiles of t1 / t2 the 8 waves form NCT x NG groups (NG = 8/NCT = 2 | 4):
-//   phase A  wave = (channel tile w % NCT, pixel tiles of group w / NCT: 6,5 | 3,3,3,2 of the 11)
-//   phase B  wave = (channel tile, 8/NG pixel tiles), shifted rows hb + ky*18 + kx of the halo image
-//   phase C  (4C/32)/8 chunks x (8 channel tiles = 8 waves) x 8 pixel tiles, store pass as in the frame kernel
+// one workgroup - or, for a small res4 launch, one workgroup per frame does not fill the chip: a workgroup owns a
+// BTY x 16-pixel tile and phase A computes t1 on its (BTY + 2) x 18 halo (HR rows = NT pixel tiles, zeros stored for halo
+// pixels outside the frame, so phase B needs no padding logic).  With NCT = C/32 channel tiles of t1 / t2 the 8 waves form
+// NCT x NG groups (NG = 8/NCT = 4 | 2 | 1 for C = 64 | 128 | 256):
+//   phase A  wave = (channel tile w % NCT, the TPG pixel tiles of group w / NCT; where NG does not divide NT the last group
+//            has one tile less: 6,5 | 3,3,3,2 of the 11); x through a 3-slot LDS-DMA ring
+//   phase B  wave = (channel tile, PB of the BTY/2 output pixel tiles), 9 C/64 steps (tap, slice) of 4 k-steps on the shifted
+//            rows hb + ky*18 + kx of the halo image
+//   phase C  (4C/32)/8 chunks x (8 channel tiles = 8 waves) x BTY/2 pixel tiles, store pass as in the frame kernel
+// One body, bneck_halo_body.h, included by every entry; a form F names (C, BTY, HW), the switches that are not geometry, and its own LDS map:
+//   HaloTile16<64>, <128>, <128, true>   res2 / res3   16 x 16 tile, 18 x 18 halo = 324 rows, 11 pixel tiles   bneck_halo_kernel<C, WL>
+//   HaloTile8x128                        res3          8 x 16 tile,  10 x 18 halo = 180 rows,  6 pixel tiles   bneck_halo128s_kernel
+//   HalfFrame16                          res4          8 x 16 = half a frame, same halo and pixel tiles        bneck_half16_kernel
+// Per pixel the arithmetic and its order are the same in every form (and those of the frame kernel), so a result does not
+// depend on which of them ran it (bit-identical: tests).
+namespace {
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a pixel tile's LDS offset has to be an immediate
+template <int N, class Fn>
+__device__ __forceinline__ void for_tiles(Fn&& f) {
+    if constexpr (N > 0) {
+        for_tiles<N - 1>(f);
+        f(std::integral_constant<int, N - 1>{});
+    }
+}
+
+// Everything that follows from (C, tile rows, frame edge); the tile is 16 pixels wide, its halo raster 18.
+template <int C_, int BTY_, int HW_>
+struct HaloGeom {
+    static constexpr int C = C_, CIN = 4 * C, BTY = BTY_, BTX = 16, HTX = 18, HW = HW_;
+    static constexpr int HR = (BTY + 2) * HTX;       // halo rows: 324 | 180
+    static constexpr int NT = (HR + 31) / 32;        // pixel tiles of the halo: 11 | 6
+    static constexpr int MH = NT * 32;               // rows of a t1 slice: 352 | 192
+    static constexpr int NGA = (HR + 7) / 8;         // 1-KB row groups of an x K-tile: 41 | 23
+    static constexpr int NXG = (NGA + 7) / 8;        // ... per wave at most (wave, wave + 8, ...): 6 | 3
+    static constexpr int TPX = HW / BTX, TPF = (HW / BTY) * TPX;   // tiles per frame row / per frame (TPX = 1: a half-frame walk, x0 = 0)
+    static constexpr int NSL = C / 64, NCT = C / 32, NG = 8 / NCT;
+    static constexpr int TPG = (NT + NG - 1) / NG;   // pixel tiles per group in phase A (3 | 6)
+    static constexpr bool EVEN = TPG * NG == NT;     // false: the last group has one tile less (16-row tile: 11 tiles)
+    static constexpr int HA0 = (TPG + 1) / 2, HA1 = TPG - HA0;   // rolling halves in phase A
+    static constexpr int NPO = BTY * BTX / 32;       // output pixel tiles: 8 | 4 (phase C: per wave, in halves of NPO / 2)
+    static constexpr int PB = NPO / NG, HB = PB / 2; // pixel tiles per wave in phase B and per rolling half
+    static constexpr int NCH = (CIN / 32) / 8;       // output chunks of phase C
+    static constexpr int WB0_OFF = 0, WB1_OFF = 0;   // no LDS weight ring unless a form with WL lays one out
+    static_assert(NG >= 1 && NG * NCT == 8 && TPG * NG - NT >= 0 && TPG * NG - NT <= 1 && HA1 >= 1 && HB >= 1, "geometry");
+};
+
+// res3 (C = 128, 32x32 frames) and res2 (C = 64, 64x64), 16 x 16-pixel tile, ONE workgroup per CU.
 // LDS: [0, 125952) x ring (3 slots of 41 row groups) -> t1 (C/64 slices x 352 rows) -> t2 (C/64 x 256 rows); staging at 128 KB.
 // WL (round 5, C = 128): the weight fragments of phases A and B reach the waves THROUGH LDS - one LDS-DMA copy per workgroup, read by
 // the two waves that share a channel tile - instead of each wave streaming its own copy from L2 into registers.  A CU takes only
@@ -440,1020 +481,87 @@ __global__ __launch_bounds__(512) void bneck_wide_stage_kernel(BneckStageArgs s)
 // 14.6 k cycles; profiles/r05_gemm_tile_bench.txt), and 426 KB of the 1 855 KB a tile moves were second copies.  Same fragments,
 // same k order: bit-identical to WL = false.  Rings: phase A two 16-KB K-tiles in the (then idle) staging area; phase B two 32-KB
 // double steps in [t1 end, bias block) and the staging area, one workgroup barrier per double step.
-template <int C, bool WL = false>
-__global__ __launch_bounds__(512) void bneck_halo_kernel(BneckWideArgs p) {
-    constexpr int CIN = 4 * C, HW = (C == 128) ? 32 : 64, BT = 16, HT = 18, HR = HT * HT, MH = 352, NGA = 41;
-    static_assert(!WL || C == 128, "the LDS weight rings are laid out for C = 128");
-    constexpr int TPX = HW / BT, TPF = TPX * TPX;    // tiles per frame edge / per frame
-    constexpr int NSL = C / 64, NCT = C / 32, NG = 8 / NCT;
-    constexpr int TPG = (11 + NG - 1) / NG;          // pixel tiles per group in phase A (6 | 3), the last group has one less
-    constexpr int HA0 = (TPG + 1) / 2, HA1 = TPG - HA0;   // rolling halves in phase A
-    constexpr int PB = 8 / NG, HB = PB / 2;          // pixel tiles per wave in phase B and per rolling half (4,2 | 2,1)
-    constexpr int SLOT = NGA * 1024;                 // 41984 B per x K-tile
-    constexpr int T1S = MH * ROWB, T2S = 256 * ROWB; // slice sizes of the t1 / t2 images
-    constexpr int STG_OFF = 131072;
-    constexpr int BIAS_OFF = 3 * SLOT;               // ba | bb | bc as floats in the gap below the staging area instead of a global
+template <int C_, bool WL_>
+struct HaloTile16 : HaloGeom<C_, 16, (C_ == 128) ? 32 : 64> {
+    using G = HaloGeom<C_, 16, (C_ == 128) ? 32 : 64>;
+    static constexpr bool WL = WL_;
+    static constexpr bool ROWKEY = false;            // t1 is swizzled by the halo raster's column (round 5, see the t1 epilogue)
+    static constexpr bool REV = true;                // p.rev walks the tiles backwards (the tower's snake direction)
+    static constexpr bool TUNING = true;             // the ablation hooks (HALO_ABL builds, the YS2ABL debug bit) exist in this form only
+    static constexpr bool STAMPS = true;
+    static_assert(!WL || G::C == 128, "the LDS weight rings are laid out for C = 128");
+    static constexpr int SLOT = G::NGA * 1024;       // 41984 B per x K-tile
+    static constexpr int T1S = G::MH * ROWB, T2S = G::NPO * 32 * ROWB;   // slice sizes of the t1 / t2 images
+    static constexpr int STG_OFF = 131072;
+    static constexpr int BIAS_OFF = 3 * SLOT;        // ba | bb | bc as floats in the gap below the staging area instead of a global
                                                      // load at the head of every epilogue / chunk (measured neutral here: 248 vs 254 us
                                                      // within box variance; it mattered in the two-workgroup res2 kernel)
-    static_assert(BIAS_OFF + 6 * C * 4 <= STG_OFF, "bias block");
-    static_assert(3 * SLOT <= STG_OFF && NSL * T1S <= STG_OFF && 2 * SLOT + MH * ROWB <= WIDE_LDS && TPG * (NG - 1) + TPG - 1 == 11, "geometry");
-    __shared__ __attribute__((aligned(16))) unsigned char lds[WIDE_LDS];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lrow = lane & 31, lhalf = lane >> 5;
-    const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
-    const int L = p.rev ? (int)gridDim.x - 1 - xcd_remap(blockIdx.x, gridDim.x) : xcd_remap(blockIdx.x, gridDim.x);
-    const int b = L / TPF, tl = L - b * TPF;
-    const int y0 = (tl / TPX) * BT, x0 = (tl % TPX) * BT;
-    const bf16_t* X = static_cast<const bf16_t*>(p.x) + (size_t)b * HW * HW * CIN;
-    bf16_t* Y = static_cast<bf16_t*>(p.y) + (size_t)b * HW * HW * CIN;
-    const bf16_t* zeros = static_cast<const bf16_t*>(p.zeros);
-    const int ctw = wave % NCT, grp = wave / NCT;
-    if (tid < 2 * C) *reinterpret_cast<float*>(lds + BIAS_OFF + tid * 4) = tid < C ? p.ba[tid] : p.bb[tid - C];
-    if (tid < 4 * C) *reinterpret_cast<float*>(lds + BIAS_OFF + 2 * C * 4 + tid * 4) = p.bc[tid];      // visible after phase A's barriers
-    uint4 wn[4];                                     // first weight fragments of the next phase, requested one phase early
-    auto stamp = [&](int k) {
-        if (p.ts && tid == 0) p.ts[(size_t)blockIdx.x * 8 + k] = __builtin_amdgcn_s_memtime();
-    };
-    stamp(0);
-    // WL: double step d of phase B = steps 2d, 2d + 1 = 8 consecutive fragments (8 KB) of each of the 4 channel tiles -> ring slot d & 1
-    constexpr int WB0_OFF = NSL * T1S, WB1_OFF = STG_OFF;
+    static constexpr int LDS_BYTES = WIDE_LDS;
+    static constexpr int WB0_OFF = G::NSL * T1S, WB1_OFF = STG_OFF;      // WL: the two slots of phase B's weight ring
+    static_assert(BIAS_OFF + 6 * G::C * 4 <= STG_OFF, "bias block");
+    static_assert(3 * SLOT <= STG_OFF && G::NSL * T1S <= STG_OFF && 2 * SLOT + G::MH * ROWB <= WIDE_LDS && STG_OFF + 8 * 4096 <= LDS_BYTES, "LDS map");
     static_assert(!WL || (WB0_OFF + 32768 <= BIAS_OFF), "phase B weight ring");
-    auto wb_issue = [&](int d) {
-        unsigned char* slot = lds + ((d & 1) ? WB1_OFF : WB0_OFF);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int ct = wave >> 1, sub = (wave & 1) * 4 + j;
-            dma16(wfrag(p.fb, ct, 9 * C / 16, d * 8 + sub, lane), slot + (ct * 8 + sub) * 1024);
-        }
-    };
-    // (Tried: picking the residual of output chunk 0 out of the ring while its x K-tile is resident in phase A, to save
-    // re-reading half of x in phase C — 64 more live registers on top of phase A's 96 accumulator + 32 weight registers
-    // = 141 VGPR spills.  Dropped.)
+};
 
-    // ================================================================ phase A: t1 = relu(Wa x + ba) on the halo, K = CIN
-    {
-        constexpr int NK = CIN / 64;
-        f32x16 acc[TPG];
-#pragma unroll
-        for (int i = 0; i < TPG; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-        const int rsub = lane >> 3, cpos = lane & 7;
-        const int np = (NGA - wave + 7) / 8;         // row groups of this wave: wave, wave+8, ... (6 for wave 0, else 5)
-        const bf16_t* xsrc[6];
-        unsigned okmask = 0;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const int g = wave + 8 * i;
-            const int hr = g * 8 + rsub;
-            const int hy = hr / HT, hx = hr - hy * HT;
-            const int y = y0 - 1 + hy, x = x0 - 1 + hx;
-            const bool ok = g < NGA && hr < HR && y >= 0 && y < HW && x >= 0 && x < HW;
-            xsrc[i] = ok ? X + ((size_t)y * HW + x) * CIN + (cpos ^ ((hr >> 1) & 7)) * 8 : zeros;
-            okmask |= ok ? (1u << i) : 0u;
-        }
-        auto issue_x = [&](int kt) {
-            unsigned char* sb = lds + (kt % 3) * SLOT;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                const int g = wave + 8 * i;
-                if (g < NGA) dma16((HALO_ABL & 4) ? zeros : xsrc[i] + (((okmask >> i) & 1u) ? kt * 64 : 0), sb + g * 1024);
-            }
-        };
-        u32x4 wq[2][4];
-        auto load_w = [&](int kt, int set) {
-            if constexpr (WL) {
-                // K-tile kt of all NCT channel tiles = 16 fragments = 16 KB into ring slot kt & 1: wave w copies fragments (ct = w >> 1,
-                // ks = 2 (w & 1), + 1); the queue order W(kt + 1) | X(kt + 2) per iteration is that of the register path
-#pragma unroll
-                for (int j = 0; j < 2; ++j) {
-                    const int ct = wave >> 1, ks = (wave & 1) * 2 + j;
-                    dma16(wfrag(p.fa, ct, CIN / 16, kt * 4 + ks, lane), lds + STG_OFF + (kt & 1) * 16384 + (ct * 4 + ks) * 1024);
-                }
-            } else {
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks)
-                    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(wq[set][ks]) : "v"(wfrag(p.fa, ctw, CIN / 16, kt * 4 + ks, lane)) : "memory");
-            }
-        };
-        const int pt0 = grp * TPG;                   // pixel tiles pt0 .. ; the last group lacks its final tile (there are 11)
-        const bool full = grp + 1 < NG;
-        load_w(0, 0);
-        issue_x(0);
-        issue_x(1);
-        for (int kt2 = 0; kt2 < NK; kt2 += 2)
-#pragma unroll
-        for (int par = 0; par < 2; ++par) {
-            const int kt = kt2 + par;
-            if (kt + 1 < NK) wait_vmcnt_n(np); else wait_vmcnt<0>();   // only X(kt+1) is younger than W(kt)
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            if (kt + 1 < NK) load_w(kt + 1, par ^ 1);
-            if (kt + 2 < NK) issue_x(kt + 2);        // slot (kt+2) % 3 == slot of tile kt-1: done for every wave
-            const unsigned xb = lds_base + (kt % 3) * SLOT;
-            u32x4 pf[TPG];
-            // pixel tile pt0 + t of this lane = row (pt0 + t)*32 + lrow: one swizzle key for every t -> one address per k-step,
-            // the tile as an immediate offset
-            const unsigned xrow = xb + (pt0 * 32 + lrow) * ROWB;
-            auto rd = [&](int ks, int half) {
-                const unsigned a = xrow + (((2 * ks + lhalf) ^ ((lrow >> 1) & 7)) << 4);
-                auto one = [&](auto tc) {
-                    constexpr int t = decltype(tc)::value;
-                    if (t >= (half ? HA0 : 0) && t < (half ? TPG : HA0) && (t < TPG - 1 || full)) pf[t] = lds_read_b128_o<t * 4096>(a);
-                };
-                one(std::integral_constant<int, 0>{}); one(std::integral_constant<int, 1>{}); one(std::integral_constant<int, 2>{});
-                if constexpr (TPG == 6) { one(std::integral_constant<int, 3>{}); one(std::integral_constant<int, 4>{}); one(std::integral_constant<int, 5>{}); }
-                static_assert(TPG == 3 || TPG == 6, "tile offsets are immediates");
-            };
-            if constexpr (WL) {                      // this wave's four fragments of the K-tile: issued first, so every counted wait below covers them
-                const unsigned wa = lds_base + STG_OFF + (kt & 1) * 16384 + ctw * 4096 + lane * 16;
-                wq[par][0] = lds_read_b128_o<0>(wa); wq[par][1] = lds_read_b128_o<1024>(wa);
-                wq[par][2] = lds_read_b128_o<2048>(wa); wq[par][3] = lds_read_b128_o<3072>(wa);
-            }
-            rd(0, 0);
-            rd(0, 1);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const u32x4 w = wq[par][ks];
-                if (full) lgkm_wait<HA1>(); else lgkm_wait<HA1 - 1>();       // half 0 landed (half 1 may be in flight)
-#pragma unroll
-                for (int t = 0; t < HA0; ++t) acc[t] = mfma_bf16(w, pf[t], acc[t]);
-                if (ks < 3) rd(ks + 1, 0);
-                if (ks < 3) lgkm_wait<HA0>(); else lgkm_wait<0>();
-#pragma unroll
-                for (int t = HA0; t < TPG; ++t)
-                    if (t < TPG - 1 || full) acc[t] = mfma_bf16(w, pf[t], acc[t]);
-                if (ks < 3) rd(ks + 1, 1);
-            }
-        }
-        __builtin_amdgcn_s_barrier();                // the ring is dead: its space becomes t1
-        asm volatile("" ::: "memory");
-        stamp(1);
-        if constexpr (WL) {
-            // phase B's first two double steps go out under the t1 epilogue: slot 0 = [t1 end, bias block) - part of the x ring until
-            // the barrier above -, slot 1 = the staging area (phase A's weight ring, dead as well)
-            wb_issue(0);
-            wb_issue(1);
-        } else {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) wn[ks] = *wfrag(p.fb, ctw, 9 * C / 16, ks, lane);
-        }
-        float4 bq[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const float4*>(lds + BIAS_OFF + (ctw * 32 + 8 * g + 4 * lhalf) * 4);
-#pragma unroll
-        for (int i = 0; i < TPG; ++i) {
-            if (i == TPG - 1 && !full) break;
-            const int hr = (pt0 + i) * 32 + lrow;
-            const int hy = hr / HT, hx = hr - hy * HT;
-            const int y = y0 - 1 + hy, x = x0 - 1 + hx;
-            const bool in = y >= 0 && y < HW && x >= 0 && x < HW;
-            if (hr < HR) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    u32x2 pk;
-                    pk.x = relu2_bf16(acc[i][4 * g] + bq[g].x, acc[i][4 * g + 1] + bq[g].y) & (in ? 0xffffffffu : 0u);
-                    pk.y = relu2_bf16(acc[i][4 * g + 2] + bq[g].z, acc[i][4 * g + 3] + bq[g].w) & (in ? 0xffffffffu : 0u);
-                    // swizzle key from the COLUMN of the halo raster, not from the row index (round 5): phase B's 16-lane read groups are
-                    // {x .. x+3, x+12 .. x+15} of one raster line and {x+4 .. x+11} of the next - 16 consecutive columns, so (hx & 1, hx >> 1)
-                    // puts them on 16 different 16-byte slots (the line pitch 18 is even: a row's 128-byte half is its column's parity);
-                    // with (hr >> 1) & 7 two pairs of every group shared a slot (PMC: 32 % of the kernel's LDS cycles were conflicts)
-                    lds_write_b64(lds_base + (ctw >> 1) * T1S + hr * ROWB + ((((ctw & 1) * 4 + g) ^ ((hx >> 1) & 7)) << 4) + 8 * lhalf, pk);
-                }
-            }
-        }
-        lds_wait();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        stamp(2);
-    }
-
-    // ================================================================ phase B: t2 = relu(Wb (*) t1 + bb), 9 taps x NSL slices
-    {
-        constexpr int KSB = 9 * C / 16, NSTEP = 9 * NSL;
-        f32x16 acc[PB];
-#pragma unroll
-        for (int i = 0; i < PB; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-        int hb[PB];                                  // halo row of this lane's output pixel at tap (0,0)
-#pragma unroll
-        for (int i = 0; i < PB; ++i) {
-            const int q = (grp * PB + i) * 32 + lrow;
-            hb[i] = (q >> 4) * HT + (q & 15);
-        }
-        if constexpr (WL) {
-            // Software-pipelined form (round 5): the fragment reads of a k-step - 4 pixel tiles - are issued a WHOLE k-step ahead into the
-            // other of two register sets, and across the step boundary the next step's four weight fragments and first pixel fragments
-            // go out under the last k-step's MFMAs; the workgroup barrier of a double step sits in front of that prefetch.  (The
-            // half-step lookahead of the register-weights form left every step opening with ~10 exposed LDS reads.)
-            static_assert(!WL || (NSTEP % 2 == 0 && PB == 4), "double steps of four pixel tiles");
-            u32x4 pfb[2][PB], wcb[2][4];
-            auto rd_all = [&](int buf, int step, int ks) {
-                const int tap = step / NSL, sl = step - tap * NSL;
-                const unsigned key = (((lrow & 15) + tap % 3) >> 1) & 7;     // the raster column of every pixel tile of this lane: (q & 15) + kx
-                const unsigned x = ((2 * ks + lhalf) ^ key) << 4;
-#pragma unroll
-                for (int i = 0; i < PB; ++i) pfb[buf][i] = lds_read_b128(lds_base + sl * T1S + (hb[i] + (tap / 3) * HT + (tap % 3)) * ROWB + x);
-            };
-            auto rd_w = [&](int buf, int step) {
-                const unsigned wa = lds_base + (((step >> 1) & 1) ? WB1_OFF : WB0_OFF) + (ctw * 8 + (step & 1) * 4) * 1024 + lane * 16;
-                wcb[buf][0] = lds_read_b128_o<0>(wa); wcb[buf][1] = lds_read_b128_o<1024>(wa);
-                wcb[buf][2] = lds_read_b128_o<2048>(wa); wcb[buf][3] = lds_read_b128_o<3072>(wa);
-            };
-            // double step 0 has landed for this wave (double step 1's four pieces may be younger); the barrier publishes it
-            wait_vmcnt<4>();
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            rd_w(0, 0);
-            rd_all(0, 0, 0);
-#pragma unroll 1
-            for (int d = 0; d < NSTEP / 2; ++d) {
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int step = 2 * d + h;
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) {
-                        if (ks < 3) {
-                            rd_all((ks + 1) & 1, step, ks + 1);
-                            lgkm_wait<PB>();
-                        } else if (step + 1 < NSTEP) {
-                            if (h == 1) {
-                                // double step d + 1: this wave's pieces have landed (nothing younger is in flight), the barrier publishes
-                                // them and says every wave has read the last weights of double step d: its slot takes d + 2
-                                wait_vmcnt<0>();
-                                __builtin_amdgcn_s_barrier();
-                                asm volatile("" ::: "memory");
-                                if (d + 2 < NSTEP / 2) wb_issue(d + 2);
-                            }
-                            rd_w(h ^ 1, step + 1);
-                            rd_all(0, step + 1, 0);
-                            lgkm_wait<PB + 4>();
-                        } else {
-                            lgkm_wait<0>();
-                        }
-#pragma unroll
-                        for (int i = 0; i < PB; ++i) acc[i] = mfma_bf16(wcb[h][ks], pfb[ks & 1][i], acc[i]);
-                    }
-                }
-            }
-        } else {
-#pragma unroll 1
-        for (int step = 0; step < NSTEP; ++step) {   // step = tap * NSL + slice
-            const int tap = step / NSL, sl = step - tap * NSL;
-            u32x4 wc[4];
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) wc[ks] = as_u32x4(wn[ks]);
-            if (step + 1 < NSTEP) {
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) wn[ks] = *wfrag(p.fb, ctw, KSB, (step + 1) * 4 + ks, lane);
-            }
-            unsigned rowa[PB];
-#pragma unroll
-            for (int i = 0; i < PB; ++i) {
-                const int hr = hb[i] + (tap / 3) * HT + (tap % 3);
-                rowa[i] = lds_base + sl * T1S + hr * ROWB;
-            }
-            const unsigned rkey = (((lrow & 15) + tap % 3) >> 1) & 7;    // the raster column of every pixel tile of this lane: (q & 15) + kx
-            u32x4 pf[PB];
-            auto rd = [&](int ks, int half) {
-                const int ch = 2 * ks + lhalf;
-#pragma unroll
-                for (int i = 0; i < HB; ++i) pf[half * HB + i] = lds_read_b128(rowa[half * HB + i] + ((ch ^ rkey) << 4));
-            };
-            rd(0, 0);
-            rd(0, 1);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                lgkm_wait<HB>();
-#pragma unroll
-                for (int i = 0; i < HB; ++i) acc[i] = mfma_bf16(wc[ks], pf[i], acc[i]);
-                if (ks < 3) rd(ks + 1, 0);
-                if (ks < 3) lgkm_wait<HB>(); else lgkm_wait<0>();
-#pragma unroll
-                for (int i = HB; i < PB; ++i) acc[i] = mfma_bf16(wc[ks], pf[i], acc[i]);
-                if (ks < 3) rd(ks + 1, 1);
-            }
-        }
-        }
-        __builtin_amdgcn_s_barrier();                // every wave is done reading t1: t2 takes its place
-        asm volatile("" ::: "memory");
-        stamp(3);
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) wn[ks] = *wfrag(p.fc, wave, C / 16, ks, lane);
-        float4 bq[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const float4*>(lds + BIAS_OFF + (C + ctw * 32 + 8 * g + 4 * lhalf) * 4);
-#pragma unroll
-        for (int i = 0; i < PB; ++i) {
-            const int px = (grp * PB + i) * 32 + lrow;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                u32x2 pk;
-                pk.x = relu2_bf16(acc[i][4 * g] + bq[g].x, acc[i][4 * g + 1] + bq[g].y);
-                pk.y = relu2_bf16(acc[i][4 * g + 2] + bq[g].z, acc[i][4 * g + 3] + bq[g].w);
-                lds_write_b64(lds_base + (ctw >> 1) * T2S + px * ROWB + ((((ctw & 1) * 4 + g) ^ ((px >> 1) & 7)) << 4) + 8 * lhalf, pk);
-            }
-        }
-        lds_wait();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        stamp(4);
-    }
-
-    // ================================================================ phase C: y = relu(Wc t2 + bc + x), chunks of 8 channel tiles
-    {
-        constexpr int KSC = C / 16, NCH = (CIN / 32) / 8, NSTEP = NCH * NSL;
-        f32x16 acc[8];
-        float* stg = reinterpret_cast<float*>(lds + STG_OFF + wave * 4096);
-        const int u = lane & 3, prr = lane >> 2;
-        auto pix = [&](int q) { return (size_t)((y0 + (q >> 4)) * HW + x0 + (q & 15)) * CIN; };   // tile pixel q -> frame offset
-#pragma unroll 1
-        for (int chunk = 0; chunk < NCH; ++chunk) {
-            const int ct = chunk * 8 + wave;
-            const size_t cofs = (size_t)ct * 32 + 8 * u;
-            uint4 rr[2];                             // residual of the first pixel tile: in flight under the chunk's MFMAs
-#pragma unroll
-            for (int it = 0; it < 2; ++it) rr[it] = (HALO_ABL & 1) ? make_uint4(0, 0, 0, 0) : *reinterpret_cast<const uint4*>(X + pix(it * 16 + prr) + cofs);
-            {
-                float4 bq[4];
-#pragma unroll
-                for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const float4*>(lds + BIAS_OFF + (2 * C + ct * 32 + 8 * g + 4 * lhalf) * 4);
-#pragma unroll
-                for (int i = 0; i < 8; ++i)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        acc[i][4 * g] = bq[g].x; acc[i][4 * g + 1] = bq[g].y; acc[i][4 * g + 2] = bq[g].z; acc[i][4 * g + 3] = bq[g].w;
-                    }
-            }
-#pragma unroll 1
-            for (int sl = 0; sl < NSL; ++sl) {
-                u32x4 wc[4];
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) wc[ks] = as_u32x4(wn[ks]);
-                const int nxt = chunk * NSL + sl + 1;
-                if (nxt < NSTEP) {
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) wn[ks] = *wfrag(p.fc, (nxt / NSL) * 8 + wave, KSC, (nxt % NSL) * 4 + ks, lane);
-                }
-                const unsigned tb = lds_base + sl * T2S;
-                u32x4 pf[8];
-                const unsigned trow = tb + lrow * ROWB;
-                auto rd = [&](int ks, int half) {
-                    const unsigned a = trow + (((2 * ks + lhalf) ^ ((lrow >> 1) & 7)) << 4);
-                    if (half == 0) { pf[0] = lds_read_b128_o<0>(a); pf[1] = lds_read_b128_o<4096>(a); pf[2] = lds_read_b128_o<8192>(a); pf[3] = lds_read_b128_o<12288>(a); }
-                    else { pf[4] = lds_read_b128_o<16384>(a); pf[5] = lds_read_b128_o<20480>(a); pf[6] = lds_read_b128_o<24576>(a); pf[7] = lds_read_b128_o<28672>(a); }
-                };
-                rd(0, 0);
-                rd(0, 1);
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    lgkm_wait<4>();
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) acc[i] = mfma_bf16(wc[ks], pf[i], acc[i]);
-                    if (ks < 3) rd(ks + 1, 0);
-                    if (ks < 3) lgkm_wait<4>(); else lgkm_wait<0>();
-#pragma unroll
-                    for (int i = 4; i < 8; ++i) acc[i] = mfma_bf16(wc[ks], pf[i], acc[i]);
-                    if (ks < 3) rd(ks + 1, 1);
-                }
-            }
-            if (chunk == NCH - 1) stamp(5);
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int slot = (2 * g + lhalf) ^ (lrow & 7);
-                    *reinterpret_cast<float4*>(stg + lrow * 32 + slot * 4) = make_float4(acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]);
-                }
-                uint4 rn[2];
-                if (i < 7) {
-#pragma unroll
-                    for (int it = 0; it < 2; ++it) rn[it] = (HALO_ABL & 1) ? make_uint4(0, 0, 0, 0) : *reinterpret_cast<const uint4*>(X + pix((i + 1) * 32 + it * 16 + prr) + cofs);
-                }
-#pragma unroll
-                for (int it = 0; it < 2; ++it) {
-                    const int pr = it * 16 + prr;
-                    const float4 v0 = *reinterpret_cast<const float4*>(stg + pr * 32 + (((2 * u) ^ (pr & 7)) << 2));
-                    const float4 v1 = *reinterpret_cast<const float4*>(stg + pr * 32 + (((2 * u + 1) ^ (pr & 7)) << 2));
-                    const unsigned w4[4] = {rr[it].x, rr[it].y, rr[it].z, rr[it].w};
-                    const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                    unsigned pk[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        pk[k] = relu2_bf16(v[2 * k] + __uint_as_float(w4[k] << 16), v[2 * k + 1] + __uint_as_float(w4[k] & 0xffff0000u));
-                    if ((HALO_ABL & 2) && pk[0] != 0x12345678u) continue;
-                    if (ABL(p.debug, 16) && ((((i * 32 + pr) >> 4) | (i * 32 + pr)) & 1)) continue;      // ablation YS2ABL: even pixels only (see bneck_wide_body)
-                    *reinterpret_cast<uint4*>(Y + pix(i * 32 + pr) + cofs) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-                }
-                if (i < 7) { rr[0] = rn[0]; rr[1] = rn[1]; }
-            }
-        }
-        stamp(6);
-    }
-}
-
-// ---------------------------------------------------------------- res3, small tile: two workgroups per CU
-// bneck_halo_kernel<128> above runs ONE workgroup per CU: its memory phases (A: 360 KB x halo in, C: residual in / y out) and
-// its MFMA-bound phase B alternate (31 k + 27 k + 27 k cycles per tile) instead of overlapping.  Same dataflow on an 8 x 16-pixel
-// tile (10 x 18 halo = 180 rows = 6 pixel tiles): 75 KB of LDS and <= 128 VGPRs, so two workgroups share a CU and one sits in
-// the matrix cores while the other waits on memory (what bneck_halo64s_kernel does for res2).
-//   phase A  wave = (channel tile w & 3, pixel tiles 3 g .. 3 g + 2 of the 6 with g = w >> 2); x through a 3-slot LDS-DMA ring
-//   phase B  wave = (channel tile w & 3, pixel tiles 2 g, 2 g + 1 of the 4 output tiles), 18 steps (tap, slice) of 4 k-steps
-//   phase C  2 chunks x (8 channel tiles = 8 waves) x 4 pixel tiles, store pass through the per-wave staging tile
+// res3, small tile: two workgroups per CU.  HaloTile16<128> runs ONE workgroup per CU: its memory phases (A: 360 KB x halo in,
+// C: residual in / y out) and its MFMA-bound phase B alternate (31 k + 27 k + 27 k cycles per tile) instead of overlapping.  On an
+// 8 x 16-pixel tile: 75 KB of LDS and <= 128 VGPRs (__launch_bounds__(512, 4) on the entry), so two workgroups share a CU and one
+// sits in the matrix cores while the other waits on memory (what bneck_halo64s_kernel does for res2).
 // LDS: [0, 73728) ring (3 x 24 KB) -> t1 (2 slices x 192 rows) [0, 49152) -> t2 (2 x 128 rows) [0, 32768) | staging [32768, 65536);
-//      [73728, 76800) biases.  Per pixel the arithmetic and its order are those of bneck_halo_kernel<128> (bit-identical output).
+//      [73728, 76800) biases.
 // MEASURED SLOWER and therefore off by default (tunable HALO128S=1 selects it; tests keep it bit-identical): 272 against 230 us per
 // block at B = 256 (tower 3.73 against 3.54 ms).  What works for res2 does not carry over: with C = 128 every wave re-streams ~1 MB of
 // weight fragments per tile from L2 through the texture cache (phase B alone 590 KB) - per 128 pixels now instead of per 256 -
 // which is ~16 k cache accesses per tile against ~19 k cycles of MFMA issue, the halo grows from 1.27 x to 1.41 x of the tile, and
 // the 128-VGPR budget of two workgroups per CU costs 31 spilled registers.
-__global__ __launch_bounds__(512, 4) void bneck_halo128s_kernel(BneckWideArgs p) {
-    constexpr int C = 128, CIN = 512, HW = 32, BTY = 8, BTX = 16, HTX = 18, HR = 180, MH = 192, NGA = 23;
-    constexpr int TPX = HW / BTX, TPF = (HW / BTY) * TPX;          // 2 tiles across, 8 per frame
-    constexpr int NSL = 2, NCT = 4, TPG = 3;
-    constexpr int SLOT = 24576;
-    constexpr int T1S = MH * ROWB, T2S = 128 * ROWB;
-    constexpr int STG_OFF = 32768, BIAS_OFF = 3 * SLOT, LDS_BYTES = BIAS_OFF + 6 * C * 4;       // 76800
-    static_assert(NSL * T1S <= 3 * SLOT && NSL * T2S <= STG_OFF && STG_OFF + 8 * 4096 <= 3 * SLOT && 2 * LDS_BYTES <= WIDE_LDS, "LDS map");
-    __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lrow = lane & 31, lhalf = lane >> 5;
-    const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
-    const int L = xcd_remap(blockIdx.x, gridDim.x);
-    const int b = L / TPF, tl = L - b * TPF;
-    const int y0 = (tl / TPX) * BTY, x0 = (tl % TPX) * BTX;
-    const bf16_t* X = static_cast<const bf16_t*>(p.x) + (size_t)b * HW * HW * CIN;
-    bf16_t* Y = static_cast<bf16_t*>(p.y) + (size_t)b * HW * HW * CIN;
-    const bf16_t* zeros = static_cast<const bf16_t*>(p.zeros);
-    const int ctw = wave & 3, grp = wave >> 2;
-    if (tid < 2 * C) *reinterpret_cast<float*>(lds + BIAS_OFF + tid * 4) = tid < C ? p.ba[tid] : p.bb[tid - C];
-    *reinterpret_cast<float*>(lds + BIAS_OFF + 2 * C * 4 + tid * 4) = p.bc[tid];             // 512 threads, 512 channels; visible after phase A's barriers
-    uint4 wn[4];                                     // first weight fragments of the next phase, requested one phase early
-    auto stamp = [&](int k) {
-        if (p.ts && tid == 0) p.ts[(size_t)blockIdx.x * 8 + k] = __builtin_amdgcn_s_memtime();
-    };
-    stamp(0);
+struct HaloTile8x128 : HaloGeom<128, 8, 32> {
+    static constexpr bool WL = false;
+    static constexpr bool ROWKEY = true;             // t1 still swizzled by the ROW index, on the write and on phase B's read: the column
+                                                     // key of round 5 was never carried over to this form.  Inconsistent with the other
+                                                     // two, but correct, and changing it would change this form's LDS conflicts: left.
+    static constexpr bool REV = false;
+    static constexpr bool TUNING = false;
+    static constexpr bool STAMPS = true;
+    static constexpr int SLOT = 24576;
+    static constexpr int T1S = MH * ROWB, T2S = NPO * 32 * ROWB;
+    static constexpr int STG_OFF = 32768, BIAS_OFF = 3 * SLOT, LDS_BYTES = BIAS_OFF + 6 * C * 4;       // 76800
+    static_assert(NGA * 1024 <= SLOT && NSL * T1S <= 3 * SLOT && NSL * T2S <= STG_OFF && STG_OFF + 8 * 4096 <= 3 * SLOT && 2 * LDS_BYTES <= WIDE_LDS, "LDS map");
+};
 
-    // ================================================================ phase A: t1 = relu(Wa x + ba) on the halo, K = CIN
-    {
-        constexpr int NK = CIN / 64;
-        f32x16 acc[TPG];
-#pragma unroll
-        for (int i = 0; i < TPG; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-        const int rsub = lane >> 3, cpos = lane & 7;
-        const int np = (NGA - wave + 7) / 8;         // row groups of this wave: wave, wave + 8, wave + 16 (< 23)
-        const bf16_t* xsrc[3];
-        unsigned okmask = 0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const int g = wave + 8 * i;
-            const int hr = g * 8 + rsub;
-            const int hy = hr / HTX, hx = hr - hy * HTX;
-            const int y = y0 - 1 + hy, x = x0 - 1 + hx;
-            const bool ok = g < NGA && hr < HR && y >= 0 && y < HW && x >= 0 && x < HW;
-            xsrc[i] = ok ? X + ((size_t)y * HW + x) * CIN + (cpos ^ ((hr >> 1) & 7)) * 8 : zeros;
-            okmask |= ok ? (1u << i) : 0u;
-        }
-        auto issue_x = [&](int kt) {
-            unsigned char* sb = lds + (kt % 3) * SLOT;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const int g = wave + 8 * i;
-                if (g < NGA) dma16(xsrc[i] + (((okmask >> i) & 1u) ? kt * 64 : 0), sb + g * 1024);
-            }
-        };
-        u32x4 wq[2][4];
-        auto load_w = [&](int kt, int set) {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(wq[set][ks]) : "v"(wfrag(p.fa, ctw, CIN / 16, kt * 4 + ks, lane)) : "memory");
-        };
-        const int pt0 = grp * TPG;
-        load_w(0, 0);
-        issue_x(0);
-        issue_x(1);
-        for (int kt2 = 0; kt2 < NK; kt2 += 2)
-#pragma unroll
-        for (int par = 0; par < 2; ++par) {
-            const int kt = kt2 + par;
-            if (kt + 1 < NK) wait_vmcnt_n(np); else wait_vmcnt<0>();   // only X(kt+1) is younger than W(kt)
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            if (kt + 1 < NK) load_w(kt + 1, par ^ 1);
-            if (kt + 2 < NK) issue_x(kt + 2);        // slot (kt+2) % 3 == slot of tile kt-1: done for every wave
-            const unsigned xb = lds_base + (kt % 3) * SLOT;
-            u32x4 pf[TPG];
-            const unsigned xrow = xb + (pt0 * 32 + lrow) * ROWB;
-            auto rd = [&](int ks, int half) {
-                const unsigned a = xrow + (((2 * ks + lhalf) ^ ((lrow >> 1) & 7)) << 4);
-                if (half == 0) { pf[0] = lds_read_b128_o<0>(a); pf[1] = lds_read_b128_o<4096>(a); }
-                else pf[2] = lds_read_b128_o<8192>(a);
-            };
-            rd(0, 0);
-            rd(0, 1);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const u32x4 w = wq[par][ks];
-                lgkm_wait<1>();                      // half 0 landed (half 1 may be in flight)
-                acc[0] = mfma_bf16(w, pf[0], acc[0]);
-                acc[1] = mfma_bf16(w, pf[1], acc[1]);
-                if (ks < 3) rd(ks + 1, 0);
-                if (ks < 3) lgkm_wait<2>(); else lgkm_wait<0>();
-                acc[2] = mfma_bf16(w, pf[2], acc[2]);
-                if (ks < 3) rd(ks + 1, 1);
-            }
-        }
-        __builtin_amdgcn_s_barrier();                // the ring is dead: its space becomes t1
-        asm volatile("" ::: "memory");
-        stamp(1);
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) wn[ks] = *wfrag(p.fb, ctw, 9 * C / 16, ks, lane);
-        float4 bq[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const float4*>(lds + BIAS_OFF + (ctw * 32 + 8 * g + 4 * lhalf) * 4);
-#pragma unroll
-        for (int i = 0; i < TPG; ++i) {
-            const int hr = (pt0 + i) * 32 + lrow;
-            const int hy = hr / HTX, hx = hr - hy * HTX;
-            const int y = y0 - 1 + hy, x = x0 - 1 + hx;
-            const bool in = y >= 0 && y < HW && x >= 0 && x < HW;
-            if (hr < HR) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    u32x2 pk;
-                    pk.x = relu2_bf16(acc[i][4 * g] + bq[g].x, acc[i][4 * g + 1] + bq[g].y) & (in ? 0xffffffffu : 0u);
-                    pk.y = relu2_bf16(acc[i][4 * g + 2] + bq[g].z, acc[i][4 * g + 3] + bq[g].w) & (in ? 0xffffffffu : 0u);
-                    lds_write_b64(lds_base + (ctw >> 1) * T1S + hr * ROWB + ((((ctw & 1) * 4 + g) ^ ((hr >> 1) & 7)) << 4) + 8 * lhalf, pk);
-                }
-            }
-        }
-        lds_wait();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        stamp(2);
-    }
-
-    // ================================================================ phase B: t2 = relu(Wb (*) t1 + bb), 9 taps x NSL slices
-    {
-        constexpr int KSB = 9 * C / 16, NSTEP = 9 * NSL;
-        f32x16 acc[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-        int hb[2];                                   // halo row of this lane's output pixel at tap (0,0)
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int q = (grp * 2 + i) * 32 + lrow;
-            hb[i] = (q >> 4) * HTX + (q & 15);
-        }
-#pragma unroll 1
-        for (int step = 0; step < NSTEP; ++step) {   // step = tap * NSL + slice
-            const int tap = step / NSL, sl = step - tap * NSL;
-            u32x4 wc[4];
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) wc[ks] = as_u32x4(wn[ks]);
-            if (step + 1 < NSTEP) {
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) wn[ks] = *wfrag(p.fb, ctw, KSB, (step + 1) * 4 + ks, lane);
-            }
-            unsigned rowa[2], rkey[2];
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const int hr = hb[i] + (tap / 3) * HTX + (tap % 3);
-                rowa[i] = lds_base + sl * T1S + hr * ROWB;
-                rkey[i] = (hr >> 1) & 7;
-            }
-            u32x4 pf[2];
-            auto rd = [&](int ks, int half) {
-                const int ch = 2 * ks + lhalf;
-                pf[half] = lds_read_b128(rowa[half] + ((ch ^ rkey[half]) << 4));
-            };
-            rd(0, 0);
-            rd(0, 1);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                lgkm_wait<1>();
-                acc[0] = mfma_bf16(wc[ks], pf[0], acc[0]);
-                if (ks < 3) rd(ks + 1, 0);
-                if (ks < 3) lgkm_wait<1>(); else lgkm_wait<0>();
-                acc[1] = mfma_bf16(wc[ks], pf[1], acc[1]);
-                if (ks < 3) rd(ks + 1, 1);
-            }
-        }
-        __builtin_amdgcn_s_barrier();                // every wave is done reading t1: t2 takes its place
-        asm volatile("" ::: "memory");
-        stamp(3);
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) wn[ks] = *wfrag(p.fc, wave, C / 16, ks, lane);
-        float4 bq[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const float4*>(lds + BIAS_OFF + (C + ctw * 32 + 8 * g + 4 * lhalf) * 4);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int px = (grp * 2 + i) * 32 + lrow;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                u32x2 pk;
-                pk.x = relu2_bf16(acc[i][4 * g] + bq[g].x, acc[i][4 * g + 1] + bq[g].y);
-                pk.y = relu2_bf16(acc[i][4 * g + 2] + bq[g].z, acc[i][4 * g + 3] + bq[g].w);
-                lds_write_b64(lds_base + (ctw >> 1) * T2S + px * ROWB + ((((ctw & 1) * 4 + g) ^ ((px >> 1) & 7)) << 4) + 8 * lhalf, pk);
-            }
-        }
-        lds_wait();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        stamp(4);
-    }
-
-    // ================================================================ phase C: y = relu(Wc t2 + bc + x), 2 chunks of 8 channel tiles
-    {
-        constexpr int KSC = C / 16, NCH = (CIN / 32) / 8, NSTEP = NCH * NSL;
-        f32x16 acc[4];
-        float* stg = reinterpret_cast<float*>(lds + STG_OFF + wave * 4096);
-        const int u = lane & 3, prr = lane >> 2;
-        auto pix = [&](int q) { return (size_t)((y0 + (q >> 4)) * HW + x0 + (q & 15)) * CIN; };   // tile pixel q -> frame offset
-#pragma unroll 1
-        for (int chunk = 0; chunk < NCH; ++chunk) {
-            const int ct = chunk * 8 + wave;
-            const size_t cofs = (size_t)ct * 32 + 8 * u;
-            uint4 rr[2];                             // residual of the first pixel tile: in flight under the chunk's MFMAs
-#pragma unroll
-            for (int it = 0; it < 2; ++it) rr[it] = *reinterpret_cast<const uint4*>(X + pix(it * 16 + prr) + cofs);
-            {
-                float4 bq[4];
-#pragma unroll
-                for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const float4*>(lds + BIAS_OFF + (2 * C + ct * 32 + 8 * g + 4 * lhalf) * 4);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        acc[i][4 * g] = bq[g].x; acc[i][4 * g + 1] = bq[g].y; acc[i][4 * g + 2] = bq[g].z; acc[i][4 * g + 3] = bq[g].w;
-                    }
-            }
-#pragma unroll 1
-            for (int sl = 0; sl < NSL; ++sl) {
-                u32x4 wc[4];
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) wc[ks] = as_u32x4(wn[ks]);
-                const int nxt = chunk * NSL + sl + 1;
-                if (nxt < NSTEP) {
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) wn[ks] = *wfrag(p.fc, (nxt / NSL) * 8 + wave, KSC, (nxt % NSL) * 4 + ks, lane);
-                }
-                const unsigned tb = lds_base + sl * T2S;
-                u32x4 pf[4];
-                const unsigned trow = tb + lrow * ROWB;
-                auto rd = [&](int ks, int half) {
-                    const unsigned a = trow + (((2 * ks + lhalf) ^ ((lrow >> 1) & 7)) << 4);
-                    if (half == 0) { pf[0] = lds_read_b128_o<0>(a); pf[1] = lds_read_b128_o<4096>(a); }
-                    else { pf[2] = lds_read_b128_o<8192>(a); pf[3] = lds_read_b128_o<12288>(a); }
-                };
-                rd(0, 0);
-                rd(0, 1);
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    lgkm_wait<2>();
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) acc[i] = mfma_bf16(wc[ks], pf[i], acc[i]);
-                    if (ks < 3) rd(ks + 1, 0);
-                    if (ks < 3) lgkm_wait<2>(); else lgkm_wait<0>();
-#pragma unroll
-                    for (int i = 2; i < 4; ++i) acc[i] = mfma_bf16(wc[ks], pf[i], acc[i]);
-                    if (ks < 3) rd(ks + 1, 1);
-                }
-            }
-            if (chunk == NCH - 1) stamp(5);
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int slot = (2 * g + lhalf) ^ (lrow & 7);
-                    *reinterpret_cast<float4*>(stg + lrow * 32 + slot * 4) = make_float4(acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]);
-                }
-                uint4 rn[2];
-                if (i < 3) {
-#pragma unroll
-                    for (int it = 0; it < 2; ++it) rn[it] = *reinterpret_cast<const uint4*>(X + pix((i + 1) * 32 + it * 16 + prr) + cofs);
-                }
-#pragma unroll
-                for (int it = 0; it < 2; ++it) {
-                    const int pr = it * 16 + prr;
-                    const float4 v0 = *reinterpret_cast<const float4*>(stg + pr * 32 + (((2 * u) ^ (pr & 7)) << 2));
-                    const float4 v1 = *reinterpret_cast<const float4*>(stg + pr * 32 + (((2 * u + 1) ^ (pr & 7)) << 2));
-                    const unsigned w4[4] = {rr[it].x, rr[it].y, rr[it].z, rr[it].w};
-                    const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                    unsigned pk[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        pk[k] = relu2_bf16(v[2 * k] + __uint_as_float(w4[k] << 16), v[2 * k + 1] + __uint_as_float(w4[k] & 0xffff0000u));
-                    *reinterpret_cast<uint4*>(Y + pix(i * 32 + pr) + cofs) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-                }
-                if (i < 3) { rr[0] = rn[0]; rr[1] = rn[1]; }
-            }
-        }
-        stamp(6);
-    }
-}
-
-// ---------------------------------------------------------------- res4, half-frame tile: small batches
-// The frame kernel above gives a frame to ONE workgroup, so a launch of B frames occupies B of the 256 CUs: an evaluation-size
-// batch (a sequence's 50 - 130 (frame, object) units, or one half of it after the two-stream split) leaves most of the chip idle for
-// the five res4 identity blocks.  Here a workgroup owns an 8 x 16-pixel HALF frame (10 x 16 halo = 180 rows with the two
-// out-of-frame columns zero, 6 pixel tiles): 2 B workgroups per launch.  Dataflow of bneck_halo_kernel with C = 256 (wave =
-// channel tile in phases A and B, = output-channel tile of a chunk in phase C); per pixel the arithmetic and its order are those
-// of the frame kernel, so a frame's result does not depend on which of the two ran it (bit-identical: tests).
+// res4, half-frame tile: small batches.  The frame kernel above gives a frame to ONE workgroup, so a launch of B frames occupies B
+// of the 256 CUs: an evaluation-size batch (a sequence's 50 - 130 (frame, object) units, or one half of it after the two-stream
+// split) leaves most of the chip idle for the five res4 identity blocks.  Here a workgroup owns an 8 x 16-pixel HALF frame (10 x 18
+// halo = 180 rows with the two out-of-frame columns zero, 6 pixel tiles): 2 B workgroups per launch; wave = channel tile in
+// phases A and B.  Which launches take it: bneck_half16_wanted below (the batch table is there).
 // LDS: [0, 73728) x ring (3 x 24 KB) -> t1 (4 slices x 192 rows) [0, 98304) -> t2 (4 x 128 rows) [0, 65536) | staging [65536, 98304);
 //      [98304, 104448) biases.
+struct HalfFrame16 : HaloGeom<256, 8, 16> {
+    static constexpr bool WL = false;
+    static constexpr bool ROWKEY = false;            // column key, as HaloTile16
+    static constexpr bool REV = false;
+    static constexpr bool TUNING = false;
+    static constexpr bool STAMPS = false;            // this form never had phase stamps
+    static constexpr int SLOT = 24576;
+    static constexpr int T1S = MH * ROWB, T2S = NPO * 32 * ROWB;
+    static constexpr int STG_OFF = NSL * T2S, BIAS_OFF = NSL * T1S, LDS_BYTES = BIAS_OFF + 6 * C * 4;       // 65536, 98304, 104448
+    static_assert(NGA * 1024 <= SLOT && 3 * SLOT <= NSL * T1S && STG_OFF + 8 * 4096 <= BIAS_OFF && LDS_BYTES <= WIDE_LDS, "LDS map");
+};
+}  // namespace
+
+template <int CMID, bool WLDS = false>
+__global__ __launch_bounds__(512) void bneck_halo_kernel(BneckWideArgs p) {
+    using F = HaloTile16<CMID, WLDS>;
+#include "bneck_halo_body.h"
+}
+
+__global__ __launch_bounds__(512, 4) void bneck_halo128s_kernel(BneckWideArgs p) {   // two workgroups per CU: <= 128 VGPRs
+    using F = HaloTile8x128;
+#include "bneck_halo_body.h"
+}
+
 __global__ __launch_bounds__(512) void bneck_half16_kernel(BneckWideArgs p) {
-    constexpr int C = 256, CIN = 1024, HW = 16, BTY = 8, HTX = 18, HR = 180, MH = 192, NGA = 23;
-    constexpr int TPF = HW / BTY;                    // 2 tiles per frame
-    constexpr int NSL = 4;
-    constexpr int SLOT = 24576;
-    constexpr int T1S = MH * ROWB, T2S = 128 * ROWB;
-    constexpr int STG_OFF = NSL * T2S, BIAS_OFF = NSL * T1S, LDS_BYTES = BIAS_OFF + 6 * C * 4;       // 65536, 98304, 104448
-    static_assert(3 * SLOT <= NSL * T1S && STG_OFF + 8 * 4096 <= BIAS_OFF && LDS_BYTES <= WIDE_LDS, "LDS map");
-    __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lrow = lane & 31, lhalf = lane >> 5;
-    const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
-    const int L = xcd_remap(blockIdx.x, gridDim.x);
-    const int b = L / TPF, tl = L - b * TPF;
-    const int y0 = tl * BTY, x0 = 0;
-    const bf16_t* X = static_cast<const bf16_t*>(p.x) + (size_t)b * HW * HW * CIN;
-    bf16_t* Y = static_cast<bf16_t*>(p.y) + (size_t)b * HW * HW * CIN;
-    const bf16_t* zeros = static_cast<const bf16_t*>(p.zeros);
-    const int ctw = wave;
-    *reinterpret_cast<float*>(lds + BIAS_OFF + tid * 4) = tid < C ? p.ba[tid] : p.bb[tid - C];
-    *reinterpret_cast<float*>(lds + BIAS_OFF + 2 * C * 4 + tid * 4) = p.bc[tid];                     // visible after phase A's barriers
-    *reinterpret_cast<float*>(lds + BIAS_OFF + 2 * C * 4 + (tid + 512) * 4) = p.bc[tid + 512];
-    uint4 wn[4];                                     // first weight fragments of the next phase, requested one phase early
-
-    // ================================================================ phase A: t1 = relu(Wa x + ba) on the halo, K = CIN
-    {
-        constexpr int NK = CIN / 64;
-        f32x16 acc[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-        const int rsub = lane >> 3, cpos = lane & 7;
-        const int np = (NGA - wave + 7) / 8;         // row groups of this wave: wave, wave + 8, wave + 16 (< 23)
-        const bf16_t* xsrc[3];
-        unsigned okmask = 0;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const int g = wave + 8 * i;
-            const int hr = g * 8 + rsub;
-            const int hy = hr / HTX, hx = hr - hy * HTX;
-            const int y = y0 - 1 + hy, x = x0 - 1 + hx;
-            const bool ok = g < NGA && hr < HR && y >= 0 && y < HW && x >= 0 && x < HW;
-            xsrc[i] = ok ? X + ((size_t)y * HW + x) * CIN + (cpos ^ ((hr >> 1) & 7)) * 8 : zeros;
-            okmask |= ok ? (1u << i) : 0u;
-        }
-        auto issue_x = [&](int kt) {
-            unsigned char* sb = lds + (kt % 3) * SLOT;
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                const int g = wave + 8 * i;
-                if (g < NGA) dma16(xsrc[i] + (((okmask >> i) & 1u) ? kt * 64 : 0), sb + g * 1024);
-            }
-        };
-        u32x4 wq[2][4];
-        auto load_w = [&](int kt, int set) {
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks)
-                asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(wq[set][ks]) : "v"(wfrag(p.fa, ctw, CIN / 16, kt * 4 + ks, lane)) : "memory");
-        };
-        load_w(0, 0);
-        issue_x(0);
-        issue_x(1);
-        for (int kt2 = 0; kt2 < NK; kt2 += 2)
-#pragma unroll
-        for (int par = 0; par < 2; ++par) {
-            const int kt = kt2 + par;
-            if (kt + 1 < NK) wait_vmcnt_n(np); else wait_vmcnt<0>();   // only X(kt+1) is younger than W(kt)
-            __builtin_amdgcn_s_barrier();
-            asm volatile("" ::: "memory");
-            if (kt + 1 < NK) load_w(kt + 1, par ^ 1);
-            if (kt + 2 < NK) issue_x(kt + 2);        // slot (kt+2) % 3 == slot of tile kt-1: done for every wave
-            const unsigned xb = lds_base + (kt % 3) * SLOT;
-            u32x4 pf[6];
-            const unsigned xrow = xb + lrow * ROWB;
-            auto rd = [&](int ks, int half) {
-                const unsigned a = xrow + (((2 * ks + lhalf) ^ ((lrow >> 1) & 7)) << 4);
-                if (half == 0) { pf[0] = lds_read_b128_o<0>(a); pf[1] = lds_read_b128_o<4096>(a); pf[2] = lds_read_b128_o<8192>(a); }
-                else { pf[3] = lds_read_b128_o<12288>(a); pf[4] = lds_read_b128_o<16384>(a); pf[5] = lds_read_b128_o<20480>(a); }
-            };
-            rd(0, 0);
-            rd(0, 1);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const u32x4 w = wq[par][ks];
-                lgkm_wait<3>();                      // half 0 landed (half 1 may be in flight)
-#pragma unroll
-                for (int t = 0; t < 3; ++t) acc[t] = mfma_bf16(w, pf[t], acc[t]);
-                if (ks < 3) rd(ks + 1, 0);
-                if (ks < 3) lgkm_wait<3>(); else lgkm_wait<0>();
-#pragma unroll
-                for (int t = 3; t < 6; ++t) acc[t] = mfma_bf16(w, pf[t], acc[t]);
-                if (ks < 3) rd(ks + 1, 1);
-            }
-        }
-        __builtin_amdgcn_s_barrier();                // the ring is dead: its space becomes t1
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) wn[ks] = *wfrag(p.fb, ctw, 9 * C / 16, ks, lane);
-        float4 bq[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const float4*>(lds + BIAS_OFF + (ctw * 32 + 8 * g + 4 * lhalf) * 4);
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            const int hr = i * 32 + lrow;
-            const int hy = hr / HTX, hx = hr - hy * HTX;
-            const int y = y0 - 1 + hy, x = x0 - 1 + hx;
-            const bool in = y >= 0 && y < HW && x >= 0 && x < HW;
-            if (hr < HR) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    u32x2 pk;
-                    pk.x = relu2_bf16(acc[i][4 * g] + bq[g].x, acc[i][4 * g + 1] + bq[g].y) & (in ? 0xffffffffu : 0u);
-                    pk.y = relu2_bf16(acc[i][4 * g + 2] + bq[g].z, acc[i][4 * g + 3] + bq[g].w) & (in ? 0xffffffffu : 0u);
-                    lds_write_b64(lds_base + (ctw >> 1) * T1S + hr * ROWB + ((((ctw & 1) * 4 + g) ^ ((hx >> 1) & 7)) << 4) + 8 * lhalf, pk);   // column key: see bneck_halo_kernel
-                }
-            }
-        }
-        lds_wait();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    }
-
-    // ================================================================ phase B: t2 = relu(Wb (*) t1 + bb), 9 taps x NSL slices
-    {
-        constexpr int KSB = 9 * C / 16, NSTEP = 9 * NSL;
-        f32x16 acc[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
-        int hb[4];                                   // halo row of this lane's output pixel at tap (0,0)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int q = i * 32 + lrow;
-            hb[i] = (q >> 4) * HTX + (q & 15);
-        }
-#pragma unroll 1
-        for (int step = 0; step < NSTEP; ++step) {   // step = tap * NSL + slice
-            const int tap = step / NSL, sl = step - tap * NSL;
-            u32x4 wc[4];
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) wc[ks] = as_u32x4(wn[ks]);
-            if (step + 1 < NSTEP) {
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) wn[ks] = *wfrag(p.fb, ctw, KSB, (step + 1) * 4 + ks, lane);
-            }
-            unsigned rowa[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int hr = hb[i] + (tap / 3) * HTX + (tap % 3);
-                rowa[i] = lds_base + sl * T1S + hr * ROWB;
-            }
-            const unsigned rkey = (((lrow & 15) + tap % 3) >> 1) & 7;    // column key (see bneck_halo_kernel)
-            u32x4 pf[4];
-            auto rd = [&](int ks, int half) {
-                const int ch = 2 * ks + lhalf;
-#pragma unroll
-                for (int i = 0; i < 2; ++i) pf[half * 2 + i] = lds_read_b128(rowa[half * 2 + i] + ((ch ^ rkey) << 4));
-            };
-            rd(0, 0);
-            rd(0, 1);
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                lgkm_wait<2>();
-#pragma unroll
-                for (int i = 0; i < 2; ++i) acc[i] = mfma_bf16(wc[ks], pf[i], acc[i]);
-                if (ks < 3) rd(ks + 1, 0);
-                if (ks < 3) lgkm_wait<2>(); else lgkm_wait<0>();
-#pragma unroll
-                for (int i = 2; i < 4; ++i) acc[i] = mfma_bf16(wc[ks], pf[i], acc[i]);
-                if (ks < 3) rd(ks + 1, 1);
-            }
-        }
-        __builtin_amdgcn_s_barrier();                // every wave is done reading t1: t2 takes its place
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) wn[ks] = *wfrag(p.fc, wave, C / 16, ks, lane);
-        float4 bq[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const float4*>(lds + BIAS_OFF + (C + ctw * 32 + 8 * g + 4 * lhalf) * 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int px = i * 32 + lrow;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                u32x2 pk;
-                pk.x = relu2_bf16(acc[i][4 * g] + bq[g].x, acc[i][4 * g + 1] + bq[g].y);
-                pk.y = relu2_bf16(acc[i][4 * g + 2] + bq[g].z, acc[i][4 * g + 3] + bq[g].w);
-                lds_write_b64(lds_base + (ctw >> 1) * T2S + px * ROWB + ((((ctw & 1) * 4 + g) ^ ((px >> 1) & 7)) << 4) + 8 * lhalf, pk);
-            }
-        }
-        lds_wait();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    }
-
-    // ================================================================ phase C: y = relu(Wc t2 + bc + x), 4 chunks of 8 channel tiles
-    {
-        constexpr int KSC = C / 16, NCH = (CIN / 32) / 8, NSTEP = NCH * NSL;
-        f32x16 acc[4];
-        float* stg = reinterpret_cast<float*>(lds + STG_OFF + wave * 4096);
-        const int u = lane & 3, prr = lane >> 2;
-        auto pix = [&](int q) { return (size_t)((y0 + (q >> 4)) * HW + x0 + (q & 15)) * CIN; };   // tile pixel q -> frame offset
-#pragma unroll 1
-        for (int chunk = 0; chunk < NCH; ++chunk) {
-            const int ct = chunk * 8 + wave;
-            const size_t cofs = (size_t)ct * 32 + 8 * u;
-            uint4 rr[2];                             // residual of the first pixel tile: in flight under the chunk's MFMAs
-#pragma unroll
-            for (int it = 0; it < 2; ++it) rr[it] = *reinterpret_cast<const uint4*>(X + pix(it * 16 + prr) + cofs);
-            {
-                float4 bq[4];
-#pragma unroll
-                for (int g = 0; g < 4; ++g) bq[g] = *reinterpret_cast<const float4*>(lds + BIAS_OFF + (2 * C + ct * 32 + 8 * g + 4 * lhalf) * 4);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-                        acc[i][4 * g] = bq[g].x; acc[i][4 * g + 1] = bq[g].y; acc[i][4 * g + 2] = bq[g].z; acc[i][4 * g + 3] = bq[g].w;
-                    }
-            }
-#pragma unroll 1
-            for (int sl = 0; sl < NSL; ++sl) {
-                u32x4 wc[4];
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) wc[ks] = as_u32x4(wn[ks]);
-                const int nxt = chunk * NSL + sl + 1;
-                if (nxt < NSTEP) {
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) wn[ks] = *wfrag(p.fc, (nxt / NSL) * 8 + wave, KSC, (nxt % NSL) * 4 + ks, lane);
-                }
-                const unsigned tb = lds_base + sl * T2S;
-                u32x4 pf[4];
-                const unsigned trow = tb + lrow * ROWB;
-                auto rd = [&](int ks, int half) {
-                    const unsigned a = trow + (((2 * ks + lhalf) ^ ((lrow >> 1) & 7)) << 4);
-                    if (half == 0) { pf[0] = lds_read_b128_o<0>(a); pf[1] = lds_read_b128_o<4096>(a); }
-                    else { pf[2] = lds_read_b128_o<8192>(a); pf[3] = lds_read_b128_o<12288>(a); }
-                };
-                rd(0, 0);
-                rd(0, 1);
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    lgkm_wait<2>();
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) acc[i] = mfma_bf16(wc[ks], pf[i], acc[i]);
-                    if (ks < 3) rd(ks + 1, 0);
-                    if (ks < 3) lgkm_wait<2>(); else lgkm_wait<0>();
-#pragma unroll
-                    for (int i = 2; i < 4; ++i) acc[i] = mfma_bf16(wc[ks], pf[i], acc[i]);
-                    if (ks < 3) rd(ks + 1, 1);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const int slot = (2 * g + lhalf) ^ (lrow & 7);
-                    *reinterpret_cast<float4*>(stg + lrow * 32 + slot * 4) = make_float4(acc[i][4 * g], acc[i][4 * g + 1], acc[i][4 * g + 2], acc[i][4 * g + 3]);
-                }
-                uint4 rn[2];
-                if (i < 3) {
-#pragma unroll
-                    for (int it = 0; it < 2; ++it) rn[it] = *reinterpret_cast<const uint4*>(X + pix((i + 1) * 32 + it * 16 + prr) + cofs);
-                }
-#pragma unroll
-                for (int it = 0; it < 2; ++it) {
-                    const int pr = it * 16 + prr;
-                    const float4 v0 = *reinterpret_cast<const float4*>(stg + pr * 32 + (((2 * u) ^ (pr & 7)) << 2));
-                    const float4 v1 = *reinterpret_cast<const float4*>(stg + pr * 32 + (((2 * u + 1) ^ (pr & 7)) << 2));
-                    const unsigned w4[4] = {rr[it].x, rr[it].y, rr[it].z, rr[it].w};
-                    const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-                    unsigned pk[4];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k)
-                        pk[k] = relu2_bf16(v[2 * k] + __uint_as_float(w4[k] << 16), v[2 * k + 1] + __uint_as_float(w4[k] & 0xffff0000u));
-                    *reinterpret_cast<uint4*>(Y + pix(i * 32 + pr) + cofs) = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-                }
-                if (i < 3) { rr[0] = rn[0]; rr[1] = rn[1]; }
-            }
-        }
-    }
+    using F = HalfFrame16;
+#include "bneck_halo_body.h"
 }
 
 // ---------------------------------------------------------------- res2, small tile: two workgroups per CU
@@ -1833,50 +941,52 @@ __global__ __launch_bounds__(512, 4) void bneck_halo64s_kernel(BneckWideArgs p) 
             __builtin_amdgcn_s_barrier();            // every wave's part of the y half is in LDS
             asm volatile("" ::: "memory");
             constexpr int NT = (ND / 32) * 2;        // output tiles of the half: channel tiles x 2 pixel tiles
-            if (wave < NT) {
-                const int ct = wave % (ND / 32), pt = wave / (ND / 32);
-                f32x16 ad;                           // from zero, bias added after the sum: the order of the kernels this replaces
-#pragma unroll
-                for (int r = 0; r < 16; ++r) ad[r] = 0.f;
-                const int row = pt * 32 + lrow;
-                // addresses as (one register + immediates): left to itself hipcc computes all 16 weight pointers and 16 LDS
-                // addresses ahead of the store pass and spills them (25 dwords of scratch traffic per tile)
-                unsigned ya[4];
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) ya[ks] = lds_base + row * ROWB + (((2 * ks + lhalf) ^ ((row >> 1) & 7)) << 4);
-                const uint4* wb = wfrag(p.fd, ct, 16, 0, lane);
-                asm volatile("" : "+v"(wb), "+v"(ya[0]), "+v"(ya[1]), "+v"(ya[2]), "+v"(ya[3]));
-                uint4 wv[2][4];
-#pragma unroll
-                for (int ks = 0; ks < 4; ++ks) wv[0][ks] = wb[ks * 64];
-                auto slice = [&](auto slc) {
-                    constexpr int SL = decltype(slc)::value;
-                    if constexpr (SL < 3) {
-                        const uint4* wn_ = wb + (SL + 1) * 256;
-                        asm volatile("" : "+v"(wn_));
-#pragma unroll
-                        for (int ks = 0; ks < 4; ++ks) wv[(SL + 1) & 1][ks] = wn_[ks * 64];
+            if constexpr (ND > 0) {                  // no phase D otherwise: ND / 32 = 0 must not be divided by
+                if (wave < NT) {
+                    const int ct = wave % (ND / 32), pt = wave / (ND / 32);
+                    f32x16 ad;                           // from zero, bias added after the sum: the order of the kernels this replaces
+    #pragma unroll
+                    for (int r = 0; r < 16; ++r) ad[r] = 0.f;
+                    const int row = pt * 32 + lrow;
+                    // addresses as (one register + immediates): left to itself hipcc computes all 16 weight pointers and 16 LDS
+                    // addresses ahead of the store pass and spills them (25 dwords of scratch traffic per tile)
+                    unsigned ya[4];
+    #pragma unroll
+                    for (int ks = 0; ks < 4; ++ks) ya[ks] = lds_base + row * ROWB + (((2 * ks + lhalf) ^ ((row >> 1) & 7)) << 4);
+                    const uint4* wb = wfrag(p.fd, ct, 16, 0, lane);
+                    asm volatile("" : "+v"(wb), "+v"(ya[0]), "+v"(ya[1]), "+v"(ya[2]), "+v"(ya[3]));
+                    uint4 wv[2][4];
+    #pragma unroll
+                    for (int ks = 0; ks < 4; ++ks) wv[0][ks] = wb[ks * 64];
+                    auto slice = [&](auto slc) {
+                        constexpr int SL = decltype(slc)::value;
+                        if constexpr (SL < 3) {
+                            const uint4* wn_ = wb + (SL + 1) * 256;
+                            asm volatile("" : "+v"(wn_));
+    #pragma unroll
+                            for (int ks = 0; ks < 4; ++ks) wv[(SL + 1) & 1][ks] = wn_[ks * 64];
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                        u32x4 pd[4];
+                        pd[0] = lds_read_b128_o<SL * YS>(ya[0]); pd[1] = lds_read_b128_o<SL * YS>(ya[1]);
+                        pd[2] = lds_read_b128_o<SL * YS>(ya[2]); pd[3] = lds_read_b128_o<SL * YS>(ya[3]);
+                        lds_wait();
+    #pragma unroll
+                        for (int ks = 0; ks < 4; ++ks) ad = mfma_bf16(as_u32x4(wv[SL & 1][ks]), pd[ks], ad);
+                        __builtin_amdgcn_sched_barrier(0);
+                    };
+                    slice(std::integral_constant<int, 0>{}); slice(std::integral_constant<int, 1>{});
+                    slice(std::integral_constant<int, 2>{}); slice(std::integral_constant<int, 3>{});
+                    const int q = half * 64 + row;
+                    bf16_t* o = T1O + ((size_t)(y0 + (q >> 4)) * HW + x0 + (q & 15)) * ND + ct * 32 + 4 * lhalf;
+    #pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        const float4 bq = *reinterpret_cast<const float4*>(p.bd + ct * 32 + 8 * g + 4 * lhalf);
+                        uint2 pk;
+                        pk.x = relu2_bf16(ad[4 * g] + bq.x, ad[4 * g + 1] + bq.y);
+                        pk.y = relu2_bf16(ad[4 * g + 2] + bq.z, ad[4 * g + 3] + bq.w);
+                        *reinterpret_cast<uint2*>(o + 8 * g) = pk;
                     }
-                    __builtin_amdgcn_sched_barrier(0);
-                    u32x4 pd[4];
-                    pd[0] = lds_read_b128_o<SL * YS>(ya[0]); pd[1] = lds_read_b128_o<SL * YS>(ya[1]);
-                    pd[2] = lds_read_b128_o<SL * YS>(ya[2]); pd[3] = lds_read_b128_o<SL * YS>(ya[3]);
-                    lds_wait();
-#pragma unroll
-                    for (int ks = 0; ks < 4; ++ks) ad = mfma_bf16(as_u32x4(wv[SL & 1][ks]), pd[ks], ad);
-                    __builtin_amdgcn_sched_barrier(0);
-                };
-                slice(std::integral_constant<int, 0>{}); slice(std::integral_constant<int, 1>{});
-                slice(std::integral_constant<int, 2>{}); slice(std::integral_constant<int, 3>{});
-                const int q = half * 64 + row;
-                bf16_t* o = T1O + ((size_t)(y0 + (q >> 4)) * HW + x0 + (q & 15)) * ND + ct * 32 + 4 * lhalf;
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const float4 bq = *reinterpret_cast<const float4*>(p.bd + ct * 32 + 8 * g + 4 * lhalf);
-                    uint2 pk;
-                    pk.x = relu2_bf16(ad[4 * g] + bq.x, ad[4 * g + 1] + bq.y);
-                    pk.y = relu2_bf16(ad[4 * g + 2] + bq.z, ad[4 * g + 3] + bq.w);
-                    *reinterpret_cast<uint2*>(o + 8 * g) = pk;
                 }
             }
             if (half == 0) {
