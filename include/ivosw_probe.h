@@ -29,6 +29,14 @@ int ivosw_bneck_wide_probe(const void* x, void* y, const void* wa, const float* 
                            const void* wc, const float* bc, void* frag, int B, int H, int W, int Cin, int Cmid,
                            unsigned long long* ts, ivosw_stream_t stream);
 
+/* Tuning probe: a RUN of n (1 .. 6) res4 identity blocks on B frames [B,16,16,1024].  w: n x (wa | wb | wc) K-major packed bf16,
+ * bias: n x (ba[256] | bb[256] | bc[1024]); `frag`: device scratch of w's size + 256 B, the last 256 zero; y: n frame buffers, block j
+ * writes y[j] and reads y[j - 1] (x for j = 0).  chain = 1: the chained stage kernel in one launch (with inplace = 1 the blocks between
+ * the first and the last write over their input, only y[0] and y[n - 1] are written); chain = 0: one launch per block.
+ * ts [n][B][8] uint64 phase stamps or NULL.                                                                              */
+int ivosw_bneck_wide_stage_probe(const void* x, void* y, const void* w, const float* bias, void* frag, int n, int B, int chain,
+                                 int inplace, unsigned long long* ts, ivosw_stream_t stream);
+
 /* Tuning probe (round 5): the one-wave-per-SIMD, 4 x 4-register-tile contraction of the attainable-roof measurement
  * (csrc/gemm_bt.h; tools/ubench/gemm_tile_bench.hip times it): C [M][N] bf16 = act(A [M][K] . B [N][K]^T + bias [N]),
  * both operands K-major bf16, fp32 accumulation, act = ReLU when relu != 0.  M % 256 == 0, N % 256 == 0, K % 32 == 0, K >= 32.

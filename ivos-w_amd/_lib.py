@@ -186,6 +186,7 @@ PROBE_SIGNATURES = {
     "ivosw_lstm_probe": (_i, [_p, _p]),
     "ivosw_bneck_probe": (_i, [_p] * 11 + [_i] * 5 + [_p, _p]),
     "ivosw_bneck_wide_probe": (_i, [_p] * 9 + [_i] * 5 + [_p, _p]),
+    "ivosw_bneck_wide_stage_probe": (_i, [_p] * 5 + [_i] * 4 + [_p, _p]),
     "ivosw_res2_stage_probe": (_i, [_p] * 4 + [_i] * 2 + [_p, _p]),
     "ivosw_gemm_bt_probe": (_i, [_p] * 4 + [_i] * 4 + [_p, _p]),
 }

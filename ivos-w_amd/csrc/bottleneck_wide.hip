@@ -65,18 +65,30 @@ __device__ __forceinline__ void bneck_wide_body(const BneckWideArgs& p, unsigned
     static_assert((IMG_BYTES == 131072 && NACC == 8) || (IMG_BYTES == 65536 && NACC == 4), "tile geometry");
     static_assert(IMG_BYTES + 8 * 4096 <= WIDE_LDS, "LDS budget");
     static_assert(4 * SLICE <= IMG_BYTES, "x ring: 4 slots");
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lrow = lane & 31, lhalf = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // The lane id is taken afresh (two v_mbcnt) by every phase: whatever hipcc derives from ONE lane id it computes once in front of the
+    // chained kernel's block loop and keeps for all phases - at 256 registers, in scratch (24 registers, reloaded at every phase head)
+    auto lane_id = [] {
+        unsigned l;
+        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
+        return (int)l;
+    };
     const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
     const bf16_t* X = static_cast<const bf16_t*>(p.x) + (size_t)blockIdx.x * NPX * CIN;
     bf16_t* Y = static_cast<bf16_t*>(p.y) + (size_t)blockIdx.x * NPX * CIN;
 
     auto stamp = [&](int k) {
-        if (p.ts && tid == 0) p.ts[(size_t)blockIdx.x * 8 + k] = __builtin_amdgcn_s_memtime();
+        if (p.ts && wave == 0 && lane_id() == 0) p.ts[(size_t)blockIdx.x * 8 + k] = __builtin_amdgcn_s_memtime();
     };
     stamp(0);
-    if (tid < 32) *reinterpret_cast<unsigned*>(lds + STG_OFF + tid * 4) = 0u;   // the zero row of phase B (visible after phase A's barriers)
+    // the zero rows of phase B (visible after phase A's barriers): one, or for the frame form one at the head of each of the first six
+    // staging tiles (its reads of tiles 1 .. 6 are immediates of 0 .. 5 x 4096 B from one address, the padding lanes' included)
+    const int tid = wave * 64 + lane_id();
+    if (HW == 16 && FR == 1) {
+        if (tid < 192) *reinterpret_cast<unsigned*>(lds + STG_OFF + (tid >> 5) * 4096 + (tid & 31) * 4) = 0u;
+    } else if (tid < 32) {
+        *reinterpret_cast<unsigned*>(lds + STG_OFF + tid * 4) = 0u;
+    }
     f32x16 acc[NACC];                                // [channel tile c of the wave][pixel tile i] at c * NPT + i
     auto zero_acc = [&]() {
 #pragma unroll
@@ -109,6 +121,7 @@ __device__ __forceinline__ void bneck_wide_body(const BneckWideArgs& p, unsigned
     // ================================================================ phase A: t1 = relu(Wa x + ba), K = CIN
     {
         constexpr int NK = CIN / 64, XG = NPX / 64;  // K-tiles of x through a 4-slot ring, XG 1-KB row groups per wave and tile
+        const int lane = lane_id(), lrow = lane & 31, lhalf = lane >> 5;
         const int rsub = lane >> 3, cpos = lane & 7;
         const bf16_t* xsrc[XG];
 #pragma unroll
@@ -171,8 +184,7 @@ __device__ __forceinline__ void bneck_wide_body(const BneckWideArgs& p, unsigned
         // live across phase B, i.e. spills them — and the second call then waits on ~15 serialised scratch reloads
         // (21.5k cycles for the t2 store against 4.2k for the identical t1 store).  Laundering the lane ids makes each call
         // recompute them.
-        int lrow_ = lrow, lhalf_ = lhalf;
-        asm volatile("" : "+v"(lrow_), "+v"(lhalf_));
+        const int lane_ = lane_id(), lrow_ = lane_ & 31, lhalf_ = lane_ >> 5;
 #pragma unroll
         for (int c = 0; c < CPW; ++c) {
             const int ct = wave * CPW + c;
@@ -204,78 +216,155 @@ __device__ __forceinline__ void bneck_wide_body(const BneckWideArgs& p, unsigned
     {
         zero_acc();
         constexpr int KSB = 9 * C / 16;
-        // this lane's pixel in tile i: index i*32 + lrow -> (frame, y, x)
-        int pyy[NPT], pxx[NPT], pfr[NPT];
+        const int lane = lane_id(), lrow = lane & 31, lhalf = lane >> 5;
+        if constexpr (HW == 16 && FR == 1) {
+            // The frame form (round 7).  Pixel tile i of a lane is row 32 i + lrow of the image, so the tap's shifted row is 32 i + sh with
+            // sh = lrow + 16 ky + kx: the swizzle key ((32 i + sh) >> 1) & 7 does not depend on the tile, a lane's column test not either, and its
+            // row test can fail only in tile 0 (ky = -1, upper frame edge) and tile 7 (ky = +1, lower edge).  Three addresses per (tap, slice)
+            // therefore serve all eight fragment reads of a k-step - tile 0, tiles 1 .. 6 as immediates from tile 1's row, tile 7 - and k-step
+            // ks is address ^ (ks << 5) (the chunk 2 ks + lhalf XOR the key, in bits 4 .. 6 of a 128-byte-aligned row).  Padding lanes read
+            // one of the zero rows at the head of the staging tiles; the middle address takes its immediates there too, hence six rows.
+            // They are rebuilt from v_mbcnt at every (tap, slice): nothing lane-derived lives across the phase (at 256 registers it was
+            // spilled), and the registers that frees hold a SECOND fragment set: the eight reads of k-step s + 1 are issued in front of
+            // k-step s's eight MFMAs (a full step of lookahead instead of half of one), across slices and taps as well, and wait on a
+            // counted lgkmcnt(8).  Weight fragments alternate between two register sets (no copy), the next (tap, slice)'s in flight.
+            // Every accumulator still takes one MFMA per k-step, in the same k order: the sums are the old loop's, bit for bit.
+            static_assert(C == 256 && NPT == 8 && CPW == 1 && NSL == 4 && STG_OFF % ROWB == 0 && SLICE % ROWB == 0, "frame form");
+            constexpr int NG = 9 * NSL;                  // (tap, slice) groups of 4 k-steps
+            u32x4 pg[NPT];                               // the second fragment set: k-step ks reads into / multiplies from set ks & 1
+            unsigned fa0, fam, fa7;
+            auto group_addr = [&](int g) {
+                const int tap = g / NSL, sl = g - tap * NSL;
+                const int ky = tap / 3 - 1, kx = tap - (tap / 3) * 3 - 1;
+                unsigned lid;
+                asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lid));
+                const int lr_ = (int)(lid & 31), lh_ = (int)(lid >> 5);
+                const int sh = lr_ + ky * HW + kx;
+                const bool okx = (unsigned)((lr_ & (HW - 1)) + kx) < (unsigned)HW;
+                const bool ok0 = okx && (ky >= 0 || lr_ >= HW), ok7 = okx && (ky <= 0 || lr_ < HW);
+                const unsigned slot = (unsigned)((lh_ ^ (sh >> 1)) & 7) << 4;
+                const unsigned row = (unsigned)(sl * SLICE + sh * ROWB) + slot, zrow = (unsigned)STG_OFF + slot;   // row < 0 only where !ok0
+                fa0 = ok0 ? row : zrow;
+                fam = okx ? row + 4096u : zrow;
+                fa7 = ok7 ? row + 7u * 4096u : zrow;
+            };
+            auto rd_step = [&](u32x4 (&f)[NPT], int ks) {
+                const unsigned x = (unsigned)ks << 5;
+                const unsigned a0 = lds_base + (fa0 ^ x), am = lds_base + (fam ^ x), a7 = lds_base + (fa7 ^ x);
+                f[0] = lds_read_b128_o<0>(a0);
+                f[1] = lds_read_b128_o<0>(am); f[2] = lds_read_b128_o<4096>(am); f[3] = lds_read_b128_o<8192>(am);
+                f[4] = lds_read_b128_o<12288>(am); f[5] = lds_read_b128_o<16384>(am); f[6] = lds_read_b128_o<20480>(am);
+                f[7] = lds_read_b128_o<0>(a7);
+            };
+            auto mm_step = [&](const u32x4& w, const u32x4 (&f)[NPT]) {
 #pragma unroll
-        for (int i = 0; i < NPT; ++i) {
-            const int q = i * 32 + lrow;
-            pfr[i] = q / (HW * HW);
-            pyy[i] = (q / HW) % HW;
-            pxx[i] = q % HW;
-        }
-        uint4 wn[4][CPW];
+                for (int i = 0; i < NPT; ++i) acc[i] = mfma_bf16(w, f[i], acc[i]);
+            };
+            // weight fragments: two sets of four, the next group's requested at the head of this one (four to seven k-steps ahead of their
+            // use: every wave streams its own 1 KB per k-step through the CU's L1, which is close to what that path takes, and three
+            // steps of lookahead measured 17 % slower); a wave-uniform base and a 32-bit lane offset
+            uint4 wq[2][4];
+            const char* wbase = static_cast<const char*>(p.fb) + (size_t)wave * KSB * 1024;
+            const unsigned woff = (unsigned)lane * 16u;
+            auto load_w = [&](int g, int set) {
 #pragma unroll
-        for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-            for (int c = 0; c < CPW; ++c) wn[ks][c] = *wfrag(p.fb, wave * CPW + c, KSB, ks, lane);
-        for (int tap = 0; tap < 9; ++tap) {
-            const int ky = tap / 3 - 1, kx = tap - (tap / 3) * 3 - 1;
-            // shifted source row of this lane in every pixel tile; the 3x3's zero padding: out-of-frame lanes read a
-            // 128-B row of zeros parked in the (still unused) store-staging area instead of being masked afterwards
-            unsigned roff[NPT];                      // byte offset of the row; its swizzle key is (row >> 1) & 7 = (roff >> 8) & 7
-            unsigned vmask = 0;
-            // the lane's pixel coordinates are rebuilt from the lane id HERE, once per tap (two v_mbcnt + a few ALU ops): kept across the phase they
-            // were spilled at 256 registers, and their reload - a scratch load followed by vmcnt(0) - opened every tap (round 6, late)
-            unsigned lid;
-            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lid));
-            const int lr_ = (int)(lid & 31);
-#pragma unroll
-            for (int i = 0; i < NPT; ++i) {
-                const int q_ = i * 32 + lr_;
-                pfr[i] = q_ / (HW * HW); pyy[i] = (q_ / HW) % HW; pxx[i] = q_ % HW;
-            }
-#pragma unroll
-            for (int i = 0; i < NPT; ++i) {
-                const int y = pyy[i] + ky, x = pxx[i] + kx;
-                const bool ok = (unsigned)y < (unsigned)HW && (unsigned)x < (unsigned)HW;
-                roff[i] = ok ? ((pfr[i] * HW + y) * HW + x) * ROWB : STG_OFF;
-                vmask |= ok ? (1u << i) : 0u;
-            }
+                for (int ks = 0; ks < 4; ++ks) wq[set][ks] = *reinterpret_cast<const uint4*>(wbase + (size_t)g * 4096 + ks * 1024 + woff);
+            };
+            load_w(0, 0);
+            group_addr(0);
+            rd_step(pf, 0);
+            static_assert(NG % 2 == 0, "two groups per trip");
 #pragma unroll 1
-            for (int sl = 0; sl < NSL; ++sl) {
-                u32x4 wc[4][CPW];
+            for (int g2 = 0; g2 < NG; g2 += 2)
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks)
+            for (int par = 0; par < 2; ++par) {          // par == g & 1: the weight set is a compile-time constant
+                // no branch in the loop: the last group requests its own fragments and reads its own first k-step once more (in bounds,
+                // unused), and the reads are drained behind the loop
+                const int g = g2 + par, gn = g + 1 < NG ? g + 1 : g;
+                load_w(gn, par ^ 1);
 #pragma unroll
-                    for (int c = 0; c < CPW; ++c) wc[ks][c] = as_u32x4(wn[ks][c]);
-                const int nstep = (tap * NSL + sl + 1) * 4;     // next (tap, slice)'s fragments: in flight under this one's MFMAs
-                if (nstep < KSB) {
+                for (int ks = 0; ks < 4; ++ks) {
+                    if (ks == 3) group_addr(gn);
+                    if (ks & 1) rd_step(pf, (ks + 1) & 3); else rd_step(pg, ks + 1);
+                    lgkm_wait<NPT>();                    // this step's eight reads are back; the next step's eight stay in flight
+                    if (ks & 1) mm_step(as_u32x4(wq[par][ks]), pg); else mm_step(as_u32x4(wq[par][ks]), pf);
+                }
+            }
+            lgkm_wait<0>();
+        } else {
+            // this lane's pixel in tile i: index i*32 + lrow -> (frame, y, x)
+            int pyy[NPT], pxx[NPT], pfr[NPT];
+#pragma unroll
+            for (int i = 0; i < NPT; ++i) {
+                const int q = i * 32 + lrow;
+                pfr[i] = q / (HW * HW);
+                pyy[i] = (q / HW) % HW;
+                pxx[i] = q % HW;
+            }
+            uint4 wn[4][CPW];
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                for (int c = 0; c < CPW; ++c) wn[ks][c] = *wfrag(p.fb, wave * CPW + c, KSB, ks, lane);
+            for (int tap = 0; tap < 9; ++tap) {
+                const int ky = tap / 3 - 1, kx = tap - (tap / 3) * 3 - 1;
+                // shifted source row of this lane in every pixel tile; the 3x3's zero padding: out-of-frame lanes read a
+                // 128-B row of zeros parked in the (still unused) store-staging area instead of being masked afterwards
+                unsigned roff[NPT];                      // byte offset of the row; its swizzle key is (row >> 1) & 7 = (roff >> 8) & 7
+                unsigned vmask = 0;
+                // the lane's pixel coordinates are rebuilt from the lane id HERE, once per tap (two v_mbcnt + a few ALU ops): kept across the phase they
+                // were spilled at 256 registers, and their reload - a scratch load followed by vmcnt(0) - opened every tap (round 6, late)
+                unsigned lid;
+                asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lid));
+                const int lr_ = (int)(lid & 31);
+#pragma unroll
+                for (int i = 0; i < NPT; ++i) {
+                    const int q_ = i * 32 + lr_;
+                    pfr[i] = q_ / (HW * HW); pyy[i] = (q_ / HW) % HW; pxx[i] = q_ % HW;
+                }
+#pragma unroll
+                for (int i = 0; i < NPT; ++i) {
+                    const int y = pyy[i] + ky, x = pxx[i] + kx;
+                    const bool ok = (unsigned)y < (unsigned)HW && (unsigned)x < (unsigned)HW;
+                    roff[i] = ok ? ((pfr[i] * HW + y) * HW + x) * ROWB : STG_OFF;
+                    vmask |= ok ? (1u << i) : 0u;
+                }
+#pragma unroll 1
+                for (int sl = 0; sl < NSL; ++sl) {
+                    u32x4 wc[4][CPW];
 #pragma unroll
                     for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-                        for (int c = 0; c < CPW; ++c) wn[ks][c] = *wfrag(p.fb, wave * CPW + c, KSB, nstep + ks, lane);
-                }
-                unsigned rowa[NPT];                  // row address in slice sl (the zero row is not per slice)
+                        for (int c = 0; c < CPW; ++c) wc[ks][c] = as_u32x4(wn[ks][c]);
+                    const int nstep = (tap * NSL + sl + 1) * 4;     // next (tap, slice)'s fragments: in flight under this one's MFMAs
+                    if (nstep < KSB) {
 #pragma unroll
-                for (int t = 0; t < NPT; ++t) rowa[t] = lds_base + roff[t] + (((vmask >> t) & 1u) ? sl * SLICE : 0);
-                auto rd = [&](int ks, int half) {
-                    const int ch = 2 * ks + lhalf;
+                        for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-                    for (int i = 0; i < HP; ++i) {
-                        const int t = half * HP + i;
-                        pf[t] = lds_read_b128(rowa[t] + ((ch ^ ((roff[t] >> 8) & 7)) << 4));
+                            for (int c = 0; c < CPW; ++c) wn[ks][c] = *wfrag(p.fb, wave * CPW + c, KSB, nstep + ks, lane);
                     }
-                };
-                rd(0, 0);
-                rd(0, 1);
+                    unsigned rowa[NPT];                  // row address in slice sl (the zero row is not per slice)
 #pragma unroll
-                for (int ks = 0; ks < 4; ++ks) {
-                    lgkm_wait<HP>();
-                    mm_half(wc[ks], 0);
-                    if (ks < 3) rd(ks + 1, 0);
-                    if (ks < 3) lgkm_wait<HP>(); else lgkm_wait<0>();
-                    mm_half(wc[ks], 1);
-                    if (ks < 3) rd(ks + 1, 1);
+                    for (int t = 0; t < NPT; ++t) rowa[t] = lds_base + roff[t] + (((vmask >> t) & 1u) ? sl * SLICE : 0);
+                    auto rd = [&](int ks, int half) {
+                        const int ch = 2 * ks + lhalf;
+#pragma unroll
+                        for (int i = 0; i < HP; ++i) {
+                            const int t = half * HP + i;
+                            pf[t] = lds_read_b128(rowa[t] + ((ch ^ ((roff[t] >> 8) & 7)) << 4));
+                        }
+                    };
+                    rd(0, 0);
+                    rd(0, 1);
+#pragma unroll
+                    for (int ks = 0; ks < 4; ++ks) {
+                        lgkm_wait<HP>();
+                        mm_half(wc[ks], 0);
+                        if (ks < 3) rd(ks + 1, 0);
+                        if (ks < 3) lgkm_wait<HP>(); else lgkm_wait<0>();
+                        mm_half(wc[ks], 1);
+                        if (ks < 3) rd(ks + 1, 1);
+                    }
                 }
             }
         }
@@ -290,6 +379,7 @@ __device__ __forceinline__ void bneck_wide_body(const BneckWideArgs& p, unsigned
     {
         constexpr int KSC = C / 16, NCH = (CIN / 32) / (8 * CPW), NSTEP = NCH * NSL;
         static_assert(NCH == 4, "four output chunks");
+        const int lane = lane_id(), lrow = lane & 31, lhalf = lane >> 5;
         float* stg = reinterpret_cast<float*>(lds + STG_OFF + wave * 4096);
         const int u = lane & 3, prr = lane >> 2;     // store pass: 8-channel group u of a 32-channel tile, pixel sub-row prr
         uint4 wn[4][CPW];
@@ -1359,6 +1449,52 @@ extern "C" int ivosw_bneck_wide_probe(const void* x, void* y, const void* wa, co
     launch_fragpack(wb, Cmid, 9 * Cmid, f + n1, st);
     launch_fragpack(wc, Cin, Cmid, f + n1 + n2, st);
     launch_bneck_wide(a, st);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+// Tuning probe: a RUN of n (1 .. 6) res4 identity blocks on B frames of 16 x 16 x 1024, block j with its own weights w[j] = (wa | wb | wc,
+// K-major packed bf16) and biases bias[j] = (ba[256] | bb[256] | bc[1024]); `frag`: device scratch, size of w + 256 B, the last 256 zero.  y holds n frame
+// buffers [n][B][16][16][1024]: block j writes y[j] and reads y[j - 1] (x for j = 0).  chain = 1: the chained stage kernel, ONE launch
+// (refused where the tower would not chain either: STAGE_RUN = 0, or a frame count that takes the half-frame kernel); with inplace = 1
+// the blocks between the first and the last write over their input, as the tower's INPLACE4 does, and only y[0] and y[n - 1] are
+// written.  chain = 0: one launch per block through launch_bneck_wide.  ts: [n][B][8] phase stamps or NULL.
+extern "C" int ivosw_bneck_wide_stage_probe(const void* x, void* y, const void* w, const float* bias, void* frag, int n, int B, int chain,
+                                            int inplace, unsigned long long* ts, ivosw_stream_t stream) {
+    using namespace ivosw;
+    IVOSW_REQUIRE(x && y && w && bias && frag, "null pointer");
+    IVOSW_REQUIRE(n >= 1 && n <= 6 && B > 0, "1 .. 6 blocks, at least one frame");
+    IVOSW_ON_DEVICE_OF(y);
+    hipStream_t st = as_stream(stream);
+    constexpr int Cm = 256, Cin = 1024, H = 16;
+    constexpr size_t n1 = (size_t)Cm * Cin * 2, n2 = (size_t)Cm * 9 * Cm * 2, WB = 2 * n1 + n2, NB = 6 * Cm;
+    const size_t fe = (size_t)B * H * H * Cin * 2;
+    BneckStageArgs sa{};
+    const char* xin = static_cast<const char*>(x);
+    for (int j = 0; j < n; ++j) {
+        char* f = static_cast<char*>(frag) + j * WB;
+        const float* b = bias + j * NB;
+        char* yj = static_cast<char*>(y) + (size_t)j * fe;
+        if (chain && inplace && j > 0 && j < n - 1) yj = const_cast<char*>(xin);
+        BneckWideArgs& a = sa.blk[sa.n++];
+        a.x = xin; a.y = yj; a.fa = f; a.ba = b; a.fb = f + n1; a.bb = b + Cm; a.fc = f + n1 + n2; a.bc = b + 2 * Cm;
+        a.B = B; a.H = H; a.W = H; a.Cin = Cin; a.Cmid = Cm; a.ts = ts ? ts + (size_t)j * B * 8 : nullptr;
+        a.zeros = static_cast<char*>(frag) + n * WB;  // the caller provides 256 zeroed bytes behind the n weight copies (half-frame form)
+        xin = yj;
+    }
+    if (chain) IVOSW_REQUIRE(bneck_stage_fusable(sa.blk[0]), "shape is not covered by the chained stage kernel");
+    for (int j = 0; j < n; ++j) {
+        const char* wj = static_cast<const char*>(w) + j * WB;
+        char* f = static_cast<char*>(frag) + j * WB;
+        launch_fragpack(wj, Cm, Cin, f, st);
+        launch_fragpack(wj + n1, Cm, 9 * Cm, f + n1, st);
+        launch_fragpack(wj + n1 + n2, Cin, Cm, f + n1 + n2, st);
+    }
+    if (chain) {
+        launch_bneck_wide_stage(sa, st);
+    } else {
+        for (int j = 0; j < n; ++j) launch_bneck_wide(sa.blk[j], st);
+    }
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }
