@@ -1,7 +1,8 @@
 /* Tuning probes of libivosw — NOT part of the product ABI (include/ivosw.h, libivosw_hip.so).
  *
  * libivosw_probe.so is a superset build of the same sources with -DIVOSW_PROBES: every entry of ivosw.h plus the entries below -
- * single-kernel launches with s_memtime phase stamps and the micro-benchmark contraction of round 5.  tools/ and one GPU test load it;
+ * single-kernel launches with s_memtime phase stamps, the micro-benchmark contraction of round 5 and the single-launch entries of the per-kernel
+ * tests.  tools/ and the per-kernel GPU tests load it;
  * nothing a reference maintainer binds lives here.                                                                               */
 #ifndef IVOSW_PROBE_H
 #define IVOSW_PROBE_H
@@ -51,6 +52,29 @@ int ivosw_gemm_bt_probe(const void* A, const void* B, const float* bias, void* C
  * (y_s2 != 0: the even pixels, [B,32,32,256]), t1out [B,64,64,128]; ts [B*32][16] uint64 phase stamps or NULL.            */
 int ivosw_res2_stage_probe(const void* packed, const void* x, void* y, void* t1out, int B, int y_s2, unsigned long long* ts,
                            ivosw_stream_t stream);
+
+/* Test probe: ONE launch of one bf16 conv layer of the tower on caller-provided device tensors (tests/test_gpu_layer_kernels.py holds every
+ * output element to the float64 restatement of tests/layer_ref.py).  Everything ConvArgs (csrc/conv.h) expresses for bf16:
+ * x [B,H,W,Cin]; w K-major packed [Cout][ksize*ksize*Cin (+ Cin2)], K = (ky*ksize + kx)*Cin + c; fp32 bias [Cout]; res [B,Ho,Wo,Cout] or NULL;
+ * x2 [B,H2,W2,Cin2] or NULL, sampled at (oy*stride2, ox*stride2) (1x1 only); ksize 1 or 3; Ho = (H + 2 pad - ksize) / stride + 1;
+ * y [B,Ho,Wo,Cout]; zeros: >= 256 B of device zeros; rev: 1 = pixel tiles in descending order.
+ * kernel = 0: the generic selector (conv_igemm_* / conv3x3_patch_kernel by shape, batch and tunables), *ran = its ConvKernel id (csrc/conv.h);
+ * kernel = 1: conv1x1_wide_kernel - w is reordered into `frag` (device scratch of w's size) on the device first -, *ran = its NPT (8 or 4);
+ * kernel = 2: the 8-phase contraction, *ran = 1 with a residual, else 0.
+ * A shape the chosen kernel does not take is refused ("not covered"): nothing is launched, y and frag stay as they were.  frag may be NULL
+ * for kernel 0 and 2; ran may be NULL. */
+int ivosw_conv_probe(const void* x, const void* w, const float* bias, const void* res, const void* x2, void* y, const void* zeros,
+                     void* frag, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, int relu, int rev,
+                     int H2, int W2, int Cin2, int stride2, int kernel, int* ran, ivosw_stream_t stream);
+
+/* Test probe: ONE launch of stage_first_kernel (res3's first block behind its conv1; csrc/stage_first.hip): t1 [B,64,64,128];
+ * x2 [B,H2,W2,256] with (H2 = W2 = 64, stride2 = 2) or (H2 = W2 = 32, stride2 = 1); w2 K-major [128][9*128]; wc [512][128 + 256]
+ * ([conv3 | downsample]); fp32 b2 [128], bc [512]; `frag`: device scratch of w2's + wc's size for their fragment-ordered copies, made on
+ * the device; zeros: >= 256 B of device zeros; y [B,Ho,Wo,512].  Any other geometry (Ho = Wo = 32 is the kernel's only one) is refused
+ * ("not covered") before anything is launched. */
+int ivosw_stage_first_probe(const void* t1, const void* x2, const void* w2, const float* b2, const void* wc, const float* bc, void* frag,
+                            const void* zeros, void* y, int B, int Ho, int Wo, int H2, int W2, int stride2, int rev,
+                            ivosw_stream_t stream);
 
 #ifdef __cplusplus
 }

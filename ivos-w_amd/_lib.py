@@ -189,6 +189,8 @@ PROBE_SIGNATURES = {
     "ivosw_bneck_wide_stage_probe": (_i, [_p] * 5 + [_i] * 4 + [_p, _p]),
     "ivosw_res2_stage_probe": (_i, [_p] * 4 + [_i] * 2 + [_p, _p]),
     "ivosw_gemm_bt_probe": (_i, [_p] * 4 + [_i] * 4 + [_p, _p]),
+    "ivosw_conv_probe": (_i, [_p] * 8 + [_i] * 15 + [C.POINTER(_i), _p]),
+    "ivosw_stage_first_probe": (_i, [_p] * 9 + [_i] * 7 + [_p]),
 }
 
 _lib = None

@@ -960,4 +960,69 @@ extern "C" int ivosw_res2_stage_probe(const void* packed, const void* x, void* y
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }
+
+// Test probe: one bf16 layer launch on the caller's tensors through one of the three paths of launch_layer above; *ran = the instantiation.
+extern "C" int ivosw_conv_probe(const void* x, const void* w, const float* bias, const void* res, const void* x2, void* y, const void* zeros,
+                                void* frag, int B, int H, int W, int Cin, int Cout, int ksize, int stride, int pad, int relu, int rev,
+                                int H2, int W2, int Cin2, int stride2, int kernel, int* ran, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(x && w && bias && y && zeros, "null pointer");
+    IVOSW_REQUIRE(kernel >= 0 && kernel <= 2 && (kernel != 1 || frag), "kernel is 0 (selector), 1 (wide, needs frag) or 2 (8-phase)");
+    IVOSW_REQUIRE(B > 0 && H > 0 && W > 0 && (ksize == 1 || ksize == 3) && stride >= 1 && stride <= 2 && pad >= 0 && pad <= ksize / 2 &&
+                  Cin > 0 && Cin % 64 == 0 && Cout > 0 && Cout % 64 == 0 && (Cout == 64 || Cout % 128 == 0),
+                  "shape is not covered by the bf16 layer kernels (Cin % 64, Cout 64 or % 128, ksize 1 / 3, stride 1 / 2)");
+    IVOSW_REQUIRE(!x2 || (ksize == 1 && Cin2 > 0 && Cin2 % 64 == 0 && stride2 >= 1 && H2 > 0 && W2 > 0),
+                  "shape is not covered: the K-extension belongs to 1x1 layers, Cin2 % 64 == 0");
+    IVOSW_ON_DEVICE_OF(y);
+    hipStream_t st = as_stream(stream);
+    ConvArgs q{};
+    q.x = x; q.w = w; q.bias = bias; q.res = res; q.y = y; q.zeros = zeros;
+    q.B = B; q.H = H; q.W = W; q.Cin = Cin; q.Cout = Cout; q.KH = q.KW = ksize; q.stride = stride; q.pad = pad; q.relu = relu; q.rev = rev;
+    q.Ho = (H + 2 * pad - ksize) / stride + 1; q.Wo = (W + 2 * pad - ksize) / stride + 1;
+    if (x2) { q.x2 = x2; q.Cin2 = Cin2; q.H2 = H2; q.W2 = W2; q.stride2 = stride2; }
+    // every kernel samples x2 at (oy * stride2, ox * stride2) without a bounds test: the last sample must lie inside the frame
+    IVOSW_REQUIRE(!x2 || ((q.Ho - 1) * stride2 < H2 && (q.Wo - 1) * stride2 < W2), "shape is not covered: x2 is sampled outside its frame");
+    const int K = ksize * ksize * Cin + (x2 ? Cin2 : 0);
+    const long M = (long)B * q.Ho * q.Wo;
+    IVOSW_REQUIRE(M * std::max(Cout, K) < (1L << 31), "too many frames for a probe launch");
+    int id = 0;
+    if (kernel == 1) {
+        IVOSW_REQUIRE(conv1x1_wide_ok(q), "layer is not covered by conv1x1_wide_kernel");
+        // launch_conv1x1_wide's own rule (bottleneck_wide.hip): fewer 256-pixel tiles than WIDE_SMALL -> 128-pixel tiles
+        id = (int)((M + 255) / 256) * (Cout / 256) < tune_get("WIDE_SMALL", 0) ? 4 : 8;
+        launch_fragpack(w, Cout, K, frag, st);
+        launch_conv1x1_wide(q, frag, st);
+    } else if (kernel == 2) {
+        IVOSW_REQUIRE(conv1x1_g8_ok(q), "layer is not covered by the 8-phase contraction");
+        id = res ? 1 : 0;
+        launch_conv1x1_g8(q, st);
+    } else {
+        id = (int)conv_select(q, IVOSW_BF16, false);
+        launch_conv(q, IVOSW_BF16, false, st);
+    }
+    if (ran) *ran = id;
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+// Test probe: one launch of stage_first_kernel on the caller's tensors, the K-major weights reordered into `frag` on the device first.
+extern "C" int ivosw_stage_first_probe(const void* t1, const void* x2, const void* w2, const float* b2, const void* wc, const float* bc,
+                                       void* frag, const void* zeros, void* y, int B, int Ho, int Wo, int H2, int W2, int stride2, int rev,
+                                       ivosw_stream_t stream) {
+    IVOSW_REQUIRE(t1 && x2 && w2 && b2 && wc && bc && frag && zeros && y, "null pointer");
+    IVOSW_ON_DEVICE_OF(y);
+    hipStream_t st = as_stream(stream);
+    constexpr int Cm = 128, C2 = 256;
+    char* f = static_cast<char*>(frag);
+    const size_t n2 = (size_t)Cm * 9 * Cm * 2;
+    StageFirstArgs q{};
+    q.t1 = t1; q.x2 = x2; q.y = y; q.zeros = zeros; q.fw2 = f; q.b2 = b2; q.fwc = f + n2; q.bc = bc;
+    q.B = B; q.Ho = Ho; q.Wo = Wo; q.Cm = Cm; q.C2 = C2; q.H2 = H2; q.W2 = W2; q.stride2 = stride2; q.rev = rev;
+    // refuse BEFORE the weight reordering: a refused call launches nothing and leaves `frag` as it was
+    IVOSW_REQUIRE(B > 0 && B <= 1024 && stage_first_ok(q), "shape is not covered by stage_first_kernel");
+    launch_fragpack(w2, Cm, 9 * Cm, f, st);
+    launch_fragpack(wc, 4 * Cm, Cm + C2, f + n2, st);
+    launch_stage_first(q, st);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
 #endif  // IVOSW_PROBES
