@@ -76,6 +76,29 @@ int ivosw_stage_first_probe(const void* t1, const void* x2, const void* w2, cons
                             const void* zeros, void* y, int B, int Ho, int Wo, int H2, int W2, int stride2, int rev,
                             ivosw_stream_t stream);
 
+/* Test probe: ONE launch of res2 (three bottlenecks at 64 x 64) + res3's forwarded conv1 on caller-provided device tensors and weights
+ * (tests/test_gpu_res2_stem_kernels.py holds every output element to the float64 restatement of tests/res2_ref.py).  x [B,64,64,64] bf16;
+ * w, bias: HOST arrays of IVOSW_RES2_PROBE_NW device pointers, K-major bf16 weights and fp32 biases in the order
+ *   conv1 of res2's blocks 0, 1, 2 and of res3's first block ([64][64], [64][256], [64][256], [128][256]),
+ *   conv2 of blocks 0, 1, 2 ([64][9*64], K = (ky*3 + kx)*64 + c), conv3 of blocks 0, 1, 2 ([256][64]), block 0's downsample ([256][64]);
+ * frag: IVOSW_RES2_PROBE_FRAG_BYTES of device scratch for what the kernels read, made on the device; zeros: >= 256 B of device zeros;
+ * y [B,64,64,256] (y_s2 != 0: the even pixels, [B,32,32,256]); t1out [B,64,64,128]; rev: 1 = tiles in descending order.
+ * form = 0: res2_stage_kernel on fragment-ordered copies (launch_fragpack; block 0's [conv3 | downsample] through launch_concat_k, as
+ * ivosw_assess_pack makes them); form = 1: res2_chain_kernel on the fragment stream of launch_res2_chain_pack.
+ * *ran (may be NULL) = kind + 4 * (y_s2 != 0), kind 0: res2_stage_kernel, 1: res2_chain_kernel one tile per workgroup (tunable
+ * R2C_PERSIST = 0), 2: res2_chain_kernel persistent.  A NULL operand, B outside 1 .. 1024 or another form is refused before anything is
+ * launched: y, t1out and frag stay as they were. */
+#define IVOSW_RES2_PROBE_NW 11
+#define IVOSW_RES2_PROBE_FRAG_BYTES 655360
+int ivosw_res2_probe(const void* x, const void* const* w, const float* const* bias, void* frag, const void* zeros, void* y, void* t1out,
+                     int B, int y_s2, int rev, int form, int* ran, ivosw_stream_t stream);
+
+/* Test probe: ONE launch of stem_pool_kernel (7x7/2 convolution + folded BN + ReLU + 3x3/2 max-pool; csrc/stem.hip): roi [B,256,256,4] bf16;
+ * w: the filter bank in the packed arena's layout, [64][8 ky][8 px][4 ch] bf16 with ky == 7 and px == 7 zero (as pack_stem_kernel writes
+ * it); fp32 bias [64]; out [B,64,64,64]; rev: 1 = tiles in descending order.  A NULL operand or B outside 1 .. 1024 is refused before
+ * anything is launched. */
+int ivosw_stem_probe(const void* roi, const void* w, const float* bias, void* out, int B, int rev, ivosw_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

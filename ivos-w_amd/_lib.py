@@ -191,7 +191,10 @@ PROBE_SIGNATURES = {
     "ivosw_gemm_bt_probe": (_i, [_p] * 4 + [_i] * 4 + [_p, _p]),
     "ivosw_conv_probe": (_i, [_p] * 8 + [_i] * 15 + [C.POINTER(_i), _p]),
     "ivosw_stage_first_probe": (_i, [_p] * 9 + [_i] * 7 + [_p]),
+    "ivosw_res2_probe": (_i, [_p] * 7 + [_i] * 4 + [C.POINTER(_i), _p]),      # w, bias: host arrays of RES2_PROBE_NW device pointers
+    "ivosw_stem_probe": (_i, [_p] * 4 + [_i] * 2 + [_p]),
 }
+RES2_PROBE_NW, RES2_PROBE_FRAG_BYTES = 11, 655360           # IVOSW_RES2_PROBE_NW, IVOSW_RES2_PROBE_FRAG_BYTES of include/ivosw_probe.h
 
 _lib = None
 _probe = None

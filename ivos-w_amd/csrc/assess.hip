@@ -1025,4 +1025,75 @@ extern "C" int ivosw_stage_first_probe(const void* t1, const void* x2, const voi
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }
+
+// Test probe: one launch of res2 + res3's forwarded conv1 on the caller's tensors and K-major weights; what the chosen kernel reads is
+// made in `frag` on the device first, by the launches ivosw_assess_pack makes it with.  *ran = the instantiation.
+extern "C" int ivosw_res2_probe(const void* x, const void* const* w, const float* const* bias, void* frag, const void* zeros, void* y,
+                                void* t1out, int B, int y_s2, int rev, int form, int* ran, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(x && w && bias && frag && zeros && y && t1out, "null pointer");
+    for (int i = 0; i < IVOSW_RES2_PROBE_NW; ++i) IVOSW_REQUIRE(w[i] && bias[i], "null pointer among the weights or biases");
+    IVOSW_REQUIRE(form == 0 || form == 1, "form is 0 (res2_stage_kernel) or 1 (res2_chain_kernel)");
+    IVOSW_REQUIRE(B > 0 && B <= 1024, "B must be in 1 .. 1024");
+    IVOSW_ON_DEVICE_OF(y);
+    hipStream_t st = as_stream(stream);
+    // w / bias: conv1 x 4 | conv2 x 3 | conv3 x 3 | downsample
+    const void* const* w1 = w; const void* const* w2 = w + 4; const void* const* w3 = w + 7; const void* wd = w[10];
+    const float* const* b1 = bias; const float* const* b2 = bias + 4; const float* const* b3 = bias + 7; const float* bd = bias[10];
+    char* f = static_cast<char*>(frag);
+    int id = 0;
+    if (form == 1) {
+        IVOSW_REQUIRE(res2_chain_stream_bytes() <= IVOSW_RES2_PROBE_FRAG_BYTES, "internal: the fragment stream outgrew the probe's scratch");
+        Res2ChainPackArgs q{};
+        for (int b = 0; b < 4; ++b) { q.w1[b] = static_cast<const bf16_t*>(w1[b]); q.b1[b] = b1[b]; }
+        for (int b = 0; b < 3; ++b) { q.w2[b] = static_cast<const bf16_t*>(w2[b]); q.b2[b] = b2[b]; q.w3[b] = static_cast<const bf16_t*>(w3[b]); q.b3[b] = b3[b]; }
+        q.wd = static_cast<const bf16_t*>(wd); q.bd = bd; q.out = f;
+        Res2ChainArgs c{};
+        c.x = x; c.y = y; c.t1out = t1out; c.wstream = f; c.zeros = zeros; c.B = B; c.y_s2 = y_s2 ? 1 : 0; c.rev = rev ? 1 : 0;
+        IVOSW_REQUIRE(res2_chain_ok(c), "internal: res2_chain_ok");
+        id = tune_get("R2C_PERSIST", 1) != 0 ? 2 : 1;            // launch_res2_chain's own rule (res2_chain.hip)
+        launch_res2_chain_pack(q, st);
+        launch_res2_chain(c, st);
+    } else {
+        size_t off = 0;
+        auto take = [&](size_t bytes) { char* p = f + off; off += align_up(bytes, 256); return p; };
+        constexpr size_t E = 2;                                   // bytes per bf16
+        char* fa0 = take(64 * 64 * E);
+        char* fb[3]; for (int b = 0; b < 3; ++b) fb[b] = take(64 * 576 * E);
+        char* cat_w = take(256 * 128 * E);
+        char* cat_fw = take(256 * 128 * E);
+        float* cat_b = reinterpret_cast<float*>(take(256 * sizeof(float)));
+        char* fc[3] = {cat_fw, take(256 * 64 * E), take(256 * 64 * E)};
+        char* fd[3] = {take(64 * 256 * E), take(64 * 256 * E), take(128 * 256 * E)};
+        IVOSW_REQUIRE(off <= IVOSW_RES2_PROBE_FRAG_BYTES, "internal: the fragment copies outgrew the probe's scratch");
+        Res2StageArgs q{};
+        q.x = x; q.y = y; q.t1out = t1out; q.zeros = zeros; q.B = B; q.y_s2 = y_s2 ? 1 : 0; q.rev = rev ? 1 : 0;
+        q.fa0 = fa0; q.ba0 = b1[0];
+        for (int b = 0; b < 3; ++b) {
+            q.fb[b] = fb[b]; q.bb[b] = b2[b];
+            q.fc[b] = fc[b]; q.bc[b] = b == 0 ? cat_b : b3[b];
+            q.fd[b] = fd[b]; q.bd[b] = b1[b + 1];
+        }
+        IVOSW_REQUIRE(res2_stage_ok(q), "internal: res2_stage_ok");
+        launch_fragpack(w1[0], 64, 64, fa0, st);
+        for (int b = 0; b < 3; ++b) launch_fragpack(w2[b], 64, 576, fb[b], st);
+        launch_concat_k(w3[0], b3[0], 64, wd, bd, 64, 256, IVOSW_BF16, cat_w, cat_b, st);
+        launch_fragpack(cat_w, 256, 128, cat_fw, st);
+        for (int b = 1; b < 3; ++b) launch_fragpack(w3[b], 256, 64, fc[b], st);
+        for (int b = 0; b < 3; ++b) launch_fragpack(w1[b + 1], b == 2 ? 128 : 64, 256, fd[b], st);
+        launch_res2_stage(q, st);
+    }
+    if (ran) *ran = id + (y_s2 ? 4 : 0);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+// Test probe: one launch of stem_pool_kernel on the caller's ROI tiles and packed filter bank.
+extern "C" int ivosw_stem_probe(const void* roi, const void* w, const float* bias, void* out, int B, int rev, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(roi && w && bias && out, "null pointer");
+    IVOSW_REQUIRE(B > 0 && B <= 1024, "B must be in 1 .. 1024");
+    IVOSW_ON_DEVICE_OF(out);
+    launch_stem_pool(roi, w, bias, B, out, as_stream(stream), rev ? 1 : 0);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
 #endif  // IVOSW_PROBES
