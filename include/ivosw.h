@@ -899,6 +899,31 @@ int ivosw_robot_skeleton_fits(int H, int W);
 int ivosw_robot_skeleton(const uint8_t* gt, const uint8_t* pred, int n, int H, int W, const int32_t* units_host, int m, int cap,
                          int32_t* points, int32_t* counts, int32_t* iters, uint32_t* skel, ivosw_stream_t stream);
 
+/* ivosw_robot_skeleton_box: the same outputs by the same rule for ANY frame size in [1, 65535]^2 and for objects in [0, 255].
+ * Windowing rule: the kernel first finds the bounding box of the unit's error region - rows by0 .. by1, 32-pixel words bw0 .. bw1 - and
+ *   keeps two bit planes of that box only ((by1 - by0 + 1) x (bw1 - bw0 + 1) words), thinning them with everything outside the WINDOW read
+ *   as 0.  The result is bit-identical to the full-frame rule: thinning only clears bits, so every pixel outside the box is 0 at the start
+ *   and at every later sub-iteration; a decision inside the box therefore reads the same eight neighbours in both forms (a neighbour
+ *   outside the box is 0 in the full plane and "outside" in the window), by induction over the sub-iterations the planes agree inside
+ *   the box, the same sub-iterations delete something, and iters is the same (its cap stays max(H, W) of the FRAME).  points, counts,
+ *   iters and skel are in frame coordinates (skel is written in full, 0 outside the box); a caller cannot tell that the window existed.
+ *   An empty region: counts = 0, iters = 0, skel all zero, no point written.
+ * Where the planes live, per unit: if 2 * box words * 4 + 256 bytes fit the launch's dynamic LDS - min(2 * H * ceil(W/32) * 4 + 256,
+ *   160 KB), so a size ivosw_robot_skeleton accepts never needs more - in LDS; otherwise in the unit's slice of `workspace`, device
+ *   memory of ivosw_robot_box_workspace_bytes(H, W, m) = m * 2 * H * ceil(W/32) * 4 bytes, 4-byte aligned, owned by the caller, content
+ *   irrelevant before and undefined after.  That query (host only) returns 0 when ivosw_robot_skeleton_fits(H, W) - workspace may then be
+ *   NULL - and a negative value for H or W outside [1, 65535] or m < 1.  Still one launch per 64 units, one workgroup per unit, no host
+ *   loop, no grid-wide synchronisation, no atomics on global memory; asynchronous on `stream`, capture-safe.
+ * Object 0 (the background) is a unit like any other: its plane is gt == 0 && pred != 0, the false positives.  A NULL pred means "nothing
+ *   predicted", which has no false positive: a table that holds object 0 is refused when pred is NULL (the message names the unit).
+ * Refused (IVOSW_ERR_ARG) before any pointer is used, nothing launched, nothing written: everything ivosw_robot_skeleton refuses except
+ *   the size limit and object 0 (objects outside [0, 255]); object 0 with a NULL pred; a size that does not fit with a NULL workspace
+ *   or workspace_bytes below the need (the message states the bytes needed).                                                     */
+long ivosw_robot_box_workspace_bytes(int H, int W, int m);
+int ivosw_robot_skeleton_box(const uint8_t* gt, const uint8_t* pred, int n, int H, int W, const int32_t* units_host, int m, int cap,
+                             int32_t* points, int32_t* counts, int32_t* iters, uint32_t* skel, uint32_t* workspace,
+                             size_t workspace_bytes, ivosw_stream_t stream);
+
 /* ------------------------------------------------------------------ launch-sequence capture ---- */
 /* HIP-graph capture of any sequence of the calls above on one stream (not in the reference: it replaces the ~40 host
  * launches per Agent.update_agent step, models/agent.py:128-160, by ONE hipGraphLaunch).  begin puts `stream` (non-null)

@@ -99,6 +99,14 @@ int ivosw_res2_probe(const void* x, const void* const* w, const float* const* bi
  * anything is launched. */
 int ivosw_stem_probe(const void* roi, const void* w, const float* bias, void* out, int B, int rev, ivosw_stream_t stream);
 
+/* Test probe: ivosw_robot_skeleton_box's launcher with the launch's dynamic LDS size as an argument, lds_budget_bytes in [256, 163840]
+ * (256: every non-empty box keeps its planes in the workspace), so that a test can send a 3 x 33 frame through the global planes and
+ * tools/robot_box_probe.py can time the two plane homes on one region.  The workspace (m * 2 * H * ceil(W/32) * 4 bytes) is needed
+ * whenever two full-frame planes + 256 bytes exceed the budget; every other argument and refusal as in ivosw_robot_skeleton_box. */
+int ivosw_robot_box_probe(const uint8_t* gt, const uint8_t* pred, int n, int H, int W, const int32_t* units_host, int m, int cap,
+                          int32_t* points, int32_t* counts, int32_t* iters, uint32_t* skel, uint32_t* workspace,
+                          size_t workspace_bytes, int lds_budget_bytes, ivosw_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,6 +165,8 @@ SIGNATURES = {
     "ivosw_rough_roi": (_i, [_p, _p, _i, _i, _i, _i, _p, _sz, _p]),
     "ivosw_robot_skeleton_fits": (_i, [_i, _i]),
     "ivosw_robot_skeleton": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p]),
+    "ivosw_robot_box_workspace_bytes": (C.c_long, [_i, _i, _i]),
+    "ivosw_robot_skeleton_box": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
     "ivosw_graph_begin": (_i, [_p]),
     "ivosw_graph_end": (_i, [_p, C.POINTER(_p), C.POINTER(_i)]),
     "ivosw_graph_launch": (_i, [_p, _p]),
@@ -193,6 +195,7 @@ PROBE_SIGNATURES = {
     "ivosw_stage_first_probe": (_i, [_p] * 9 + [_i] * 7 + [_p]),
     "ivosw_res2_probe": (_i, [_p] * 7 + [_i] * 4 + [C.POINTER(_i), _p]),      # w, bias: host arrays of RES2_PROBE_NW device pointers
     "ivosw_stem_probe": (_i, [_p] * 4 + [_i] * 2 + [_p]),
+    "ivosw_robot_box_probe": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _sz, _i, _p]),
 }
 RES2_PROBE_NW, RES2_PROBE_FRAG_BYTES = 11, 655360           # IVOSW_RES2_PROBE_NW, IVOSW_RES2_PROBE_FRAG_BYTES of include/ivosw_probe.h
 

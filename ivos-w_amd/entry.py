@@ -86,6 +86,9 @@ DEFAULTS = dict(
                                        # the ground truth, whatever was predicted), or "errors": along the skeleton of each object's error region
                                        # gt == o and pred != o of the masks last submitted, thinned on the device (utils.robot.interact)
     robot_min_nodes=4,                 # robot=errors: an error skeleton of fewer connected pixels draws no path (davisinteractive's min_nb_nodes)
+    robot_background=False,            # robot=errors: true draws on the background too - paths of object 0 along the skeleton of the false
+                                       # positives gt == 0 and pred != 0 (as davisinteractive's robot does), which tell the VOS model "this is
+                                       # not an object"; false: no call, file or log line differs
     report_save_dir="results",
     eval_max_nb_interactions=8,        # the eval scripts fix 8 interactions on the val subset (eval_agent_manet.py:64-65)
     data=dict(num_workers=0, root_dir_davis="data/DAVIS", root_dir_scribble_youtube_vos="data/Scribble_Youtube_VOS",
@@ -175,6 +178,17 @@ def robot_option(cfg):
     if mode == "errors" and cfg.get("scribbles", "frame") != "paths":
         raise ValueError("robot=errors draws paths: it needs scribbles=paths")
     return mode, min_nodes
+
+
+def robot_background_option(cfg):
+    """cfg.robot_background (absent: False).  Refused: a value that is not a bool; true unless robot=errors (the ground-truth robot knows no
+    prediction, so it has no false positive to draw on)."""
+    on = cfg.get("robot_background", False)
+    if not isinstance(on, bool):
+        raise ValueError(f"robot_background must be true or false, got {on!r}")
+    if on and cfg.get("robot", "gt") != "errors":
+        raise ValueError("robot_background=true draws on the false positives of a prediction: it needs robot=errors")
+    return on
 
 
 def qa_option(cfg):
@@ -373,6 +387,7 @@ def parse_cli(argv, **overrides):
         qa_option(cfg)
         scribbles_option(cfg)
         robot_option(cfg)
+        robot_background_option(cfg)
     except ValueError as e:
         raise SystemExit(f"[ivos-w] {e}")
     return _attr(cfg)
@@ -486,13 +501,14 @@ class SyntheticSession:
     ``scribbles="paths"``: then the annotated frame's entry holds real paths - ``robot_paths`` on the ground truth, or with
     ``robot="errors"`` the paths of ``utils.robot.interact`` along the error skeletons of the masks last submitted for this sample
     (none yet: the objects themselves); ``robot_paths`` stands in only when no object at all yields a path.  ``drew`` names the robot
-    that drew the last scribbles: "gt", "errors" or "gt (no error path)"."""
+    that drew the last scribbles: "gt", "errors" or "gt (no error path)".  ``robot_background`` (with ``robot="errors"``): the error
+    robot also draws paths of object 0 on the false positives of the masks last submitted (none before the first submission)."""
 
     def __init__(self, davis, subset, metric_to_optimize, max_nb_interactions, report_save_dir, seed=0, rounds=1, scribbles="frame",
-                 robot="gt", robot_min_nodes=4):
+                 robot="gt", robot_min_nodes=4, robot_background=False):
         self.davis, self.metric, self.max_nb = davis, metric_to_optimize, int(max_nb_interactions)
         self.scribble_mode = scribbles
-        self.robot, self.robot_min_nodes = robot, int(robot_min_nodes)
+        self.robot, self.robot_min_nodes, self.robot_background = robot, int(robot_min_nodes), bool(robot_background)
         self.drew, self._submitted = None, None
         self.report_save_dir = report_save_dir
         rs = np.random.RandomState(77 + seed)
@@ -527,8 +543,9 @@ class SyntheticSession:
             mine, self.drew = None, "gt"
             if self.robot == "errors":                                # every node of the skeleton path: the polyline stays on the error region
                 from .utils import robot as R
+                extra = dict(background=True) if self.robot_background else {}
                 mine, self.drew = R.interact(gt, self._submitted, n_objects, self._frame, min_nb_nodes=self.robot_min_nodes,
-                                             nb_points=None), "errors"
+                                             nb_points=None, **extra), "errors"
                 if not mine:
                     mine, self.drew = None, "gt (no error path)"
             if mine is None:
@@ -592,7 +609,8 @@ class StandInVOS:
     """Deterministic stand-in for the VOS backbone: stride-4 logits whose error grows with the distance to the nearest annotated
     frame (the ground truth shifted by 1.5 px per frame of distance, plus seeded noise).  Annotated frames come out (almost) exact,
     so annotating the worst frame helps most — the structure the agent learns from.  ``scribble_low`` = (frame, int8 [h // 4, w // 4]
-    scribble map on the device): the scribbled object's logit gains 8 at the scribbled low-resolution pixels of that frame."""
+    scribble map on the device): the scribbled object's logit gains 8 at the scribbled low-resolution pixels of that frame (a scribble of
+    object 0, which ``robot_background`` draws, raises channel 0: the background logit)."""
 
     def __init__(self, device, seed=0):
         self.device, self.seed = device, seed
@@ -672,6 +690,7 @@ def run_eval(cfg, backbone="MANet"):
     qa = qa_option(cfg)
     scribble_mode = scribbles_option(cfg)
     robot, robot_min_nodes = robot_option(cfg)
+    robot_background = robot_background_option(cfg)
     oracle_chain = metric_option(cfg) == "device" and cfg.setting == "oracle" and cfg.method in ("ours", "worst")
     cfg.phase = "eval"
     cfg.data.subset = "val"
@@ -698,7 +717,7 @@ def run_eval(cfg, backbone="MANet"):
     corr_all, rec_time, seen_seq = misc.AverageMeter(), misc.AverageMeter(), {}
     qa_sess = QaSession(cfg, qa, metric, masks) if any(qa) else None
     with SyntheticSession(davis, cfg.data.subset, metric, max_nb, report_dir, seed=int(cfg.seed), scribbles=scribble_mode, robot=robot,
-                          robot_min_nodes=robot_min_nodes) as sess, \
+                          robot_min_nodes=robot_min_nodes, **(dict(robot_background=True) if robot_background else {})) as sess, \
             (qa_sess or contextlib.nullcontext()):
         while sess.next():
             sequence, scribbles, first_scribble = sess.get_scribbles(only_last=True)
@@ -725,6 +744,9 @@ def run_eval(cfg, backbone="MANet"):
                 scribble_text = f"scribble: {len(scribbles['scribbles'][drawn])} paths "
                 if robot == "errors":
                     scribble_text += f"robot: {sess.drew} "
+                    if robot_background:                              # (a path of object 0 raises the stand-in's background logit: channel 0)
+                        n_bg = sum(1 for p in scribbles["scribbles"][drawn] if p.get("object_id") == 0)
+                        scribble_text = scribble_text[:-1] + f" ({n_bg} background) "
             if scribble_low is None:                                  # (tests/test_qa_option.py replaces _segment by a six-argument double)
                 labels, all_P = _segment(vos, davis, sequence, n_objects, annotated, store)
             else:

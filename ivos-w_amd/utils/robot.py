@@ -1,14 +1,17 @@
 """The error-driven scribble robot (``csrc/robot.hip``): scribbles where the segmentation is wrong.  For every object of the annotated frame
-the device thins the error region ``gt == o and pred != o`` to a skeleton - one workgroup per (frame, object) unit, entirely in LDS, one
-launch - and the few hundred skeleton pixels that come back become paths in davisinteractive's schema on the host.
+the device thins the error region ``gt == o and pred != o`` to a skeleton - one workgroup per (frame, object) unit, one launch - and the
+few hundred skeleton pixels that come back become paths in davisinteractive's schema on the host.
 
 davisinteractive's ``InteractiveScribblesRobot`` does the same on the CPU with skimage's skeletoniser at every interaction of every
 episode.  Neither package is a dependency of this one and the robot is not in the reference tree: the rules - Zhang-Suen thinning as
 published, the component / double-BFS / resampling step below - are stated in ``include/ivosw.h`` and, as numpy, in ``tests/robot_ref.py``.
 They are this project's DEFINITION; parity with the library's own robot is restated, not recorded.
 
-Not built: scribbles on the background (object 0), which the library's robot draws on false positives; sizes beyond the LDS limit
-(``fits``: 480 x 854 fits, 720p does not - the robot serves DAVIS 480p).
+Two entries, the same bits.  A size whose two full-frame bit planes fit the LDS of one workgroup (``fits``: 480 x 854 does) goes to
+``ivosw_robot_skeleton`` as long as no unit names object 0.  Every other call - 720p, 1080p, any size up to 65535 x 65535, and the
+background - goes to ``ivosw_robot_skeleton_box``, which keeps planes of the error region's bounding box only: in LDS when the box fits,
+else in a cached device workspace.  The background (object 0) is drawn on the false positives ``gt == 0 and pred != 0``, as the library's
+robot draws it; ``interact(..., background=True)`` asks for it.
 
 There is no CPU fallback for ``skeleton_points``; ``paths_from_points`` is host work.
 """
@@ -47,14 +50,31 @@ def _launch(gt, pred, units, cap, want_bits):
     n, H, W = gt.shape
     buf = torch.empty(m * (2 + max(cap, 0)), dtype=torch.int32, device=gt.device)
     bits = torch.empty((m, H, (W + 31) // 32), dtype=torch.int32, device=gt.device) if want_bits else None
-    L.check(L.lib().ivosw_robot_skeleton(L.dptr(gt), None if pred is None else L.dptr(pred), n, H, W, table.ctypes.data, m, cap,
-                                         L.torch_ptr(buf, 2 * m), L.dptr(buf), L.torch_ptr(buf, m), None if bits is None else L.dptr(bits),
-                                         L.stream_ptr(gt.device)), "robot_skeleton")
+    lib = L.lib()
+    args = (L.dptr(gt), None if pred is None else L.dptr(pred), n, H, W, table.ctypes.data, m, cap,
+            L.torch_ptr(buf, 2 * m), L.dptr(buf), L.torch_ptr(buf, m), None if bits is None else L.dptr(bits))
+    if lib.ivosw_robot_skeleton_fits(H, W) and not (table[:, 1] == 0).any():
+        L.check(lib.ivosw_robot_skeleton(*args, L.stream_ptr(gt.device)), "robot_skeleton")
+        return buf, m, bits
+    need = max(int(lib.ivosw_robot_box_workspace_bytes(H, W, max(m, 1))), 0)       # (a refused size: the entry says why)
+    ws = _workspace(gt.device, need) if need else None
+    L.check(lib.ivosw_robot_skeleton_box(*args, None if ws is None else L.dptr(ws), need, L.stream_ptr(gt.device)), "robot_skeleton_box")
     return buf, m, bits
 
 
+_ws = {}                      # (device, bytes) -> uint8 tensor: the global planes of boxes beyond LDS (calls on one stream are ordered)
+
+
+def _workspace(device, nbytes):
+    key = (torch.device(device), int(nbytes))
+    if key not in _ws:
+        _ws[key] = torch.empty(int(nbytes), dtype=torch.uint8, device=device)
+    return _ws[key]
+
+
 def skeleton_points(gt, pred, units, cap=4096, want_bits=False):
-    """``ivosw_robot_skeleton`` on device label maps ``gt`` and ``pred`` (uint8 [n,H,W]; ``pred`` None: all background) for ``units`` =
+    """``ivosw_robot_skeleton`` (a size that ``fits``, no object 0) or ``ivosw_robot_skeleton_box`` (any other call; the same bits) on
+    device label maps ``gt`` and ``pred`` (uint8 [n,H,W]; ``pred`` None: all background, no unit of object 0 then) for ``units`` =
     [(frame, object), ...]: device tensors ``(points, counts, iters)`` - int32 [m,cap] skeleton pixels as (y << 16) | x in raster order,
     int32 [m] true pixel counts (also beyond ``cap``) and int32 [m] iteration counts (-1: not converged) - and, ``want_bits``, the
     skeleton's bit planes [m,H,ceil(W/32)] as a fourth (bit x & 31 of word x >> 5; an int32 tensor holding the uint32 words).  The three
@@ -147,16 +167,18 @@ def paths_from_points(points, count, size, object_id, min_nb_nodes=4, max_paths=
     return out
 
 
-def interact(gt, pred, n_objects, frame, cap=4096, **kw):
+def interact(gt, pred, n_objects, frame, cap=4096, background=False, **kw):
     """The scribbles of one frame in davisinteractive's schema: a list of paths for the objects 1 .. ``n_objects`` in ascending order, drawn
     along the skeleton of each object's error region on ``frame``.  ``gt`` and ``pred``: device uint8 [n,H,W] (``pred`` None: nothing
     predicted yet, the error region is the object).  An object without an error skeleton of at least ``min_nb_nodes`` connected pixels
-    gets no path; the background (object 0) gets none either.  ``kw``: ``min_nb_nodes``, ``max_paths``, ``nb_points`` of
+    gets no path.  ``background``: the background is scribbled too - unit (frame, 0), the false positives ``gt == 0 and pred != 0``; its
+    paths carry ``object_id=0`` and come first, so the list stays ascending in object id.  With ``pred`` None nothing is predicted, no
+    false positive exists and the background is skipped.  ``kw``: ``min_nb_nodes``, ``max_paths``, ``nb_points`` of
     ``paths_from_points``.  One launch, one device-to-host copy of [counts | iters | points], then the numpy step."""
     frame, n_objects = int(frame), int(n_objects)
     if n_objects < 1:
         return []
-    units = [(frame, o) for o in range(1, n_objects + 1)]
+    units = [(frame, o) for o in range(0 if background and pred is not None else 1, n_objects + 1)]
     buf, m, _ = _launch(gt, pred, units, cap, False)
     flat = buf.cpu().numpy()                                      # the one copy (and the one synchronisation)
     counts_h, points_h = flat[:m], flat[2 * m:].reshape(m, -1)
