@@ -662,6 +662,70 @@ int ivosw_qa_counts_videos(const ivosw_qa_video_t* videos, int n_videos, int64_t
 int ivosw_qa_targets(const int64_t* counts, const int* n_obj, const int* lengths, int n_seqs, int metric, const float* scores,
                      double* target, uint8_t* valid, float* loss, float* diff, int* n_valid, ivosw_stream_t stream);
 
+/* ------------------------------------------------------------------ augmented assessment samples: one fused warp per batch ---- */
+/* Replaces what an AssessNet training loop does to its samples on the host (datasets/transforms_assess.py: Resize, RandomAffine with
+ * its retry loop, AdditiveNoise, RandomContrast, RandomHorizontalFlip, ToTensor and the upload): every sample (video v, frame f, object
+ * o) of a batch is resampled through ONE inverse affine map from sources that already live on the device, at one output size Ho x Wo.
+ *
+ * videos: a HOST array of n_videos (1 .. IVOSW_MAX_JF_VIDEOS) descriptors with DEVICE pointers: frames (IVOSW_FRAMES_F32 [n,3,H,W] or
+ * IVOSW_FRAMES_RGBX8 [n,H,W,4]), gt uint8 [n,H,W], planes uint8 [n_obj][n][H][W] (what ivosw_qa_quantize writes), obj_ids.
+ * samples_host: a HOST array of n_samples rows, read during the call only: v, f, o (o indexes obj_ids), n_cand (0 ..
+ * IVOSW_QA_AUG_MAX_CAND) candidate inverse maps and one post map of six fp32 each (a b c d e f), noise, contrast.  The rows travel in the
+ * kernel arguments, a group of samples per launch (at most 64; as many as fit the 4 KB a launch carries), so the call allocates
+ * nothing, copies nothing and is capture-safe.
+ *
+ * THE SAMPLING RULE (the definition; every fp32 operation is rounded by itself, no FMA contraction):
+ *   coordinates  destination pixel (x, y), inverse map M:  sx = fl(fl(fl(a*x) + fl(b*y)) + c),  sy = fl(fl(fl(d*x) + fl(e*y)) + f).
+ *                The full map of a candidate is post applied to (x, y) first, then the candidate; the call composes the two in
+ *                float64 - a' = a*pa + b*pd, b' = a*pb + b*pe, c' = (a*pc + b*pf) + c, the second row likewise, each float64 operation
+ *                rounded by itself - and rounds to fp32 once.  "No candidate" is post alone.
+ *   bilinear     (img, prob)  x0 = floor(sx), fx = sx - x0, the same in y; taps (x0 | x0+1, y0 | y0+1); a tap outside the source reads
+ *                0.0; top = v00 + fx * (v10 - v00), bot = v01 + fx * (v11 - v01), v = top + fy * (bot - top).  Integer translations,
+ *                the flip and the identity therefore copy source values exactly.
+ *   sources      fp32 frames as they are; an RGBX8 byte and a plane byte b as float32(b) / 255.0f, correctly rounded (the ROI
+ *                sampler's conversion; equal to float32(float64(b) / 255) for all 256 bytes).
+ *   nearest      (label)  tap (floor(sx + 0.5f), floor(sy + 0.5f)); outside the source 0, inside gt[tap] == obj_ids[o].
+ *   photometric  (img only)  t = clip(fl(v + noise), 0, 1), out = clip(fl(t * contrast), 0, 1).
+ *   mask         255 where prob > 0.8f, else 0 (on an unwarped plane: byte >= 205, metrics' QA_THRESHOLD).
+ * Where a map's coordinates overflow fp32 (an infinite or NaN sx or sy) the values of that pixel are undefined.
+ *
+ * Candidate selection (RandomAffine's retry loop without a host round trip): a first launch finds, for every candidate and for "no
+ * candidate", whether the nearest-warped label over the Ho x Wo grid holds a 0 and whether it holds a 1 - one workgroup per pair, two
+ * flag bytes stored by one lane, no atomics - into the caller's workspace (ivosw_qa_augment_ws_bytes(n_samples); 0 for a refused
+ * count; ws may be NULL when every n_cand is 0, and the launch is skipped then).  The warp launch takes, per sample, the first
+ * candidate whose number of distinct label values equals that of "no candidate" - the reference's len(np.unique(segmap_aug)) ==
+ * num_objs - else "no candidate", its fallback to the untransformed sample, and writes its index (n_cand for none) to chosen.
+ *
+ * Outputs (device): img fp32 [N,3,Ho,Wo], prob fp32 [N,Ho,Wo], label uint8 [N,Ho,Wo] (1 = the object), mask uint8 [N,Ho,Wo], chosen
+ * int32 [N].  label with obj_ids = [1] and mask with thr = 205 are what ivosw_qa_counts_videos takes as a 1-object video of N frames.
+ * One destination pixel per lane is the only path: four pixels of a row per lane with float4 stores were built and measured slower
+ * (the taps are gathers; profiles/augment_probe.txt of the change that added this entry), so there is no vector variant and no switch.
+ * Refused (IVOSW_ERR_ARG) before any launch, nothing written, the message names the argument or the sample: a NULL pointer; n_videos
+ * outside 1 .. 32; n_samples < 1 (or above IVOSW_QA_AUG_MAX_SAMPLES); Ho or Wo outside 1 .. 65535; Ho * Wo >= 2^31; a video with
+ * n_frames, H or W < 1, H or W > 2^24, H * W >= 2^31 or n_obj outside 1 .. 32; an unknown frames_kind; frames off the 4-byte grid; a sample whose v,
+ * f or o is out of range; n_cand outside 0 .. 12; a non-finite map entry, noise or contrast; a workspace that is too small; an output
+ * that overlaps a source or the workspace; a workspace that overlaps a source.                                                                                          */
+#define IVOSW_QA_AUG_MAX_CAND 12
+#define IVOSW_QA_AUG_MAX_SAMPLES (1 << 20)
+typedef struct ivosw_qa_aug_video {
+    const void* frames;                          /* device */
+    const uint8_t* gt;                           /* device */
+    const uint8_t* planes;                       /* device */
+    int frames_kind;                             /* IVOSW_FRAMES_* */
+    int n_frames, H, W, n_obj;
+    uint8_t obj_ids[32];
+} ivosw_qa_aug_video_t;
+typedef struct ivosw_qa_aug_sample {
+    int v, f, o, n_cand;
+    float cand[IVOSW_QA_AUG_MAX_CAND][6];
+    float post[6];
+    float noise, contrast;
+} ivosw_qa_aug_sample_t;
+size_t ivosw_qa_augment_ws_bytes(int n_samples);
+int ivosw_qa_augment(const ivosw_qa_aug_video_t* videos, int n_videos, const ivosw_qa_aug_sample_t* samples_host, int n_samples,
+                     int Ho, int Wo, float* img, float* prob, uint8_t* label, uint8_t* mask, int32_t* chosen, void* ws,
+                     size_t ws_bytes, ivosw_stream_t stream);
+
 /* ------------------------------------------------------------------ segmentation epilogue (8f-4) */
 /* Replaces, per frame batch, F.interpolate(logits, (H,W), 'bilinear', align_corners=True) -> argmax(dim=1)
  * [-> .float()] and the final torch.softmax(cat(probs), 1) of utils/utils_manet.py:78-84,110-116,146-151,

@@ -25,6 +25,7 @@ MAX_SEQS = 128                                       # IVOSW_MAX_SEQS
 MAX_CANDIDATES = 16                                  # IVOSW_MAX_CANDIDATES
 FRAMES_F32, FRAMES_RGBX8 = 0, 1                      # IVOSW_FRAMES_*
 MAX_JF_VIDEOS = 32                                   # IVOSW_MAX_JF_VIDEOS
+QA_AUG_MAX_CAND = 12                                 # IVOSW_QA_AUG_MAX_CAND
 METRIC_J, METRIC_F, METRIC_J_AND_F = 0, 1, 2         # IVOSW_METRIC_*
 OUT_RGB8, OUT_RGBX8 = 0, 1                           # IVOSW_OUT_*
 OVERLAY_DAVIS, OVERLAY_FADE, OVERLAY_CHECKER, OVERLAY_COLOR = 0, 1, 2, 3      # IVOSW_OVERLAY_*
@@ -51,6 +52,18 @@ class QaVideo(C.Structure):
     """ivosw_qa_video_t: one video of ivosw_qa_counts_videos (device label map and byte planes [O,N,H,W], the plane threshold)."""
     _fields_ = [("gt", C.c_void_p), ("planes", C.c_void_p), ("n_frames", C.c_int), ("H", C.c_int), ("W", C.c_int), ("n_obj", C.c_int),
                 ("obj_ids", C.c_uint8 * 32), ("bound_pix", C.c_int), ("thr", C.c_uint8)]
+
+
+class AugVideo(C.Structure):
+    """ivosw_qa_aug_video_t: one source video of ivosw_qa_augment (device frames, label map and byte planes [O,N,H,W])."""
+    _fields_ = [("frames", C.c_void_p), ("gt", C.c_void_p), ("planes", C.c_void_p), ("frames_kind", C.c_int), ("n_frames", C.c_int),
+                ("H", C.c_int), ("W", C.c_int), ("n_obj", C.c_int), ("obj_ids", C.c_uint8 * 32)]
+
+
+class AugSample(C.Structure):
+    """ivosw_qa_aug_sample_t: one sample of ivosw_qa_augment (host row: source unit, candidate and post inverse maps, noise, contrast)."""
+    _fields_ = [("v", C.c_int), ("f", C.c_int), ("o", C.c_int), ("n_cand", C.c_int), ("cand", C.c_float * 6 * 12), ("post", C.c_float * 6),
+                ("noise", C.c_float), ("contrast", C.c_float)]
 
 
 class Overlay(C.Structure):
@@ -153,6 +166,8 @@ SIGNATURES = {
     "ivosw_qa_counts_ws_bytes": (_sz, [_p, _i]),
     "ivosw_qa_counts_videos": (_i, [_p, _i, _p, _p, _sz, _p]),
     "ivosw_qa_targets": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "ivosw_qa_augment_ws_bytes": (_sz, [_i]),
+    "ivosw_qa_augment": (_i, [_p, _i, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
     "ivosw_seg_epilogue": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, C.c_long, C.c_long, _p, _p, _p, _p]),
     "ivosw_atnet_epilogue": (_i, [_p, _p] + [_i] * 8 + [_f, _f, _f, _p, _p, C.c_long, _p, _p, _p]),
     "ivosw_ipn_dilate": (_i, [_p, _i, _i, _i, _i, _p, _p]),

@@ -79,6 +79,10 @@ DEFAULTS = dict(
     qa_report=False,                   # true (wild setting, method ours | worst): per interaction the reference's training-loop measures of the
                                        # AssessNet scores against the true per-unit targets - qa_loss (mean squared), qa_diff (mean absolute)
                                        # and valid/units - beside corr, and their session means under "qa" in summary.json
+    qa_augment=False,                  # true (needs qa_report=true): the report line gains `aug loss .. diff .. n ..`, the same measures on ONE
+                                       # augmented copy of every unit under the reference's train transform (Resize, RandomAffine, AdditiveNoise,
+                                       # RandomContrast, RandomHorizontalFlip; datasets.transforms_assess: one fused warp on the device), seeded
+                                       # from the run's seed, and "qa" in summary.json an "augmented" entry; false: no call, file or log line differs
     scribbles="frame",                 # what the synthetic session's robot hands out: "frame" (a scribble only names the annotated frame), or
                                        # "paths": one real polyline per object in davisinteractive's schema, drawn on the device at the stand-in's
                                        # logit resolution (utils.scribbles.scribble_maps) and fed to the stand-in VOS model
@@ -211,6 +215,17 @@ def qa_option(cfg):
     return save_probs, qa_report
 
 
+def qa_augment_option(cfg):
+    """cfg.qa_augment (absent: False).  Refused: a value that is not a bool; true without qa_report=true (the augmented measures extend
+    the report, there is nothing to extend elsewhere)."""
+    on = cfg.get("qa_augment", False)
+    if not isinstance(on, bool):
+        raise ValueError(f"qa_augment must be true or false, got {on!r}")
+    if on and cfg.get("qa_report", False) is not True:
+        raise ValueError("qa_augment=true needs qa_report=true: it adds the measures of the augmented samples to that report")
+    return on
+
+
 _QA_LABELS_NOTE = ("[ivos-w] qa_report under masks=labels: the soft values are gone, the report scores the one-hot planes of the label map "
                    "(255 where the label is the object, else 0)")
 
@@ -229,8 +244,30 @@ class QaSession:
             utils_agent.score_tap = []
             if masks == "labels":
                 print(_QA_LABELS_NOTE)
+        self.augment = None                                                # qa_augment: (assess_net, seed), set by enable_augment
+        self.aug_frames = None                                             # the frames of the current sequence, set by the loop
         if self.save_probs:
             print(f"[ivos-w] save_probs=true: 8-bit probability planes of every interaction under {self.out_dir} (quantised on the device)")
+
+    def enable_augment(self, assess_net, seed):
+        """qa_augment=true: ``after`` also reports on one augmented copy of every unit (utils_agent.assess_report_augmented)."""
+        from .utils import misc
+        self.augment = (assess_net, int(seed))
+        self.aug_loss, self.aug_diff, self.aug_valid, self.aug_calls = misc.AverageMeter(), misc.AverageMeter(), 0, 0
+        print("[ivos-w] qa_augment=true: the report also scores one augmented copy of every unit (train transform, one fused warp on the device)")
+
+    def _after_augmented(self, gt_masks, planes, n_objects):
+        from .utils import utils_agent
+        assess_net, seed = self.augment
+        rep, _ = utils_agent.assess_report_augmented([(self.aug_frames, gt_masks, planes, n_objects)], assess_net, self.metric,
+                                                     seed=seed + self.aug_calls)
+        self.aug_calls += 1
+        loss, diff, n_valid = float(rep[0, 0]), float(rep[0, 1]), int(rep[0, 2])
+        if n_valid:
+            self.aug_loss.update(loss)
+            self.aug_diff.update(diff)
+        self.aug_valid += n_valid
+        return f"aug loss {loss:.4f} diff {diff:.4f} n {n_valid} "
 
     def __enter__(self):
         return self
@@ -267,13 +304,19 @@ class QaSession:
             self.diff.update(diff)
         self.valid += n_valid
         self.units += units
-        return f"qa_loss: {loss:.4f} qa_diff: {diff:.4f} valid: {n_valid}/{units} "
+        text = f"qa_loss: {loss:.4f} qa_diff: {diff:.4f} valid: {n_valid}/{units} "
+        if self.augment is not None:
+            text += self._after_augmented(gt_masks, planes, n_objects)
+        return text
 
     def summary(self):
         """The "qa" block of summary.json (None without qa_report)."""
         if not self.qa_report:
             return None
-        return {"loss": float(self.loss.avg), "diff": float(self.diff.avg), "valid": int(self.valid), "units": int(self.units)}
+        out = {"loss": float(self.loss.avg), "diff": float(self.diff.avg), "valid": int(self.valid), "units": int(self.units)}
+        if self.augment is not None:
+            out["augmented"] = {"loss": float(self.aug_loss.avg), "diff": float(self.aug_diff.avg), "valid": int(self.aug_valid)}
+        return out
 
 
 def write_image(path_stem, rgb):
@@ -385,6 +428,7 @@ def parse_cli(argv, **overrides):
         metric_option(cfg)
         cfg["overlay"] = overlay_option(cfg)[0]
         qa_option(cfg)
+        qa_augment_option(cfg)
         scribbles_option(cfg)
         robot_option(cfg)
         robot_background_option(cfg)
@@ -688,6 +732,7 @@ def run_eval(cfg, backbone="MANet"):
     rescore = rescore_option(cfg)
     overlay = overlay_option(cfg)
     qa = qa_option(cfg)
+    qa_aug = qa_augment_option(cfg)
     scribble_mode = scribbles_option(cfg)
     robot, robot_min_nodes = robot_option(cfg)
     robot_background = robot_background_option(cfg)
@@ -716,6 +761,8 @@ def run_eval(cfg, backbone="MANet"):
     os.makedirs(report_dir, exist_ok=True)
     corr_all, rec_time, seen_seq = misc.AverageMeter(), misc.AverageMeter(), {}
     qa_sess = QaSession(cfg, qa, metric, masks) if any(qa) else None
+    if qa_aug:
+        qa_sess.enable_augment(assess_net, cfg.seed)
     with SyntheticSession(davis, cfg.data.subset, metric, max_nb, report_dir, seed=int(cfg.seed), scribbles=scribble_mode, robot=robot,
                           robot_min_nodes=robot_min_nodes, **(dict(robot_background=True) if robot_background else {})) as sess, \
             (qa_sess or contextlib.nullcontext()):
@@ -771,6 +818,8 @@ def run_eval(cfg, backbone="MANet"):
             if overlay[0] != "none":                                  # what the annotator is shown: the candidates with the current masks on them
                 write_overlays(overlay, report_dir, sequence, seen_seq[sequence], n_interaction, all_F, labels, n_objects, candidates, device)
             sess.submit_masks(labels, next_scribble_frame_candidates=candidates)
+            if qa_aug:
+                qa_sess.aug_frames = all_F
             qa_text = "" if qa_sess is None else qa_sess.after(sequence, seen_seq[sequence], n_interaction, davis.load_annotations(sequence),
                                                                labels, all_P, n_objects, device)
             corr = float(np.corrcoef([quality, quality_pred])[0, 1]) if quality_pred is not None else float("nan")
@@ -818,6 +867,7 @@ def run_eval_real(cfg, backbone, device):
     metric_mode = metric_option(cfg)
     overlay = overlay_option(cfg)
     qa = qa_option(cfg)
+    qa_aug = qa_augment_option(cfg)
     if masks == "labels":
         print(_MASKS_NOTE)
     misc.set_random_seed(int(cfg.seed))
@@ -834,6 +884,8 @@ def run_eval_real(cfg, backbone, device):
     seen_seq, frames_of = {}, {}
     rec_time, corr_all, final_q = misc.AverageMeter(), misc.AverageMeter(), misc.AverageMeter()
     qa_sess = QaSession(cfg, qa, metric, masks) if any(qa) else None
+    if qa_aug:
+        qa_sess.enable_augment(assess_net, cfg.seed)
     with DavisInteractiveSession(host="localhost", davis_root=root, subset=cfg.data.subset, metric_to_optimize=metric,
                                  max_nb_interactions=max_nb, max_time=int(cfg.davis_interactive.max_time_per_interaction) or None,
                                  report_save_dir=report_dir) as sess, (qa_sess or contextlib.nullcontext()):
@@ -890,6 +942,8 @@ def run_eval_real(cfg, backbone, device):
             if overlay[0] != "none":
                 write_overlays(overlay, report_dir, sequence, seen_seq[sequence], n_interaction, all_F, labels, n_objects, [next_frame], device)
             sess.submit_masks(new_masks, next_scribble_frame_candidates=[next_frame])
+            if qa_aug:
+                qa_sess.aug_frames = all_F
             qa_text = "" if qa_sess is None else qa_sess.after(sequence, seen_seq[sequence], n_interaction, gt_masks, labels, all_P, n_objects,
                                                                device)
             corr = float(np.corrcoef([quality, quality_pred])[0, 1]) if quality_pred is not None else float("nan")

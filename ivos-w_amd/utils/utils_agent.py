@@ -338,6 +338,51 @@ def assess_report(videos, scores, metric, thr=None, bound_th=0.008):
     return res.report.cpu().numpy(), res                                  # the one D2H copy of the call
 
 
+def assess_report_augmented(videos, assess_net, metric, transform=None, seed=None, batch=32, thr=None, bound_th=0.008):
+    """``assess_report`` on ONE augmented copy of every unit, as an AssessNet training step would see it, without leaving the device:
+    datasets.transforms_assess (one fused warp per batch of ``batch`` samples) -> ``assess_net.forward(img, prob)`` -> the count pass on
+    (label, mask) as a 1-object video of N frames -> ivosw_qa_targets -> ONE copy of [loss, diff, n_valid].
+    ``videos`` = [(frames (float32 device tensor | PackedFrames | host tensor), gt_labels [N,H,W], all_P | store | uint8 planes [O,N,H,W],
+    n_objects), ...], all of one frame size unless ``transform`` resizes; the units run video-major, object-major, frame-minor.
+    ``transform``: a transforms_assess.Compose (default: the reference's train pipeline at the first video's size).  ``seed``: the host
+    streams (``random``, ``np.random``) are seeded with it for the draws and put back afterwards; None draws from them as they are.
+    Returns (report float32 numpy [1, 3] = loss, diff, n_valid over all units, QaTargets)."""
+    import random as _random
+    from .. import metrics
+    from ..datasets import transforms_assess as T
+    thr = metrics.QA_THRESHOLD if thr is None else thr
+    device = next(assess_net.parameters()).device
+    table, samples = [], []
+    for v, (frames, gt, probs, n_objects) in enumerate(videos):
+        if not _is_packed(frames) and not frames.is_cuda:
+            frames = frame_cache.get(frames, device)
+        planes = probs if (isinstance(probs, torch.Tensor) and probs.dtype == torch.uint8) else metrics.quantize_probs(probs, n_objects)
+        gt = metrics._as_labels(gt, device)
+        table.append((frames, gt, planes.to(device).contiguous()))
+        samples += [(v, f, o) for o in range(int(n_objects)) for f in range(int(gt.shape[0]))]
+    if transform is None:
+        transform = T.train_transform(size=(int(table[0][1].shape[2]), int(table[0][1].shape[1])))
+    state = None
+    if seed is not None:
+        state = (_random.getstate(), np.random.get_state())
+        _random.seed(int(seed))
+        np.random.seed(int(seed) % (1 << 32))
+    try:
+        scores, labels, masks = [], [], []
+        for a in range(0, len(samples), batch):
+            out = transform(T.DeviceSamples(table, samples[a:a + batch]))
+            scores.append(assess_net.forward(out["img"], out["prob"]).reshape(-1))
+            labels.append(out["label"])
+            masks.append(out["mask"])
+    finally:
+        if state is not None:
+            _random.setstate(state[0])
+            np.random.set_state(state[1])
+    label, mask = torch.cat(labels), torch.cat(masks)
+    res = metrics.qa_targets([(label, mask[None], 1)], metric, scores=torch.cat(scores), thr=thr, bound_th=bound_th)
+    return res.report.cpu().numpy(), res                                  # the one D2H copy of the call
+
+
 def _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, counts, mask_quality, prev_frames, k=1, as_list=False,
                  rescore="all", gap=1):
     """wild/worst and wild/ours (utils/utils_agent.py:111-122) with the chain quality -> state -> Brain -> argmax on the
