@@ -7,12 +7,40 @@
 //
 // GEMM view: M = B*Ho*Wo output pixels, N = Cout, K = KH*KW*Cin.  A K-tile is 128 bytes of one filter tap
 // (64 bf16 / 32 fp32 channels), so an A row is one contiguous 128-B NHWC segment (or zeros at the border)
-// and a B row is 128 B of the K-major packed weights.  Tiles are staged global -> registers -> LDS
-// (double-buffered, one barrier per K-tile, next tile's loads in flight under the MFMAs); the LDS image is
-// XOR-swizzled at 16-B granularity (chunk ^= (row>>1)&7) so both the 8-lane ds_write_b128 groups and the
-// 16-lane ds_read_b128 groups are bank-conflict free.  bf16 mode: v_mfma_f32_32x32x16_bf16; fp32 parity
-// mode: v_mfma_f32_32x32x2_f32 (exact fp32 fma chain).  The accumulator tile goes through LDS once so that
-// global stores (and residual loads) are full 16-B-per-lane row segments.
+// and a B row is 128 B of the K-major packed weights.  The LDS image of a tile is XOR-swizzled at 16-B
+// granularity (chunk ^= (row>>1)&7) so both the 8-lane write groups and the 16-lane ds_read_b128 groups are
+// bank-conflict free.  bf16 mode: v_mfma_f32_32x32x16_bf16; fp32 parity mode: v_mfma_f32_32x32x2_f32 (exact
+// fp32 fma chain); IVOSW_F32X3: three bf16 MFMAs per pair of split operands.  The accumulator tile goes through
+// LDS once so that global stores (and residual loads) are full 16-B-per-lane row segments.
+//
+// Map of the file.  Shared pieces (mfma_tile.h holds the ones that know nothing of ConvArgs):
+//   mma_step<T>                      one fragment pair into one accumulator tile                             (mfma_tile.h)
+//   acc_clear, acc_to_lds            accumulator tiles: zero, spill to an fp32 LDS tile through the C/D map  (mfma_tile.h)
+//   ring_wait                        counted vmcnt wait of an S-deep LDS-DMA ring                            (mfma_tile.h)
+//   epilogue_store                   LDS tile + bias (+ residual) -> ReLU -> global, all three formats
+//   mma_step_x3, ktile_mma_x3        the split-format K-tile from a swizzled tile image
+//   ktile_mma_x3_rows                the same from rows with their own address and key (patch rows)
+//   WeightRows                       a patch kernel loader wave's 8-row DMA groups of a K-major weight matrix
+//   prefetch_residual                bf16 residual tile -> registers in front of the K loop
+//   PatchRows, patch_loader_run      a loader wave's rows of a halo patch; the (slice, tap) step loop of the loader waves
+// Kernels:
+//   conv_igemm_kernel                register-staged tiles (the stem): own single-buffered loop of mma_step / ktile_mma_x3
+//   conv_igemm_dma_kernel            every wave loads and multiplies: own gather + ring_wait + prefetch_residual + own K-tile body of mma_step / ktile_mma_x3
+//   conv_igemm_ws_kernel             loader waves (the same gather, written out again, + ring_wait) | compute waves (the same K-tile body)
+//                                    These three keep the gather, the four-K-step body and the zeroing and spill loops as their own text.  Around a
+//                                    loader struct hipcc schedules the set-up differently (+ 20 ... + 120 instructions; accum_offset moved in
+//                                    conv_igemm_ws_kernel<float, 4, 2, 2, 1, 3, 4, *> and others); behind a shared K-tile function or acc_clear it
+//                                    numbers the K loop's accumulator registers differently, and with those and acc_to_lds the fp32 mode lost
+//                                    0.3 - 0.75 % on alternating runs (LAB_NOTES.md, "conv.hip: shared pieces").  As written, their fp32 and
+//                                    bf16x3 code is the parent's, instruction for instruction.
+//   conv3x3_patch_kernel             bf16 3x3 on an LDS-resident patch: PatchRows + WeightRows + patch_loader_run | own fragment rows + mma_step
+//   conv3x3_patch_x3_kernel          the same in the split format: the same loader | ktile_mma_x3_rows
+//   res2_tail_x3_kernel, res3_tail_x3_kernel   3x3 -> expand + residual in one launch.  Their own text throughout: the loader waves carry
+//                                    two weight streams and the barriers between the phases, and both kernels sit at the edge of their
+//                                    register budget - res2_tail_x3_kernel goes from 200 to 256 VGPRs and spills when even its accumulator
+//                                    loops become acc_clear / acc_to_lds, res3_tail_x3_kernel keeps 64 B of scratch with shared weight rows.
+// All of them end in an accumulator spill through the C/D map (acc_to_lds in the patch kernels) and a store pass (epilogue_store, or the kernel's own pixel-mapped /
+// split-format one).
 #include <stdlib.h>
 
 #include <type_traits>
@@ -24,7 +52,6 @@
 #include "mfma_tile.h"
 
 namespace ivosw {
-
 
 // eight fp32 values -> four packed bf16 hi pairs (truncation: the top halves) and four packed lo pairs (RNE(x - hi), an exact
 // difference): the producer-side split of the IVOSW_F32X3 activation format, ~3 VALU per value ONCE instead of 24 per 8-float
@@ -176,6 +203,12 @@ __device__ __forceinline__ void split8_x3(const u32x4& c0, const u32x4& c1, u32x
         lo[q] = pack2_bf16(l0, l1);
     }
 }
+// three products per operand pair (hi, lo) x (hi, lo): ah bh + ah bl + al bh
+__device__ __forceinline__ void mma_step_x3(u32x4 ah, u32x4 al, u32x4 bh, u32x4 bl, f32x16& acc) {
+    acc = mfma_bf16(ah, bh, acc);
+    acc = mfma_bf16(ah, bl, acc);
+    acc = mfma_bf16(al, bh, acc);
+}
 // PRE: the activation K-tile is already in the split layout (every layer behind the stem: epilogue_store writes it) - hi and lo
 // fragments are read like the weights', no VALU; !PRE (the stem, whose operand is gathered from the fp32 ROI tile): split here.
 template <int TM, int TN, bool PRE>
@@ -207,15 +240,44 @@ __device__ __forceinline__ void ktile_mma_x3(f32x16 (&acc)[TM][TN], unsigned a_b
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int j = 0; j < TN; ++j) {
-                acc[i][j] = mfma_bf16(ah[i], bh[s][j], acc[i][j]);
-                acc[i][j] = mfma_bf16(ah[i], bl[s][j], acc[i][j]);
-                acc[i][j] = mfma_bf16(al[i], bh[s][j], acc[i][j]);
-            }
+            for (int j = 0; j < TN; ++j) mma_step_x3(ah[i], al[i], bh[s][j], bl[s][j], acc[i][j]);
+    }
+}
+// The same K-tile (PRE) where every pixel row has its own LDS address and swizzle key: a patch row at one filter tap (key: patch_key).
+// hi at the row's chunk 2 s + h, lo at 4 + 2 s + h.  Weights: the slot at b_base, channel tiles 0 .. TN - 1, this lane's row
+// lrow of each.  (The tail kernels write the same steps out: see the map.)
+template <int TM, int TN>
+__device__ __forceinline__ void ktile_mma_x3_rows(f32x16 (&acc)[TM][TN], const unsigned (&arow)[TM], const unsigned (&akey)[TM],
+                                                  unsigned b_base, int lrow, int lhalf) {
+    u32x4 ah[2][TM], al[2][TM], bh[2][TN], bl[2][TN];
+    auto frag_read = [&](int s, int buf) {
+        const int ch = 2 * s + lhalf;
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+            ah[buf][i] = lds_read_b128(arow[i] + ((ch ^ akey[i]) << 4));
+            al[buf][i] = lds_read_b128(arow[i] + (((4 + ch) ^ akey[i]) << 4));
+        }
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            bh[buf][j] = lds_read_b128(b_base + swz(j * 32 + lrow, ch));
+            bl[buf][j] = lds_read_b128(b_base + swz(j * 32 + lrow, 4 + ch));
+        }
+    };
+    frag_read(0, 0);
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        lds_wait();
+        if (s < 1) frag_read(1, 1);
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) mma_step_x3(ah[s][i], al[s][i], bh[s][j], bl[s][j], acc[i][j]);
     }
 }
 
-// WAVES_M x WAVES_N waves (4 total), each owning TM x TN 32x32 MFMA tiles.
+// WAVES_M x WAVES_N waves (4 total), each owning TM x TN 32x32 MFMA tiles.  Tiles are staged global -> registers -> LDS
+// (double-buffered, one barrier per K-tile, next tile's loads in flight under the MFMAs); the LDS reads are ordinary loads on
+// purpose (nothing is in flight that the compiler could not order them against), so the K loop is this kernel's own.
 template <typename T, int WAVES_M, int WAVES_N, int TM, int TN, bool STEM, bool X3 = false>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs p) {
     static_assert(!X3 || sizeof(T) == 4, "the three-pass split is a mode of the fp32 tensors");
@@ -337,32 +399,21 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs p) {
             // 16-B chunk (2*ks + lhalf): bf16 -> k = 16*ks + 8*lhalf + [0,8) (one 32x32x16 MFMA);
             // fp32 -> 4 floats feeding four 32x32x2 MFMAs (k-permutation identical for A and B)
             const int ch = 2 * ks + lhalf;
-            uint4 fa[TM], fb[TN];
+            u32x4 fa[TM], fb[TN];
 #pragma unroll
-            for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const uint4*>(As + swz((wm * TM + i) * 32 + lrow, ch));
+            for (int i = 0; i < TM; ++i) fa[i] = *reinterpret_cast<const u32x4*>(As + swz((wm * TM + i) * 32 + lrow, ch));
 #pragma unroll
-            for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const uint4*>(Bs + swz((wn * TN + j) * 32 + lrow, ch));
+            for (int j = 0; j < TN; ++j) fb[j] = *reinterpret_cast<const u32x4*>(Bs + swz((wn * TN + j) * 32 + lrow, ch));
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    if constexpr (ES == 2) {
-                        union { uint4 u; bf16x8 v; } ua, ub;
-                        ua.u = fa[i]; ub.u = fb[j];
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ua.v, ub.v, acc[i][j], 0, 0, 0);
-                    } else {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(fa[i].x), __uint_as_float(fb[j].x), acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(fa[i].y), __uint_as_float(fb[j].y), acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(fa[i].z), __uint_as_float(fb[j].z), acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(fa[i].w), __uint_as_float(fb[j].w), acc[i][j], 0, 0, 0);
-                    }
-                }
+                for (int j = 0; j < TN; ++j) mma_step<T>(fa[i], fb[j], acc[i][j]);
         }
         if (kt + 1 < nk) store_tiles(buf ^ 1);
         __syncthreads();
     }
 
-    // ---- epilogue phase 1: accumulators -> LDS fp32 tile [BM][BN] (C/D map: col = lane&31, row = (r&3)+8*(r>>2)+4*(lane>>5))
+    // ---- epilogue phase 1: accumulators -> LDS fp32 tile [BM][BN]
     float* Cs = reinterpret_cast<float*>(lds);
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -376,6 +427,45 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs p) {
             }
     __syncthreads();
     epilogue_store<T, BM, BN>(p, Cs, m0, n0, M, tid);
+}
+
+// BG 8-row groups (one 1-KiB DMA instruction each) of a K-major [rows][K] weight matrix, owned by (loader) wave `owner`: tile rows
+// (owner * BG + i) * 8 + (lane >> 3), which are rows row0 + ... of the matrix.  Source-side swizzle as in conv_igemm_dma_kernel.
+template <typename T, int BG_>
+struct WeightRows {
+    static constexpr int BG = BG_, CE = 16 / (int)sizeof(T);
+    const T* src[BG];
+    int owner;
+    __device__ __forceinline__ WeightRows(const T* Wt, int row0, int K, int owner_wave, int lane) : owner(owner_wave) {
+        const int rsub = lane >> 3, cpos = lane & 7;
+#pragma unroll
+        for (int i = 0; i < BG; ++i) {
+            const int row = (owner * BG + i) * 8 + rsub;
+            src[i] = Wt + (long)(row0 + row) * K + (cpos ^ ((row >> 1) & 7)) * CE;
+        }
+    }
+    // the tile at element offset `ofs` of every row -> the [rows][128 B] image at `slot`
+    __device__ __forceinline__ void issue(long ofs, unsigned char* slot) const {
+#pragma unroll
+        for (int i = 0; i < BG; ++i) dma16(src[i] + ofs, slot + (owner * BG + i) * 1024);
+    }
+};
+
+// residual tile -> registers before anything else (bf16: 16 B per item): its HBM/L2 latency hides under the
+// whole K loop instead of sitting in the epilogue.  These loads are older than every DMA, and loads return
+// in order, so the counted vmcnt waits of the K loop stay valid.
+template <typename T, int BM, int BN, int NT>
+__device__ __forceinline__ void prefetch_residual(const ConvArgs& p, int m0, int n0, int M, int tid, uint4 (&rres)[(BM * (BN / 8)) / NT]) {
+    if (!p.res) return;
+    const T* R = static_cast<const T*>(p.res);
+#pragma unroll
+    for (int it = 0; it < (BM * (BN / 8)) / NT; ++it) {
+        const int item = it * NT + tid;
+        const int row = item / (BN / 8), cg = item - row * (BN / 8);
+        const int m = min(m0 + row, M - 1);   // clamp instead of branching: a predicated load would be waited for at once
+        if (p.nt & 2) { const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(R + (long)m * p.Cout + n0 + cg * 8)); rres[it] = make_uint4(t[0], t[1], t[2], t[3]); }
+        else rres[it] = *reinterpret_cast<const uint4*>(R + (long)m * p.Cout + n0 + cg * 8);
+    }
 }
 
 // ---------------------------------------------------------------- LDS-DMA pipelined variant (tower convs)
@@ -473,25 +563,10 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void conv_igemm_dma_kernel(
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    // residual tile -> registers before anything else (bf16: 16 B per item): its HBM/L2 latency hides under the
-    // whole K loop instead of sitting in the epilogue.  These loads are older than every DMA, and loads return
-    // in order, so the counted vmcnt waits below stay valid.
     constexpr bool PRE = (ES == 2);
     constexpr int ITEMS = (BM * (BN / 8)) / (NW * 64);
     uint4 rres[PRE ? ITEMS : 1];
-    if constexpr (PRE) {
-        if (p.res) {
-            const T* R = static_cast<const T*>(p.res);
-#pragma unroll
-            for (int it = 0; it < ITEMS; ++it) {
-                const int item = it * (NW * 64) + tid;
-                const int row = item / (BN / 8), cg = item - row * (BN / 8);
-                const int m = min(m0 + row, M - 1);   // clamp instead of branching: a predicated load would be waited for at once
-                if (p.nt & 2) { const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(R + (long)m * p.Cout + n0 + cg * 8)); rres[it] = make_uint4(t[0], t[1], t[2], t[3]); }
-                else rres[it] = *reinterpret_cast<const uint4*>(R + (long)m * p.Cout + n0 + cg * 8);
-            }
-        }
-    }
+    if constexpr (PRE) prefetch_residual<T, BM, BN, NW * 64>(p, m0, n0, M, tid, rres);
 
 #pragma unroll
     for (int s = 0; s < S - 1; ++s)
@@ -502,21 +577,13 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void conv_igemm_dma_kernel(
     int stage = 0;            // ring slot of tile kt
     int fill = S - 1;         // ring slot the next issued tile goes to
     for (int kt = 0; kt < nk; ++kt) {
-        // tiles kt+1 .. kt+ahead were issued after tile kt and may stay in flight
-        const int ahead = min(S - 2, nk - 1 - kt);
-        if (ahead >= 2) wait_vmcnt<2 * LPT>();
-        else if (ahead == 1) wait_vmcnt<LPT>();
-        else wait_vmcnt<0>();
+        ring_wait<S, LPT>(kt, nk);
         __builtin_amdgcn_s_barrier();   // every wave's share of tile kt has landed; every wave is done with tile kt-1
         asm volatile("" ::: "memory");
         if (kt + S - 1 < nk && !ABL(p.debug, 4)) issue(kt + S - 1, fill);   // refill the slot tile kt-1 just vacated
         const unsigned a_base = lds_base + stage * STAGE_BYTES, b_base = a_base + BM * ROWB;
-        if constexpr (X3) {
-            ktile_mma_x3<TM, TN, true>(acc, a_base, b_base, wm, wn, lrow, lhalf);
-            stage = (stage + 1 == S) ? 0 : stage + 1;
-            fill = (fill + 1 == S) ? 0 : fill + 1;
-            continue;
-        }
+        if constexpr (X3) ktile_mma_x3<TM, TN, true>(acc, a_base, b_base, wm, wn, lrow, lhalf);
+        else {
         u32x4 fa[2][TM], fb[2][TN];
         auto frag_read = [&](int ks, int buf) {
             const int ch = 2 * ks + lhalf;
@@ -534,19 +601,8 @@ __global__ __launch_bounds__(WAVES_M * WAVES_N * 64) void conv_igemm_dma_kernel(
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    const u32x4 av = fa[ks & 1][i], bv = fb[ks & 1][j];
-                    if constexpr (ES == 2) {
-                        union { u32x4 u; bf16x8 v; } ua, ub;
-                        ua.u = av; ub.u = bv;
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ua.v, ub.v, acc[i][j], 0, 0, 0);
-                    } else {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(av.x), __uint_as_float(bv.x), acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(av.y), __uint_as_float(bv.y), acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(av.z), __uint_as_float(bv.z), acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(av.w), __uint_as_float(bv.w), acc[i][j], 0, 0, 0);
-                    }
-                }
+                for (int j = 0; j < TN; ++j) mma_step<T>(fa[ks & 1][i], fb[ks & 1][j], acc[i][j]);
+        }
         }
         stage = (stage + 1 == S) ? 0 : stage + 1;
         fill = (fill + 1 == S) ? 0 : fill + 1;
@@ -660,10 +716,7 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + LW) * 64) void conv_igemm_ws_k
             if (s < nk) issue(s, s);
         int fill = S - 1;
         for (int kt = 0; kt < nk; ++kt) {
-            const int ahead = min(S - 2, nk - 1 - kt);
-            if (ahead >= 2) wait_vmcnt<2 * LPT>();
-            else if (ahead == 1) wait_vmcnt<LPT>();
-            else wait_vmcnt<0>();
+            ring_wait<S, LPT>(kt, nk);
             __builtin_amdgcn_s_barrier();   // tile kt landed (all loaders); compute waves are done with tile kt-1
             if (kt + S - 1 < nk) issue(kt + S - 1, fill);
             fill = (fill + 1 == S) ? 0 : fill + 1;
@@ -678,19 +731,7 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + LW) * 64) void conv_igemm_ws_k
     constexpr bool PRE = (ES == 2) && (NW + LW) <= 12;   // 16-wave variant: 128 VGPRs per wave, no room for the residual tile
     constexpr int ITEMS = (BM * (BN / 8)) / (NW * 64);
     uint4 rres[PRE ? ITEMS : 1];
-    if constexpr (PRE) {
-        if (p.res) {
-            const T* R = static_cast<const T*>(p.res);
-#pragma unroll
-            for (int it = 0; it < ITEMS; ++it) {
-                const int item = it * (NW * 64) + tid;
-                const int row = item / (BN / 8), cg = item - row * (BN / 8);
-                const int m = min(m0 + row, M - 1);
-                if (p.nt & 2) { const u32x4 t = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(R + (long)m * p.Cout + n0 + cg * 8)); rres[it] = make_uint4(t[0], t[1], t[2], t[3]); }
-                else rres[it] = *reinterpret_cast<const uint4*>(R + (long)m * p.Cout + n0 + cg * 8);
-            }
-        }
-    }
+    if constexpr (PRE) prefetch_residual<T, BM, BN, NW * 64>(p, m0, n0, M, tid, rres);
     f32x16 acc[TM][TN];
 #pragma unroll
     for (int i = 0; i < TM; ++i)
@@ -706,11 +747,8 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + LW) * 64) void conv_igemm_ws_k
         asm volatile("" ::: "memory");
         if ABL(p.debug, 8) continue;                   // ablation: loaders + barriers only (pure fill rate of the real access pattern)
         const unsigned a_base = lds_base + stage * STAGE_BYTES, b_base = a_base + BM * ROWB;
-        if constexpr (X3) {
-            ktile_mma_x3<TM, TN, true>(acc, a_base, b_base, wm, wn, lrow, lhalf);
-            stage = (stage + 1 == S) ? 0 : stage + 1;
-            continue;
-        }
+        if constexpr (X3) ktile_mma_x3<TM, TN, true>(acc, a_base, b_base, wm, wn, lrow, lhalf);
+        else {
         u32x4 fa[2][TM], fb[2][TN];
         auto frag_read = [&](int ks, int buf) {
             const int ch = 2 * ks + lhalf;
@@ -728,19 +766,8 @@ __global__ __launch_bounds__((WAVES_M * WAVES_N + LW) * 64) void conv_igemm_ws_k
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    const u32x4 av = fa[ks & 1][i], bv = fb[ks & 1][j];
-                    if constexpr (ES == 2) {
-                        union { u32x4 u; bf16x8 v; } ua, ub;
-                        ua.u = av; ub.u = bv;
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ua.v, ub.v, acc[i][j], 0, 0, 0);
-                    } else {
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(av.x), __uint_as_float(bv.x), acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(av.y), __uint_as_float(bv.y), acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(av.z), __uint_as_float(bv.z), acc[i][j], 0, 0, 0);
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(av.w), __uint_as_float(bv.w), acc[i][j], 0, 0, 0);
-                    }
-                }
+                for (int j = 0; j < TN; ++j) mma_step<T>(fa[ks & 1][i], fb[ks & 1][j], acc[i][j]);
+        }
         }
         stage = (stage + 1 == S) ? 0 : stage + 1;
     }
@@ -780,14 +807,80 @@ __device__ __forceinline__ int patch_key(int hy, int hx) {
     return TW == 16 ? ((hx >> 1) & 7) : (((hy & 3) << 1) | ((hx >> 1) & 1));
 }
 
+// A loader wave's share of the halo patch of a tile of F frames x TH x TW pixels at (frame b0, y0, x0): 1-KB DMA row groups lw, lw + LW, ...
+// of the F * (TH + 2) * (TW + 2) patch rows (128 B of one channel slice each), with a validity mask: rows outside the image, past the
+// patch's last row and (F > 1) in frames past the batch read the page of zeros.  KEYXY: swizzle key from the patch coordinates
+// (patch_key), else from the linear row index.
+template <typename T, int LW, int TH, int TW, int F = 1, bool KEYXY = true>
+struct PatchRows {
+    static constexpr int KE = ROWB / (int)sizeof(T), CE = 16 / (int)sizeof(T);
+    static constexpr int HW2 = TW + 2, HP = (TH + 2) * HW2, HRT = F * HP;      // halo rows of the tile
+    static constexpr int NG = (HRT + 7) / 8, MAXG = (NG + LW - 1) / LW;        // 1-KB DMA row groups per patch / per wave at most
+    const T* abase[MAXG];
+    unsigned okmask;
+    int lw, np;                                                                 // np: patch row groups of this wave
+
+    __device__ __forceinline__ PatchRows(const T* X, const T* zeros, int B, int H, int W, int Cin, int b0, int y0, int x0, int lw_, int lane)
+        : okmask(0), lw(lw_), np((NG - lw_ + LW - 1) / LW) {
+        const int rsub = lane >> 3, cpos = lane & 7;
+#pragma unroll
+        for (int i = 0; i < MAXG; ++i) {
+            const int g = lw + LW * i;
+            const int hr = g * 8 + rsub;
+            const int f = F > 1 ? hr / HP : 0, rem = hr - f * HP;
+            const int hy = rem / HW2, hx = rem - hy * HW2;
+            const int y = y0 - 1 + hy, x = x0 - 1 + hx;
+            const bool ok = g < NG && hr < HRT && y >= 0 && y < H && x >= 0 && x < W && (F == 1 || b0 + f < B);   // (frames past the batch in the last F-frame tile read zeros)
+            abase[i] = ok ? X + (((long)(b0 + f) * H + y) * W + x) * Cin + (cpos ^ (KEYXY ? patch_key<TW>(hy, hx) : ((hr >> 1) & 7))) * CE : zeros;
+            okmask |= ok ? (1u << i) : 0u;
+        }
+    }
+    // channel slice c of the patch -> patch buffer pbuf
+    __device__ __forceinline__ void issue(int c, unsigned char* pbuf) const {
+#pragma unroll
+        for (int i = 0; i < MAXG; ++i) {
+            const int g = lw + LW * i;
+            if (g < NG) dma16(abase[i] + (((okmask >> i) & 1u) ? c * KE : 0), pbuf + g * 1024);
+        }
+    }
+};
+
+// The loader waves' step loop of conv3x3_patch_kernel and conv3x3_patch_x3_kernel: nc channel slices x 9 taps; two patch buffers of PB bytes
+// at pbufs (slices alternate), a WR-slot ring of WSLOT-byte weight tiles at wring; weights K-major with Cin channels per tap.
+template <int PB, int WR, int WSLOT, typename Rows, typename Wts>
+__device__ __forceinline__ void patch_loader_run(const Rows& rows, const Wts& wts, unsigned char* pbufs, unsigned char* wring, int nc, int Cin) {
+    const int nj = nc * 9;                                   // (slice, tap) steps
+    auto issue_patch = [&](int c) { rows.issue(c, pbufs + (c & 1) * PB); };
+    auto issue_w = [&](int j) {                              // weight tile of step j = slice * 9 + tap
+        const int c = j / 9, t = j - c * 9;
+        wts.issue((long)t * Cin + c * Rows::KE, wring + (j % WR) * WSLOT);
+    };
+    // issue order: P0 W0 W1 | after barrier j: W(j+2); after barrier (c,3): P(c+1)
+    issue_patch(0);
+    issue_w(0);
+    if (nj > 1) issue_w(1);
+    for (int j = 0; j < nj; ++j) {
+        const int c = j / 9, t = j - c * 9;
+        // younger than W(j) at this point: W(j+1), and P(c+1) during taps 4 and 5 (issued behind W(c*9+5))
+        int younger = (j + 1 < nj) ? Wts::BG : 0;
+        if ((t == 4 || t == 5) && c + 1 < nc) younger += rows.np;
+        wait_vmcnt_n(younger);
+        __builtin_amdgcn_s_barrier();                        // step j: its weights (and patch) landed; step j-1 is done
+        if (j + 2 < nj) issue_w(j + 2);
+        if (t == 3 && c + 1 < nc) issue_patch(c + 1);        // patch buffer (c+1)&1 was last read in slice c-1
+    }
+    __builtin_amdgcn_s_barrier();                            // matches the two epilogue barriers of the compute waves
+    __builtin_amdgcn_s_barrier();
+}
+
 template <int F, int TH, bool KEYXY = true>
 __global__ __launch_bounds__(1024) void conv3x3_patch_kernel(ConvArgs p) {
     typedef bf16_t T;
-    constexpr int TW = TH, HW2 = TW + 2, HP = (TH + 2) * HW2, HRT = F * HP;   // halo rows of the tile
-    constexpr int NG = (HRT + 7) / 8;                                          // 1-KB DMA row groups per patch
-    constexpr int PB = NG * 1024;
+    constexpr int NW = 8, LW = 8, TN = 2, BN = 128, KE = 64;
+    typedef PatchRows<T, LW, TH, TH, F, KEYXY> Rows;
+    constexpr int TW = TH, HW2 = Rows::HW2, HP = Rows::HP;
+    constexpr int PB = Rows::NG * 1024;
     constexpr int BM = F * TH * TW, TM = BM / 128;           // 256 pixels per tile (TM = 2), or 128 (F = 2 frames of 8 x 8: small launches, round 5)
-    constexpr int NW = 8, LW = 8, TN = 2, BN = 128, KE = 64, CE = 8;
     static_assert(BM == 256 || BM == 128, "a tile is 8 or 4 pixel tiles of 32");
     constexpr int WSLOT = BN * ROWB, WR = 3;
     constexpr int W_OFF = 2 * PB;
@@ -818,73 +911,16 @@ __global__ __launch_bounds__(1024) void conv3x3_patch_kernel(ConvArgs p) {
     if (wave >= NW) {
         // ================= loader wave =================
         const int lw = wave - NW;
-        const T* X = static_cast<const T*>(p.x);
-        const T* Wt = static_cast<const T*>(p.w);
-        const T* zeros = static_cast<const T*>(p.zeros);
-        const int rsub = lane >> 3, cpos = lane & 7;
-        constexpr int MAXG = (NG + LW - 1) / LW;
-        const int np = (NG - lw + LW - 1) / LW;              // patch row groups of this wave: lw, lw+8, ...
-        const T* abase[MAXG];
-        unsigned okmask = 0;
-#pragma unroll
-        for (int i = 0; i < MAXG; ++i) {
-            const int g = lw + LW * i;
-            const int hr = g * 8 + rsub;
-            const int f = hr / HP, rem = hr - f * HP;
-            const int hy = rem / HW2, hx = rem - hy * HW2;
-            const int y = y0 - 1 + hy, x = x0 - 1 + hx;
-            const bool ok = g < NG && hr < HRT && y >= 0 && y < p.H && x >= 0 && x < p.W && b0 + f < p.B;   // (frames past the batch in the last 4-frame tile read zeros)
-            abase[i] = ok ? X + (((long)(b0 + f) * p.H + y) * p.W + x) * p.Cin + (cpos ^ (KEYXY ? patch_key<TW>(hy, hx) : ((hr >> 1) & 7))) * CE : zeros;
-            okmask |= ok ? (1u << i) : 0u;
-        }
-        const T* bsrc[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int row = (lw * 2 + i) * 8 + rsub;
-            bsrc[i] = Wt + (long)(n0 + row) * K + (cpos ^ ((row >> 1) & 7)) * CE;
-        }
-        auto issue_patch = [&](int c) {
-            unsigned char* pbuf = lds + (c & 1) * PB;
-#pragma unroll
-            for (int i = 0; i < MAXG; ++i) {
-                const int g = lw + LW * i;
-                if (g < NG) dma16(abase[i] + (((okmask >> i) & 1u) ? c * KE : 0), pbuf + g * 1024);
-            }
-        };
-        auto issue_w = [&](int j) {                          // weight tile of step j = slice * 9 + tap
-            const int c = j / 9, t = j - c * 9;
-            unsigned char* sb = lds + W_OFF + (j % WR) * WSLOT;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) dma16(bsrc[i] + (long)t * p.Cin + c * KE, sb + (lw * 2 + i) * 1024);
-        };
-        // issue order: P0 W0 W1 | after barrier j: W(j+2); after barrier (c,3): P(c+1)
-        issue_patch(0);
-        issue_w(0);
-        if (nj > 1) issue_w(1);
-        for (int j = 0; j < nj; ++j) {
-            const int c = j / 9, t = j - c * 9;
-            // younger than W(j) at this point: W(j+1), and P(c+1) during taps 4 and 5 (issued behind W(c*9+5))
-            int younger = (j + 1 < nj) ? 2 : 0;
-            if ((t == 4 || t == 5) && c + 1 < nc) younger += np;
-            wait_vmcnt_n(younger);
-            __builtin_amdgcn_s_barrier();                    // step j: its weights (and patch) landed; step j-1 is done
-            if (j + 2 < nj) issue_w(j + 2);
-            if (t == 3 && c + 1 < nc) issue_patch(c + 1);    // patch buffer (c+1)&1 was last read in slice c-1
-        }
-        __builtin_amdgcn_s_barrier();                        // matches the two epilogue barriers of the compute waves
-        __builtin_amdgcn_s_barrier();
+        const Rows rows(static_cast<const T*>(p.x), static_cast<const T*>(p.zeros), p.B, p.H, p.W, p.Cin, b0, y0, x0, lw, lane);
+        const WeightRows<T, 2> wts(static_cast<const T*>(p.w), n0, K, lw, lane);
+        patch_loader_run<PB, WR, WSLOT>(rows, wts, lds, lds + W_OFF, nc, p.Cin);
         return;
     }
 
     // ================= compute wave =================
     const int wm = wave >> 1, wn = wave & 1;
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    acc_clear(acc);
     const int lrow = lane & 31, lhalf = lane >> 5;
     const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
     int hb[TM], hy0[TM], hx0[TM];                            // patch row (and line / column) of this lane's output pixel at tap (0,0)
@@ -910,6 +946,7 @@ __global__ __launch_bounds__(1024) void conv3x3_patch_kernel(ConvArgs p) {
             arow[i] = a_base + hr * ROWB;
             asw[i] = KEYXY ? patch_key<TW>(hy0[i] + ky, hx0[i] + kx) : ((hr >> 1) & 7);
         }
+        // the igemm kernels' K-tile body with its own frag_read: the A rows come from patch coordinates
         u32x4 fa[2][TM], fb[2][TN];
         auto frag_read = [&](int ks, int buf) {
             const int ch = 2 * ks + lhalf;
@@ -930,27 +967,16 @@ __global__ __launch_bounds__(1024) void conv3x3_patch_kernel(ConvArgs p) {
 #pragma unroll
             for (int i = 0; i < TM; ++i)
 #pragma unroll
-                for (int jj = 0; jj < TN; ++jj) acc[i][jj] = mfma_bf16(fa[ks & 1][i], fb[ks & 1][jj], acc[i][jj]);
+                for (int jj = 0; jj < TN; ++jj) mma_step<T>(fa[ks & 1][i], fb[ks & 1][jj], acc[i][jj]);
         }
         if (++t == 9) { t = 0; ++c; }
     }
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     float* Cs = reinterpret_cast<float*>(lds);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhalf;
-                const int col = (wn * TN + j) * 32 + lrow;
-                Cs[row * BN + col] = acc[i][j][r];
-            }
+    acc_to_lds<BN>(Cs, acc, wm * TM, wn * TN, lrow, lhalf);
     __syncthreads();
     // rows of the tile are (frame, y, x) inside the tile: map them back to NHWC pixel indices for the store pass
-    ConvArgs q = p;
-    q.res = nullptr;
     constexpr int CPR = BN / 8;
     T* Y = static_cast<T*>(p.y);
     const float4 bb0 = *reinterpret_cast<const float4*>(p.bias + n0 + (tid % CPR) * 8);
@@ -990,9 +1016,10 @@ __global__ __launch_bounds__(1024) void conv3x3_patch_kernel(ConvArgs p) {
 // K order: slice-major (all nine taps of channels 0 .. 31, then 32 .. 63) - the per-tap kernel runs tap-major, so the two differ in the last
 // bits of the fp32 sums (not bit-identical; the test compares them at 1e-6).  LDS: two patch buffers | 3-slot weight ring; the epilogue tile aliases.
 __global__ __launch_bounds__(512) void conv3x3_patch_x3_kernel(ConvArgs p) {
-    constexpr int TH = 16, TW = 16, HW2 = TW + 2, HRT = (TH + 2) * HW2;        // 324 halo rows
-    constexpr int NG = (HRT + 7) / 8, PB = NG * 1024;                          // 41 DMA row groups, 41 984 B per slice
-    constexpr int BM = 256, BN = 64, NW = 4, LW = 4, TM = 2, TN = 2, KE = 32, CE = 4;   // floats per K-tile / per 16-byte chunk
+    constexpr int TH = 16, TW = 16, NW = 4, LW = 4;
+    typedef PatchRows<float, LW, TH, TW> Rows;                                 // 324 halo rows: 41 DMA row groups, 41 984 B per slice
+    constexpr int HW2 = Rows::HW2, PB = Rows::NG * 1024;
+    constexpr int BM = 256, BN = 64, TM = 2, TN = 2, KE = 32;                  // floats per K-tile
     constexpr int WSLOT = BN * ROWB, WR = 3, W_OFF = 2 * PB;
     constexpr int EPI_BYTES = BM * BN * 4, USED = W_OFF + WR * WSLOT;
     constexpr int LDS_BYTES = USED > EPI_BYTES ? USED : EPI_BYTES;
@@ -1011,70 +1038,15 @@ __global__ __launch_bounds__(512) void conv3x3_patch_x3_kernel(ConvArgs p) {
     if (wave >= NW) {
         // ================= loader wave =================
         const int lw = wave - NW;
-        const float* X = static_cast<const float*>(p.x);
-        const float* Wt = static_cast<const float*>(p.w);
-        const float* zeros = static_cast<const float*>(p.zeros);
-        const int rsub = lane >> 3, cpos = lane & 7;
-        constexpr int MAXG = (NG + LW - 1) / LW;             // 11
-        const int np = (NG - lw + LW - 1) / LW;
-        const float* abase[MAXG];
-        unsigned okmask = 0;
-#pragma unroll
-        for (int i = 0; i < MAXG; ++i) {
-            const int g = lw + LW * i;
-            const int hr = g * 8 + rsub;
-            const int hy = hr / HW2, hx = hr - hy * HW2;
-            const int y = y0 - 1 + hy, x = x0 - 1 + hx;
-            const bool ok = g < NG && hr < HRT && y >= 0 && y < p.H && x >= 0 && x < p.W;
-            abase[i] = ok ? X + (((long)b0 * p.H + y) * p.W + x) * p.Cin + (cpos ^ patch_key<TW>(hy, hx)) * CE : zeros;
-            okmask |= ok ? (1u << i) : 0u;
-        }
-        const float* bsrc[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int row = (lw * 2 + i) * 8 + rsub;
-            bsrc[i] = Wt + (long)row * K + (cpos ^ ((row >> 1) & 7)) * CE;
-        }
-        auto issue_patch = [&](int c) {
-            unsigned char* pbuf = lds + (c & 1) * PB;
-#pragma unroll
-            for (int i = 0; i < MAXG; ++i) {
-                const int g = lw + LW * i;
-                if (g < NG) dma16(abase[i] + (((okmask >> i) & 1u) ? c * KE : 0), pbuf + g * 1024);
-            }
-        };
-        auto issue_w = [&](int j) {                          // weight tile of step j = slice * 9 + tap
-            const int c = j / 9, t = j - c * 9;
-            unsigned char* sb = lds + W_OFF + (j % WR) * WSLOT;
-#pragma unroll
-            for (int i = 0; i < 2; ++i) dma16(bsrc[i] + (long)t * p.Cin + c * KE, sb + (lw * 2 + i) * 1024);
-        };
-        // issue order: P0 W0 W1 | after barrier j: W(j+2); after barrier (c,3): P(c+1)        [as conv3x3_patch_kernel]
-        issue_patch(0);
-        issue_w(0);
-        issue_w(1);
-        for (int j = 0; j < nj; ++j) {
-            const int c = j / 9, t = j - c * 9;
-            int younger = (j + 1 < nj) ? 2 : 0;
-            if ((t == 4 || t == 5) && c + 1 < nc) younger += np;
-            wait_vmcnt_n(younger);
-            __builtin_amdgcn_s_barrier();
-            if (j + 2 < nj) issue_w(j + 2);
-            if (t == 3 && c + 1 < nc) issue_patch(c + 1);
-        }
-        __builtin_amdgcn_s_barrier();                        // matches the two epilogue barriers of the compute waves
-        __builtin_amdgcn_s_barrier();
+        const Rows rows(static_cast<const float*>(p.x), static_cast<const float*>(p.zeros), p.B, p.H, p.W, p.Cin, b0, y0, x0, lw, lane);
+        const WeightRows<float, 2> wts(static_cast<const float*>(p.w), 0, K, lw, lane);
+        patch_loader_run<PB, WR, WSLOT>(rows, wts, lds, lds + W_OFF, nc, p.Cin);
         return;
     }
 
     // ================= compute wave: pixel tiles 2 wave, 2 wave + 1 (rows 4 wave .. 4 wave + 3 of the tile) x both channel tiles =================
     f32x16 acc[TM][TN];
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    acc_clear(acc);
     const int lrow = lane & 31, lhalf = lane >> 5;
     const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)lds;
     int hb[TM], hy0[TM], hx0[TM];
@@ -1097,49 +1069,13 @@ __global__ __launch_bounds__(512) void conv3x3_patch_x3_kernel(ConvArgs p) {
             arow[i] = a_base + (hb[i] + ky * HW2 + kx) * ROWB;
             asw[i] = patch_key<TW>(hy0[i] + ky, hx0[i] + kx);
         }
-        u32x4 ah[2][TM], al[2][TM], bh[2][TN], bl[2][TN];
-        auto frag_read = [&](int s2, int buf) {              // ktile_mma_x3<PRE = true>'s chunks: hi at 2 s + h, lo at 4 + 2 s + h
-            const int ch = 2 * s2 + lhalf;
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                ah[buf][i] = lds_read_b128(arow[i] + ((ch ^ asw[i]) << 4));
-                al[buf][i] = lds_read_b128(arow[i] + (((4 + ch) ^ asw[i]) << 4));
-            }
-#pragma unroll
-            for (int jj = 0; jj < TN; ++jj) {
-                bh[buf][jj] = lds_read_b128(b_base + swz(jj * 32 + lrow, ch));
-                bl[buf][jj] = lds_read_b128(b_base + swz(jj * 32 + lrow, 4 + ch));
-            }
-        };
-        frag_read(0, 0);
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            lds_wait();
-            if (s2 < 1) frag_read(1, 1);
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int jj = 0; jj < TN; ++jj) {
-                    acc[i][jj] = mfma_bf16(ah[s2][i], bh[s2][jj], acc[i][jj]);
-                    acc[i][jj] = mfma_bf16(ah[s2][i], bl[s2][jj], acc[i][jj]);
-                    acc[i][jj] = mfma_bf16(al[s2][i], bh[s2][jj], acc[i][jj]);
-                }
-        }
+        ktile_mma_x3_rows(acc, arow, asw, b_base, lrow, lhalf);
         if (++t == 9) { t = 0; ++c; }
     }
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     float* Cs = reinterpret_cast<float*>(lds);
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = (wave * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhalf;
-                const int col = j * 32 + lrow;
-                Cs[row * BN + col] = acc[i][j][r];
-            }
+    acc_to_lds<BN>(Cs, acc, wave * TM, 0, lrow, lhalf);
     __syncthreads();                                         // the LDS-write drain + the second epilogue barrier (the loader waves count it too)
     // store pass: thread = (tile pixel, 8 channels); + bias, ReLU, split (epilogue_store's IVOSW_F32X3 branch)
     constexpr int CPR = BN / 8;
@@ -1888,13 +1824,20 @@ ConvKernel conv_select(const ConvArgs& a, int dtype, bool stem) {
 }
 
 // one name per id: the kernel's function name as a kernel trace prints it, cut at the first '<' or '('
+#pragma clang diagnostic push
+#pragma clang diagnostic error "-Wswitch"            // an id without a name does not compile
 const char* conv_kernel_name(ConvKernel id) {
-    static const char* const names[CK_COUNT] = {
-        "conv_igemm_kernel", "conv3x3_patch_kernel", "conv3x3_patch_kernel", "conv3x3_patch_kernel", "conv3x3_patch_kernel", "conv3x3_patch_kernel",
-        "conv_igemm_dma_kernel", "conv_igemm_ws_kernel", "conv_igemm_ws_kernel", "conv_igemm_dma_kernel", "conv_igemm_dma_kernel",
-        "conv3x3_patch_x3_kernel", "conv_igemm_ws_kernel", "conv_igemm_dma_kernel", "conv_igemm_dma_kernel"};
-    return names[id];
+    switch (id) {                                // per id, like launch_conv_id below: no dependence on the enum's order
+    case CK_STEM: return "conv_igemm_kernel";
+    case CK_PATCH_2F: case CK_PATCH_4F_KXY: case CK_PATCH_4F: case CK_PATCH_KXY: case CK_PATCH: return "conv3x3_patch_kernel";
+    case CK_DMA_SMALL: case CK_DMA: case CK_DMA_SHORTK: case CK_DMA64: case CK_DMA64_SHORTK: return "conv_igemm_dma_kernel";
+    case CK_WS_LW8: case CK_WS_LW4: case CK_WS64: return "conv_igemm_ws_kernel";
+    case CK_PATCH_X3: return "conv3x3_patch_x3_kernel";
+    case CK_COUNT: break;
+    }
+    return "?";                                  // CK_COUNT is no kernel: conv_select never returns it
 }
+#pragma clang diagnostic pop
 
 // the launch of an id: its grid (M rows x Cout columns of tiles) and block.  (The bf16-only and split-only kernels are instantiated
 // for their precision alone: conv_select never hands their ids to another one.)

@@ -106,4 +106,54 @@ __device__ __forceinline__ f32x16 mfma_bf16(u32x4 a, u32x4 b, f32x16 c) {
     return __builtin_amdgcn_mfma_f32_32x32x16_bf16(ua.v, ub.v, c, 0, 0, 0);
 }
 
+// one 16-byte fragment pair into one 32x32 accumulator tile.  bf16: k = 8 per lane half, one 32x32x16 MFMA; fp32: 4 floats feeding
+// four 32x32x2 MFMAs (an exact fp32 fma chain; the k-permutation is identical for A and B)
+template <typename T>
+__device__ __forceinline__ void mma_step(u32x4 a, u32x4 b, f32x16& acc) {
+    if constexpr (sizeof(T) == 2) {
+        acc = mfma_bf16(a, b, acc);
+    } else {
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.x), __uint_as_float(b.x), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.y), __uint_as_float(b.y), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.z), __uint_as_float(b.z), acc, 0, 0, 0);
+        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(a.w), __uint_as_float(b.w), acc, 0, 0, 0);
+    }
+}
+
+template <int TM, int TN>
+__device__ __forceinline__ void acc_clear(f32x16 (&acc)[TM][TN]) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+}
+
+// a wave's TM x TN accumulator tiles -> an fp32 LDS image of PITCH floats per row, starting at 32x32 tile (row_tile0, col_tile0)
+// (C/D map: col = lane&31, row = (r&3)+8*(r>>2)+4*(lane>>5))
+template <int PITCH, int TM, int TN>
+__device__ __forceinline__ void acc_to_lds(float* Cs, const f32x16 (&acc)[TM][TN], int row_tile0, int col_tile0, int lrow, int lhalf) {
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int row = (row_tile0 + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lhalf;
+                const int col = (col_tile0 + j) * 32 + lrow;
+                Cs[row * PITCH + col] = acc[i][j][r];
+            }
+}
+
+// counted wait of an S-deep LDS-DMA ring whose every tile is LPT DMA instructions of this wave: tiles kt+1 .. kt+ahead were issued
+// after tile kt and may stay in flight
+template <int S, int LPT>
+__device__ __forceinline__ void ring_wait(int kt, int nk) {
+    const int ahead = min(S - 2, nk - 1 - kt);
+    if (ahead >= 2) wait_vmcnt<2 * LPT>();
+    else if (ahead == 1) wait_vmcnt<LPT>();
+    else wait_vmcnt<0>();
+}
+
 }  // namespace ivosw
