@@ -107,6 +107,53 @@ int ivosw_robot_box_probe(const uint8_t* gt, const uint8_t* pred, int n, int H, 
                           int32_t* points, int32_t* counts, int32_t* iters, uint32_t* skel, uint32_t* workspace,
                           size_t workspace_bytes, int lds_budget_bytes, ivosw_stream_t stream);
 
+/* Test probes of the DQN step's backward kernels (csrc/brain.hip, brain_fused.h, brain_bwd.h), each the product's kernel unchanged on
+ * caller-provided fp32 device tensors; tests/test_gpu_dqn_kernels.py holds their outputs to the float64 restatements of tests/dqn_ref.py.
+ * Every entry refuses a NULL operand, and with "not covered" what its kernel does not take, before anything is launched: nothing is written. */
+
+/* ONE bwd_tail_kernel launch holding one weight-gradient job: slab z of C [nslab][M][N] = sum over the K-rows k of slab z of
+ * (A[k*lda + m] + A2[k*lda + m]) * B[k*ldb + n]; A2 may be NULL.  Slab z covers the rows [z*per, min(K, (z + 1)*per)) with
+ * per = ceil(ceil(K / nslab) / 16) * 16; a slab without rows is written as zeros.  nslab > 0 is taken as given (at most 64); nslab == 0
+ * asks for the step's own choice for `kind` (0: dW_hh, 1: dW_ih, 2: dW2).  *used (may be NULL) = the slab count that ran.
+ * M % 64 == 0, N % 128 == 0, K >= 1, lda >= M, ldb >= N, both multiples of 4, 16-byte aligned operands; anything else is not covered. */
+int ivosw_bwd_wgrad_probe(const float* A, const float* A2, const float* B, float* C, int lda, int ldb, int M, int N, int K, int nslab,
+                          int kind, int* used, ivosw_stream_t stream);
+
+/* ONE bwd_tail_kernel launch of the dgrad tiles alone (ceil(rows / 16) of them, the grid padded to a multiple of 8 as in the step):
+ * de [rows,128] = (dG + dG2) [rows,512] . wih [512,128], da1 [rows,128] = (de . w2 [128,128]) * (a1 > 0).  rows >= 1. */
+int ivosw_bwd_dgrad_probe(const float* dG, const float* dG2, const float* wih, const float* w2, const float* a1, float* de, float* da1,
+                          int rows, ivosw_stream_t stream);
+
+/* ONE bwd_tail_kernel launch holding one column-sum job: slab z of out [nsplit][N] = the sum of A[m*ld + n] over the rows m of split z,
+ * and with x [M,2] (x and outw both given or both NULL) slab z of outw [nsplit][N][2] = the sums of A[m*ld + n] * x[m*2 + c].  Split z
+ * covers the rows [z*per, min(M, (z + 1)*per)) with per = ceil(ceil(M / nsplit) / 8) * 8.  M >= 1, 1 <= N <= ld, 1 <= nsplit <= 64. */
+int ivosw_bwd_csum_probe(const float* A, const float* x, float* out, float* outw, int M, int N, int ld, int nsplit, ivosw_stream_t stream);
+
+/* The step's two bwd_tail_kernel launches and its slab reduction, built by the code the step runs (plan_bwd_tail): launch 1 = the dgrad
+ * tiles beside dW_hh, dW_ih and dW3; launch 2 = dW2 beside the four column sums; then splitk_reduce_group_kernel.  rows = B*T;
+ * dG [2][rows][512] (forward, then backward direction), hprev [2 rows,128], e, a1 [rows,128], dd1c, w4term [B,128], hcc [B,256],
+ * state [rows,2], wih [512,128], w2 [128,128]; outputs de, da1 [rows,128] and the gradient arena grads [IVOSW_BRAIN_NPARAMS], of which
+ * every tensor but decoder_fc2.bias (the head kernel's) is written; ws: IVOSW_BWD_GROUP_WS_FLOATS floats of device scratch for the slabs. */
+#define IVOSW_BWD_GROUP_WS_FLOATS ((16 + 40 + 40) * 512 * 128 + 8 * 512)
+int ivosw_bwd_group_probe(const float* dG, const float* hprev, const float* e, const float* a1, const float* dd1c, const float* hcc,
+                          const float* w4term, const float* state, const float* wih, const float* w2, float* de, float* da1, float* grads,
+                          float* ws, int B, int T, ivosw_stream_t stream);
+
+/* ONE launch of head_fused_kernel<per != 0> (csrc/brain_fused.h) with the kernel's own arguments: prm + o_w3 = W3 [128,256],
+ * prm + o_w4 = w4 [128]; q_np, q_nt, q_s [B,T]; action [B] int64; r_step, r_done [B]; d1_s [B,T,128]; hs_s [B,T,256]; outputs dq [B],
+ * dd1c, w4term [B,128], hcc, dhc [B,256], loss [1], db4 [1]; per != 0: weights [B] in and td [B] out, else both are ignored.
+ * B, T >= 1, o_w3, o_w4 >= 0, loss_kind IVOSW_DQN_LOSS_MSE or _HUBER. */
+int ivosw_head_fused_probe(const float* prm, int o_w3, int o_w4, const float* q_np, const float* q_nt, const float* q_s, const int64_t* action,
+                           const float* r_step, const float* r_done, int B, int T, float gamma, int loss_kind, float delta,
+                           const float* d1_s, const float* hs_s, float* dq, float* dd1c, float* w4term, float* hcc, float* dhc, float* loss,
+                           float* db4, int per, const float* weights, float* td, ivosw_stream_t stream);
+
+/* ONE launch of the BPTT recurrence: whh [512,128]; gates [2,N,T,512] (post-activation i, f, g, o) and cs [2,N,T,128] as the forward
+ * keeps them; dhc [N,256] = dL/d(h_fw | h_bw) at frame action[n]; dG [2,N,T,512] out, zero at the frames a direction consumes after its
+ * loss frame.  form 0: lstm_bwd_quad_kernel<1> (the step's default); form 1, 2, 4: lstm_bwd_kernel<form>.  N, T >= 1. */
+int ivosw_lstm_bwd_probe(const float* whh, const float* gates, const float* cs, const float* dhc, const int64_t* action, float* dG, int N, int T,
+                         int form, ivosw_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -211,7 +211,15 @@ PROBE_SIGNATURES = {
     "ivosw_res2_probe": (_i, [_p] * 7 + [_i] * 4 + [C.POINTER(_i), _p]),      # w, bias: host arrays of RES2_PROBE_NW device pointers
     "ivosw_stem_probe": (_i, [_p] * 4 + [_i] * 2 + [_p]),
     "ivosw_robot_box_probe": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _sz, _i, _p]),
+    # the DQN step's backward kernels alone (tests/test_gpu_dqn_kernels.py)
+    "ivosw_bwd_wgrad_probe": (_i, [_p] * 4 + [_i] * 7 + [C.POINTER(_i), _p]),
+    "ivosw_bwd_dgrad_probe": (_i, [_p] * 7 + [_i, _p]),
+    "ivosw_bwd_csum_probe": (_i, [_p] * 4 + [_i] * 4 + [_p]),
+    "ivosw_bwd_group_probe": (_i, [_p] * 14 + [_i, _i, _p]),
+    "ivosw_head_fused_probe": (_i, [_p, _i, _i] + [_p] * 6 + [_i, _i, _f, _i, _f] + [_p] * 9 + [_i, _p, _p, _p]),
+    "ivosw_lstm_bwd_probe": (_i, [_p] * 6 + [_i] * 3 + [_p]),
 }
+BWD_GROUP_WS_FLOATS = (16 + 40 + 40) * 512 * 128 + 8 * 512  # IVOSW_BWD_GROUP_WS_FLOATS
 RES2_PROBE_NW, RES2_PROBE_FRAG_BYTES = 11, 655360           # IVOSW_RES2_PROBE_NW, IVOSW_RES2_PROBE_FRAG_BYTES of include/ivosw_probe.h
 
 _lib = None

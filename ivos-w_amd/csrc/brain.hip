@@ -1246,6 +1246,89 @@ int tune_get(const char* key, int dflt);   // capi.cpp
 
 static constexpr int WG_SPLIT = 16;
 static constexpr int WG_SPLIT_MAX = 40;   // slab sets of the two long-K weight gradients are sized for this (tunables DQN_SPLIT_HH / _IH)
+static constexpr int CS_SPLIT = 8;        // row splits of the two long column sums (db2 <- de, {db1, dW1} <- da1)
+
+// K-slabs of the register-resident weight gradients (brain_bwd.h), a multiple of 48 rows where the sizes allow (the kernel's loop is
+// unrolled by three 16-row steps): about K / want rows each, at most cap slabs.  B = 128, T = 25: 200 + 184 + 96 + 4 workgroups in the
+// first launch, one round at two per CU; dW2's launch is latency-bound, so many small workgroups (48-row slabs).
+enum TailSlabKind { TAIL_SLABS_HH = 0, TAIL_SLABS_IH = 1, TAIL_SLABS_W2 = 2 };
+static int tail_slabs_for(int K, int kind) {
+    static constexpr int WANT[3] = {23, 12, 32}, CAP[3] = {WG_SPLIT_MAX, WG_SPLIT_MAX, 64};
+    const int per = std::max(48, (K / WANT[kind] + 47) / 48 * 48);
+    return std::min(CAP[kind], std::max(1, (K + per - 1) / per));
+}
+
+// What the two launches of the backward tail read and write: the step's workspace (dqn_loss_grad_impl) or a test's own tensors
+// (ivosw_bwd_group_probe).
+struct TailIO {
+    const float *dG, *dG_bw;     // [rows,512] each: dL/d(gate pre-activation), forward and backward direction (dG_bw = dG + rows*512)
+    const float *hprev;          // [2 rows,128]
+    const float *e, *a1;         // [rows,128]
+    const float *dd1c, *hcc, *w4term;    // [B,128], [B,256], [B,128]
+    const float *state;          // [rows,2]
+    const float *wih, *w2;       // [512,128], [128,128]
+    float *de, *da1;             // [rows,128]
+    float *slabs_hh, *slabs_ih;  // WG_SPLIT_MAX x 512*128 each
+    float *slabs_w2;             // WG_SPLIT x 512*128 (up to 64 slabs of 128*128)
+    float *slabs_cs;             // 8*512: db2 [CS_SPLIT][128] | db1 [CS_SPLIT][128] | dW1 [CS_SPLIT][256]
+    float *grads;                // the gradient arena: dW3, dW4 and db3 are written in place
+    int B, T;
+};
+struct TailPlan {
+    TailGroup t1, t2;
+    int split_hh, split_ih, split_w2;
+};
+// 1. {dgrad chain de -> da1 per 16-row tile, dW_hh, dW_ih, dW3} in one launch, 2. dW2 (it needs de) and the four column sums beside it
+static TailPlan plan_bwd_tail(const TailIO& io) {
+    const int B = io.B, rows = io.B * io.T;
+    auto tiles = [](const WgradJob& j) { return (j.M / 64) * (j.N / 128) * j.nslab; };
+    TailPlan pl{};
+    TailGroup& t1 = pl.t1;
+    t1.dg = DgradArgs{io.dG, io.dG_bw, io.wih, io.w2, io.a1, io.de, io.da1, rows};
+    t1.n_dgrad = ((rows + 15) / 16 + 7) / 8 * 8;        // padded to a multiple of 8 (XCD-aligned weight-gradient section)
+    pl.split_hh = tail_slabs_for(2 * rows, TAIL_SLABS_HH);
+    pl.split_ih = tail_slabs_for(rows, TAIL_SLABS_IH);
+    t1.w[0] = WgradJob{io.dG, nullptr, io.hprev, io.slabs_hh, 512, 128, 512, 128, 2 * rows, pl.split_hh};
+    t1.w[1] = WgradJob{io.dG, io.dG_bw, io.e, io.slabs_ih, 512, 128, 512, 128, rows, pl.split_ih};
+    t1.w[2] = WgradJob{io.dd1c, nullptr, io.hcc, io.grads + O_W3, 128, 256, 128, 256, B, 1};
+    t1.n = 3;
+    for (int i = 0; i < 3; ++i) t1.first[i + 1] = t1.first[i] + tiles(t1.w[i]);
+    for (int i = 4; i <= TAIL_MAX; ++i) t1.first[i] = t1.first[3];
+    TailGroup& t2 = pl.t2;
+    pl.split_w2 = tail_slabs_for(rows, TAIL_SLABS_W2);
+    t2.w[0] = WgradJob{io.de, nullptr, io.a1, io.slabs_w2, 128, 128, 128, 128, rows, pl.split_w2};
+    t2.n = 1;
+    t2.first[1] = tiles(t2.w[0]);
+    for (int i = 2; i <= TAIL_MAX; ++i) t2.first[i] = t2.first[1];
+    // ... and the four column sums beside it (they used to be a launch of their own)
+    float* s4 = io.slabs_cs;
+    t2.cs[0] = CsumJob{io.de, nullptr, s4, nullptr, rows, 128, 128, CS_SPLIT};                                          // db2 slabs
+    t2.cs[1] = CsumJob{io.da1, io.state, s4 + CS_SPLIT * 128, s4 + 2 * CS_SPLIT * 128, rows, 128, 128, CS_SPLIT};       // db1, dW1 slabs
+    t2.cs[2] = CsumJob{io.w4term, nullptr, io.grads + O_W4, nullptr, B, 128, 128, 1};
+    t2.cs[3] = CsumJob{io.dd1c, nullptr, io.grads + O_B3, nullptr, B, 128, 128, 1};
+    t2.n_cs = 4;
+    for (int i = 0; i < 4; ++i) t2.cs_first[i + 1] = t2.cs_first[i] + ((t2.cs[i].N + 31) / 32) * t2.cs[i].nsplit;
+    return pl;
+}
+static void launch_bwd_tail(const TailPlan& pl, hipStream_t st) {
+    hipLaunchKernelGGL(bwd_tail_kernel, dim3(pl.t1.n_dgrad + pl.t1.first[3]), dim3(256), 0, st, pl.t1);
+    hipLaunchKernelGGL(bwd_tail_kernel, dim3(pl.t2.first[1] + pl.t2.cs_first[4]), dim3(256), 0, st, pl.t2);
+}
+// the fixed-order reduction of every slab set of the backward tail into the gradient arena
+static ReduceGroup tail_reduce_group(float* slabs_hh, float* slabs_ih, float* slabs_w2, float* slabs_cs, float* grads, int split_hh,
+                                     int split_ih, int split_w2) {
+    ReduceGroup rg{};
+    rg.slabs[0] = slabs_hh; rg.out[0] = grads + O_WHH; rg.n[0] = 512 * 128; rg.nslab[0] = split_hh;
+    rg.slabs[1] = slabs_ih; rg.out[1] = grads + O_WIH; rg.n[1] = 512 * 128; rg.nslab[1] = split_ih;
+    rg.slabs[2] = slabs_w2; rg.out[2] = grads + O_W2; rg.n[2] = 128 * 128; rg.nslab[2] = split_w2;
+    rg.slabs[3] = slabs_cs; rg.out[3] = grads + O_B2; rg.n[3] = 128; rg.nslab[3] = CS_SPLIT;
+    rg.slabs[4] = slabs_cs + CS_SPLIT * 128; rg.out[4] = grads + O_B1; rg.n[4] = 128; rg.nslab[4] = CS_SPLIT;
+    rg.slabs[5] = slabs_cs + 2 * CS_SPLIT * 128; rg.out[5] = grads + O_W1; rg.n[5] = 256; rg.nslab[5] = CS_SPLIT;
+    return rg;
+}
+static void launch_reduce_group(const ReduceGroup& rg, hipStream_t st) {
+    hipLaunchKernelGGL(splitk_reduce_group_kernel, dim3(512 * 128 / 256, 6), dim3(256), 0, st, rg);
+}
 
 // One helper stream + four events per device: the only state the library keeps between calls (documented in
 // INTEGRATION.md).  Creation is serialised and all-or-nothing; ivosw_dqn_loss_grad holds the device's mutex while it
@@ -1793,39 +1876,11 @@ static int dqn_loss_grad_impl(const float* policy, const float* target, const fl
         int split_hh_used = split_hh, split_ih_used = split_ih, split_w2_used = WG_SPLIT;
         bool tail_colsums_done = false;
         if (tune_get("DQN_TAIL", 1)) {
-            // register-resident kernels (brain_bwd.h): {dgrad chain de -> da1 per 16-row tile, dW_hh, dW_ih, dW3} in one launch,
-            // then dW2 (it needs de)
-            auto tiles = [](const WgradJob& j) { return (j.M / 64) * (j.N / 128) * j.nslab; };
-            TailGroup t1{};
-            t1.dg = DgradArgs{w.dG, dG_bw, policy + O_WIH, policy + O_W2, a1_s, w.de, w.da1, rows};
-            t1.n_dgrad = ((rows + 15) / 16 + 7) / 8 * 8;        // padded to a multiple of 8 (XCD-aligned weight-gradient section)
-            // K-slabs of a multiple of 48 rows where the sizes allow (the kernel's loop is unrolled by three 16-row steps)
-            auto slabs_for = [](int K, int want, int cap) {
-                const int per = std::max(48, (K / want + 47) / 48 * 48);
-                return std::min(cap, std::max(1, (K + per - 1) / per));
-            };
-            split_hh_used = slabs_for(2 * rows, 23, WG_SPLIT_MAX); split_ih_used = slabs_for(rows, 12, WG_SPLIT_MAX);   // B = 128, T = 25: 200 + 184 + 96 + 4 workgroups, one round at two per CU
-            t1.w[0] = WgradJob{w.dG, nullptr, w.pol.hprev, slabs2, 512, 128, 512, 128, 2 * rows, split_hh_used};
-            t1.w[1] = WgradJob{w.dG, dG_bw, e_s, slabs3, 512, 128, 512, 128, rows, split_ih_used};
-            t1.w[2] = WgradJob{w.dd1c, nullptr, w.hcc, grads + O_W3, 128, 256, 128, 256, B, 1};
-            t1.n = 3;
-            for (int i = 0; i < 3; ++i) t1.first[i + 1] = t1.first[i] + tiles(t1.w[i]);
-            for (int i = 4; i <= TAIL_MAX; ++i) t1.first[i] = t1.first[3];
-            hipLaunchKernelGGL(bwd_tail_kernel, dim3(t1.n_dgrad + t1.first[3]), dim3(256), 0, st, t1);
-            TailGroup t2{};
-            split_w2_used = slabs_for(rows, 32, 64);            // 48-row slabs: this launch is latency-bound, so many small workgroups
-            t2.w[0] = WgradJob{w.de, nullptr, a1_s, w.slabs, 128, 128, 128, 128, rows, split_w2_used};
-            t2.n = 1;
-            t2.first[1] = tiles(t2.w[0]);
-            for (int i = 2; i <= TAIL_MAX; ++i) t2.first[i] = t2.first[1];
-            // ... and the four column sums beside it (they used to be a launch of their own)
-            t2.cs[0] = CsumJob{w.de, nullptr, slabs4, nullptr, rows, 128, 128, 8};                                   // db2 slabs
-            t2.cs[1] = CsumJob{w.da1, state, slabs4 + 8 * 128, slabs4 + 16 * 128, rows, 128, 128, 8};                // db1, dW1 slabs
-            t2.cs[2] = CsumJob{w.w4term, nullptr, grads + O_W4, nullptr, B, 128, 128, 1};
-            t2.cs[3] = CsumJob{w.dd1c, nullptr, grads + O_B3, nullptr, B, 128, 128, 1};
-            t2.n_cs = 4;
-            for (int i = 0; i < 4; ++i) t2.cs_first[i + 1] = t2.cs_first[i] + ((t2.cs[i].N + 31) / 32) * t2.cs[i].nsplit;
-            hipLaunchKernelGGL(bwd_tail_kernel, dim3(t2.first[1] + t2.cs_first[4]), dim3(256), 0, st, t2);
+            // register-resident kernels (brain_bwd.h), two launches: plan_bwd_tail
+            const TailPlan pl = plan_bwd_tail(TailIO{w.dG, dG_bw, w.pol.hprev, e_s, a1_s, w.dd1c, w.hcc, w.w4term, state, policy + O_WIH,
+                                                     policy + O_W2, w.de, w.da1, slabs2, slabs3, w.slabs, slabs4, grads, B, T});
+            split_hh_used = pl.split_hh; split_ih_used = pl.split_ih; split_w2_used = pl.split_w2;
+            launch_bwd_tail(pl, st);
             tail_colsums_done = true;
         } else {
             GemmF32 g1[4] = {gde, gw[0], gw[1], gw[2]};
@@ -1834,7 +1889,7 @@ static int dqn_loss_grad_impl(const float* policy, const float* target, const fl
             GemmF32 g2[2] = {ga, gb};
             launch_gemm_f32_group(g2, 2, st);
         }
-        constexpr int CS = 8;                           // row splits of the two long column sums
+        constexpr int CS = CS_SPLIT;                    // row splits of the two long column sums
         float* cs_b2 = slabs4;                          // [CS][128]
         float* cs_b1 = slabs4 + CS * 128;               // [CS][128]
         float* cs_w1 = slabs4 + 2 * CS * 128;           // [CS][256]
@@ -1846,15 +1901,9 @@ static int dqn_loss_grad_impl(const float* policy, const float* target, const fl
         c1.j[3] = ColsumJob{w.dd1c, nullptr, grads + O_B3, nullptr, B, 128, 128, 1};
         hipLaunchKernelGGL(colsum_group_kernel, dim3(4, 4, CS), dim3(1024), 0, st, c1);
         }
-        ReduceGroup rg{};
-        rg.slabs[0] = slabs2; rg.out[0] = grads + O_WHH; rg.n[0] = 512 * 128; rg.nslab[0] = split_hh_used;
-        rg.slabs[1] = slabs3; rg.out[1] = grads + O_WIH; rg.n[1] = 512 * 128; rg.nslab[1] = split_ih_used;
-        rg.slabs[2] = w.slabs; rg.out[2] = grads + O_W2; rg.n[2] = 128 * 128; rg.nslab[2] = split_w2_used;
-        rg.slabs[3] = cs_b2; rg.out[3] = grads + O_B2; rg.n[3] = 128; rg.nslab[3] = CS;
-        rg.slabs[4] = cs_b1; rg.out[4] = grads + O_B1; rg.n[4] = 128; rg.nslab[4] = CS;
-        rg.slabs[5] = cs_w1; rg.out[5] = grads + O_W1; rg.n[5] = 256; rg.nslab[5] = CS;
+        const ReduceGroup rg = tail_reduce_group(slabs2, slabs3, w.slabs, slabs4, grads, split_hh_used, split_ih_used, split_w2_used);
         if (defer) *defer = rg;
-        else hipLaunchKernelGGL(splitk_reduce_group_kernel, dim3(512 * 128 / 256, 6), dim3(256), 0, st, rg);
+        else launch_reduce_group(rg, st);
     } else {
         fork(2);
         hipLaunchKernelGGL(colsum_kernel, dim3(4), dim3(1024), 0, s2, w.w4term, B, 128, 128, grads + O_W4);
@@ -2236,4 +2285,133 @@ extern "C" int ivosw_lstm_probe(unsigned long long* ts, unsigned long long* ts_b
     g_lstm_probe_bwd = ts_bwd;          // BPTT kernel: 0 step start, 1 gate gradients written, 2 barrier passed, 3 matvec done, 4 / 5 loop start / end, 6 steps
     return IVOSW_OK;
 }
+
+// ---------------------------------------------------------------- test probes of the backward kernels (include/ivosw_probe.h)
+#define PROBE_COVERS(cond, what)                                             \
+    do {                                                                     \
+        if (!(cond)) {                                                       \
+            set_error("%s: not covered: %s", __func__, what);                \
+            return IVOSW_ERR_ARG;                                            \
+        }                                                                    \
+    } while (0)
+static bool aligned16_f(std::initializer_list<const void*> ps) {
+    for (const void* p : ps)
+        if (reinterpret_cast<uintptr_t>(p) & 15) return false;
+    return true;
+}
+
+extern "C" int ivosw_bwd_wgrad_probe(const float* A, const float* A2, const float* B, float* C, int lda, int ldb, int M, int N, int K,
+                                     int nslab, int kind, int* used, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(A && B && C, "null pointer");
+    PROBE_COVERS(M >= 64 && M % 64 == 0, "M must be a multiple of 64");
+    PROBE_COVERS(N >= 128 && N % 128 == 0, "N must be a multiple of 128");
+    PROBE_COVERS(K >= 1, "K must be at least 1");
+    PROBE_COVERS(lda >= M && ldb >= N && lda % 4 == 0 && ldb % 4 == 0, "lda >= M, ldb >= N, both multiples of 4");
+    PROBE_COVERS(aligned16_f({A, A2, B, C}), "operands must be 16-byte aligned");
+    PROBE_COVERS(nslab >= 0 && nslab <= 64, "nslab must be 0 .. 64");
+    PROBE_COVERS(nslab > 0 || (kind >= 0 && kind <= 2), "kind must be 0 (dW_hh), 1 (dW_ih) or 2 (dW2) when nslab == 0");
+    IVOSW_ON_DEVICE_OF(C);
+    if (nslab == 0) nslab = tail_slabs_for(K, kind);
+    TailGroup t{};
+    t.w[0] = WgradJob{A, A2, B, C, lda, ldb, M, N, K, nslab};
+    t.n = 1;
+    for (int i = 1; i <= TAIL_MAX; ++i) t.first[i] = (M / 64) * (N / 128) * nslab;
+    hipLaunchKernelGGL(bwd_tail_kernel, dim3(t.first[1]), dim3(256), 0, as_stream(stream), t);
+    IVOSW_CHECK_LAUNCH();
+    if (used) *used = nslab;
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_bwd_dgrad_probe(const float* dG, const float* dG2, const float* wih, const float* w2, const float* a1, float* de,
+                                     float* da1, int rows, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(dG && dG2 && wih && w2 && a1 && de && da1, "null pointer");
+    PROBE_COVERS(rows >= 1, "rows must be at least 1");
+    PROBE_COVERS(aligned16_f({dG, dG2, wih, w2, a1, de, da1}), "operands must be 16-byte aligned");
+    IVOSW_ON_DEVICE_OF(de);
+    TailGroup t{};
+    t.dg = DgradArgs{dG, dG2, wih, w2, a1, de, da1, rows};
+    t.n_dgrad = ((rows + 15) / 16 + 7) / 8 * 8;
+    hipLaunchKernelGGL(bwd_tail_kernel, dim3(t.n_dgrad), dim3(256), 0, as_stream(stream), t);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_bwd_csum_probe(const float* A, const float* x, float* out, float* outw, int M, int N, int ld, int nsplit,
+                                    ivosw_stream_t stream) {
+    IVOSW_REQUIRE(A && out, "null pointer");
+    IVOSW_REQUIRE((x == nullptr) == (outw == nullptr), "x and outw go together");
+    PROBE_COVERS(M >= 1 && N >= 1 && ld >= N, "M >= 1 and 1 <= N <= ld");
+    PROBE_COVERS(nsplit >= 1 && nsplit <= 64, "nsplit must be 1 .. 64");
+    PROBE_COVERS((reinterpret_cast<uintptr_t>(x) & 7) == 0, "x must be 8-byte aligned");
+    IVOSW_ON_DEVICE_OF(out);
+    TailGroup t{};
+    t.cs[0] = CsumJob{A, x, out, outw, M, N, ld, nsplit};
+    t.n_cs = 1;
+    for (int i = 1; i <= TAIL_MAX; ++i) t.cs_first[i] = ((N + 31) / 32) * nsplit;
+    hipLaunchKernelGGL(bwd_tail_kernel, dim3(t.cs_first[1]), dim3(256), 0, as_stream(stream), t);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+static_assert(IVOSW_BWD_GROUP_WS_FLOATS == (WG_SPLIT + 2 * WG_SPLIT_MAX) * 512 * 128 + 8 * 512, "the group probe's scratch holds the step's slab sets");
+extern "C" int ivosw_bwd_group_probe(const float* dG, const float* hprev, const float* e, const float* a1, const float* dd1c, const float* hcc,
+                                     const float* w4term, const float* state, const float* wih, const float* w2, float* de, float* da1,
+                                     float* grads, float* ws, int B, int T, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(dG && hprev && e && a1 && dd1c && hcc && w4term && state && wih && w2 && de && da1 && grads && ws, "null pointer");
+    PROBE_COVERS(B >= 1 && T >= 1 && (long long)B * T <= (1 << 20), "B, T >= 1 and B*T <= 2^20");
+    PROBE_COVERS(aligned16_f({dG, hprev, e, a1, dd1c, hcc, w4term, wih, w2, de, da1, grads, ws}) && (reinterpret_cast<uintptr_t>(state) & 7) == 0,
+                 "operands must be 16-byte aligned (state: 8)");
+    IVOSW_ON_DEVICE_OF(grads);
+    hipStream_t st = as_stream(stream);
+    float* slabs_w2 = ws;
+    float* slabs_hh = slabs_w2 + (size_t)WG_SPLIT * 512 * 128;
+    float* slabs_ih = slabs_hh + (size_t)WG_SPLIT_MAX * 512 * 128;
+    float* slabs_cs = slabs_ih + (size_t)WG_SPLIT_MAX * 512 * 128;
+    const TailPlan pl = plan_bwd_tail(TailIO{dG, dG + (size_t)B * T * 512, hprev, e, a1, dd1c, hcc, w4term, state, wih, w2, de, da1, slabs_hh,
+                                             slabs_ih, slabs_w2, slabs_cs, grads, B, T});
+    launch_bwd_tail(pl, st);
+    launch_reduce_group(tail_reduce_group(slabs_hh, slabs_ih, slabs_w2, slabs_cs, grads, pl.split_hh, pl.split_ih, pl.split_w2), st);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_head_fused_probe(const float* prm, int o_w3, int o_w4, const float* q_np, const float* q_nt, const float* q_s,
+                                      const int64_t* action, const float* r_step, const float* r_done, int B, int T, float gamma, int loss_kind,
+                                      float delta, const float* d1_s, const float* hs_s, float* dq, float* dd1c, float* w4term, float* hcc,
+                                      float* dhc, float* loss, float* db4, int per, const float* weights, float* td, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(prm && q_np && q_nt && q_s && action && r_step && r_done && d1_s && hs_s && dq && dd1c && w4term && hcc && dhc && loss && db4,
+                  "null pointer");
+    IVOSW_REQUIRE(!per || (weights && td), "null pointer (weights, td)");
+    PROBE_COVERS(B >= 1 && T >= 1 && o_w3 >= 0 && o_w4 >= 0, "B, T >= 1 and offsets >= 0");
+    if (const int rc = check_dqn_loss(__func__, loss_kind, delta)) return rc;
+    IVOSW_ON_DEVICE_OF(dq);
+    hipStream_t st = as_stream(stream);
+    if (per)
+        hipLaunchKernelGGL(head_fused_kernel<true>, dim3(B), dim3(256), 0, st, prm, o_w3, o_w4, q_np, q_nt, q_s, action, r_step, r_done, B, T, gamma,
+                           loss_kind, delta, d1_s, hs_s, dq, dd1c, w4term, hcc, dhc, loss, db4, weights, td);
+    else
+        hipLaunchKernelGGL(head_fused_kernel<false>, dim3(B), dim3(256), 0, st, prm, o_w3, o_w4, q_np, q_nt, q_s, action, r_step, r_done, B, T, gamma,
+                           loss_kind, delta, d1_s, hs_s, dq, dd1c, w4term, hcc, dhc, loss, db4, nullptr, nullptr);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_lstm_bwd_probe(const float* whh, const float* gates, const float* cs, const float* dhc, const int64_t* action, float* dG,
+                                    int N, int T, int form, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(whh && gates && cs && dhc && action && dG, "null pointer");
+    PROBE_COVERS(N >= 1 && T >= 1 && (long long)N * T <= (1 << 20), "N, T >= 1 and N*T <= 2^20");
+    PROBE_COVERS(form == 0 || form == 1 || form == 2 || form == 4, "form must be 0 (quad), 1, 2 or 4 (rows per workgroup)");
+    IVOSW_ON_DEVICE_OF(dG);
+    hipStream_t st = as_stream(stream);
+    LstmBwd lb{};
+    lb.whh = whh; lb.gates = gates; lb.cs = cs; lb.dhc = dhc; lb.action = action; lb.dG = dG; lb.N = N; lb.T = T; lb.ts = nullptr;
+    const int R = form ? form : 1, nwg = (2 * N + R - 1) / R;
+    if (form == 0) hipLaunchKernelGGL(lstm_bwd_quad_kernel<1>, dim3(2 * N), dim3(512), 0, st, lb);
+    else if (form == 1) hipLaunchKernelGGL(lstm_bwd_kernel<1>, dim3(nwg), dim3(512), 0, st, lb);
+    else if (form == 2) hipLaunchKernelGGL(lstm_bwd_kernel<2>, dim3(nwg), dim3(512), 0, st, lb);
+    else hipLaunchKernelGGL(lstm_bwd_kernel<4>, dim3(nwg), dim3(512), 0, st, lb);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+#undef PROBE_COVERS
 #endif  // IVOSW_PROBES
