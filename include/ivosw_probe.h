@@ -154,6 +154,50 @@ int ivosw_head_fused_probe(const float* prm, int o_w3, int o_w4, const float* q_
 int ivosw_lstm_bwd_probe(const float* whh, const float* gates, const float* cs, const float* dhc, const int64_t* action, float* dG, int N, int T,
                          int form, ivosw_stream_t stream);
 
+/* Test probes of the Brain forward kernels (csrc/brain_fused.h, csrc/brain.hip), each the product's kernel unchanged on caller-provided fp32
+ * device tensors; tests/test_gpu_dqn_fwd_kernels.py holds their outputs to the float64 restatements of tests/dqn_ref.py.  The recurrence
+ * and the recurrence + decoder kernel are launched by the functions the forward drivers call (launch_lstm_fwd, launch_lstm_fwd_pair,
+ * launch_lstm_fwd_ragged, launch_fwd_mega), the form by their rule (lstm_fwd_form_for).  Every entry refuses a NULL operand, and with
+ * "not covered" what its kernel does not take, before anything is launched: nothing is written.  Per-job arguments are HOST arrays of njobs
+ * entries (device pointers, ints); `prm` is a parameter arena in the state_dict layout (IVOSW_BRAIN_NPARAMS floats, 16-byte aligned). */
+
+/* ONE enc_fused_kernel launch of njobs = 1 or 2 jobs (job 1's tiles behind job 0's), without a drawn minibatch.  Job i: its rows
+ * [0, rows0) are x[row*2 + c], [rows0, rows) are x2[(row - rows0)*2 + c]; gx [rows,512] is written for every row, a1 and e [rows,128] for
+ * the rows >= keep_row.  1 <= rows <= 2^20, 0 <= rows0 <= rows, 0 <= keep_row <= rows. */
+int ivosw_enc_fused_probe(int njobs, const float* const* prm, const float* const* x, const float* const* x2, const int* rows0, const int* rows,
+                          const int* keep_row, float* const* gx, float* const* a1, float* const* e, ivosw_stream_t stream);
+
+/* ONE dec_fused_kernel launch of njobs = 1 or 2 jobs: hs [rows,256] (16-byte aligned) -> q [rows] for every row, d1 [rows,128] for the rows
+ * >= keep_row. */
+int ivosw_dec_fused_probe(int njobs, const float* const* prm, const float* const* hs, const int* rows, const int* keep_row, float* const* d1,
+                          float* const* q, ivosw_stream_t stream);
+
+/* ONE launch of the forward recurrence: whh [512,128] (16-byte aligned), gx [N,T,512] -> hs [N,T,256] (h_fw | h_bw after frame t) and, for
+ * the samples >= keep_from and indexed from keep_from, gates [2,N-keep_from,T,512] (i, f, g, o after their activations), cs and hprev
+ * [2,N-keep_from,T,128] (hprev: h before the frame).  gates, cs and hprev are given together or all NULL (nothing is kept).
+ * form 1, 2, 4: lstm_fwd_kernel<form>; 11, 12, 14: lstm_fwd_quad_kernel<form - 10>; 20: lstm_fwd_mfma_kernel (refused below 2 N = 8, as the
+ * product never sends it fewer rows); 0: the product's own choice at this N.  *ran (may be NULL) = the form that ran.
+ * N, T >= 1, N*T <= 2^20, 0 <= keep_from <= N. */
+int ivosw_lstm_fwd_probe(const float* whh, const float* gx, float* hs, float* gates, float* cs, float* hprev, int N, int T, int keep_from,
+                         int form, int* ran, ivosw_stream_t stream);
+
+/* ONE lstm_fwd_mfma_pair_kernel launch on two argument sets (host arrays of two entries each; T is shared): job 1's workgroups behind job
+ * 0's.  Each job as in ivosw_lstm_fwd_probe with the mfma form (2 N >= 8). */
+int ivosw_lstm_fwd_pair_probe(const float* const* whh, const float* const* gx, float* const* hs, float* const* gates, float* const* cs,
+                              float* const* hprev, const int* N, int T, const int* keep_from, ivosw_stream_t stream);
+
+/* ONE lstm_fwd_quad_ragged_kernel launch: n_seqs sequences of lengths[k] frames (host array) laid end to end in gx [rows,512] and
+ * hs [rows,256]; the sequence table is built by the check ivosw_brain_forward_ragged runs on its lengths, with its refusals. */
+int ivosw_lstm_fwd_ragged_probe(const float* whh, const float* gx, float* hs, const int* lengths, int n_seqs, ivosw_stream_t stream);
+
+/* ONE brain_fwd_mega_kernel launch (recurrence + decoder; tunable FWD_MEGA) of njobs = 1 or 2 jobs with a shared T.  Job i: W_hh, W3, b3,
+ * w4, b4 out of prm; gx [N,T,512]; hs [N,T,256] is written for the samples >= hs_from; gates, cs, hprev (together or all NULL) and
+ * d1 [N*T,128] for the samples >= keep_from (with NULL gates nothing is kept, d1 included); q [N*T] for every row.  2 N >= 8 per job, and T
+ * such that 2 T rows of 260 floats fit the kernel's 150 KB of dynamic LDS (T <= 73); 0 <= keep_from, hs_from <= N. */
+int ivosw_fwd_mega_probe(int njobs, const float* const* prm, const float* const* gx, float* const* hs, float* const* gates, float* const* cs,
+                         float* const* hprev, float* const* d1, float* const* q, const int* N, int T, const int* keep_from, const int* hs_from,
+                         ivosw_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -218,6 +218,13 @@ PROBE_SIGNATURES = {
     "ivosw_bwd_group_probe": (_i, [_p] * 14 + [_i, _i, _p]),
     "ivosw_head_fused_probe": (_i, [_p, _i, _i] + [_p] * 6 + [_i, _i, _f, _i, _f] + [_p] * 9 + [_i, _p, _p, _p]),
     "ivosw_lstm_bwd_probe": (_i, [_p] * 6 + [_i] * 3 + [_p]),
+    # the Brain forward kernels alone (tests/test_gpu_dqn_fwd_kernels.py); per-job arguments are host arrays (ctypes arrays of c_void_p / c_int)
+    "ivosw_enc_fused_probe": (_i, [_i] + [_p] * 10),
+    "ivosw_dec_fused_probe": (_i, [_i] + [_p] * 7),
+    "ivosw_lstm_fwd_probe": (_i, [_p] * 6 + [_i] * 4 + [C.POINTER(_i), _p]),
+    "ivosw_lstm_fwd_pair_probe": (_i, [_p] * 7 + [_i, _p, _p]),
+    "ivosw_lstm_fwd_ragged_probe": (_i, [_p] * 4 + [_i, _p]),
+    "ivosw_fwd_mega_probe": (_i, [_i] + [_p] * 9 + [_i, _p, _p, _p]),
 }
 BWD_GROUP_WS_FLOATS = (16 + 40 + 40) * 512 * 128 + 8 * 512  # IVOSW_BWD_GROUP_WS_FLOATS
 RES2_PROBE_NW, RES2_PROBE_FRAG_BYTES = 11, 655360           # IVOSW_RES2_PROBE_NW, IVOSW_RES2_PROBE_FRAG_BYTES of include/ivosw_probe.h

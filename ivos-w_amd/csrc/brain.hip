@@ -1071,6 +1071,60 @@ static LstmFwd lstm_fwd_args(const FwdPass& f, int T) {
     lf.gates = f.b->gates; lf.cs = f.b->cs; lf.hprev = f.b->hprev;
     return lf;
 }
+// The recurrence's form is chosen in ONE place and launched in ONE place: both forward drivers below and the test probe
+// (ivosw_lstm_fwd_probe) go through these.  A form's number: R = 1, 2, 4 rows per workgroup of lstm_fwd_kernel<R>, 10 + R of
+// lstm_fwd_quad_kernel<R>, LSTM_FORM_MFMA the 4x4x1 MFMA kernel (four rows per workgroup, at least eight rows).
+constexpr int LSTM_FORM_QUAD = 10, LSTM_FORM_MFMA = 20;
+static bool lstm_fwd_form_known(int form) {
+    const int R = form > LSTM_FORM_QUAD ? form - LSTM_FORM_QUAD : form;
+    return form == LSTM_FORM_MFMA || R == 1 || R == 2 || R == 4;
+}
+static int lstm_fwd_form_for(int N) {
+    const int R = rows_per_wg(2 * N);
+    if (!tune_get("LSTM_QUAD", 1)) return R;
+    if (tune_get("LSTM_MFMA", 1) && 2 * N >= 8) return LSTM_FORM_MFMA;
+    return LSTM_FORM_QUAD + R;
+}
+static void launch_lstm_fwd(int form, const LstmFwd& lf, hipStream_t st) {
+    const int rows = 2 * lf.N;
+    const int R = form == LSTM_FORM_MFMA ? 4 : form > LSTM_FORM_QUAD ? form - LSTM_FORM_QUAD : form, nwg = (rows + R - 1) / R;
+    switch (form) {
+        case LSTM_FORM_MFMA: hipLaunchKernelGGL(lstm_fwd_mfma_kernel, dim3(nwg), dim3(512), 0, st, lf); break;
+        case LSTM_FORM_QUAD + 1: hipLaunchKernelGGL(lstm_fwd_quad_kernel<1>, dim3(nwg), dim3(512), 0, st, lf); break;
+        case LSTM_FORM_QUAD + 2: hipLaunchKernelGGL(lstm_fwd_quad_kernel<2>, dim3(nwg), dim3(512), 0, st, lf); break;
+        case LSTM_FORM_QUAD + 4: hipLaunchKernelGGL(lstm_fwd_quad_kernel<4>, dim3(nwg), dim3(512), 0, st, lf); break;
+        case 1: hipLaunchKernelGGL(lstm_fwd_kernel<1>, dim3(nwg), dim3(512), 0, st, lf); break;
+        case 2: hipLaunchKernelGGL(lstm_fwd_kernel<2>, dim3(nwg), dim3(512), 0, st, lf); break;
+        default: hipLaunchKernelGGL(lstm_fwd_kernel<4>, dim3(nwg), dim3(512), 0, st, lf); break;
+    }
+}
+// the policy pass and the target pass in one launch of the MFMA recurrence (each pass has at least eight rows)
+static void launch_lstm_fwd_pair(const LstmFwd& a, const LstmFwd& b, hipStream_t st) {
+    LstmFwdPair pr{};
+    pr.j[0] = a;
+    pr.j[1] = b;
+    pr.first1 = (2 * a.N + 3) / 4;
+    hipLaunchKernelGGL(lstm_fwd_mfma_pair_kernel, dim3(pr.first1 + (2 * b.N + 3) / 4), dim3(512), 0, st, pr);
+}
+static void launch_lstm_fwd_ragged(const float* whh, const float* gx, float* hs, const SeqTable& tab, int n_seqs, hipStream_t st) {
+    hipLaunchKernelGGL(lstm_fwd_quad_ragged_kernel, dim3(2 * n_seqs), dim3(512), 0, st, whh, gx, hs, tab);
+}
+// recurrence + decoder in one kernel: a pair of samples' 2 T rows of [h_fw | h_bw] must fit the kernel's dynamic LDS
+constexpr size_t MEGA_LDS_LIMIT = 150 * 1024;
+static bool fwd_mega_fits(int T) { return mega_lds_bytes(T) <= MEGA_LDS_LIMIT; }
+static void launch_fwd_mega(const FwdMega* jobs, int n, hipStream_t st) {
+    static std::once_flag once;
+    std::call_once(once, [] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(brain_fwd_mega_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)MEGA_LDS_LIMIT); (void)hipGetLastError(); });
+    FwdMegaPair mp{};
+    int wgs[2] = {0, 0};
+    for (int i = 0; i < n; ++i) {
+        mp.j[i] = jobs[i];
+        wgs[i] = (jobs[i].N + 1) / 2;
+    }
+    mp.first1 = wgs[0];
+    hipLaunchKernelGGL(brain_fwd_mega_kernel, dim3(wgs[0] + wgs[1]), dim3(512), mega_lds_bytes(jobs[0].T), st, mp);
+}
+
 static bool fused_forward_ok(const FwdPass* f, int n) {
     if (!tune_get("DQN_FUSED", 1) || !tune_get("LSTM_QUAD", 1)) return false;
     if (n == 2) return tune_get("LSTM_MFMA", 1) && 2 * f[0].N >= 8 && 2 * f[1].N >= 8;   // the pair launch is the MFMA recurrence
@@ -1093,37 +1147,21 @@ static void brain_forward_fused(const FwdPass* f, int n, int T, hipStream_t st, 
     // recurrence + decoder in one kernel (FWD_MEGA, default OFF: measured 201 us per DQN step against 185.5 us for the separate
     // decoder launch - the decoder's 16 us run on 192 workgroups after their recurrences instead of on the whole chip) when every
     // pass is batched enough for the MFMA recurrence and the pair's 2 T rows of [h_fw | h_bw] fit LDS
-    bool mega = tune_get("FWD_MEGA", 0) && tune_get("LSTM_MFMA", 1) && mega_lds_bytes(T) <= 150 * 1024;
+    bool mega = tune_get("FWD_MEGA", 0) && tune_get("LSTM_MFMA", 1) && fwd_mega_fits(T);
     for (int i = 0; i < n; ++i) mega = mega && 2 * f[i].N >= 8;
     if (mega) {
-        static std::once_flag once;
-        std::call_once(once, [] { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(brain_fwd_mega_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024); (void)hipGetLastError(); });
-        FwdMegaPair mp{};
-        int wgs[2] = {0, 0};
+        FwdMega jobs[2] = {};
         for (int i = 0; i < n; ++i) {
             const FwdBufs& b = *f[i].b;
             const int keep_from = b.gates ? b.keep_from : f[i].N;
-            mp.j[i] = FwdMega{f[i].prm, b.gx, b.hs, b.gates, b.cs, b.hprev, b.d1, b.q, f[i].N, T, keep_from, keep_from, tune_get("MEGA_DBG", 0)};
-            wgs[i] = (f[i].N + 1) / 2;
+            jobs[i] = FwdMega{f[i].prm, b.gx, b.hs, b.gates, b.cs, b.hprev, b.d1, b.q, f[i].N, T, keep_from, keep_from, tune_get("MEGA_DBG", 0)};
         }
-        mp.first1 = wgs[0];
-        hipLaunchKernelGGL(brain_fwd_mega_kernel, dim3(wgs[0] + wgs[1]), dim3(512), mega_lds_bytes(T), st, mp);
+        launch_fwd_mega(jobs, n, st);
         return;
     }
-    if (n == 2) {
-        LstmFwdPair pr{};
-        pr.j[0] = lstm_fwd_args(f[0], T);
-        pr.j[1] = lstm_fwd_args(f[1], T);
-        pr.first1 = (2 * f[0].N + 3) / 4;
-        hipLaunchKernelGGL(lstm_fwd_mfma_pair_kernel, dim3(pr.first1 + (2 * f[1].N + 3) / 4), dim3(512), 0, st, pr);
-    } else {
-        const LstmFwd lf = lstm_fwd_args(f[0], T);
-        const int N = f[0].N, R = rows_per_wg(2 * N), nwg = (2 * N + R - 1) / R;
-        if (tune_get("LSTM_MFMA", 1) && 2 * N >= 8) hipLaunchKernelGGL(lstm_fwd_mfma_kernel, dim3((2 * N + 3) / 4), dim3(512), 0, st, lf);
-        else if (R == 1) hipLaunchKernelGGL(lstm_fwd_quad_kernel<1>, dim3(nwg), dim3(512), 0, st, lf);
-        else if (R == 2) hipLaunchKernelGGL(lstm_fwd_quad_kernel<2>, dim3(nwg), dim3(512), 0, st, lf);
-        else hipLaunchKernelGGL(lstm_fwd_quad_kernel<4>, dim3(nwg), dim3(512), 0, st, lf);
-    }
+    // (fused_forward_ok: LSTM_QUAD is on here, so the form is a quad or the MFMA one)
+    if (n == 2) launch_lstm_fwd_pair(lstm_fwd_args(f[0], T), lstm_fwd_args(f[1], T), st);
+    else launch_lstm_fwd(lstm_fwd_form_for(f[0].N), lstm_fwd_args(f[0], T), st);
     hipLaunchKernelGGL(dec_fused_kernel, dim3(tiles[0] + tiles[1]), dim3(256), 0, st, dg, O_W3, O_B3, O_W4, O_B4);
 }
 
@@ -1146,17 +1184,7 @@ static void brain_forward_internal(const float* prm, const float* x, int N, int 
     lf.whh = prm + O_WHH; lf.gx = b.gx; lf.hs = b.hs; lf.N = N; lf.T = T;
     lf.keep_from = b.gates ? b.keep_from : N;
     lf.gates = b.gates; lf.cs = b.cs; lf.hprev = b.hprev;
-    const int R = rows_per_wg(2 * N);
-    const int nwg = (2 * N + R - 1) / R;
-    if (tune_get("LSTM_QUAD", 1) && tune_get("LSTM_MFMA", 1) && 2 * N >= 8) {
-        hipLaunchKernelGGL(lstm_fwd_mfma_kernel, dim3((2 * N + 3) / 4), dim3(512), 0, st, lf);
-    } else if (tune_get("LSTM_QUAD", 1)) {
-        if (R == 1) hipLaunchKernelGGL(lstm_fwd_quad_kernel<1>, dim3(nwg), dim3(512), 0, st, lf);
-        else if (R == 2) hipLaunchKernelGGL(lstm_fwd_quad_kernel<2>, dim3(nwg), dim3(512), 0, st, lf);
-        else hipLaunchKernelGGL(lstm_fwd_quad_kernel<4>, dim3(nwg), dim3(512), 0, st, lf);
-    } else if (R == 1) hipLaunchKernelGGL(lstm_fwd_kernel<1>, dim3(nwg), dim3(512), 0, st, lf);
-    else if (R == 2) hipLaunchKernelGGL(lstm_fwd_kernel<2>, dim3(nwg), dim3(512), 0, st, lf);
-    else hipLaunchKernelGGL(lstm_fwd_kernel<4>, dim3(nwg), dim3(512), 0, st, lf);
+    launch_lstm_fwd(lstm_fwd_form_for(N), lf, st);
     // d1 = relu(relu(hcat) * W3^T + b3)
     g = GemmF32{};
     g.A = b.hs; g.sam = 256; g.sak = 1; g.relu_a = 1; g.B = prm + O_W3; g.sbk = 1; g.sbn = 256; g.C = b.d1; g.ldc = 128;
@@ -1464,7 +1492,7 @@ extern "C" int ivosw_brain_forward_ragged(const float* params, const float* x, c
         dg.j[0] = DecJob{params, b.hs, b.d1, q, R, R};
         eg.first1 = dg.first1 = tiles;
         hipLaunchKernelGGL(enc_fused_kernel, dim3(tiles), dim3(256), 0, st, eg, O_W1, O_B1, O_W2, O_B2, O_WIH);
-        hipLaunchKernelGGL(lstm_fwd_quad_ragged_kernel, dim3(2 * n_seqs), dim3(512), 0, st, params + O_WHH, b.gx, b.hs, tab);
+        launch_lstm_fwd_ragged(params + O_WHH, b.gx, b.hs, tab, n_seqs, st);
         hipLaunchKernelGGL(dec_fused_kernel, dim3(tiles), dim3(256), 0, st, dg, O_W3, O_B3, O_W4, O_B4);
     } else {
         // DQN_FUSED or LSTM_QUAD switched off: the N = 1 path of ivosw_brain_forward per sequence, on that sequence's slices
@@ -2410,6 +2438,127 @@ extern "C" int ivosw_lstm_bwd_probe(const float* whh, const float* gates, const 
     else if (form == 1) hipLaunchKernelGGL(lstm_bwd_kernel<1>, dim3(nwg), dim3(512), 0, st, lb);
     else if (form == 2) hipLaunchKernelGGL(lstm_bwd_kernel<2>, dim3(nwg), dim3(512), 0, st, lb);
     else hipLaunchKernelGGL(lstm_bwd_kernel<4>, dim3(nwg), dim3(512), 0, st, lb);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+// ---------------------------------------------------------------- test probes of the forward kernels (include/ivosw_probe.h)
+extern "C" int ivosw_enc_fused_probe(int njobs, const float* const* prm, const float* const* x, const float* const* x2, const int* rows0,
+                                     const int* rows, const int* keep_row, float* const* gx, float* const* a1, float* const* e,
+                                     ivosw_stream_t stream) {
+    IVOSW_REQUIRE(prm && x && x2 && rows0 && rows && keep_row && gx && a1 && e, "null pointer");
+    PROBE_COVERS(njobs == 1 || njobs == 2, "one or two jobs");
+    EncGroup eg{};
+    int tiles[2] = {0, 0};
+    for (int i = 0; i < njobs; ++i) {
+        IVOSW_REQUIRE(prm[i] && x[i] && x2[i] && gx[i] && a1[i] && e[i], "null pointer");
+        PROBE_COVERS(rows[i] >= 1 && rows[i] <= (1 << 20), "rows must be 1 .. 2^20");
+        PROBE_COVERS(rows0[i] >= 0 && rows0[i] <= rows[i] && keep_row[i] >= 0 && keep_row[i] <= rows[i], "0 <= rows0, keep_row <= rows");
+        PROBE_COVERS(aligned16_f({prm[i]}), "the parameter arena must be 16-byte aligned");
+        eg.j[i] = EncJob{prm[i], x[i], x2[i], gx[i], a1[i], e[i], rows0[i], rows[i], keep_row[i]};
+        tiles[i] = (rows[i] + FM - 1) / FM;
+    }
+    IVOSW_ON_DEVICE_OF(gx[0]);
+    eg.first1 = tiles[0];
+    hipLaunchKernelGGL(enc_fused_kernel, dim3(tiles[0] + tiles[1]), dim3(256), 0, as_stream(stream), eg, O_W1, O_B1, O_W2, O_B2, O_WIH);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_dec_fused_probe(int njobs, const float* const* prm, const float* const* hs, const int* rows, const int* keep_row,
+                                     float* const* d1, float* const* q, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(prm && hs && rows && keep_row && d1 && q, "null pointer");
+    PROBE_COVERS(njobs == 1 || njobs == 2, "one or two jobs");
+    DecGroup dg{};
+    int tiles[2] = {0, 0};
+    for (int i = 0; i < njobs; ++i) {
+        IVOSW_REQUIRE(prm[i] && hs[i] && d1[i] && q[i], "null pointer");
+        PROBE_COVERS(rows[i] >= 1 && rows[i] <= (1 << 20), "rows must be 1 .. 2^20");
+        PROBE_COVERS(keep_row[i] >= 0 && keep_row[i] <= rows[i], "0 <= keep_row <= rows");
+        PROBE_COVERS(aligned16_f({prm[i], hs[i]}), "the parameter arena and hs must be 16-byte aligned");
+        dg.j[i] = DecJob{prm[i], hs[i], d1[i], q[i], rows[i], keep_row[i]};
+        tiles[i] = (rows[i] + FM - 1) / FM;
+    }
+    IVOSW_ON_DEVICE_OF(q[0]);
+    dg.first1 = tiles[0];
+    hipLaunchKernelGGL(dec_fused_kernel, dim3(tiles[0] + tiles[1]), dim3(256), 0, as_stream(stream), dg, O_W3, O_B3, O_W4, O_B4);
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+// what every recurrence probe checks of one argument set; 0 or the error code with the message set
+static int lstm_fwd_probe_args(const char* who, const float* whh, const float* gx, float* hs, float* gates, float* cs, float* hprev, int N, int T,
+                               int keep_from, LstmFwd* lf) {
+    if (!(whh && gx && hs)) { set_error("%s: null pointer", who); return IVOSW_ERR_ARG; }
+    if ((gates == nullptr) != (cs == nullptr) || (gates == nullptr) != (hprev == nullptr)) {
+        set_error("%s: not covered: gates, cs and hprev are given together or not at all", who);
+        return IVOSW_ERR_ARG;
+    }
+    if (!(N >= 1 && T >= 1 && (long long)N * T <= (1 << 20))) { set_error("%s: not covered: N, T >= 1 and N*T <= 2^20", who); return IVOSW_ERR_ARG; }
+    if (!(keep_from >= 0 && keep_from <= N)) { set_error("%s: not covered: 0 <= keep_from <= N", who); return IVOSW_ERR_ARG; }
+    if (!aligned16_f({whh})) { set_error("%s: not covered: whh must be 16-byte aligned", who); return IVOSW_ERR_ARG; }
+    *lf = LstmFwd{};
+    lf->whh = whh; lf->gx = gx; lf->hs = hs; lf->gates = gates; lf->cs = cs; lf->hprev = hprev; lf->N = N; lf->T = T;
+    lf->keep_from = gates ? keep_from : N;               // (as lstm_fwd_args)
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_lstm_fwd_probe(const float* whh, const float* gx, float* hs, float* gates, float* cs, float* hprev, int N, int T,
+                                    int keep_from, int form, int* ran, ivosw_stream_t stream) {
+    LstmFwd lf;
+    if (const int rc = lstm_fwd_probe_args(__func__, whh, gx, hs, gates, cs, hprev, N, T, keep_from, &lf)) return rc;
+    PROBE_COVERS(form == 0 || lstm_fwd_form_known(form), "form must be 0 (the product's choice), 1, 2, 4 (plain), 11, 12, 14 (quad) or 20 (mfma)");
+    PROBE_COVERS(form != LSTM_FORM_MFMA || 2 * N >= 8, "the mfma form needs at least eight rows (2 N >= 8)");
+    IVOSW_ON_DEVICE_OF(hs);
+    if (form == 0) form = lstm_fwd_form_for(N);
+    launch_lstm_fwd(form, lf, as_stream(stream));
+    IVOSW_CHECK_LAUNCH();
+    if (ran) *ran = form;
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_lstm_fwd_pair_probe(const float* const* whh, const float* const* gx, float* const* hs, float* const* gates, float* const* cs,
+                                         float* const* hprev, const int* N, int T, const int* keep_from, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(whh && gx && hs && gates && cs && hprev && N && keep_from, "null pointer");
+    LstmFwd lf[2];
+    for (int i = 0; i < 2; ++i) {
+        if (const int rc = lstm_fwd_probe_args(__func__, whh[i], gx[i], hs[i], gates[i], cs[i], hprev[i], N[i], T, keep_from[i], &lf[i])) return rc;
+        PROBE_COVERS(2 * N[i] >= 8, "the pair launch is the mfma form: each job needs at least eight rows (2 N >= 8)");
+    }
+    IVOSW_ON_DEVICE_OF(hs[0]);
+    launch_lstm_fwd_pair(lf[0], lf[1], as_stream(stream));
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_lstm_fwd_ragged_probe(const float* whh, const float* gx, float* hs, const int* lengths, int n_seqs, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(whh && gx && hs && lengths, "null pointer");
+    PROBE_COVERS(aligned16_f({whh}), "whh must be 16-byte aligned");
+    SeqTable tab;
+    if (ragged_rows(__func__, lengths, n_seqs, &tab) < 0) return IVOSW_ERR_ARG;
+    IVOSW_ON_DEVICE_OF(hs);
+    launch_lstm_fwd_ragged(whh, gx, hs, tab, n_seqs, as_stream(stream));
+    IVOSW_CHECK_LAUNCH();
+    return IVOSW_OK;
+}
+
+extern "C" int ivosw_fwd_mega_probe(int njobs, const float* const* prm, const float* const* gx, float* const* hs, float* const* gates,
+                                    float* const* cs, float* const* hprev, float* const* d1, float* const* q, const int* N, int T,
+                                    const int* keep_from, const int* hs_from, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(prm && gx && hs && gates && cs && hprev && d1 && q && N && keep_from && hs_from, "null pointer");
+    PROBE_COVERS(njobs == 1 || njobs == 2, "one or two jobs");
+    FwdMega jobs[2] = {};
+    for (int i = 0; i < njobs; ++i) {
+        IVOSW_REQUIRE(prm[i] && d1[i] && q[i], "null pointer");
+        LstmFwd lf;
+        if (const int rc = lstm_fwd_probe_args(__func__, prm[i] + O_WHH, gx[i], hs[i], gates[i], cs[i], hprev[i], N[i], T, keep_from[i], &lf)) return rc;
+        PROBE_COVERS(2 * N[i] >= 8, "each job needs at least eight rows (2 N >= 8)");
+        PROBE_COVERS(hs_from[i] >= 0 && hs_from[i] <= N[i], "0 <= hs_from <= N");
+        PROBE_COVERS(fwd_mega_fits(T), "2 T rows of [h_fw | h_bw] exceed the kernel's LDS");
+        jobs[i] = FwdMega{prm[i], gx[i], hs[i], gates[i], cs[i], hprev[i], d1[i], q[i], N[i], T, lf.keep_from, hs_from[i], 0};
+    }
+    IVOSW_ON_DEVICE_OF(q[0]);
+    launch_fwd_mega(jobs, njobs, as_stream(stream));
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }

@@ -2,6 +2,8 @@
 csrc/brain_fused.h: head_fused_kernel; csrc/brain.hip: lstm_bwd_quad_kernel, lstm_bwd_kernel), one function per operation, and the fixtures
 of tests/test_gpu_dqn_kernels.py.  tests/test_dqn_ref.py pins the functions, composed in the step's order, to
 oracle.brain_oracle.dqn_loss_and_grads(..., dtype=np.float64) and asserts every fixture's preconditions - no GPU is needed for either.
+The second half of the file does the same for the Brain forward kernels (tests/test_gpu_dqn_fwd_kernels.py): enc, dec, lstm_step, lstm_fwd,
+their bounds and fixtures, pinned to oracle.brain_oracle.brain_forward(..., np.float64, keep=True).
 
 Every function takes a dtype: float64 is the reference, float32 the "same restatement in fp32" that the yardsticks of the GPU tests name."""
 import numpy as np
@@ -383,3 +385,253 @@ def lstm_fixture(N, T):
     dhc = (0.1 * rng.standard_normal((N, 2 * H))).astype(np.float32)
     action = np.array([(0, T - 1, T // 2, min(1, T - 1))[n % 4] for n in range(N)], np.int64)
     return dict(whh=whh, gates=gates, cs=cs, dhc=dhc, action=action)
+
+
+# ================================================================ the Brain forward (tests/test_gpu_dqn_fwd_kernels.py)
+# Float64 restatements of enc_fused_kernel, dec_fused_kernel (csrc/brain_fused.h), the recurrence forms and brain_fwd_mega_kernel
+# (csrc/brain.hip), their error bounds and their fixtures.  P is a dict of the ten state_dict tensors (SHAPES below); arena(P) lays it out
+# as the kernels read it.  tests/test_dqn_ref.py pins the composition enc -> lstm_fwd -> dec to oracle.brain_oracle.brain_forward.
+SHAPES = {name: shape for name, _, shape in ARENA}
+LOG2E32 = np.float32(1.4426950408889634)
+
+
+def arena(P):
+    """The fp32 parameter arena (state_dict order) of a parameter dict."""
+    flat = np.zeros(NPARAMS, np.float32)
+    for name, off, shape in ARENA:
+        flat[off:off + int(np.prod(shape))] = np.asarray(P[name], np.float32).reshape(-1)
+    return flat
+
+
+def enc(P, x, dtype=np.float64):
+    """x [rows,2] -> a1 = relu(x W1^T + b1), e = a1 W2^T + b2, gx = e W_ih^T."""
+    f = dtype
+    a1 = np.maximum(x.astype(f) @ P["encoder_fc1.weight"].astype(f).T + P["encoder_fc1.bias"].astype(f), 0)
+    e = a1 @ P["encoder_fc2.weight"].astype(f).T + P["encoder_fc2.bias"].astype(f)
+    return a1, e, e @ P["lstm_cell.weight_ih"].astype(f).T
+
+
+def enc_bounds(P, x):
+    """Per-element bounds of (a1, e, gx) against enc in float64: each stage an fp32 sum of K products (and a bias) in any order,
+    (K + 2) 2^-23 sum |a||b|, on ITS input - within the previous stage's bound of the reference's -, plus that bound carried through |W|.
+    relu moves nothing by more than its argument moved."""
+    ab = lambda k: np.abs(np.asarray(P[k], np.float64))
+    a1, e, _ = enc(P, x)
+    b_a1 = sum_bound(2, np.abs(x.astype(np.float64)) @ ab("encoder_fc1.weight").T + ab("encoder_fc1.bias"))
+    w2 = ab("encoder_fc2.weight").T
+    b_e = sum_bound(128, (a1 + b_a1) @ w2 + ab("encoder_fc2.bias")) + b_a1 @ w2
+    wih = ab("lstm_cell.weight_ih").T
+    return b_a1, b_e, sum_bound(128, (np.abs(e) + b_e) @ wih) + b_e @ wih
+
+
+def dec(P, hs, dtype=np.float64):
+    """hs [rows,256] -> d1 = relu(relu(hs) W3^T + b3), q = d1 w4 + b4."""
+    f = dtype
+    d1 = np.maximum(np.maximum(hs.astype(f), 0) @ P["decoder_fc1.weight"].astype(f).T + P["decoder_fc1.bias"].astype(f), 0)
+    return d1, d1 @ P["decoder_fc2.weight"].astype(f)[0] + P["decoder_fc2.bias"].astype(f)[0]
+
+
+def dec_bounds(P, hs):
+    """(bound of d1, bound of q): K = 256 on relu(hs), then K = 128 on the kernel's own d1 plus d1's bound carried through |w4|."""
+    ab = lambda k: np.abs(np.asarray(P[k], np.float64))
+    d1, _ = dec(P, hs)
+    b_d1 = sum_bound(256, np.maximum(hs.astype(np.float64), 0) @ ab("decoder_fc1.weight").T + ab("decoder_fc1.bias"))
+    w4 = ab("decoder_fc2.weight")[0]
+    return b_d1, sum_bound(128, (d1 + b_d1) @ w4 + ab("decoder_fc2.bias")[0]) + b_d1 @ w4
+
+
+def _sig(x):
+    return 1.0 / (1.0 + np.exp(-x))
+
+
+def lstm_step(whh, gx_t, hprev, cprev, dtype=np.float64):
+    """One frame of the cell: gx_t [..,512], hprev, cprev [..,128] -> (gates [..,512] after their activations (i, f, g, o), c, h)."""
+    f = dtype
+    pre = gx_t.astype(f) + hprev.astype(f) @ whh.astype(f).T
+    gates = np.concatenate([_sig(pre[..., :2 * H]), np.tanh(pre[..., 2 * H:3 * H]), _sig(pre[..., 3 * H:])], -1).astype(f)
+    c = gates[..., H:2 * H] * cprev.astype(f) + gates[..., :H] * gates[..., 2 * H:3 * H]
+    return gates, c, gates[..., 3 * H:] * np.tanh(c)
+
+
+def prev_frame(d, t):
+    """The frame direction d consumed before frame t (-1 / T: none)."""
+    return t - 1 if d == 0 else t + 1
+
+
+def lstm_fwd(whh, gx, dtype=np.float64):
+    """Both directions from a zero state: gx [N,T,512] -> hs [N,T,256] (h_fw | h_bw after frame t), gates [2,N,T,512], cs, hprev [2,N,T,128]
+    (hprev: h before the frame), in the layouts the kernels write."""
+    f = dtype
+    N, T, _ = gx.shape
+    hs, gates = np.zeros((N, T, 2 * H), f), np.zeros((2, N, T, 4 * H), f)
+    cs, hprev = np.zeros((2, N, T, H), f), np.zeros((2, N, T, H), f)
+    for d in range(2):
+        h, c = np.zeros((N, H), f), np.zeros((N, H), f)
+        for t in (range(T) if d == 0 else range(T - 1, -1, -1)):
+            hprev[d, :, t] = h
+            gates[d, :, t], c, h = lstm_step(whh, gx[:, t], h, c, f)
+            cs[d, :, t], hs[:, t, d * H:(d + 1) * H] = c, h
+    return hs, gates, cs, hprev
+
+
+# ---- the device's activation expressions in fp32 numpy (common.h: fast_exp, fast_rcp, fast_tanh; lstm_fwd_*: sg, act)
+def _fma32(a, b, c):
+    """fl32(a b + c) for fp32 a, c and b in {1, 2}: the product is exact in float64 and so is the sum of two fp32 numbers of this range."""
+    return (a.astype(np.float64) * b + c).astype(np.float32)
+
+
+def gate_act32(pre, gk):
+    """x log2e -> exp2 -> 1 + . -> reciprocal -> fma(sg, gk, 1 - gk) with x = -gk pre: the sigmoid (gk = 1) and, as 2 sigmoid(2x) - 1, the tanh
+    (gk = 2) of the gate pre-activations, every operation rounded to fp32."""
+    pre = np.asarray(pre, np.float32)
+    g = np.float32(gk)
+    with np.errstate(over="ignore"):
+        sg = np.float32(1.0) / (np.float32(1.0) + np.exp2((-g * pre) * LOG2E32, dtype=np.float32))
+    return _fma32(sg, float(gk), 1.0 - float(gk))
+
+
+def cell_tanh32(c):
+    """1 - 2 rcp(exp2(2c log2e) + 1), every operation rounded to fp32."""
+    c = np.asarray(c, np.float32)
+    with np.errstate(over="ignore"):
+        r = np.float32(1.0) / (np.exp2((np.float32(2.0) * c) * LOG2E32, dtype=np.float32) + np.float32(1.0))
+    return np.float32(1.0) - np.float32(2.0) * r
+
+
+ACT_MARGIN = 4      # v_exp_f32 and v_rcp_f32 may each be an ulp off where numpy rounds correctly
+
+
+def act_terms(whh, gx):
+    """The activation allowances of the step check, from the fixture alone (never from device output): ACT_MARGIN x the worst error against
+    float64 of the fp32 restatements above over the float64 chain's own pre-activations and cell states.  -> (sigmoid gates, g gate, tanh(c))."""
+    N, T, _ = gx.shape
+    _, gates, cs, hprev = lstm_fwd(whh, gx)
+    pre = gx.astype(np.float64)[None] + hprev @ whh.astype(np.float64).T
+    sgm = np.concatenate([pre[..., :2 * H], pre[..., 3 * H:]], -1)
+    e_s = np.abs(gate_act32(sgm, 1).astype(np.float64) - _sig(sgm.astype(np.float32).astype(np.float64))).max()
+    g = pre[..., 2 * H:3 * H]
+    e_g = np.abs(gate_act32(g, 2).astype(np.float64) - np.tanh(g.astype(np.float32).astype(np.float64))).max()
+    e_c = np.abs(cell_tanh32(cs).astype(np.float64) - np.tanh(cs.astype(np.float32).astype(np.float64))).max()
+    return ACT_MARGIN * float(e_s), ACT_MARGIN * float(e_g), ACT_MARGIN * float(e_c)
+
+
+def _peak_slope(kind, x, r):
+    """The largest slope of sigmoid (kind 0) or tanh (kind 1) on [x - r, x + r]: both slopes peak at 0 and fall off monotonically."""
+    z = np.where(np.abs(x) <= r, 0.0, np.abs(x) - r)
+    if kind == 0:
+        s = _sig(z)
+        return s * (1 - s)
+    return 1 - np.tanh(z) ** 2
+
+
+def step_bounds(whh, gx_t, hprev, cprev, acts):
+    """Allowances of (gates, c, h) of ONE step against lstm_step in float64 on the same gx_t, hprev, cprev.  The pre-activation is an fp32
+    sum of 128 products and gx_t in any order: lin = (128 + 2) 2^-23 (sum |h||w| + |gx_t|); a gate moves by at most the activation's largest
+    slope within lin of the reference's pre-activation times lin, plus the activation term of act_terms.  c = f c' + i g and h = o tanh(c)
+    carry the gates' allowances through their factors and add 2^-23 of each rounded product and sum."""
+    a_s, a_g, a_c = acts
+    w = np.abs(whh.astype(np.float64))
+    pre = gx_t.astype(np.float64) + hprev.astype(np.float64) @ whh.astype(np.float64).T
+    lin = sum_bound(128, np.abs(hprev.astype(np.float64)) @ w.T + np.abs(gx_t.astype(np.float64)))
+    kind = np.zeros(4 * H, np.int64)
+    kind[2 * H:3 * H] = 1
+    slope = np.where(kind == 1, _peak_slope(1, pre, lin), _peak_slope(0, pre, lin))
+    b_g = slope * lin + np.where(kind == 1, a_g, a_s)
+    gates, c, h = lstm_step(whh, gx_t, hprev, cprev)
+    i, fg, g, o = (np.abs(gates[..., k * H:(k + 1) * H]) for k in range(4))
+    bi, bf, bg, bo = (b_g[..., k * H:(k + 1) * H] for k in range(4))
+    cp = np.abs(cprev.astype(np.float64))
+    b_c = cp * bf + (g + bg) * bi + i * bg + 2 * U23 * (fg * cp + i * g)
+    tc = np.abs(np.tanh(c))
+    b_h = tc * bo + (o + bo) * (_peak_slope(1, c, b_c) * b_c + a_c) + U23 * np.abs(h)
+    return b_g, b_c, b_h
+
+
+# ---- fixtures of the forward tests
+ENC_ROWS = (1, 47, 48, 49, 97)
+
+
+def enc_cases(rows):
+    """(rows0, keep_row) of the table: the x / x2 boundary at rows (no x2), inside the second tile and after the first row; the kept rows from
+    0, from inside the second tile, and none."""
+    return [(r0, k) for r0 in sorted({rows, 50, 1}, reverse=True) if r0 <= rows for k in sorted({0, 50, rows}) if k <= rows]
+
+
+TWO_JOBS = ((49, 1, 48), (47, 47, 0))       # (rows, rows0, keep_row) of the two-job cases: job 0, job 1 (its tiles start at workgroup 2)
+
+
+def _edge_rows(x):
+    """The relu's edge in the input: rows of +0, -0, negatives and the smallest subnormal of either sign, from the last row backwards (every
+    tile shape has its tail rows among them), as many as fit."""
+    edge = np.array([[0.0, 0.0], [-0.0, -0.0], [-1.0, -2.0], [SUBNORMAL, 0.0], [0.0, -SUBNORMAL], [-SUBNORMAL, SUBNORMAL]], np.float32)
+    n = min(len(edge), x.shape[0])
+    x[x.shape[0] - n:] = edge[:n] if x.shape[0] >= len(edge) else edge[[3, 1, 0, 2, 4, 5][:n]]
+    return x
+
+
+def brain_params(seed, exact):
+    """A parameter dict.  exact: W1, b1 in {-2 .. 2} with b1 nowhere 0 (a subnormal input is absorbed: a1 stays an integer), W2, b2, W_ih in
+    {-1, 0, 1}, W3, w4, b3, b4 in {-1, 0, 1}.  dense: torch's default ranges; units 0 .. 3 of encoder_fc1 have b1 = 0 and the weight rows
+    (1, 0), (-1, 0), (0, 1), (0, -1), so that their pre-activation IS +-x: the relu sees +0, -0 and +-subnormal exactly."""
+    rng = np.random.default_rng([21, seed, int(exact)])
+    P = {}
+    for name, _, shape in ARENA:
+        if exact:
+            P[name] = ints(rng, shape, -1, 1)
+        else:
+            s = 1.0 / np.sqrt(shape[-1] if len(shape) > 1 else 128)
+            P[name] = rng.uniform(-s, s, shape).astype(np.float32)
+    if exact:
+        P["encoder_fc1.weight"] = ints(rng, (128, 2))
+        b1 = ints(rng, (128,))
+        P["encoder_fc1.bias"] = np.where(b1 == 0, np.float32(1.0), b1).astype(np.float32)
+    else:
+        P["encoder_fc1.weight"][:4] = np.array([[1, 0], [-1, 0], [0, 1], [0, -1]], np.float32)
+        P["encoder_fc1.bias"][:4] = 0.0
+    return P
+
+
+def enc_fixture(rows, exact, seed=0):
+    """x [rows,2]: integers in {-2 .. 2} (exact) or uniform in [0, 1) as the states are (dense), with the edge rows of _edge_rows."""
+    rng = np.random.default_rng([22, rows, int(exact), seed])
+    x = ints(rng, (rows, 2)) if exact else rng.uniform(0, 1, (rows, 2)).astype(np.float32)
+    return _edge_rows(x)
+
+
+def dec_fixture(rows, exact, seed=0):
+    """hs [rows,256] with the mask classes in every row: integers in {-2 .. 2} (exact; the subnormal is no integer and stays out) or
+    uniform in (-1, 1) as h is (dense, all five classes)."""
+    rng = np.random.default_rng([23, rows, int(exact), seed])
+    if exact:
+        return with_mask_classes(ints(rng, (rows, 256)), True)
+    return with_mask_classes(rng.uniform(-1, 1, (rows, 256)).astype(np.float32))
+
+
+FWD_T = (1, 2, 3, 9)
+FORM_MFMA = 20
+FWD_FORMS_SMALL = (1, 2, 4, 11, 12, 14)                      # lstm_fwd_kernel<R>, lstm_fwd_quad_kernel<R> (10 + R): N in FWD_N_SMALL
+FWD_N_SMALL, FWD_N_MFMA = (1, 3), (4, 5, 6)
+FORM_NAMES = {1: "plain<1>", 2: "plain<2>", 4: "plain<4>", 11: "quad<1>", 12: "quad<2>", 14: "quad<4>", 20: "mfma"}
+RAGGED_LENGTHS = (1, 2, 9, 1)
+MEGA_T = (1, 32, 33)
+
+
+def product_form(N):
+    """The recurrence form the forward drivers choose at N samples with the default tunables (csrc/brain.hip: lstm_fwd_form_for)."""
+    rows = 2 * N
+    return FORM_MFMA if rows >= 8 else 10 + (1 if rows <= 256 else 2 if rows <= 512 else 4)
+
+
+def fwd_fixture(N, T, seed=0):
+    """whh in torch's default range, gx [N,T,512] unit normal (the scale W_ih e has on trained weights)."""
+    rng = np.random.default_rng([24, N, T, seed])
+    s = 1.0 / np.sqrt(H)
+    return rng.uniform(-s, s, (4 * H, H)).astype(np.float32), rng.standard_normal((N, T, 4 * H)).astype(np.float32)
+
+
+def saturating_fixture(N, T):
+    """gx = +-100 with every combination of the four gates' signs (unit j of sample n at frame t: combination (j + n + t) mod 16)."""
+    whh, _ = fwd_fixture(N, T, 1)
+    j = np.arange(H)[None, None, :] + np.arange(N)[:, None, None] + np.arange(T)[None, :, None]
+    gx = np.concatenate([np.where((j >> k) & 1, 100.0, -100.0) for k in range(4)], -1).astype(np.float32)
+    return whh, gx

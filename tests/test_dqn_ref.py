@@ -1,5 +1,6 @@
-"""tests/dqn_ref.py on the CPU: its float64 restatements, composed in the step's order, ARE oracle.brain_oracle.dqn_loss_and_grads in float64,
-and its fixtures have the properties the GPU tests (tests/test_gpu_dqn_kernels.py) lean on."""
+"""tests/dqn_ref.py on the CPU: its float64 restatements, composed in the step's order, ARE oracle.brain_oracle.dqn_loss_and_grads and
+oracle.brain_oracle.brain_forward in float64, and its fixtures have the properties the GPU tests (tests/test_gpu_dqn_kernels.py,
+tests/test_gpu_dqn_fwd_kernels.py) lean on."""
 import numpy as np
 import pytest
 
@@ -162,3 +163,112 @@ def test_lstm_fixture_covers_first_last_and_middle_loss_frames():
     assert len({int(v) for v in fx["action"][:4]}) >= 3          # rows of one workgroup (forms 2 and 4) stop at different steps
     ref = R.bptt(**fx)
     assert not ref[~R.live_frames(fx["action"], 130, 9)].any() and np.abs(ref[R.live_frames(fx["action"], 130, 9)]).min(-1).max() > 0
+
+
+# ---------------------------------------------------------------- the forward restatements and fixtures
+def _close(got, want, what):
+    assert got.shape == want.shape, what
+    assert np.abs(got - want).max() <= 1e-12 * np.abs(want).max(), what
+
+
+@pytest.mark.parametrize("N,T", [(5, 9), (3, 1), (2, 4)])
+def test_the_forward_restatements_composed_are_the_oracle_in_float64(N, T):
+    """enc -> lstm_fwd -> dec reproduce the oracle's q and every tensor it keeps to 1e-12 of each tensor's scale; hprev is hs of the frame
+    the direction consumed before; lstm_fwd is lstm_step frame by frame."""
+    rng = np.random.default_rng([2, N, T])
+    P = _params(rng)
+    x = rng.uniform(-1, 1, (N, T, 2))
+    q_o, c = O.brain_forward(P, x, np.float64, keep=True)
+    assert R.SHAPES == SHAPES
+    a1, e, gx = R.enc(P, x.reshape(-1, 2))
+    hs, gates, cs, hprev = R.lstm_fwd(P["lstm_cell.weight_hh"], gx.reshape(N, T, 512))
+    d1, q = R.dec(P, hs.reshape(-1, 256))
+    _close(a1.reshape(N, T, 128), c["a1"], "a1")
+    _close(e.reshape(N, T, 128), c["e"], "e")
+    _close(hs, np.concatenate([c["hs"][0], c["hs"][1]], 2), "hs")
+    _close(gates, c["gates"], "gates")
+    _close(cs, c["cs"], "cs")
+    _close(d1.reshape(N, T, 128), c["d1"], "d1")
+    _close(q.reshape(N, T), q_o, "q")
+    want = np.zeros_like(c["hs"])                        # (the step's hprev of test_the_restatements_composed_are_the_oracle_in_float64)
+    want[0, :, 1:], want[1, :, :-1] = hs[:, :-1, :128], hs[:, 1:, 128:]
+    assert np.array_equal(hprev, want)
+    for d, t in ((0, T - 1), (1, 0)):                    # the last step of either direction, from the chain's own state
+        tp = R.prev_frame(d, t)
+        cprev = cs[d, :, tp] if 0 <= tp < T else np.zeros((N, 128))
+        g, cc, h = R.lstm_step(P["lstm_cell.weight_hh"], gx.reshape(N, T, 512)[:, t], hprev[d, :, t], cprev)
+        assert np.array_equal(g, gates[d, :, t]) and np.array_equal(cc, cs[d, :, t]) and np.array_equal(h, hs[:, t, d * 128:(d + 1) * 128])
+    assert np.array_equal(R.arena(P)[82432:82432 + 512 * 128].reshape(512, 128), P["lstm_cell.weight_hh"])
+
+
+def test_forward_case_tables_reach_every_tile_edge():
+    assert R.enc_cases(1) == [(1, 0), (1, 1)]
+    assert R.enc_cases(48) == [(48, 0), (48, 48), (1, 0), (1, 48)]
+    assert set(R.enc_cases(97)) == {(r0, k) for r0 in (97, 50, 1) for k in (0, 50, 97)}       # both thresholds inside the second tile
+    assert R.ENC_ROWS == (1, 47, 48, 49, 97) and [r for r, _, _ in R.TWO_JOBS] == [49, 47]
+    assert [R.product_form(N) for N in (3, 4, 130)] == [11, 20, 20]
+    assert R.FWD_T == (1, 2, 3, 9) and R.FWD_N_SMALL == (1, 3) and R.FWD_N_MFMA == (4, 5, 6) and R.MEGA_T == (1, 32, 33)
+    assert 2 * 3 % 4 == 2 and 2 * 5 % 4 == 2 and 2 * 4 % 4 == 0 and 2 * 6 % 4 == 0       # a tail of two rows at N = 3 and 5, a workgroup across
+    assert 3 % 4 != 0 and 5 % 4 != 0 and 6 % 4 != 0                                         # the direction boundary at N = 3, 5 and 6
+    lds = lambda T: 2 * T * (2 * 128 + 4) * 4
+    assert lds(73) <= 150 * 1024 < lds(74)                                                 # T = 74 is the first the mega kernel refuses
+
+
+def test_exact_forward_fixtures_have_integer_partial_sums_below_2_24_and_the_relu_edges():
+    ab = lambda t: np.abs(np.asarray(t, np.float64))
+    for seed in (0, 1):
+        P = R.brain_params(seed, True)
+        assert all(_is_integer(v) for v in P.values()) and not (P["encoder_fc1.bias"] == 0).any()
+        for rows in R.ENC_ROWS:
+            x = R.enc_fixture(rows, True, seed)
+            a1, e, gx = R.enc(P, x)
+            assert _is_integer(a1) and _is_integer(e) and _is_integer(gx), "a subnormal input reached a sum"
+            m1 = ab(x) @ ab(P["encoder_fc1.weight"]).T + ab(P["encoder_fc1.bias"])
+            m2 = m1 @ ab(P["encoder_fc2.weight"]).T + ab(P["encoder_fc2.bias"])
+            assert (m2 @ ab(P["lstm_cell.weight_ih"]).T).max() < EXACT_LIMIT
+            assert (a1 == 0).any() and (a1 > 0).any()
+            if rows >= 6:
+                assert (x == R.SUBNORMAL).any() and (x == -R.SUBNORMAL).any() and (x < -0.5).any()
+                assert ((x == 0) & np.signbit(x)).any() and ((x == 0) & ~np.signbit(x)).any()
+            hs = R.dec_fixture(rows, True, seed)
+            assert _is_integer(hs) and all(R.has_every_mask_class(r, integer=True) for r in hs)
+            m = np.maximum(hs, 0).astype(np.float64) @ ab(P["decoder_fc1.weight"]).T + ab(P["decoder_fc1.bias"])
+            assert (m @ ab(P["decoder_fc2.weight"])[0] + ab(P["decoder_fc2.bias"])[0]).max() < EXACT_LIMIT
+            d1, _ = R.dec(P, hs)
+            assert (d1 == 0).any() and (d1 > 0).any()
+
+
+def test_dense_forward_fixtures_put_the_relu_on_its_edge():
+    P = R.brain_params(0, False)
+    assert not P["encoder_fc1.bias"][:4].any() and (P["encoder_fc1.bias"][4:] != 0).all()
+    for rows in R.ENC_ROWS:
+        x = R.enc_fixture(rows, False)
+        a1, _, _ = R.enc(P, x)
+        assert np.array_equal(a1[:, 0], np.maximum(x[:, 0], 0).astype(np.float64)) and np.array_equal(a1[:, 3], np.maximum(-x[:, 1], 0).astype(np.float64))
+        assert (a1[:, :4] == R.SUBNORMAL).any()                      # the smallest subnormal passes the relu as itself
+        if rows >= 6:
+            assert sorted(set(a1[-6:, :4].ravel().tolist())) == [0.0, float(R.SUBNORMAL), 1.0, 2.0]
+        assert all(R.has_every_mask_class(r) for r in R.dec_fixture(rows, False))
+        b_a1, b_e, b_gx = R.enc_bounds(P, x)
+        assert (b_a1[:, :4] <= 4 * R.U23 * float(np.abs(x).max())).all() and b_gx.max() < 1e-3 and b_gx.min() > 0
+
+
+def test_recurrence_fixtures_saturate_and_bound_as_the_gpu_tests_assume():
+    for N, T in ((3, 9), (5, 3)):
+        whh, gx = R.saturating_fixture(N, T)
+        signs = {tuple(bool(gx[n, t, k * 128 + j] > 0) for k in range(4)) for n in range(N) for t in range(T) for j in range(128)}
+        assert len(signs) == 16 and (np.abs(gx) == 100).all()
+        hs, gates, cs, hprev = R.lstm_fwd(whh, gx)
+        pre = gx[None].astype(np.float64) + hprev @ whh.astype(np.float64).T
+        assert np.abs(pre).min() >= 95, "exp2 of 95 log2(e) = 137 overflows fp32, of -137 vanishes beside 1"
+        assert np.isfinite(hs).all() and np.abs(cs).max() <= T
+    whh, gx = R.fwd_fixture(5, 9)
+    a_s, a_g, a_c = R.act_terms(whh, gx)
+    assert 0 < a_s < 2e-6 and 0 < a_g < 2e-6 and 0 < a_c < 2e-6           # a handful of fp32 ulps of numbers below 1
+    hs, gates, cs, hprev = R.lstm_fwd(whh, gx)
+    b_g, b_c, b_h = R.step_bounds(whh, gx[:, 4], hprev[0, :, 4], cs[0, :, 3], (a_s, a_g, a_c))
+    assert b_g.min() >= a_s and b_g.max() < 1e-4 and b_c.max() < 1e-4 and b_h.max() < 1e-4
+    x = np.array([-100.0, -3.0, -0.0, 0.0, 0.5, 3.0, 100.0], np.float32)
+    assert np.abs(R.gate_act32(x, 1) - 1 / (1 + np.exp(-x.astype(np.float64)))).max() < 3e-7
+    assert np.abs(R.gate_act32(x, 2) - np.tanh(x.astype(np.float64))).max() < 3e-7 and np.abs(R.cell_tanh32(x) - np.tanh(x.astype(np.float64))).max() < 3e-7
+    assert R.gate_act32(x, 1)[[0, -1]].tolist() == [0.0, 1.0] and R.gate_act32(x, 2)[[0, -1]].tolist() == [-1.0, 1.0]
