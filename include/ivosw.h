@@ -432,6 +432,16 @@ int ivosw_assess_forward_u8(const void* packed, int dtype, const uint8_t* rgbx, 
 int ivosw_assess_forward_objects_u8(const void* packed, int dtype, const uint8_t* rgbx, int n_frames, const float* masks,
                                     long mask_stride_frame, long mask_stride_obj, int n_obj, int H, int W, float* scores,
                                     void* ws, size_t ws_bytes, int chunk, ivosw_stream_t stream);
+/* ivosw_assess_forward[_u8] with the pooled features handed out: features [B,2048] fp32 = the 8 x 8 average pool of res5, the rows fc1
+ * is applied to (scores[u] = features[u] . fc1.weight + fc1.bias, by the pooling head's own summation) - what ivosw_head_fit fits on.
+ * The arguments of the forward entries without tap_stage / tap_out.  Any B and any chunk, the two-stream split included: the pooling
+ * head of every chunk group stores its rows at features + first unit * 2048 itself, so there is no workspace copy and no extra
+ * launch; scores and features are bit for bit the forward entry's scores and its tap 8 wherever that tap exists (B <= chunk).  The
+ * existing entries enqueue exactly what they did.  Refused as the forward entries refuse, plus a NULL features.                      */
+int ivosw_assess_forward_features(const void* packed, int dtype, const float* tf, const float* tp, int B, int H, int W,
+                                  float* scores, float* features, void* ws, size_t ws_bytes, int chunk, ivosw_stream_t stream);
+int ivosw_assess_forward_features_u8(const void* packed, int dtype, const uint8_t* rgbx, const float* tp, int B, int H, int W,
+                                     float* scores, float* features, void* ws, size_t ws_bytes, int chunk, ivosw_stream_t stream);
 /* Several videos in ONE pass: the front end reads every unit through a table of per-video descriptors, the tower behind it sees 256 x 256
  * tiles and does not care where one came from, so K sessions fill one full-size pass instead of K small ones.
  * `videos` is a HOST array of n_videos (1 .. IVOSW_MAX_VIDEOS) descriptors with DEVICE pointers; it is read during the call only and
@@ -725,6 +735,49 @@ size_t ivosw_qa_augment_ws_bytes(int n_samples);
 int ivosw_qa_augment(const ivosw_qa_aug_video_t* videos, int n_videos, const ivosw_qa_aug_sample_t* samples_host, int n_samples,
                      int Ho, int Wo, float* img, float* prob, uint8_t* label, uint8_t* mask, int32_t* chosen, void* ws,
                      size_t ws_bytes, ivosw_stream_t stream);
+
+/* ------------------------------------------------------------------ AssessNet's score head fitted on the device ---- */
+/* Replaces the reference's AssessNet optimiser loop (quality_assessment.py:230-270 and :286: the per-sample loss loop with its
+ * `union[n] > 0` filter and `continue`, loss.backward(), param.grad.data.clamp_(-1, 1), torch.optim.SGD with momentum and weight
+ * decay, ExponentialLR once per epoch) for the HEAD: fc1 (2048 -> 1) on the pooled features of a frozen trunk
+ * (ivosw_assess_forward_features).  The trunk runs with folded BatchNorm here, so training it is not representable on this path.
+ * ONE launch runs n_steps minibatch steps of n_fits (1 .. IVOSW_HEAD_FIT_MAX_FITS) independent fits, one workgroup per fit; the fits
+ * share the feature bank and differ in their hyper-parameters, index tables and state.
+ *   feat [M,2048] fp32, target [M] fp32, valid [M] uint8 (the reference's union[n] > 0)                                   device
+ *   order int32 [n_fits, n_steps, B]: the row indices of every minibatch, drawn by the host as the DataLoader's shuffle with drop_last
+ *         would; 1 <= B <= IVOSW_HEAD_FIT_MAX_BATCH.  An index outside [0, M) is the caller's error (not checked on the device).  device
+ *   lr    fp32 [n_fits, n_steps]: the rate of every step (lr0 * gamma**epoch formed in float64 by the host, rounded once).      device
+ *   momentum, weight_decay fp32 [n_fits], zero_grad, eval_only int [n_fits] (0 / 1): HOST arrays, they travel in the kernel arguments.
+ *   in / out state, so that a call continues the previous one: w [n_fits,2048], b [n_fits], the momentum buffers buf_w, buf_b and
+ *         the gradient accumulators grad_w, grad_b of the same shapes (fp32), steps_taken int32 [n_fits] (taken steps so far).   device
+ *   log   fp32 [n_fits, n_steps, 3]: loss, diff, counter of every step.                                                          device
+ *
+ * THE STEP (the definition; every fp32 operation is rounded by itself, no FMA contraction; tests/head_fit_ref.py restates it).
+ * For the rows n = 0 .. B-1 of the step, idx = order[fit, step, n], x = feat[idx]:
+ *   dot      64 partial sums, lane l = 0 .. 63: a_l = 0, then for j = 0 .. 7, q = 0 .. 3 in this order, k = 256 j + 4 l + q:
+ *            a_l = fl(a_l + fl(x[k] * w[k])); then for o = 32, 16, 8, 4, 2, 1: a_l = fl(a_l + a_(l xor o)) for all l at once.
+ *   pred_n = fl(a_0 + b);  e_n = fl(pred_n - target[idx]) where valid[idx] != 0, else the row takes no part.
+ *   c = the number of valid rows.  c == 0: the reference's `continue` - w, b, buffers, accumulators and steps_taken stay as they
+ *            are, bit for bit, and the log row is (0, 0, 0).
+ *   sums     over the valid rows in ascending n, each from 0.0f: S2 += fl(e_n * e_n), S1 += |e_n|, Se += e_n, and per channel k
+ *            Sk += fl(e_n * x[k]).
+ *   log      loss = fl(S2 / c), diff = fl(S1 / c), counter = c (as fp32).  eval_only: the step ends here.
+ *   gradient g_w[k] = fl(fl(2 / c) * Sk), g_b = fl(fl(2 / c) * Se).
+ *   clamp    G = fl((zero_grad ? 0.0f : G_prev) + g), then G = min(max(G, -1), 1), stored back CLAMPED: what
+ *            param.grad.data.clamp_ leaves behind for the next backward() when zero_grad() is never called, as in the reference.
+ *   SGD      d = fl(G + fl(weight_decay * p)); buf = d if steps_taken == 0 else fl(fl(momentum * buf) + d);
+ *            p = fl(p - fl(lr * buf)); after all parameters: steps_taken += 1.
+ * No global atomics, no cross-workgroup synchronisation, no fences, no scratch, no allocation (capture-safe).  Results are
+ * bit-identical run to run, and a fit's results are the same bits alone or as any member of a 32-fit launch.
+ * Refused (IVOSW_ERR_ARG) before anything touches the GPU: a NULL pointer, M < 1, n_fits outside 1 .. 32, B outside 1 .. 256,
+ * n_steps < 1, n_fits * n_steps * B >= 2^31, feat off the 16-byte grid, w / buf_w / grad_w off the 8-byte grid, a NaN momentum or
+ * weight_decay.                                                                                                                   */
+#define IVOSW_HEAD_FIT_MAX_FITS 32
+#define IVOSW_HEAD_FIT_MAX_BATCH 256
+int ivosw_head_fit(const float* feat, const float* target, const uint8_t* valid, int M, const int32_t* order, const float* lr,
+                   int n_fits, int n_steps, int B, const float* momentum, const float* weight_decay, const int* zero_grad,
+                   const int* eval_only, float* w, float* b, float* buf_w, float* buf_b, float* grad_w, float* grad_b,
+                   int32_t* steps_taken, float* log, ivosw_stream_t stream);
 
 /* ------------------------------------------------------------------ segmentation epilogue (8f-4) */
 /* Replaces, per frame batch, F.interpolate(logits, (H,W), 'bilinear', align_corners=True) -> argmax(dim=1)

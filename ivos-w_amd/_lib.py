@@ -26,6 +26,7 @@ MAX_CANDIDATES = 16                                  # IVOSW_MAX_CANDIDATES
 FRAMES_F32, FRAMES_RGBX8 = 0, 1                      # IVOSW_FRAMES_*
 MAX_JF_VIDEOS = 32                                   # IVOSW_MAX_JF_VIDEOS
 QA_AUG_MAX_CAND = 12                                 # IVOSW_QA_AUG_MAX_CAND
+HEAD_FIT_MAX_FITS, HEAD_FIT_MAX_BATCH = 32, 256      # IVOSW_HEAD_FIT_MAX_*
 METRIC_J, METRIC_F, METRIC_J_AND_F = 0, 1, 2         # IVOSW_METRIC_*
 OUT_RGB8, OUT_RGBX8 = 0, 1                           # IVOSW_OUT_*
 OVERLAY_DAVIS, OVERLAY_FADE, OVERLAY_CHECKER, OVERLAY_COLOR = 0, 1, 2, 3      # IVOSW_OVERLAY_*
@@ -137,6 +138,8 @@ SIGNATURES = {
     "ivosw_assess_forward_objects": (_i, [_p, _i, _p, _i, _p, C.c_long, C.c_long, _i, _i, _i, _p, _p, _sz, _i, _p]),
     "ivosw_assess_forward_u8": (_i, [_p, _i, _p, _p, _i, _i, _i, _p, _p, _sz, _i, _i, _p, _p]),
     "ivosw_assess_forward_objects_u8": (_i, [_p, _i, _p, _i, _p, C.c_long, C.c_long, _i, _i, _i, _p, _p, _sz, _i, _p]),
+    "ivosw_assess_forward_features": (_i, [_p, _i, _p, _p, _i, _i, _i, _p, _p, _p, _sz, _i, _p]),
+    "ivosw_assess_forward_features_u8": (_i, [_p, _i, _p, _p, _i, _i, _i, _p, _p, _p, _sz, _i, _p]),
     "ivosw_assess_videos_units": (C.c_long, [_p, _i]),
     "ivosw_mask_bbox_videos": (_i, [_p, _i, _p, _p, _p]),
     "ivosw_roi_sample_videos": (_i, [_p, _i, _p, _i, _p, _p]),
@@ -168,6 +171,7 @@ SIGNATURES = {
     "ivosw_qa_targets": (_i, [_p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "ivosw_qa_augment_ws_bytes": (_sz, [_i]),
     "ivosw_qa_augment": (_i, [_p, _i, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _sz, _p]),
+    "ivosw_head_fit": (_i, [_p, _p, _p, _i, _p, _p, _i, _i, _i, _p, _p, _p, _p] + [_p] * 8 + [_p]),
     "ivosw_seg_epilogue": (_i, [_p, _i, _i, _i, _i, _i, _i, _p, C.c_long, C.c_long, _p, _p, _p, _p]),
     "ivosw_atnet_epilogue": (_i, [_p, _p] + [_i] * 8 + [_f, _f, _f, _p, _p, C.c_long, _p, _p, _p]),
     "ivosw_ipn_dilate": (_i, [_p, _i, _i, _i, _i, _p, _p]),

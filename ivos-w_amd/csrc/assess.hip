@@ -327,7 +327,7 @@ extern "C" const char* ivosw_assess_dominant_kernel(int dtype) {
 // ids != NULL (with vt): the B rows of the pass are the entries of a unit list, row i = unit ids[i]; chunks and stream halves cut the LIST
 static int assess_forward_impl(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int B, int H, int W,
                                float* scores, void* ws, size_t ws_bytes, int chunk, int tap_stage, void* tap_out,
-                               ivosw_stream_t stream, const VideoTable* vt = nullptr, const int32_t* ids = nullptr);
+                               ivosw_stream_t stream, const VideoTable* vt = nullptr, const int32_t* ids = nullptr, float* features = nullptr);
 
 extern "C" int ivosw_assess_forward(const void* packed, int dtype, const float* tf, const float* tp, int B, int H, int W,
                                     float* scores, void* ws, size_t ws_bytes, int chunk, int tap_stage, void* tap_out,
@@ -367,6 +367,23 @@ extern "C" int ivosw_assess_forward_objects_u8(const void* packed, int dtype, co
                                                void* ws, size_t ws_bytes, int chunk, ivosw_stream_t stream) {
     return assess_forward_objects_impl(packed, dtype, FrameSrc{rgbx, 1}, n_frames, masks, mask_stride_frame, mask_stride_obj, n_obj, H, W,
                                        scores, ws, ws_bytes, chunk, stream);
+}
+
+// The same pass with the pooled features handed out (include/ivosw.h): any B and chunk, the two-stream split included - the pooling head
+// of every chunk group writes its rows at features + first unit * 2048, nothing is copied.
+extern "C" int ivosw_assess_forward_features(const void* packed, int dtype, const float* tf, const float* tp, int B, int H, int W,
+                                             float* scores, float* features, void* ws, size_t ws_bytes, int chunk, ivosw_stream_t stream) {
+    IVOSW_REQUIRE(features, "null pointer (features)");
+    return assess_forward_impl(packed, dtype, FrameSrc{tf, 0}, tp, SampleMap{B, (long)H * W, 0}, B, H, W, scores, ws, ws_bytes, chunk, 0,
+                               nullptr, stream, nullptr, nullptr, features);
+}
+
+extern "C" int ivosw_assess_forward_features_u8(const void* packed, int dtype, const uint8_t* rgbx, const float* tp, int B, int H, int W,
+                                                float* scores, float* features, void* ws, size_t ws_bytes, int chunk,
+                                                ivosw_stream_t stream) {
+    IVOSW_REQUIRE(features, "null pointer (features)");
+    return assess_forward_impl(packed, dtype, FrameSrc{rgbx, 1}, tp, SampleMap{B, (long)H * W, 0}, B, H, W, scores, ws, ws_bytes, chunk, 0,
+                               nullptr, stream, nullptr, nullptr, features);
 }
 
 // Several videos in one pass (include/ivosw.h): the table is validated and built on the host, then the chunk loop, the two-stream split
@@ -448,7 +465,7 @@ static int assess_forward_units_impl(const char* who, const void* packed, int dt
 // script != NULL: nothing is enqueued, the tower launches the range would make are appended as text (ivosw_assess_describe)
 static void assess_forward_range(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int u0, int B,
                                  int H, int W, float* scores, void* ws, int chunk, int tap_stage, void* tap_out, int slot, hipStream_t st,
-                                 const VideoTable* vt, const int32_t* ids, std::string* script = nullptr);
+                                 const VideoTable* vt, const int32_t* ids, std::string* script = nullptr, float* features = nullptr);
 
 // One helper stream + two events per device for the two-stream split (created on first use, all-or-nothing; the call holds
 // the device's mutex while it enqueues so two host threads cannot interleave their fork / join pairs).
@@ -484,7 +501,7 @@ Side2* side2_for_current_device() {
 
 static int assess_forward_impl(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int B, int H, int W,
                                float* scores, void* ws, size_t ws_bytes, int chunk, int tap_stage, void* tap_out,
-                               ivosw_stream_t stream, const VideoTable* vt, const int32_t* ids) {
+                               ivosw_stream_t stream, const VideoTable* vt, const int32_t* ids, float* features) {
     IVOSW_REQUIRE(packed && (vt || (fs.p && tp)) && scores && ws, "null pointer");
     IVOSW_REQUIRE(vt || !fs.u8 || (reinterpret_cast<uintptr_t>(fs.p) & 3) == 0, "rgbx must be 4-byte aligned");
     IVOSW_ON_DEVICE_OF(scores);
@@ -514,8 +531,9 @@ static int assess_forward_impl(const void* packed, int dtype, const FrameSrc& fs
         bool ok = hipEventRecord(sd->ev[0], st) == hipSuccess && hipStreamWaitEvent(sd->stream, sd->ev[0], 0) == hipSuccess;
         if (ok) {
             span_group_begin();
-            assess_forward_range(packed, dtype, fs, tp, sm, 0, B0, H, W, scores, ws, std::min(default_chunk(dtype), B0), 0, nullptr, 0, st, vt, ids);
-            assess_forward_range(packed, dtype, fs, tp, sm, B0, B1, H, W, scores + B0, ws1, std::min(default_chunk(dtype), B1), 0, nullptr, 1, sd->stream, vt, ids);
+            assess_forward_range(packed, dtype, fs, tp, sm, 0, B0, H, W, scores, ws, std::min(default_chunk(dtype), B0), 0, nullptr, 0, st, vt, ids, nullptr, features);
+            assess_forward_range(packed, dtype, fs, tp, sm, B0, B1, H, W, scores + B0, ws1, std::min(default_chunk(dtype), B1), 0, nullptr, 1, sd->stream, vt, ids, nullptr,
+                                 features ? features + (size_t)B0 * 2048 : nullptr);
             span_group_end();
             ok = hipEventRecord(sd->ev[1], sd->stream) == hipSuccess && hipStreamWaitEvent(st, sd->ev[1], 0) == hipSuccess;
             if (!ok) {
@@ -528,7 +546,7 @@ static int assess_forward_impl(const void* packed, int dtype, const FrameSrc& fs
         }
         (void)hipGetLastError();        // the fork failed before anything was enqueued on the side stream: run on one stream
     }
-    assess_forward_range(packed, dtype, fs, tp, sm, 0, B, H, W, scores, ws, chunk, tap_stage, tap_out, 0, st, vt, ids);
+    assess_forward_range(packed, dtype, fs, tp, sm, 0, B, H, W, scores, ws, chunk, tap_stage, tap_out, 0, st, vt, ids, nullptr, features);
     IVOSW_CHECK_LAUNCH();
     return IVOSW_OK;
 }
@@ -825,7 +843,7 @@ static void run_stage(Tower& T, int s, const char* x, int nb, char* out, int fof
 
 static void assess_forward_range(const void* packed, int dtype, const FrameSrc& fs, const float* tp, const SampleMap& sm, int u0, int B,
                                  int H, int W, float* scores, void* ws, int chunk, int tap_stage, void* tap_out, int slot, hipStream_t st,
-                                 const VideoTable* vt, const int32_t* ids, std::string* script) {
+                                 const VideoTable* vt, const int32_t* ids, std::string* script, float* features) {
     const Plan& P = plan_for(dtype);
     const size_t es = (dtype == IVOSW_BF16) ? 2 : 4;
     const char* base = static_cast<const char*>(packed);
@@ -901,7 +919,8 @@ static void assess_forward_range(const void* packed, int dtype, const FrameSrc& 
         // K6: 8x8 average pool + fc1
         span_close(st, slot);
         launch_pool_fc(bf.pa, n3, dtype, reinterpret_cast<const float*>(base + P.fcw_off),
-                       reinterpret_cast<const float*>(base + P.fcb_off), scores + f3, tap_stage == 8 ? bf.pooled : nullptr, st);
+                       reinterpret_cast<const float*>(base + P.fcb_off), scores + f3,
+                       features ? features + (size_t)f3 * 2048 : tap_stage == 8 ? bf.pooled : nullptr, st);      // features: each pool group's rows straight to the caller
         tap(8, bf.pooled, (size_t)n3 * 2048 * sizeof(float));
     }
 }

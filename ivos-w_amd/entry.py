@@ -1193,6 +1193,76 @@ def main_generate(argv=None):
     return run_eval(cfg, "MANet")
 
 
+# ------------------------------------------------------------------------------------------ quality_assessment.py (the head fit)
+# the reference's configs/config.yaml, assess_net section, and the keys this script adds (fit, zero_grad, augment_copies, val_fraction)
+ASSESS_NET_DEFAULTS = dict(num_epochs=50, lr=5e-6, gamma=0.95, momentum=0.9, weight_decay=5e-4, train_batch_size=32, fit="head", zero_grad=True,
+                           augment_copies=1, val_fraction=0.1)
+
+
+def run_fit_head(cfg):
+    """quality_assessment.py on this path: AssessNet's score head fitted to the back end's samples on the device (utils_agent.fit_assess_head).
+    Writes <ckpt_dir>/assess_net.pt and <report_save_dir>/quality_assessment/{summary.json, head_fit_bank.npz}; returns the summary."""
+    from .models.assessment import AssessNet
+    from .utils import misc, utils_agent, utils_manet
+    from . import synth
+    a = cfg.assess_net
+    if isinstance(a.get("lr"), str):                                   # a sweep: assess_net.lr=[1e-5,5e-6]
+        try:
+            a["lr"] = [float(v) for v in a["lr"].strip("[]()").split(",") if v.strip()]
+        except ValueError:
+            raise SystemExit(f"[ivos-w] assess_net.lr must be a number or a list like [1e-5,5e-6], got {a['lr']!r}")
+    try:
+        opts = utils_agent.head_fit_options(cfg)
+    except ValueError as e:
+        raise SystemExit(f"[ivos-w] {e}")
+    if not torch.cuda.is_available():
+        raise SystemExit("[ivos-w] the hot path needs an MI355X (no CPU fallback)")
+    device = torch.device(f"cuda:{cfg.gpu_id}")
+    print("[ivos-w] quality_assessment: no DAVIS frames and dumped samples on this path: the synthetic session and the stand-in VOS model "
+          "supply them; assess_net.fit=head (fc1 on the pooled features of the frozen trunk)")
+    misc.set_random_seed(int(cfg.seed))
+    davis = SyntheticDavis(cfg, device)
+    vos = StandInVOS(device, seed=int(cfg.seed))
+    assess_net = AssessNet(precision=cfg.precision)
+    ck = os.path.join(cfg.ckpt_dir, "assess_net.pt")
+    if not misc.load_network_checkpoint(ck, assess_net, device="cpu"):
+        print(f"[ivos-w] no {ck}: AssessNet starts from the seeded synthetic weights")
+        assess_net.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in synth.assessnet_state_dict(0, spread=True).items()})
+    assess_net = assess_net.to(device).eval()
+    videos = []
+    for seq, info in davis.dataset.items():                            # every sequence after its first interaction (frame 0 annotated)
+        w, h = info["image_size"]
+        store = utils_manet.ProbStore(info["num_frames"], info["num_objects"] + 1, h, w, device)
+        _, all_P = _segment(vos, davis, seq, info["num_objects"], [0], store)
+        videos.append((davis.load_frames(seq), davis.load_annotations(seq), all_P, info["num_objects"]))
+    metric = cfg.davis_interactive.metric
+    bank = {}
+    fit = utils_agent.fit_assess_head(videos, assess_net, metric, cfg, seed=int(cfg.seed), bank_out=bank)
+    res = fit["result"]
+    for e in range(res.num_epochs):                                    # the reference's epoch line
+        print(f"* Epoch: [{e:3d}]\tLoss: {res.epoch_loss[res.best, e]:.6f}\tdiff: {res.epoch_diff[res.best, e]:.6f}")
+    misc.save_network_checkpoint(cfg.ckpt_dir, assess_net)
+    report_dir = os.path.join(cfg.report_save_dir, "quality_assessment")
+    os.makedirs(report_dir, exist_ok=True)
+    np.savez(os.path.join(report_dir, "head_fit_bank.npz"), **{k: v for k, v in bank.items() if v is not None},
+             epoch_loss=res.epoch_loss, epoch_diff=res.epoch_diff, log=res.log.cpu().numpy())
+    chosen = {k: (float(v) if isinstance(v, float) else v) for k, v in fit["chosen"].items()}
+    summary = {"fit": dict(before=fit["before"], after=fit["after"], holdout=fit["holdout"], chosen=chosen, metric=metric,
+                           num_epochs=res.num_epochs, steps_per_epoch=res.steps_per_epoch, batch_size=res.batch_size,
+                           epoch_loss=[float(v) for v in res.epoch_loss[res.best]], epoch_diff=[float(v) for v in res.epoch_diff[res.best]])}
+    with open(os.path.join(report_dir, "summary.json"), "w") as fp:
+        json.dump(summary, fp)
+    print(f"# fit: loss {fit['before']['loss']:.6f} -> {fit['after']['loss']:.6f}  diff {fit['before']['diff']:.6f} -> {fit['after']['diff']:.6f}  "
+          f"n {fit['after']['n']}  lr {chosen['lr']:g}  -> {os.path.join(cfg.ckpt_dir, 'assess_net.pt')}")
+    summary["report_dir"] = report_dir
+    return summary
+
+
+def main_quality_assessment(argv=None):
+    cfg = parse_cli(sys.argv[1:] if argv is None else argv, seed=2019, assess_net=dict(ASSESS_NET_DEFAULTS))     # the reference's set_random_seed(2019)
+    return run_fit_head(cfg)
+
+
 def main_train(argv=None):
     cfg = parse_cli(sys.argv[1:] if argv is None else argv, phase="train")
     _print_metric_mode(cfg)

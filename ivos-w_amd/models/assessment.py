@@ -12,7 +12,8 @@ needed and nothing is downloaded.  ``precision='fp32'`` (default) is the parity 
 1e-4 rtol of the reference CPU path); ``precision='bf16x3'`` keeps fp32 tensors and the 1e-4 bar but runs every contraction
 - the stem included - as three bf16 MFMA passes on (hi, lo) splits (a b ~ ah bh + ah bl + al bh: error ~ 2^-17 per product, 16 / 3 of
 the fp32 matrix rate); ``precision='bf16'`` is the throughput mode (bf16 operands, fp32 accumulate).
-Inference only (eval-mode BatchNorm): AssessNet training is outside the hot path.
+Inference only (eval-mode BatchNorm): training the trunk is outside this path (folded BatchNorm cannot represent it); the score head
+fc1 is fitted on the device on the pooled features of the frozen trunk (``forward_features`` / ``fit_head`` / ``set_head``).
 """
 import ctypes
 import os
@@ -269,6 +270,17 @@ class ScoreCache:
     def clear(self):
         self.planes, self.scores, self.key, self.src = None, None, None, None
         self.units, self._rescored = 0, 0
+
+
+class HeadFitResult:
+    """What ``AssessNet.fit_head`` returns.  ``log``: the device tensor [n_configs, n_steps, 3] of every step's loss, diff and counter;
+    ``epoch_loss`` / ``epoch_diff`` [n_configs, num_epochs] float64: their means over the steps of an epoch that were taken (the
+    reference's ``* Epoch`` line); ``w`` [n_configs,2048], ``b`` [n_configs]: the fitted heads (host, fp32); with a holdout
+    ``holdout_loss`` / ``holdout_diff`` / ``holdout_n`` [n_configs]: one eval-only pass over the held-out rows; ``best``: the config
+    with the lowest held-out loss (without held-out rows: the lowest last-epoch loss); ``configs``: the hyper-parameters as run."""
+
+    def chosen(self):
+        return self.w[self.best], self.b[self.best]
 
 
 class AssessNet(nn.Module):
@@ -568,6 +580,160 @@ class AssessNet(nn.Module):
             views.append(scores[off:off + o * n].view(o, n))
             off += o * n
         return views
+
+    def forward_features(self, tf, tp):
+        """``forward`` with the pooled features handed out (ivosw_assess_forward_features): -> (scores [B], features [B,2048] fp32), both
+        on the device, no synchronisation.  Any B and chunk; the scores are ``forward``'s bit for bit, the features what fc1 is applied
+        to - the rows ``fit_head`` fits on.  tf may be a PackedFrames (the 8-bit path)."""
+        if self.training:
+            raise RuntimeError("AssessNet on the MI355X path is inference-only (eval-mode BatchNorm); call .eval()")
+        u8 = isinstance(tf, PackedFrames)
+        if u8:
+            B, H, W = tf.n, tf.H, tf.W
+            tf = tf.rgbx
+        else:
+            tf = tf.detach().to(torch.float32).contiguous()
+            B, C, H, W = tf.shape
+            assert C == 3
+        tp = tp.detach().to(torch.float32).contiguous()
+        assert tuple(tp.shape) == (B, H, W)
+        dev = tf.device
+        packed = self._ensure_packed()
+        lib, dt = L.lib(), _DTYPES[self.precision]
+        nbytes = lib.ivosw_assess_ws_bytes(dt, B, H, W, self.chunk)
+        ws = self._ws.get(nbytes, dev)
+        scores = torch.empty(B, dtype=torch.float32, device=dev)
+        features = torch.empty(B, 2048, dtype=torch.float32, device=dev)
+        fwd = lib.ivosw_assess_forward_features_u8 if u8 else lib.ivosw_assess_forward_features
+        L.check(fwd(L.dptr(packed), dt, L.dptr(tf), L.dptr(tp), B, H, W, L.dptr(scores), L.dptr(features), L.dptr(ws), nbytes, self.chunk,
+                    L.stream_ptr(dev)), "assess_forward_features_u8" if u8 else "assess_forward_features")
+        return scores, features
+
+    # ------------------------------------------------------------------ fitting the score head
+    def fit_head(self, features, targets, valid, *, lr, momentum, weight_decay, gamma, num_epochs, batch_size, seed, zero_grad=True,
+                 configs=None, holdout=None):
+        """The reference's optimiser loop (quality_assessment.py: per-sample MSE over the rows with a non-empty union, backward,
+        clamp_(-1, 1), SGD with momentum and weight decay, ExponentialLR per epoch) applied to fc1 on a bank of pooled features
+        (``forward_features``) with the trunk frozen: ivosw_head_fit, every epoch of every config in one launch per 32 configs.
+
+        features [M,2048] fp32, targets [M], valid [M] (bool / uint8) on the device.  ``holdout``: row indices (or a bool mask) kept out
+        of the fit; one eval-only pass scores them per config afterwards.  ``configs``: a list of dicts overriding lr, momentum,
+        weight_decay, gamma, zero_grad - a sweep; every config starts from the present fc1 and sees the same shuffles (numpy
+        RandomState(seed): one permutation of the training rows per epoch, cut into full batches like DataLoader(shuffle=True,
+        drop_last=True)).  zero_grad=False is the reference as written: it never calls zero_grad(), so the clamped gradients accumulate.
+        Nothing is written to fc1 (``set_head`` does that).  One device-to-host copy, at the end."""
+        dev = features.device
+        features = features.detach().to(torch.float32).contiguous()
+        M = int(features.shape[0])
+        if features.dim() != 2 or features.shape[1] != 2048 or M < 1:
+            raise ValueError(f"features must be [M,2048] with M >= 1, got {tuple(features.shape)}")
+        targets = targets.detach().to(device=dev, dtype=torch.float32).contiguous().view(-1)
+        valid = valid.detach().to(device=dev).ne(0).to(torch.uint8).contiguous().view(-1)
+        if targets.numel() != M or valid.numel() != M:
+            raise ValueError("targets and valid must hold one entry per feature row")
+        base = dict(lr=lr, momentum=momentum, weight_decay=weight_decay, gamma=gamma, zero_grad=zero_grad)
+        cfgs = [dict(base)] if not configs else [dict(base, **c) for c in configs]
+        for c in cfgs:
+            extra = set(c) - set(base)
+            if extra:
+                raise ValueError(f"fit_head: unknown config keys {sorted(extra)} (a config may set {sorted(base)})")
+        num_epochs, batch_size = int(num_epochs), int(batch_size)
+        if num_epochs < 1:
+            raise ValueError("num_epochs must be at least 1")
+        if not 1 <= batch_size <= L.HEAD_FIT_MAX_BATCH:
+            raise ValueError(f"batch_size must be 1 .. {L.HEAD_FIT_MAX_BATCH}, got {batch_size}")
+        held = np.zeros(M, dtype=bool)
+        if holdout is not None:
+            h = holdout.detach().cpu().numpy() if isinstance(holdout, torch.Tensor) else np.asarray(holdout)
+            if h.dtype == bool:
+                if h.shape != (M,):
+                    raise ValueError("a holdout mask must hold one entry per feature row")
+                held = h.copy()
+            else:
+                if h.size and (h.min() < 0 or h.max() >= M):
+                    raise ValueError("holdout index out of range")
+                held[h.astype(np.int64)] = True
+        train_rows, held_rows = np.flatnonzero(~held), np.flatnonzero(held)
+        steps = len(train_rows) // batch_size
+        if steps < 1:
+            raise ValueError(f"fit_head: {len(train_rows)} training rows do not fill one batch of {batch_size} (drop_last)")
+        rng = np.random.RandomState(int(seed))
+        order = np.concatenate([train_rows[rng.permutation(len(train_rows))[:steps * batch_size]] for _ in range(num_epochs)])
+        order = order.astype(np.int32).reshape(num_epochs * steps, batch_size)
+        assert order.min() >= 0 and order.max() < M                       # the table the kernel trusts
+        n_steps, n_cfg = num_epochs * steps, len(cfgs)
+        lr_tab = np.stack([np.repeat(np.array([float(c["lr"]) * float(c["gamma"]) ** e for e in range(num_epochs)],
+                                              dtype=np.float64).astype(np.float32), steps) for c in cfgs])
+        # the held-out rows as full batches of one size: the largest divisor of their count that a launch takes
+        hb = max([d for d in range(1, min(L.HEAD_FIT_MAX_BATCH, len(held_rows)) + 1) if len(held_rows) % d == 0], default=0)
+        h_steps = len(held_rows) // hb if hb else 0
+        lib, st = L.lib(), L.stream_ptr(dev)
+        order_d = torch.from_numpy(order).to(dev)
+        h_order_d = torch.from_numpy(held_rows.astype(np.int32)).to(dev) if hb else None
+        lr_d = torch.from_numpy(lr_tab).to(dev)
+        # everything the host wants back, in one flat tensor: w | b | log | held-out log
+        n_w, n_log, n_hlog = n_cfg * 2048, n_cfg * n_steps * 3, n_cfg * h_steps * 3
+        out = torch.zeros(n_w + n_cfg + n_log + n_hlog, dtype=torch.float32, device=dev)
+        w = out[:n_w].view(n_cfg, 2048)
+        b = out[n_w:n_w + n_cfg]
+        log = out[n_w + n_cfg:n_w + n_cfg + n_log].view(n_cfg, n_steps, 3)
+        hlog = out[n_w + n_cfg + n_log:].view(n_cfg, h_steps, 3)
+        w.copy_(self.fc1.weight.detach().to(device=dev, dtype=torch.float32).view(1, 2048).expand(n_cfg, 2048))
+        b.copy_(self.fc1.bias.detach().to(device=dev, dtype=torch.float32).view(1).expand(n_cfg))
+        state_w = torch.zeros(2, n_cfg, 2048, dtype=torch.float32, device=dev)         # momentum buffers | gradient accumulators of w
+        state_b = torch.zeros(2, n_cfg, dtype=torch.float32, device=dev)               # ... of b
+        taken = torch.zeros(n_cfg, dtype=torch.int32, device=dev)
+        f_arr, i_arr = (lambda v: (ctypes.c_float * len(v))(*v)), L.int_array
+        for g in range(0, n_cfg, L.HEAD_FIT_MAX_FITS):
+            grp = cfgs[g:g + L.HEAD_FIT_MAX_FITS]
+            k = len(grp)
+            mom, wd = f_arr([float(c["momentum"]) for c in grp]), f_arr([float(c["weight_decay"]) for c in grp])
+            zg = i_arr([1 if c["zero_grad"] else 0 for c in grp])
+            ptrs = [L.torch_ptr(out, g * 2048), L.torch_ptr(out, n_w + g), L.torch_ptr(state_w, g * 2048), L.torch_ptr(state_b, g),
+                    L.torch_ptr(state_w, (n_cfg + g) * 2048), L.torch_ptr(state_b, n_cfg + g), L.torch_ptr(taken, g)]
+            # (one index table serves the whole group: every fit of a launch reads its own [n_steps,B] slice, so the table is repeated)
+            order_g = order_d.unsqueeze(0).expand(k, n_steps, batch_size).contiguous()
+            L.check(lib.ivosw_head_fit(L.dptr(features), L.dptr(targets), L.dptr(valid), M, L.dptr(order_g), L.torch_ptr(lr_d, g * n_steps),
+                                       k, n_steps, batch_size, mom, wd, zg, i_arr([0] * k), *ptrs, L.torch_ptr(out, n_w + n_cfg + g * n_steps * 3), st),
+                    "head_fit")
+            if hb:
+                h_order_g = h_order_d.view(1, h_steps, hb).expand(k, h_steps, hb).contiguous()
+                L.check(lib.ivosw_head_fit(L.dptr(features), L.dptr(targets), L.dptr(valid), M, L.dptr(h_order_g),
+                                           L.torch_ptr(lr_d, g * n_steps), k, h_steps, hb, mom, wd, zg, i_arr([1] * k), *ptrs,
+                                           L.torch_ptr(out, n_w + n_cfg + n_log + g * h_steps * 3), st), "head_fit (held-out rows)")
+        host = out.cpu().numpy().astype(np.float64)                         # the one device-to-host copy
+        w_h, b_h = host[:n_w].reshape(n_cfg, 2048), host[n_w:n_w + n_cfg]
+        log_h = host[n_w + n_cfg:n_w + n_cfg + n_log].reshape(n_cfg, num_epochs, steps, 3)
+        hlog_h = host[n_w + n_cfg + n_log:].reshape(n_cfg, h_steps, 3)
+        took = np.maximum((log_h[..., 2] > 0).sum(2), 1)                    # the reference's meters average over the steps it took
+        res = HeadFitResult()
+        res.configs, res.steps_per_epoch, res.num_epochs, res.batch_size = cfgs, steps, num_epochs, batch_size
+        res.log = log
+        res.epoch_loss, res.epoch_diff = log_h[..., 0].sum(2) / took, log_h[..., 1].sum(2) / took
+        res.w, res.b = torch.from_numpy(w_h.astype(np.float32)), torch.from_numpy(b_h.astype(np.float32))
+        res.holdout_loss = res.holdout_diff = res.holdout_n = None
+        if holdout is not None:
+            n = hlog_h[..., 2].sum(1) if hb else np.zeros(n_cfg)
+            d = np.maximum(n, 1)
+            res.holdout_n = n.astype(np.int64)
+            res.holdout_loss = (hlog_h[..., 0] * hlog_h[..., 2]).sum(1) / d if hb else np.zeros(n_cfg)
+            res.holdout_diff = (hlog_h[..., 1] * hlog_h[..., 2]).sum(1) / d if hb else np.zeros(n_cfg)
+        key = res.holdout_loss if (res.holdout_n is not None and res.holdout_n.min() > 0) else res.epoch_loss[:, -1]
+        key = np.where(np.isfinite(key), key, np.inf)
+        res.best = int(np.argmin(key))
+        return res
+
+    def set_head(self, w, b):
+        """Write fc1 in place (w: 2048 values, b: one) and drop the packed copy: a later ``forward`` scores with this head.  Nothing else
+        of the network changes."""
+        w = torch.as_tensor(w).detach().reshape(-1)
+        b = torch.as_tensor(b).detach().reshape(-1)
+        if w.numel() != 2048 or b.numel() != 1:
+            raise ValueError(f"set_head takes 2048 weights and one bias, got {w.numel()} and {b.numel()}")
+        with torch.no_grad():
+            self.fc1.weight.copy_(w.to(self.fc1.weight).view(1, 2048))
+            self.fc1.bias.copy_(b.to(self.fc1.bias))
+        self.invalidate_packed()
 
     def forward_tap(self, tf, tp, tap):
         """Debug/test hook: also returns one intermediate (NHWC; see ``_TAPS``)."""

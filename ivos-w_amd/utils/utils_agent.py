@@ -383,6 +383,125 @@ def assess_report_augmented(videos, assess_net, metric, transform=None, seed=Non
     return res.report.cpu().numpy(), res                                  # the one D2H copy of the call
 
 
+def _assess_bank(videos, assess_net, metric, transform, copies, batch, thr, bound_th):
+    """``copies`` passes of ``transform`` over every unit of ``videos`` (the tuples of ``assess_report_augmented``) through
+    ``assess_net.forward_features`` and the count pass: (scores [copies * U], features [copies * U, 2048], QaTargets, U), row = copy * U +
+    unit, all on the device, no synchronisation.  The caller seeds the host streams."""
+    from .. import metrics
+    from ..datasets import transforms_assess as T
+    device = next(assess_net.parameters()).device
+    table, samples = [], []
+    for v, (frames, gt, probs, n_objects) in enumerate(videos):
+        if not _is_packed(frames) and not frames.is_cuda:
+            frames = frame_cache.get(frames, device)
+        planes = probs if (isinstance(probs, torch.Tensor) and probs.dtype == torch.uint8) else metrics.quantize_probs(probs, n_objects)
+        gt = metrics._as_labels(gt, device)
+        table.append((frames, gt, planes.to(device).contiguous()))
+        samples += [(v, f, o) for o in range(int(n_objects)) for f in range(int(gt.shape[0]))]
+    size = (int(table[0][1].shape[2]), int(table[0][1].shape[1]))
+    if transform is None:
+        transform = T.train_transform(size=size)
+    elif transform == "plain":
+        transform = T.Compose([T.Resize(size=size), T.ToTensor()])
+    scores, feats, labels, masks = [], [], [], []
+    for _ in range(copies):
+        for a in range(0, len(samples), batch):
+            out = transform(T.DeviceSamples(table, samples[a:a + batch]))
+            sc, ft = assess_net.forward_features(out["img"], out["prob"])
+            scores.append(sc)
+            feats.append(ft)
+            labels.append(out["label"])
+            masks.append(out["mask"])
+    scores = torch.cat(scores)
+    res = metrics.qa_targets([(torch.cat(labels), torch.cat(masks)[None], 1)], metric, scores=scores, thr=thr, bound_th=bound_th)
+    return scores, torch.cat(feats), res, len(samples)
+
+
+def head_fit_options(cfg):
+    """The ``assess_net`` keys of a head fit, checked: -> dict(lrs, momentum, weight_decay, gamma, num_epochs, train_batch_size, zero_grad,
+    augment_copies, val_fraction).  ``cfg`` is the whole config or its ``assess_net`` block.  ``fit`` must be ``head``: training the trunk
+    is outside this path (it runs with folded BatchNorm, which cannot represent it)."""
+    from .. import _lib as L
+    a = cfg["assess_net"] if "assess_net" in cfg else cfg
+    fit = a.get("fit", "head")
+    if fit != "head":
+        raise ValueError(f"assess_net.fit={fit!r}: only 'head' is accepted - trunk training is outside this path (the tower runs with "
+                         "folded BatchNorm; fc1 is fitted on the pooled features of the frozen trunk)")
+    lr = a.get("lr", 5e-6)
+    lrs = [float(v) for v in lr] if isinstance(lr, (list, tuple)) else [float(lr)]
+    if not lrs or any(not (v > 0 and np.isfinite(v)) for v in lrs):
+        raise ValueError(f"assess_net.lr must be a positive number or a non-empty list of them, got {lr!r}")
+    o = dict(lrs=lrs, momentum=float(a.get("momentum", 0.9)), weight_decay=float(a.get("weight_decay", 5e-4)), gamma=float(a.get("gamma", 0.95)),
+             num_epochs=int(a.get("num_epochs", 50)), train_batch_size=int(a.get("train_batch_size", 32)), zero_grad=a.get("zero_grad", True),
+             augment_copies=int(a.get("augment_copies", 1)), val_fraction=float(a.get("val_fraction", 0.1)))
+    if isinstance(o["zero_grad"], str):
+        if o["zero_grad"].lower() not in ("true", "false"):
+            raise ValueError(f"assess_net.zero_grad must be true or false, got {o['zero_grad']!r}")
+        o["zero_grad"] = o["zero_grad"].lower() == "true"
+    o["zero_grad"] = bool(o["zero_grad"])
+    if not 0 <= o["momentum"] < 1 or o["weight_decay"] < 0 or not 0 < o["gamma"] <= 1:
+        raise ValueError("assess_net: momentum in [0, 1), weight_decay >= 0 and gamma in (0, 1] are required")
+    if o["num_epochs"] < 1 or o["augment_copies"] < 1:
+        raise ValueError("assess_net.num_epochs and assess_net.augment_copies must be at least 1")
+    if not 1 <= o["train_batch_size"] <= L.HEAD_FIT_MAX_BATCH:
+        raise ValueError(f"assess_net.train_batch_size must be 1 .. {L.HEAD_FIT_MAX_BATCH}, got {o['train_batch_size']}")
+    if not 0 <= o["val_fraction"] < 1:
+        raise ValueError(f"assess_net.val_fraction must be in [0, 1), got {o['val_fraction']}")
+    return o
+
+
+def fit_assess_head(videos, assess_net, metric, cfg, transform=None, seed=None, thr=None, bound_th=0.008, log=print, bank_out=None):
+    """Calibrate AssessNet's score head to a VOS back end: ``videos`` as ``assess_report_augmented`` takes them.  Draws
+    ``assess_net.augment_copies`` augmented copies of every unit in batches of ``train_batch_size`` -> ``forward_features`` ->
+    ``metrics.qa_targets`` into one feature bank on the device; holds out ``val_fraction`` of the UNITS (all copies of a held-out unit);
+    ``AssessNet.fit_head`` (ivosw_head_fit: every epoch of every config in one launch) with the reference's hyper-parameters - a list in
+    ``assess_net.lr`` is a sweep, the config with the lowest held-out loss wins; ``set_head``.  Returns dict(before, after: loss, diff, n
+    on the un-augmented units; chosen: the config; result: the HeadFitResult; holdout: the chosen config's held-out loss, diff, n).
+    ``bank_out``: a dict that receives the bank (features, target, valid, holdout rows as host numpy) - for tests and post-mortems."""
+    import random as _random
+    from .. import metrics
+    o = head_fit_options(cfg)
+    thr = metrics.QA_THRESHOLD if thr is None else thr
+    seed = 2019 if seed is None else int(seed)            # the reference's set_random_seed(2019)
+    state = (_random.getstate(), np.random.get_state())
+    _random.seed(seed)
+    np.random.seed(seed % (1 << 32))
+    try:
+        plain = lambda: _assess_bank(videos, assess_net, metric, "plain", 1, o["train_batch_size"], thr, bound_th)[2].report
+        before = plain()
+        _, feats, res, U = _assess_bank(videos, assess_net, metric, transform, o["augment_copies"], o["train_batch_size"], thr, bound_th)
+    finally:
+        _random.setstate(state[0])
+        np.random.set_state(state[1])
+    n_hold = int(round(o["val_fraction"] * U))
+    if o["val_fraction"] > 0 and U >= 2:
+        n_hold = min(max(n_hold, 1), U - 1)
+    held_units = np.sort(np.random.RandomState(seed).permutation(U)[:n_hold])
+    holdout = (np.arange(o["augment_copies"])[:, None] * U + held_units[None]).reshape(-1) if n_hold else None
+    rows = o["augment_copies"] * (U - n_hold)
+    batch = min(o["train_batch_size"], rows)
+    if batch != o["train_batch_size"]:
+        log(f"fit_assess_head: {rows} training rows: the batch is {batch}, not train_batch_size={o['train_batch_size']}")
+    log(f"fit_assess_head: fit=head, {o['augment_copies']} x {U} units ({n_hold} held out), {len(o['lrs'])} config(s), "
+        + ("zero_grad=true (plain SGD)" if o["zero_grad"] else "zero_grad=false (the reference's accumulating clamped gradients)"))
+    target32 = res.target.to(torch.float32)
+    if bank_out is not None:
+        bank_out.update(features=feats.cpu().numpy(), target=target32.cpu().numpy(), valid=res.valid.cpu().numpy(),
+                        holdout=None if holdout is None else holdout.copy(), batch_size=batch, seed=seed,
+                        w0=assess_net.fc1.weight.detach().cpu().numpy().reshape(-1).copy(), b0=float(assess_net.fc1.bias.detach().cpu()))
+    fit = assess_net.fit_head(feats, target32, res.valid, lr=o["lrs"][0], momentum=o["momentum"], weight_decay=o["weight_decay"],
+                              gamma=o["gamma"], num_epochs=o["num_epochs"], batch_size=batch, seed=seed, zero_grad=o["zero_grad"],
+                              configs=[dict(lr=v) for v in o["lrs"]], holdout=holdout)
+    assess_net.set_head(*fit.chosen())
+    after = plain()
+    rep = torch.cat([before, after]).cpu().numpy()                      # [loss, diff, n] before | after
+    as_dict = lambda r: dict(loss=float(r[0]), diff=float(r[1]), n=int(r[2]))
+    out = dict(before=as_dict(rep[0]), after=as_dict(rep[1]), chosen=dict(fit.configs[fit.best], index=fit.best), result=fit, holdout=None)
+    if fit.holdout_n is not None:
+        out["holdout"] = dict(loss=float(fit.holdout_loss[fit.best]), diff=float(fit.holdout_diff[fit.best]), n=int(fit.holdout_n[fit.best]))
+    return out
+
+
 def _wild_assess(method, assess_net, agent, device, n_objects, all_F, all_P, counts, mask_quality, prev_frames, k=1, as_list=False,
                  rescore="all", gap=1):
     """wild/worst and wild/ours (utils/utils_agent.py:111-122) with the chain quality -> state -> Brain -> argmax on the
