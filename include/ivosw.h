@@ -1041,6 +1041,48 @@ int ivosw_robot_skeleton_box(const uint8_t* gt, const uint8_t* pred, int n, int 
                              int32_t* points, int32_t* counts, int32_t* iters, uint32_t* skel, uint32_t* workspace,
                              size_t workspace_bytes, ivosw_stream_t stream);
 
+/* ------------------------------------------------------------------ robot paths (the skeleton's pixels become node lists) */
+/* ivosw_robot_paths: the paths the robot draws along a skeleton, on the device, from the outputs of ivosw_robot_skeleton[_box] as they
+ * are.  The rule is tests/robot_ref.py's path step (components, bfs, farthest, longest_path, longest_paths, resample) and, level by
+ * level, tests/robot_paths_ref.py; the result is bit for bit that of the restatement.  It is this project's DEFINITION.
+ *
+ * Nodes: the first counts[k] entries of points[k], decoded as UNSIGNED (y << 16) | x, in ascending raster order; node index = position.
+ * Components: 8-connected.  A component's first pixel is its lowest node; components of fewer than min_nb_nodes nodes are dropped.
+ * Directions: N, NE, E, SE, S, SW, W, NW = (dy, dx) (-1,0) (-1,1) (0,1) (1,1) (1,0) (1,-1) (0,-1) (-1,-1), numbered 0 .. 7.
+ * BFS from a source s, stated without an order of execution: dist is the graph distance from s.  The queue holds s at position 0; the
+ *   nodes of level d + 1 follow those of level d.  parent[q] is the neighbour of q at distance dist[q] - 1 that stands FIRST in the queue;
+ *   the nodes of level d + 1 stand in ascending order of (queue position of parent, direction parent -> q).  This is the order in which a
+ *   FIFO that visits every node's neighbours in the direction order appends them, and the parents it records.
+ * Farthest node: the highest dist; a tie goes to the lower node index.
+ * Path of a component: BFS from its first pixel gives the farthest node a; BFS from a gives the farthest node b; the path is a, ..., b
+ *   with every node the parent of the next in the SECOND BFS.  len = dist[b] + 1.
+ * Selection: the max_paths longest paths, longest first; a tie goes to the component with the lower first pixel.
+ * Resampling, nb_points > 0: n = min(nb_points, len).  The kept positions are rint(fl64(i * fl64((len - 1) / (n - 1)))) for i < n - 1 and
+ *   len - 1 for i = n - 1 (n == 1: position 0), in float64 with round-half-to-even; a position equal to its predecessor is dropped
+ *   (np.linspace(0, len - 1, n).round() followed by np.unique).  nb_points <= 0 keeps every node.
+ *
+ *   points, counts  device int32 [m,cap] and [m], as written by ivosw_robot_skeleton[_box] (counts[k] <= 0 reads as an empty unit).
+ *   H, W            the map size the points lie on (checked only: the points carry their coordinates).
+ *   nodes           device int32 [m,max_paths,slot,2] = (px, py): ivosw_scribble_raster's point format, 8-byte aligned.  Slot r of unit k holds the nodes of
+ *                   its r-th path; behind the path's last node the slot REPEATS that node up to `slot` entries.  A slot without a path,
+ *                   every slot of a unit with status 1 and the offending slot under status 2 hold (-1, -1) throughout.
+ *   lens            device int32 [m,max_paths]: the nodes of path r of unit k after resampling; 0 = no such path (also under status 1
+ *                   and for the offending slot under status 2).
+ *   status          device int32 [m]: 0 ok; 1 counts[k] > cap (the skeleton was truncated: no path is given); 2 a path longer than slot
+ *                   (only with nb_points <= 0; the unit's other paths are given).
+ * With that layout the static host table {(k * max_paths + r) * slot, slot, object_k, map} is valid for ivosw_scribble_raster as it
+ * stands: a repeated node is a zero-length segment, which plots the same pixel under the same path index, and a segment with an end point
+ * outside the map - (-1, -1) - is not drawn.
+ * One workgroup per unit, 64 units per launch, a longer list in groups; every table lives in LDS (36 bytes per node of cap + 256), which
+ * bounds cap: ivosw_robot_paths_max_cap() (host only) returns the largest cap whose tables fit the 160 KB of one gfx950 workgroup
+ * (4544).  No global atomics, nothing allocated, nothing copied, asynchronous on `stream`, capture-safe.
+ * Refused (IVOSW_ERR_ARG) before anything is launched, nothing written, the message names the argument: a NULL points, counts, nodes,
+ * lens or status, nodes off the 8-byte grid, m < 1, cap outside [1, ivosw_robot_paths_max_cap()], H or W outside [1, 65535], min_nb_nodes < 1, max_paths outside
+ * [1, 8], slot outside [1, cap], nb_points > slot.                                                                                  */
+int ivosw_robot_paths_max_cap(void);
+int ivosw_robot_paths(const int32_t* points, const int32_t* counts, int m, int cap, int H, int W, int min_nb_nodes, int max_paths,
+                      int nb_points, int slot, int32_t* nodes, int32_t* lens, int32_t* status, ivosw_stream_t stream);
+
 /* ------------------------------------------------------------------ launch-sequence capture ---- */
 /* HIP-graph capture of any sequence of the calls above on one stream (not in the reference: it replaces the ~40 host
  * launches per Agent.update_agent step, models/agent.py:128-160, by ONE hipGraphLaunch).  begin puts `stream` (non-null)

@@ -186,6 +186,8 @@ SIGNATURES = {
     "ivosw_robot_skeleton": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p]),
     "ivosw_robot_box_workspace_bytes": (C.c_long, [_i, _i, _i]),
     "ivosw_robot_skeleton_box": (_i, [_p, _p, _i, _i, _i, _p, _i, _i, _p, _p, _p, _p, _p, _sz, _p]),
+    "ivosw_robot_paths_max_cap": (_i, []),
+    "ivosw_robot_paths": (_i, [_p, _p] + [_i] * 8 + [_p, _p, _p, _p]),
     "ivosw_graph_begin": (_i, [_p]),
     "ivosw_graph_end": (_i, [_p, C.POINTER(_p), C.POINTER(_i)]),
     "ivosw_graph_launch": (_i, [_p, _p]),

@@ -10,12 +10,14 @@ OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libivosw_hip.so")
 PROBE_LIB = os.path.join(HERE, "libivosw_probe.so")     # superset build with the tuning probes of include/ivosw_probe.h (tools/, one GPU test)
 PROBE_SOURCES = ["assess.hip", "bottleneck.hip", "bottleneck_wide.hip", "brain.hip", "robot.hip"]      # the translation units that hold a probe entry
-SOURCES = ["capi.cpp", "brain.hip", "dqn.hip", "assess_front.hip", "conv.hip", "bottleneck.hip", "bottleneck_wide.hip", "res2_stage.hip", "res2_chain.hip", "gemm_8phase.hip", "stage_first.hip", "stem.hip", "assess.hip", "metrics.hip", "qa.hip", "qa_augment.hip", "head_fit.hip", "seg_epilogue.hip", "atnet_epilogue.hip", "ipn_glue.hip", "overlay.hip", "scribble.hip", "robot.hip", "p2p.hip"]  # missing files are skipped
+SOURCES = ["capi.cpp", "brain.hip", "dqn.hip", "assess_front.hip", "conv.hip", "bottleneck.hip", "bottleneck_wide.hip", "res2_stage.hip", "res2_chain.hip", "gemm_8phase.hip", "stage_first.hip", "stem.hip", "assess.hip", "metrics.hip", "qa.hip", "qa_augment.hip", "head_fit.hip", "seg_epilogue.hip", "atnet_epilogue.hip", "ipn_glue.hip", "overlay.hip", "scribble.hip", "robot.hip", "robot_paths.hip", "p2p.hip"]  # missing files are skipped
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # per-file flags: res2_chain.hip runs one wave per SIMD (512 registers) and wants its MFMA accumulators in VGPRs (no v_accvgpr_read per
 # epilogue value: - 10 % on the block body, tools/ubench/chain_bench.hip)
 # qa_augment.hip and head_fit.hip state bit-exact fp32 rules (include/ivosw.h): no FMA contraction anywhere in the unit, host composition included
-EXTRA = {"res2_chain.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "qa_augment.hip": ["-ffp-contract=off"], "head_fit.hip": ["-ffp-contract=off"]}
+# robot_paths.hip states a bit-exact float64 rule (the resampling indices)
+EXTRA = {"res2_chain.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form"], "qa_augment.hip": ["-ffp-contract=off"], "head_fit.hip": ["-ffp-contract=off"],
+         "robot_paths.hip": ["-ffp-contract=off"]}
 if os.environ.get("IVOSW_ABLATION") == "1":      # tuning builds only: compiles the ablation switches in (common.h)
     FLAGS.append("-DIVOSW_ABLATION=1")
 

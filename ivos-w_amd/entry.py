@@ -93,6 +93,9 @@ DEFAULTS = dict(
     robot_background=False,            # robot=errors: true draws on the background too - paths of object 0 along the skeleton of the false
                                        # positives gt == 0 and pred != 0 (as davisinteractive's robot does), which tell the VOS model "this is
                                        # not an object"; false: no call, file or log line differs
+    robot_paths="host",                # robot=errors: where the skeleton's pixels become paths: "host" (utils.robot.paths_from_points, numpy), or
+                                       # "device": components, double BFS and resampling in one more launch (ivosw_robot_paths; the same paths)
+                                       # and the stand-in's scribble map drawn straight from the device nodes; host: no call, file or log line differs
     report_save_dir="results",
     eval_max_nb_interactions=8,        # the eval scripts fix 8 interactions on the val subset (eval_agent_manet.py:64-65)
     data=dict(num_workers=0, root_dir_davis="data/DAVIS", root_dir_scribble_youtube_vos="data/Scribble_Youtube_VOS",
@@ -193,6 +196,20 @@ def robot_background_option(cfg):
     if on and cfg.get("robot", "gt") != "errors":
         raise ValueError("robot_background=true draws on the false positives of a prediction: it needs robot=errors")
     return on
+
+
+ROBOT_PATHS_MODES = ("host", "device")
+
+
+def robot_paths_option(cfg):
+    """cfg.robot_paths (absent: "host").  Refused: a value that is not one of ROBOT_PATHS_MODES; "device" unless robot=errors (the
+    ground-truth robot has no skeleton to walk)."""
+    mode = cfg.get("robot_paths", "host")
+    if not isinstance(mode, str) or mode not in ROBOT_PATHS_MODES:
+        raise ValueError(f"robot_paths must be 'host' or 'device', got {mode!r}")
+    if mode == "device" and cfg.get("robot", "gt") != "errors":
+        raise ValueError("robot_paths=device walks the error skeletons on the device: it needs robot=errors")
+    return mode
 
 
 def qa_option(cfg):
@@ -432,6 +449,7 @@ def parse_cli(argv, **overrides):
         scribbles_option(cfg)
         robot_option(cfg)
         robot_background_option(cfg)
+        robot_paths_option(cfg)
     except ValueError as e:
         raise SystemExit(f"[ivos-w] {e}")
     return _attr(cfg)
@@ -546,10 +564,13 @@ class SyntheticSession:
     ``robot="errors"`` the paths of ``utils.robot.interact`` along the error skeletons of the masks last submitted for this sample
     (none yet: the objects themselves); ``robot_paths`` stands in only when no object at all yields a path.  ``drew`` names the robot
     that drew the last scribbles: "gt", "errors" or "gt (no error path)".  ``robot_background`` (with ``robot="errors"``): the error
-    robot also draws paths of object 0 on the false positives of the masks last submitted (none before the first submission)."""
+    robot also draws paths of object 0 on the false positives of the masks last submitted (none before the first submission).
+    ``robot_paths="device"`` (with ``robot="errors"``): the paths come from ``utils.robot.interact_device`` - the same list - and
+    ``device_paths`` keeps the ``DevicePaths`` of the last scribbles (None when the error robot did not draw them)."""
 
     def __init__(self, davis, subset, metric_to_optimize, max_nb_interactions, report_save_dir, seed=0, rounds=1, scribbles="frame",
-                 robot="gt", robot_min_nodes=4, robot_background=False):
+                 robot="gt", robot_min_nodes=4, robot_background=False, robot_paths="host"):
+        self.robot_paths, self.device_paths = robot_paths, None
         self.davis, self.metric, self.max_nb = davis, metric_to_optimize, int(max_nb_interactions)
         self.scribble_mode = scribbles
         self.robot, self.robot_min_nodes, self.robot_background = robot, int(robot_min_nodes), bool(robot_background)
@@ -588,10 +609,15 @@ class SyntheticSession:
             if self.robot == "errors":                                # every node of the skeleton path: the polyline stays on the error region
                 from .utils import robot as R
                 extra = dict(background=True) if self.robot_background else {}
-                mine, self.drew = R.interact(gt, self._submitted, n_objects, self._frame, min_nb_nodes=self.robot_min_nodes,
-                                             nb_points=None, **extra), "errors"
+                if self.robot_paths == "device":                      # interact(paths="device"), with the device nodes kept for the map
+                    self.device_paths = R.interact_device(gt, self._submitted, n_objects, self._frame, min_nb_nodes=self.robot_min_nodes,
+                                                          nb_points=None, **extra)
+                    mine, self.drew = self.device_paths.to_scribbles(), "errors"
+                else:
+                    mine, self.drew = R.interact(gt, self._submitted, n_objects, self._frame, min_nb_nodes=self.robot_min_nodes,
+                                                 nb_points=None, **extra), "errors"
                 if not mine:
-                    mine, self.drew = None, "gt (no error path)"
+                    mine, self.drew, self.device_paths = None, "gt (no error path)", None
             if mine is None:
                 mine = robot_paths(gt[self._frame].cpu().numpy(), n_objects)
         scribbles = dict(sequence=seq, annotated_frame=self._frame, scribbles=[mine if f == self._frame else [] for f in range(n)])
@@ -736,6 +762,7 @@ def run_eval(cfg, backbone="MANet"):
     scribble_mode = scribbles_option(cfg)
     robot, robot_min_nodes = robot_option(cfg)
     robot_background = robot_background_option(cfg)
+    robot_paths = robot_paths_option(cfg)
     oracle_chain = metric_option(cfg) == "device" and cfg.setting == "oracle" and cfg.method in ("ours", "worst")
     cfg.phase = "eval"
     cfg.data.subset = "val"
@@ -764,7 +791,8 @@ def run_eval(cfg, backbone="MANet"):
     if qa_aug:
         qa_sess.enable_augment(assess_net, cfg.seed)
     with SyntheticSession(davis, cfg.data.subset, metric, max_nb, report_dir, seed=int(cfg.seed), scribbles=scribble_mode, robot=robot,
-                          robot_min_nodes=robot_min_nodes, **(dict(robot_background=True) if robot_background else {})) as sess, \
+                          robot_min_nodes=robot_min_nodes, **(dict(robot_background=True) if robot_background else {}),
+                          **(dict(robot_paths="device") if robot_paths == "device" else {})) as sess, \
             (qa_sess or contextlib.nullcontext()):
         while sess.next():
             sequence, scribbles, first_scribble = sess.get_scribbles(only_last=True)
@@ -787,10 +815,16 @@ def run_eval(cfg, backbone="MANet"):
             if scribble_mode == "paths":                              # the paths drawn at the stand-in's stride-4 logit resolution, as MANet
                 from .utils import scribbles as S                     # draws them at its embedding resolution
                 drawn = int(scribbles["annotated_frame"])
-                scribble_low = (drawn, S.scribble_maps(scribbles, (h // 4, w // 4), frames=[drawn], device=device)[0])
+                if robot_paths == "device" and sess.device_paths is not None:     # the nodes never left the device: only the table goes up
+                    from .utils import robot as R
+                    scribble_low = (drawn, R.maps_from_paths(sess.device_paths, (h // 4, w // 4))[0])
+                else:
+                    scribble_low = (drawn, S.scribble_maps(scribbles, (h // 4, w // 4), frames=[drawn], device=device)[0])
                 scribble_text = f"scribble: {len(scribbles['scribbles'][drawn])} paths "
                 if robot == "errors":
                     scribble_text += f"robot: {sess.drew} "
+                    if robot_paths == "device" and sess.device_paths is not None:
+                        scribble_text += "(device paths) "
                     if robot_background:                              # (a path of object 0 raises the stand-in's background logit: channel 0)
                         n_bg = sum(1 for p in scribbles["scribbles"][drawn] if p.get("object_id") == 0)
                         scribble_text = scribble_text[:-1] + f" ({n_bg} background) "

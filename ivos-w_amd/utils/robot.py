@@ -13,7 +13,9 @@ background - goes to ``ivosw_robot_skeleton_box``, which keeps planes of the err
 else in a cached device workspace.  The background (object 0) is drawn on the false positives ``gt == 0 and pred != 0``, as the library's
 robot draws it; ``interact(..., background=True)`` asks for it.
 
-There is no CPU fallback for ``skeleton_points``; ``paths_from_points`` is host work.
+There is no CPU fallback for ``skeleton_points``; ``paths_from_points`` is host work.  ``paths_device`` is the same path step on the
+device (``csrc/robot_paths.hip``: ``ivosw_robot_paths``, bit for bit the same paths), ``interact_device`` and ``interact_maps`` chain it
+behind the skeleton - and in front of ``ivosw_scribble_raster`` - without a copy or a synchronisation; ``interact(paths="device")`` opts in.
 """
 import numpy as np
 import torch
@@ -167,14 +169,135 @@ def paths_from_points(points, count, size, object_id, min_nb_nodes=4, max_paths=
     return out
 
 
-def interact(gt, pred, n_objects, frame, cap=4096, background=False, **kw):
+class DevicePaths:
+    """The outputs of ``ivosw_robot_paths`` for m units: ``nodes`` int32 [m,max_paths,slot,2] = (x, y), ``lens`` int32 [m,max_paths] and
+    ``status`` int32 [m], three views of ONE device buffer [nodes | lens | status], so that one copy brings them home.  ``objects``: the
+    object id of every unit; ``size`` = (H, W) of the maps the nodes lie on; ``counts``: the skeleton's device counts (read only to word a
+    refusal)."""
+
+    def __init__(self, buf, objects, size, max_paths, slot, cap, counts=None, frame=None):
+        self.buf, self.objects, self.size = buf, [int(o) for o in objects], tuple(int(v) for v in size)
+        self.max_paths, self.slot, self.cap, self.counts, self.frame = int(max_paths), int(slot), int(cap), counts, frame
+        m, n = len(self.objects), len(self.objects) * self.max_paths * self.slot * 2
+        self.nodes = buf[:n].view(m, self.max_paths, self.slot, 2)
+        self.lens = buf[n:n + m * self.max_paths].view(m, self.max_paths)
+        self.status = buf[n + m * self.max_paths:]
+
+    def to_scribbles(self):
+        """The one copy (and the one synchronisation): the list ``interact`` returns - the same dicts, the same floats, the same order.
+        A unit whose skeleton did not fit the cap (status 1) is the ValueError of ``interact``; a path longer than ``slot`` (status 2) is
+        a ValueError that names ``slot``."""
+        m = len(self.objects)
+        if m == 0:
+            return []
+        flat = self.buf.cpu().numpy()
+        H, W = self.size
+        n = m * self.max_paths * self.slot * 2
+        nodes, lens, status = flat[:n].reshape(m, self.max_paths, self.slot, 2), flat[n:n + m * self.max_paths].reshape(m, -1), flat[n + m * self.max_paths:]
+        out = []
+        for k, o in enumerate(self.objects):
+            if status[k] == 1:
+                count = "" if self.counts is None else f" {int(self.counts[k])}"
+                where = f"object {o}" if self.frame is None else f"frame {self.frame}, object {o}"
+                raise ValueError(f"robot: unit {k} ({where}): the skeleton has{count} pixels, more than cap = {self.cap}")
+            if status[k] == 2:
+                raise ValueError(f"robot: unit {k} (object {o}): a path has more nodes than slot = {self.slot} (nb_points=None keeps every "
+                                 f"node: give a larger slot, at most cap = {self.cap})")
+            for r in range(self.max_paths):
+                if lens[k, r] > 0:
+                    out.append(dict(path=[[(x + 0.5) / W, (y + 0.5) / H] for x, y in nodes[k, r, :lens[k, r]].tolist()], object_id=o,
+                                    start_time=0, end_time=0))
+        return out
+
+    def table(self, map_index=0):
+        """The static host table of ``ivosw_scribble_raster`` over ``nodes`` as its point array: int32 [m * max_paths, 4] =
+        {(k * max_paths + r) * slot, slot, object_k, map_index}.  A slot behind its path repeats the last node (zero-length segments: the
+        same pixel under the same path index) and a slot without a path holds (-1, -1), which the draw kernel does not draw."""
+        rows = [((k * self.max_paths + r) * self.slot, self.slot, o, int(map_index)) for k, o in enumerate(self.objects)
+                for r in range(self.max_paths)]
+        return np.array(rows, dtype=np.int32).reshape(-1, 4)
+
+
+def paths_device(points, counts, objects, size, min_nb_nodes=4, max_paths=2, nb_points=8, slot=None):
+    """``ivosw_robot_paths`` on the device tensors ``skeleton_points`` returns (``points`` int32 [m,cap], ``counts`` int32 [m]) for units of
+    the objects ``objects`` on maps of ``size`` = (H, W): a ``DevicePaths``.  ``nb_points`` None keeps every node.  ``slot``: the entries
+    per path (None: ``nb_points``, or ``cap`` when every node is kept).  One launch per 64 units, no copy, no synchronisation."""
+    H, W = (int(v) for v in size)
+    m, cap = points.shape
+    objects = [int(o) for o in objects]
+    if len(objects) != m or counts.numel() != m:
+        raise ValueError(f"robot: {m} units of points, {counts.numel()} counts and {len(objects)} objects")
+    nb = 0 if nb_points is None else int(nb_points)
+    if nb_points is not None and nb < 1:
+        raise ValueError(f"robot: nb_points must be None or >= 1, got {nb_points!r}")
+    slot = (nb if nb > 0 else cap) if slot is None else int(slot)
+    max_paths = int(max_paths)
+    buf = torch.empty(m * max(max_paths, 0) * max(slot, 0) * 2 + m * max(max_paths, 0) + m, dtype=torch.int32, device=points.device)
+    n = m * max_paths * slot * 2
+    L.check(L.lib().ivosw_robot_paths(L.dptr(points, torch.int32), L.dptr(counts, torch.int32), m, cap, H, W, int(min_nb_nodes), max_paths, nb,
+                                      slot, L.dptr(buf), L.torch_ptr(buf, max(n, 0)), L.torch_ptr(buf, max(n, 0) + m * max(max_paths, 0)),
+                                      L.stream_ptr(points.device)), "robot_paths")
+    return DevicePaths(buf, objects, (H, W), max_paths, slot, cap, counts)
+
+
+def interact_device(gt, pred, n_objects, frame, cap=4096, background=False, **kw):
+    """``interact`` without leaving the device: skeleton -> paths, two launches, no copy, no synchronisation.  A ``DevicePaths`` whose
+    ``to_scribbles()`` is the list ``interact`` returns; ``kw``: ``min_nb_nodes``, ``max_paths``, ``nb_points``, ``slot`` of
+    ``paths_device``."""
+    frame, n_objects = int(frame), int(n_objects)
+    if n_objects < 1:
+        return DevicePaths(torch.empty(0, dtype=torch.int32, device=gt.device), [], gt.shape[1:], kw.get("max_paths", 2), 1, cap)
+    units = [(frame, o) for o in range(0 if background and pred is not None else 1, n_objects + 1)]
+    buf, m, _ = _launch(gt, pred, units, cap, False)
+    out = paths_device(buf[2 * m:].view(m, int(cap)), buf[:m], [o for _, o in units], gt.shape[1:], **kw)
+    out.frame = frame
+    return out
+
+
+def maps_from_paths(paths, size=None, default_value=-1, roi_dist=None, as_float=False):
+    """The scribble map [1,h,w] of a ``DevicePaths`` drawn by ``ivosw_scribble_raster`` straight from the device nodes: only the static
+    table is uploaded.  ``size`` None or the paths' own size: the nodes as they are ((x + 0.5) / W packs back to x exactly).  Another
+    ``size`` = (h, w): every node is scaled with ``scribbles.pack``'s own expression in float64 on the device, px = min(int((x + 0.5) / W
+    * w), w - 1) (a few elementwise tensor operations on the node array; (-1, -1) stays (-1, -1)), so the map is that of ``scribble_maps``
+    on the host paths at that size.  No synchronisation."""
+    from . import scribbles as S
+    H, W = paths.size
+    h, w = (H, W) if size is None else (int(v) for v in size)
+    m = len(paths.objects)
+    if m == 0:
+        return S.raster(np.zeros((0, 2), np.int32), np.zeros((0, 4), np.int32), 1, (h, w), paths.buf.device, default_value, roi_dist, as_float)
+    nodes = paths.nodes
+    if (h, w) != (H, W):
+        v = nodes.to(torch.float64)
+        scaled = torch.stack([torch.clamp(((v[..., 0] + 0.5) / W * w).to(torch.int32), max=w - 1),
+                              torch.clamp(((v[..., 1] + 0.5) / H * h).to(torch.int32), max=h - 1)], -1)
+        nodes = torch.where(nodes < 0, nodes, scaled).contiguous()
+    return S.raster_device(nodes, paths.table(0), 1, (h, w), default_value, roi_dist, as_float)
+
+
+def interact_maps(gt, pred, n_objects, frame, size=None, default_value=-1, roi_dist=None, as_float=False, **kw):
+    """skeleton -> paths -> raster with no synchronisation: ``(maps, DevicePaths)``, ``maps`` a device int8 (``as_float``: float32)
+    [1,h,w].  With ``size`` None or the frame size, ``maps`` is ``scribble_maps({"scribbles": [interact(...)]}, size)`` bit for bit
+    whenever ``interact`` draws a path at all (without one ``scribble_maps`` returns no map; this returns one map of ``default_value``).
+    Another ``size`` is served too: see ``maps_from_paths``.  ``kw``: ``cap``, ``background`` and the keywords of ``paths_device``."""
+    paths = interact_device(gt, pred, n_objects, frame, **kw)
+    return maps_from_paths(paths, size, default_value, roi_dist, as_float), paths
+
+
+def interact(gt, pred, n_objects, frame, cap=4096, background=False, paths="host", **kw):
     """The scribbles of one frame in davisinteractive's schema: a list of paths for the objects 1 .. ``n_objects`` in ascending order, drawn
     along the skeleton of each object's error region on ``frame``.  ``gt`` and ``pred``: device uint8 [n,H,W] (``pred`` None: nothing
     predicted yet, the error region is the object).  An object without an error skeleton of at least ``min_nb_nodes`` connected pixels
     gets no path.  ``background``: the background is scribbled too - unit (frame, 0), the false positives ``gt == 0 and pred != 0``; its
     paths carry ``object_id=0`` and come first, so the list stays ascending in object id.  With ``pred`` None nothing is predicted, no
     false positive exists and the background is skipped.  ``kw``: ``min_nb_nodes``, ``max_paths``, ``nb_points`` of
-    ``paths_from_points``.  One launch, one device-to-host copy of [counts | iters | points], then the numpy step."""
+    ``paths_from_points``.  One launch, one device-to-host copy of [counts | iters | points], then the numpy step.  ``paths="device"``:
+    the path step runs on the device too (``interact_device(...).to_scribbles()``: two launches, one copy of the finished paths; the same
+    list); any other value is a ValueError."""
+    if paths not in ("host", "device"):
+        raise ValueError(f"robot: paths must be 'host' or 'device', got {paths!r}")
+    if paths == "device":
+        return interact_device(gt, pred, n_objects, frame, cap, background, **kw).to_scribbles()
     frame, n_objects = int(frame), int(n_objects)
     if n_objects < 1:
         return []

@@ -102,6 +102,36 @@ def raster(points, table, n_maps, size, device=None, default_value=-1, roi_dist=
     return out
 
 
+def raster_device(d_points, table, n_maps, size, default_value=-1, roi_dist=None, as_float=False, bresenham=True):
+    """``raster`` for points that are already on the device: ``d_points`` a contiguous device int32 tensor [..., 2] = (px, py) (the
+    ``nodes`` of ``utils.robot.DevicePaths``, for one), ``table`` the host path table over its flattened points.  Only the table is
+    uploaded; the maps are drawn on the points' device.  A point outside the map ends the segments it belongs to (the draw kernel's
+    rule), so a caller may mark unused points with (-1, -1).  One memset, two launches, no synchronisation."""
+    H, W = _size(size, "raster_device")
+    n_maps = int(n_maps)
+    if not isinstance(d_points, torch.Tensor) or not d_points.is_cuda or d_points.dtype != torch.int32 or d_points.shape[-1:] != (2,):
+        raise TypeError("raster_device: d_points must be a device int32 tensor [..., 2]")
+    if not -128 <= int(default_value) <= 127:
+        raise ValueError(f"scribbles: default_value {default_value} outside int8")
+    dev = d_points.device
+    out = torch.empty((n_maps, H, W), dtype=torch.float32 if as_float else torch.int8, device=dev)
+    if n_maps == 0:
+        return out
+    table = np.ascontiguousarray(table, dtype=np.int32).reshape(-1, 4)
+    P, n_paths = d_points.numel() // 2, len(table)
+    lib = L.lib()
+    need = lib.ivosw_scribble_raster_ws_bytes(n_maps, H, W)
+    if need == 0:
+        raise ValueError(f"scribbles: {n_maps} maps of {H} x {W} are more than 2^31 - 1 pixels")
+    ws = _ws.setdefault(dev, L.Workspace()).get(need, dev)
+    d_table = torch.from_numpy(table.reshape(-1)).to(dev, non_blocking=True) if n_paths else None
+    L.check(lib.ivosw_scribble_raster(L.dptr(d_points) if n_paths else None, P, L.dptr(d_table) if n_paths else None,
+                                      table.ctypes.data if n_paths else None, n_paths, n_maps, H, W, int(default_value),
+                                      int(bool(bresenham)), -1 if roi_dist is None else int(roi_dist), None if as_float else L.dptr(out),
+                                      L.dptr(out) if as_float else None, L.dptr(ws), ws.numel(), L.stream_ptr(dev)), "scribble_raster")
+    return out
+
+
 def scribble_maps(scribbles, size, frames=None, device=None, default_value=-1, roi_dist=None, as_float=False):
     """The label maps of the listed frames only (None: the frames that have paths), a device tensor [m,H,W], int8 or - ``as_float`` -
     float32 with the same values.  ``roi_dist``: apply ``rough_ROI`` with that distance to every map in the same pass (None: off)."""
