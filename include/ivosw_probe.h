@@ -107,7 +107,7 @@ int ivosw_robot_box_probe(const uint8_t* gt, const uint8_t* pred, int n, int H, 
                           int32_t* points, int32_t* counts, int32_t* iters, uint32_t* skel, uint32_t* workspace,
                           size_t workspace_bytes, int lds_budget_bytes, ivosw_stream_t stream);
 
-/* Test probes of the DQN step's backward kernels (csrc/brain.hip, brain_fused.h, brain_bwd.h), each the product's kernel unchanged on
+/* Test probes of the DQN step's backward kernels (csrc/dqn_step.hip, dqn_head.h, lstm_bwd.h, brain_bwd.h), each the product's kernel unchanged on
  * caller-provided fp32 device tensors; tests/test_gpu_dqn_kernels.py holds their outputs to the float64 restatements of tests/dqn_ref.py.
  * Every entry refuses a NULL operand, and with "not covered" what its kernel does not take, before anything is launched: nothing is written. */
 
@@ -139,7 +139,7 @@ int ivosw_bwd_group_probe(const float* dG, const float* hprev, const float* e, c
                           const float* w4term, const float* state, const float* wih, const float* w2, float* de, float* da1, float* grads,
                           float* ws, int B, int T, ivosw_stream_t stream);
 
-/* ONE launch of head_fused_kernel<per != 0> (csrc/brain_fused.h) with the kernel's own arguments: prm + o_w3 = W3 [128,256],
+/* ONE launch of head_fused_kernel<per != 0> (csrc/dqn_head.h) with the kernel's own arguments: prm + o_w3 = W3 [128,256],
  * prm + o_w4 = w4 [128]; q_np, q_nt, q_s [B,T]; action [B] int64; r_step, r_done [B]; d1_s [B,T,128]; hs_s [B,T,256]; outputs dq [B],
  * dd1c, w4term [B,128], hcc, dhc [B,256], loss [1], db4 [1]; per != 0: weights [B] in and td [B] out, else both are ignored.
  * B, T >= 1, o_w3, o_w4 >= 0, loss_kind IVOSW_DQN_LOSS_MSE or _HUBER. */
@@ -154,7 +154,7 @@ int ivosw_head_fused_probe(const float* prm, int o_w3, int o_w4, const float* q_
 int ivosw_lstm_bwd_probe(const float* whh, const float* gates, const float* cs, const float* dhc, const int64_t* action, float* dG, int N, int T,
                          int form, ivosw_stream_t stream);
 
-/* Test probes of the Brain forward kernels (csrc/brain_fused.h, csrc/brain.hip), each the product's kernel unchanged on caller-provided fp32
+/* Test probes of the Brain forward kernels (csrc/brain_fused.h, csrc/lstm_fwd.h, launched by csrc/brain.hip), each the product's kernel unchanged on caller-provided fp32
  * device tensors; tests/test_gpu_dqn_fwd_kernels.py holds their outputs to the float64 restatements of tests/dqn_ref.py.  The recurrence
  * and the recurrence + decoder kernel are launched by the functions the forward drivers call (launch_lstm_fwd, launch_lstm_fwd_pair,
  * launch_lstm_fwd_ragged, launch_fwd_mega), the form by their rule (lstm_fwd_form_for).  Every entry refuses a NULL operand, and with

@@ -9,8 +9,8 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "build")
 LIB = os.path.join(HERE, "libivosw_hip.so")
 PROBE_LIB = os.path.join(HERE, "libivosw_probe.so")     # superset build with the tuning probes of include/ivosw_probe.h (tools/, one GPU test)
-PROBE_SOURCES = ["assess.hip", "bottleneck.hip", "bottleneck_wide.hip", "brain.hip", "robot.hip"]      # the translation units that hold a probe entry
-SOURCES = ["capi.cpp", "brain.hip", "dqn.hip", "assess_front.hip", "conv.hip", "bottleneck.hip", "bottleneck_wide.hip", "res2_stage.hip", "res2_chain.hip", "gemm_8phase.hip", "stage_first.hip", "stem.hip", "assess.hip", "metrics.hip", "qa.hip", "qa_augment.hip", "head_fit.hip", "seg_epilogue.hip", "atnet_epilogue.hip", "ipn_glue.hip", "overlay.hip", "scribble.hip", "robot.hip", "robot_paths.hip", "p2p.hip"]  # missing files are skipped
+PROBE_SOURCES = ["assess.hip", "bottleneck.hip", "bottleneck_wide.hip", "brain.hip", "dqn_step.hip", "robot.hip"]      # the translation units that hold a probe entry
+SOURCES = ["capi.cpp", "brain.hip", "brain_rank.hip", "dqn_step.hip", "gemm_f32.hip", "dqn.hip", "assess_front.hip", "conv.hip", "bottleneck.hip", "bottleneck_wide.hip", "res2_stage.hip", "res2_chain.hip", "gemm_8phase.hip", "stage_first.hip", "stem.hip", "assess.hip", "metrics.hip", "qa.hip", "qa_augment.hip", "head_fit.hip", "seg_epilogue.hip", "atnet_epilogue.hip", "ipn_glue.hip", "overlay.hip", "scribble.hip", "robot.hip", "robot_paths.hip", "p2p.hip"]  # missing files are skipped
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # per-file flags: res2_chain.hip runs one wave per SIMD (512 registers) and wants its MFMA accumulators in VGPRs (no v_accvgpr_read per
 # epilogue value: - 10 % on the block body, tools/ubench/chain_bench.hip)

@@ -49,7 +49,7 @@ inline int check_adam(const char* who, float beta1, float beta2, float eps, floa
     return IVOSW_OK;
 }
 
-// ---- device-resident state of the captured DQN step (dqn.hip owns the kernels; brain.hip's one-call step shares the layouts)
+// ---- device-resident state of the captured DQN step (dqn.hip owns the kernels; dqn_step.hip's one-call step shares the layouts)
 // The minibatch draw (uniform with replacement): slot b of draw number c = a splitmix64 finaliser of (seed, c, b) scaled to [0, n)
 // by a 64 x 64 -> high-64 multiply: integer arithmetic only (host mirrors: ivosw_replay_draw_index, momory_pool.draw_indices).
 struct DrawState {
@@ -90,7 +90,7 @@ struct AdamDevState {
 };
 static_assert(sizeof(AdamDevState) == 32, "AdamDevState layout (step at byte 16, ticket at byte 28)");
 
-// up to six split-K slab sets reduced in one launch (gemm_f32.h: splitk_reduce_group_kernel; brain.hip: folded into clamp + Adam)
+// up to six split-K slab sets reduced in one launch (gemm_f32.hip: splitk_reduce_group_kernel; dqn_step.hip: folded into clamp + Adam)
 constexpr int REDUCE_MAX = 6;
 struct ReduceGroup {
     const float* slabs[REDUCE_MAX];

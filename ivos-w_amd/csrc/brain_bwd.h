@@ -2,7 +2,7 @@
 // default on).  Reference arithmetic: what autograd derives for Brain.forward (models/agent.py:33-64) under
 // Agent.update_agent's loss (:128-155).
 //
-// The generic 64x64x64 LDS-staged GEMM (gemm_f32.h) ran this part as two grouped launches of 620 + 164 workgroups, 52 us for
+// The generic 64x64x64 LDS-staged GEMM (gemm_f32.hip) ran this part as two grouped launches of 620 + 164 workgroups, 52 us for
 // ~1.8 GFLOP (12 us of matrix-pipe time): every K-step paid a global -> register -> LDS -> register round trip and two
 // barriers for 32 MFMAs per wave.  Here no operand goes through LDS:
 //
@@ -17,7 +17,7 @@
 //
 // One launch runs the dgrad tiles next to the three weight gradients that do not depend on them.
 #pragma once
-#include "brain_fused.h"
+#include "common.h"
 
 namespace ivosw {
 

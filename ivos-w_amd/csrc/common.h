@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <initializer_list>
 #include <mutex>
 
 #include "../../include/ivosw.h"
@@ -12,6 +13,7 @@
 namespace ivosw {
 
 void set_error(const char* fmt, ...);
+int tune_get(const char* key, int dflt);   // capi.cpp
 
 inline hipStream_t as_stream(ivosw_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
@@ -65,18 +67,26 @@ constexpr int WAVE = 64;
 
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
-// Bump allocator over a caller-provided workspace.
+inline bool aligned16(std::initializer_list<const void*> ptrs) {
+    uintptr_t bits = 0;
+    for (const void* q : ptrs) bits |= reinterpret_cast<uintptr_t>(q);
+    return (bits & 15) == 0;
+}
+
+// Bump allocator over a caller-provided workspace.  Without a base it only counts: take() returns nullptr and the offset runs on as it
+// would over memory, so ONE function that carves a workspace also answers its size query (bytes()).
 struct Arena {
     char* base;
     size_t off;
-    explicit Arena(void* p) : base(static_cast<char*>(p)), off(0) {}
+    explicit Arena(void* p = nullptr) : base(static_cast<char*>(p)), off(0) {}
     template <typename T>
     T* take(size_t n) {
         off = align_up(off, 256);
-        T* p = reinterpret_cast<T*>(base + off);
+        T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
         off += n * sizeof(T);
         return p;
     }
+    size_t bytes() const { return align_up(off, 256); }
 };
 
 // Compute units of the current device, for the persistent kernels that size their grid by it: a per-device table, each entry
@@ -197,6 +207,18 @@ __device__ __forceinline__ int wave_max(int v) {
     for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
     return v;
 }
+
+// fp32 MFMA fragments of the Brain's kernels (brain_fused.h, brain_bwd.h, lstm_fwd.h)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+
+// a DPP move inside a quad of lanes (the quad layouts of lstm_fwd.h and lstm_bwd.h)
+struct QuadDpp {
+    template <int CTRL>
+    static __device__ __forceinline__ float mov(float v) {
+        return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, true));
+    }
+};
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 // The recurrences' activations on the hardware transcendentals (v_exp_f32 / v_rcp_f32, ~1 ulp each) instead of ocml's expf

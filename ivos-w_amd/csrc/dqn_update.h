@@ -1,5 +1,5 @@
 // The one body of the DQN update kernels, and the pieces it is made of: the last-workgroup ticket, the 16-byte arena traversal, the
-// gradient sources, the lr sources, the two optimizer rules and the target rule.  dqn.hip (the stand-alone update entries) and brain.hip
+// gradient sources, the lr sources, the two optimizer rules and the target rule.  dqn.hip (the stand-alone update entries) and dqn_step.hip
 // (the one-call step's tails) instantiate it; every kernel there is a thin __global__ wrapper that names its four choices:
 //   rule     AdamRule | SgdRule                    (clamp_adam_elem / clamp_sgd_elem and the state each keeps)
 //   gradient ArenaGrad | SlabGrad                  (the gradient arena as it stands, or reduce_on_load)
@@ -167,7 +167,7 @@ struct SgdRule {
 };
 
 // ---------------------------------------------------------------- the target
-// NoTarget, or the rule's arguments: {float* t; TargetDevState* st; int mode; float tau; int period;} (brain.hip's TargetArgs)
+// NoTarget, or the rule's arguments: {float* t; TargetDevState* st; int mode; float tau; int period;} (dqn_step.hip's TargetArgs)
 struct NoTarget {};
 
 // The rule on the W elements at i, in the thread that holds p_new.  A periodic step reads nothing of t, and touches nothing unless it fires.
@@ -217,12 +217,6 @@ __device__ __forceinline__ void clamp_update(float* __restrict__ p, int n, const
 }
 
 // ---------------------------------------------------------------- host side
-inline bool aligned16(std::initializer_list<const void*> ptrs) {
-    uintptr_t bits = 0;
-    for (const void* q : ptrs) bits |= reinterpret_cast<uintptr_t>(q);
-    return (bits & 15) == 0;
-}
-
 // Launches a traversal kernel over n elements in workgroups of `lanes`: its <true> instantiation when every array is 16-byte aligned,
 // else its <false> one, each with for_each_group's grid.
 template <class... Params, class... Args>

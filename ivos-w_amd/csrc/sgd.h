@@ -1,5 +1,5 @@
 // The clamp + SGD update of one element, shared by every SGD path (clamp_sgd_kernel in dqn.hip, the one-call step's tail in
-// brain.hip, the data-parallel step's fused all-reduce + clamp + SGD in p2p.hip) so that all of them evaluate the same expression
+// dqn_step.hip, the data-parallel step's fused all-reduce + clamp + SGD in p2p.hip) so that all of them evaluate the same expression
 // tree.  torch.optim.SGD(lr, momentum, dampening=0, weight_decay, nesterov), torch/optim/sgd.py:_single_tensor_sgd:
 //   d = g + wd*p;  buf = buf*mu + d;  d = nesterov ? d + mu*buf : buf;  p = p - lr*d
 // with the reference's clamp in front (models/agent.py:157-159) and gscale (= 1/world) before the clamp, as in clamp_adam_elem.

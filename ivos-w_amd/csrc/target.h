@@ -1,5 +1,5 @@
 // The target-network rule of the DQN step (cfg.agent.target_update = "soft" | "periodic").  ivosw_target_update (dqn.hip) and the one-call
-// step's fused tails (brain.hip) both apply it through target_group (dqn_update.h), so both evaluate the same expression.  After the
+// step's fused tails (dqn_step.hip) both apply it through target_group (dqn_update.h), so both evaluate the same expression.  After the
 // policy update of a step, per element:
 //   soft:      t = fmaf(tau, p_new - t, t)          (one rounding of the product-sum: torch.Tensor.lerp_(p, tau) on the CPU for tau < 0.5)
 //   periodic:  t = p_new when k % period == 0, k = the number of steps since the counter was last written, this one included

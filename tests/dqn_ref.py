@@ -1,5 +1,5 @@
 """Float64 restatements, in plain numpy, of what the DQN step's backward kernels compute (csrc/brain_bwd.h: wgrad_tile, dgrad_tile, csum_unit;
-csrc/brain_fused.h: head_fused_kernel; csrc/brain.hip: lstm_bwd_quad_kernel, lstm_bwd_kernel), one function per operation, and the fixtures
+csrc/dqn_head.h: head_fused_kernel; csrc/lstm_bwd.h: lstm_bwd_quad_kernel, lstm_bwd_kernel), one function per operation, and the fixtures
 of tests/test_gpu_dqn_kernels.py.  tests/test_dqn_ref.py pins the functions, composed in the step's order, to
 oracle.brain_oracle.dqn_loss_and_grads(..., dtype=np.float64) and asserts every fixture's preconditions - no GPU is needed for either.
 The second half of the file does the same for the Brain forward kernels (tests/test_gpu_dqn_fwd_kernels.py): enc, dec, lstm_step, lstm_fwd,
@@ -89,7 +89,7 @@ def first_argmax(q):
 
 def head(W3, w4, q_np, q_nt, q_s, action, r_step, r_done, gamma, kind, delta, d1, hs, weights=None, dtype=np.float64, dq=None):
     """head_fused_kernel.  W3 [128,256], w4 [128], q_* [B,T], d1 [B,T,128], hs [B,T,256]; weights [B] = prioritized replay.  The expression
-    shapes are the kernel's (brain_fused.h: dqn_dq, dqn_dq_w, dqn_loss_terms), so that dtype = float32 is the fp32 restatement.  dq given:
+    shapes are the kernel's (dqn_head.h: dqn_dq, dqn_dq_w, dqn_loss_terms), so that dtype = float32 is the fp32 restatement.  dq given:
     the decoder part is computed from THAT dq (the GPU tests pass the kernel's own, to hold each stage to its own bound).
     Returns a dict; mag_loss / mag_db4 are the magnitudes their bounds scale with (absolute values of everything that enters)."""
     B, T = q_np.shape
@@ -194,7 +194,7 @@ def rel_err(x, ref64):
 # ---------------------------------------------------------------- the tail, composed as the step composes it
 TAIL_KEYS = ("encoder_fc1.weight", "encoder_fc1.bias", "encoder_fc2.weight", "encoder_fc2.bias", "lstm_cell.weight_ih", "lstm_cell.weight_hh",
              "decoder_fc1.weight", "decoder_fc1.bias", "decoder_fc2.weight")
-# (name, offset, shape) of the gradient arena, state_dict order (csrc/brain.hip: O_W1 ...)
+# (name, offset, shape) of the gradient arena, state_dict order (csrc/brain_fwd.h: O_W1 ...)
 ARENA = (("encoder_fc1.weight", 0, (128, 2)), ("encoder_fc1.bias", 256, (128,)), ("encoder_fc2.weight", 384, (128, 128)),
          ("encoder_fc2.bias", 16768, (128,)), ("lstm_cell.weight_ih", 16896, (512, 128)), ("lstm_cell.weight_hh", 82432, (512, 128)),
          ("decoder_fc1.weight", 147968, (128, 256)), ("decoder_fc1.bias", 180736, (128,)), ("decoder_fc2.weight", 180864, (1, 128)),
@@ -389,7 +389,7 @@ def lstm_fixture(N, T):
 
 # ================================================================ the Brain forward (tests/test_gpu_dqn_fwd_kernels.py)
 # Float64 restatements of enc_fused_kernel, dec_fused_kernel (csrc/brain_fused.h), the recurrence forms and brain_fwd_mega_kernel
-# (csrc/brain.hip), their error bounds and their fixtures.  P is a dict of the ten state_dict tensors (SHAPES below); arena(P) lays it out
+# (csrc/lstm_fwd.h), their error bounds and their fixtures.  P is a dict of the ten state_dict tensors (SHAPES below); arena(P) lays it out
 # as the kernels read it.  tests/test_dqn_ref.py pins the composition enc -> lstm_fwd -> dec to oracle.brain_oracle.brain_forward.
 SHAPES = {name: shape for name, _, shape in ARENA}
 LOG2E32 = np.float32(1.4426950408889634)

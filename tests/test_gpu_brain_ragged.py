@@ -164,6 +164,73 @@ def test_ragged_forward_refusals_launch_nothing(dev, net):
     assert bool((q != -7.5).all())
 
 
+# ---------------------------------------------------------------------------------------------- workspaces of exactly the reported size
+GUARD = 1 << 20     # bytes of pattern behind the exact-size workspace: allocated memory, so a miscounted workspace shows and cannot fault
+
+
+def _exact_and_roomy(dev, nb, run):
+    """run(ws, nbytes) -> output tensors: once in a workspace of exactly the nb reported bytes, cut from a larger tensor whose rest holds a
+    byte pattern, once in a generously oversized one.  The outputs are bit-equal and the pattern is untouched."""
+    nb = int(nb)
+    assert nb > 0 and nb % 256 == 0
+    buf = torch.full((nb + GUARD,), 0xA5, dtype=torch.uint8, device=dev)
+    exact = run(buf[:nb], nb)
+    torch.cuda.synchronize(dev)
+    assert bool((buf[nb:] == 0xA5).all()), "the bytes behind the exact-size workspace were written"
+    big = torch.full((2 * nb + GUARD,), 0xA5, dtype=torch.uint8, device=dev)
+    roomy = run(big, big.numel())
+    torch.cuda.synchronize(dev)
+    assert len(exact) == len(roomy)
+    for a, b in zip(exact, roomy):
+        assert torch.equal(_bits(a), _bits(b))
+
+
+@pytest.mark.parametrize("N,T", [(1, 1), (3, 7)])
+def test_brain_forward_in_a_workspace_of_exactly_the_reported_size(dev, net, N, T):
+    lib, st = L.lib(), L.stream_ptr(dev)
+    x = torch.from_numpy(_inputs([N * T], 70 + N)).to(dev)
+
+    def run(ws, nbytes):
+        q = torch.full((N * T,), -7.5, dtype=torch.float32, device=dev)
+        L.check(lib.ivosw_brain_forward(L.dptr(net.flat), L.dptr(x), N, T, L.dptr(q), L.dptr(ws), nbytes, st), "brain_forward")
+        return (q,)
+    _exact_and_roomy(dev, lib.ivosw_brain_ws_bytes(N, T), run)
+
+
+def test_ragged_forward_in_a_workspace_of_exactly_the_reported_size(dev, net):
+    lib, st = L.lib(), L.stream_ptr(dev)
+    lengths = [1, 5, 2]
+    x, arr = torch.from_numpy(_inputs(lengths, 75)).to(dev), L.int_array(lengths)
+
+    def run(ws, nbytes):
+        q = torch.full((sum(lengths),), -7.5, dtype=torch.float32, device=dev)
+        L.check(lib.ivosw_brain_forward_ragged(L.dptr(net.flat), L.dptr(x), arr, len(lengths), L.dptr(q), L.dptr(ws), nbytes, st), "forward_ragged")
+        return (q,)
+    _exact_and_roomy(dev, lib.ivosw_brain_ragged_ws_bytes(sum(lengths)), run)
+
+
+@pytest.mark.parametrize("B,T", [(1, 1), (3, 2), (5, 25)])
+def test_dqn_loss_grad_in_a_workspace_of_exactly_the_reported_size(dev, net, B, T):
+    """(1, 1) and (3, 2) take the un-fused two-stream chain (a pass of fewer than eight rows), (5, 25) the fused one."""
+    lib, st = L.lib(), L.stream_ptr(dev)
+    tgt = Brain()
+    tgt.load_state_dict({k: torch.from_numpy(v) for k, v in synth.brain_state_dict(1).items()})
+    tgt = tgt.to(dev)
+    g = torch.Generator().manual_seed(100 * B + T)
+    state, new_state = (torch.rand(B, T, 2, generator=g).to(dev) for _ in range(2))
+    action = torch.randint(0, T, (B,), generator=g).to(dev)
+    r_step, r_done = (torch.rand(B, generator=g).to(dev) for _ in range(2))
+
+    def run(ws, nbytes):
+        grads = torch.zeros(L.BRAIN_NPARAMS, dtype=torch.float32, device=dev)
+        loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        L.check(lib.ivosw_dqn_loss_grad_ex(L.dptr(net.flat), L.dptr(tgt.flat), L.dptr(state), L.dptr(new_state), L.dptr(action), L.dptr(r_step),
+                                           L.dptr(r_done), B, T, 0.95, L.DQN_LOSS_MSE, 1.0, L.dptr(grads), L.dptr(loss), L.dptr(ws), nbytes, st),
+                "dqn_loss_grad_ex")
+        return grads, loss
+    _exact_and_roomy(dev, lib.ivosw_dqn_ws_bytes(B, T), run)
+
+
 # ---------------------------------------------------------------------------------------------- argmax
 def test_argmax_ragged_is_the_first_maximum_per_sequence(dev):
     lib, st = L.lib(), L.stream_ptr(dev)

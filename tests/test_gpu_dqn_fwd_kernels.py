@@ -1,5 +1,5 @@
 """The Brain's forward kernels - enc_fused_kernel, dec_fused_kernel (csrc/brain_fused.h), lstm_fwd_kernel<1|2|4>, lstm_fwd_quad_kernel<1|2|4>,
-lstm_fwd_mfma_kernel, lstm_fwd_mfma_pair_kernel, lstm_fwd_quad_ragged_kernel and brain_fwd_mega_kernel (csrc/brain.hip) - each ALONE through
+lstm_fwd_mfma_kernel, lstm_fwd_mfma_pair_kernel, lstm_fwd_quad_ragged_kernel and brain_fwd_mega_kernel (csrc/lstm_fwd.h) - each ALONE through
 its probe entry (include/ivosw_probe.h, libivosw_probe.so) on tensors this file makes, against the float64 restatements of tests/dqn_ref.py
 (pinned to the oracle on the CPU by tests/test_dqn_ref.py).  The rules and helpers are those of tests/test_gpu_dqn_kernels.py:
 

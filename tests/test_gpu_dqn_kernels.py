@@ -1,6 +1,6 @@
 """The backward kernels of the DQN step - bwd_tail_kernel's three units (wgrad_tile, dgrad_tile, csum_unit; csrc/brain_bwd.h), the step's two
-grouped launches of it with the slab reduction, head_fused_kernel<false|true> (csrc/brain_fused.h), lstm_bwd_quad_kernel<1> and
-lstm_bwd_kernel<1|2|4> (csrc/brain.hip) - each ALONE through its probe entry (include/ivosw_probe.h, libivosw_probe.so) on tensors this file
+grouped launches of it with the slab reduction, head_fused_kernel<false|true> (csrc/dqn_head.h), lstm_bwd_quad_kernel<1> and
+lstm_bwd_kernel<1|2|4> (csrc/lstm_bwd.h) - each ALONE through its probe entry (include/ivosw_probe.h, libivosw_probe.so) on tensors this file
 makes, against the float64 restatements of tests/dqn_ref.py (pinned to the oracle on the CPU by tests/test_dqn_ref.py).  The rules are
 those of tests/test_gpu_layer_kernels.py:
 

@@ -42,6 +42,49 @@ def test_ragged_rows_is_the_sum_of_the_lengths(lib):
     assert lib.ivosw_brain_ragged_ws_bytes(0) == 0 and lib.ivosw_brain_ragged_ws_bytes((1 << 20) + 1) == 0
 
 
+def _fwd_buffers(N, T, nkeep):
+    """The forward workspace's buffers in floats: a1, e, gx, hs, d1, q, then gates, cs, hprev of the kept samples."""
+    r = N * T
+    kept = [2 * nkeep * T * 512, 2 * nkeep * T * 128, 2 * nkeep * T * 128] if nkeep else []
+    return [r * 128, r * 128, r * 512, r * 256, r * 128, r] + kept
+
+
+def _dqn_buffers(B, T):
+    """The DQN step's: the policy pass on [s'; s] keeping s, the target pass, xcat, dq, dd1c, w4term, hcc, dhc, dG, dgx, de, da1 and the
+    four slab sets (dW2: 16, dW_hh and dW_ih: 40 each, of 512 x 128; the row-split column sums: 8 x 512)."""
+    r = B * T
+    return (_fwd_buffers(2 * B, T, B) + _fwd_buffers(B, T, 0) + [2 * r * 2, B, B * 128, B * 128, B * 256, B * 256, 2 * r * 512, r * 512,
+                                                                  r * 128, r * 128, 16 * 65536, 40 * 65536, 40 * 65536, 8 * 512])
+
+
+FWD_SLACK, DQN_SLACK = 64 * 16, 64 * 32      # floats the size formulas used to add per forward pass / per step for the 256-byte alignment
+
+
+@pytest.mark.parametrize("B,T", [(1, 1), (3, 2), (5, 25), (128, 25)])
+def test_workspace_queries_are_the_end_of_the_carve(lib, B, T):
+    """Every size query is positive, a multiple of 256, not below the plain sum of its buffers and not above what the earlier formula
+    (that sum + slack constants) gave."""
+    for got, bufs, slack in ((lib.ivosw_brain_ws_bytes(B, T), _fwd_buffers(B, T, 0), FWD_SLACK),
+                             (lib.ivosw_dqn_ws_bytes(B, T), _dqn_buffers(B, T), 2 * FWD_SLACK + DQN_SLACK)):
+        assert got > 0 and got % 256 == 0
+        assert 4 * sum(bufs) <= got <= 4 * (sum(bufs) + slack), (got, 4 * sum(bufs))
+
+
+@pytest.mark.parametrize("rows", [1, 342])
+def test_ragged_workspace_query_is_the_end_of_the_carve(lib, rows):
+    got, bufs = lib.ivosw_brain_ragged_ws_bytes(rows), _fwd_buffers(1, rows, 0)
+    assert got > 0 and got % 256 == 0
+    assert 4 * sum(bufs) <= got <= 4 * (sum(bufs) + FWD_SLACK)
+    assert got == lib.ivosw_brain_ws_bytes(1, rows)             # the flat rows are one [1, R] batch
+
+
+def test_workspace_queries_refuse_as_before(lib):
+    for B, T in ((0, 25), (-1, 25), (5, 0), (5, -3)):
+        assert lib.ivosw_brain_ws_bytes(B, T) == 0 and lib.ivosw_dqn_ws_bytes(B, T) == 0
+    assert lib.ivosw_brain_ragged_ws_bytes(0) == 0 and lib.ivosw_brain_ragged_ws_bytes(-4) == 0
+    assert lib.ivosw_brain_ragged_ws_bytes(1 << 20) > 0 and lib.ivosw_brain_ragged_ws_bytes((1 << 20) + 1) == 0
+
+
 def test_ragged_rows_refusals_name_the_sequence(lib):
     msg = lambda: lib.ivosw_last_error().decode()
     good = [3, 5, 4]

@@ -10,7 +10,7 @@ if [ "$mode" = build ]; then
   for n in "${!V[@]}"; do
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result -mllvm -amdgpu-mfma-vgpr-form ${V[$n]} -c $csrc/res2_chain.hip -o /tmp/rc_$n.o || exit 1
     objs=""
-    for s in capi.cpp brain.hip dqn.hip assess_front.hip conv.hip bottleneck.hip bottleneck_wide.hip res2_stage.hip gemm_8phase.hip stage_first.hip stem.hip assess.hip metrics.hip seg_epilogue.hip p2p.hip; do
+    for s in capi.cpp brain.hip brain_rank.hip dqn_step.hip gemm_f32.hip dqn.hip assess_front.hip conv.hip bottleneck.hip bottleneck_wide.hip res2_stage.hip gemm_8phase.hip stage_first.hip stem.hip assess.hip metrics.hip seg_epilogue.hip p2p.hip; do
       if [ -f $csrc/build/$s.probe.o ]; then objs="$objs $csrc/build/$s.probe.o"; else objs="$objs $csrc/build/$s.o"; fi
     done
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $root/tools/_variants/libprobe_$n.so $objs /tmp/rc_$n.o || exit 1
